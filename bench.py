@@ -28,9 +28,18 @@ every rank the full count.  One all-gather of ``[M, 1 + tasks]`` score rows per 
 
 Prints ONE JSON line on rank 0: ``value`` = predicted frames / second over the whole job
 (M * T * views * draws * iterations * K / wall, max over ranks) in exact fp32, CEM iterations /
-second, the roofline of the dominant kernel measured with HIP events on the launch stream, and the
-CPU baseline (the oracle restatement timed on the host cores, rank 0 at N=1 only).
-``alt_precision`` repeats the timed loop with the conv-LSTM GEMMs in the split-bf16 mode.
+second, ``ms_per_step`` = wall milliseconds of one timed planning call, and the roofline of the
+dominant kernel measured with HIP events on the launch stream during the timed calls.
+
+A plain run does only that: set up, warm up, time ``--steps`` calls, print the line.  ``--full`` adds
+the measurements that take runs of their own: ``alt_precision`` repeats the timed loop with the
+conv-LSTM GEMMs in the split-bf16 mode, and ``cpu_baseline`` times the oracle restatement on the host
+cores (rank 0 at N=1 only; ``null`` in a plain run).
+
+``--dump-outputs DIR`` writes what the LAST timed planning call returned (the executed action, the
+score vector of every CEM iteration, the elite plans and their indices) as ``DIR/<name>.npy`` in
+float32 / float64, on rank 0.  Inputs are seeded, so two builds run with the same arguments can be
+compared output for output.
 """
 import argparse
 import contextlib
@@ -89,8 +98,13 @@ def parse():
     ap.add_argument('--layer-spec', type=int, default=0, choices=(0, 32, 64, 128),
                     help='savp3: 0 = the layer table the public code selects by image size (128 x 128: six conv-LSTMs up to '
                          '256 channels); 64 = the paper\'s five-cell table')
-    ap.add_argument('--no-alt', action='store_true', help='skip the alt_precision measurement')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also run the measurements beyond the headline line: alt_precision (a second timed loop in '
+                         'the other precision mode) and cpu_baseline (the oracle on the host cores)')
+    ap.add_argument('--no-alt', action='store_true', help='--full: skip the alt_precision measurement')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed planning call returned as DIR/<name>.npy (rank 0)')
     return ap.parse_args()
 
 
@@ -444,6 +458,10 @@ class Bench(object):
             # `scores_sha` is the same string at N = 1 and at any N under strong scaling (same candidates, same bits)
             from visual_foresight_amd.video_prediction.sharding import plan_digest, gather_plan_digests
             same, shas = gather_plan_digests([plan_digest(ps, bi, act) for ps, bi, act in decided])
+        # what the last timed call handed its caller (the executed action, plan_stat) and the elite plans it acts on
+        last = {k: np.array(v) for k, v in out['plan_stat'].items()}
+        last.update(actions=np.array(out['actions']), elite_actions=np.array(ctrl._best_actions),
+                    elite_indices=np.array(ctrl._best_indices))
         if self.world > 1:
             tmax = torch.tensor([elapsed], dtype=torch.float64, device=self.dev if self.backend == 'nccl' else 'cpu')
             self.dist.all_reduce(tmax, op=self.dist.ReduceOp.MAX)
@@ -460,7 +478,7 @@ class Bench(object):
                     rollouts=(hi - lo) * max(self.draws, 1) * self.ncam * self.iters * a.steps,
                     elites=[int(i) for i in ctrl._best_indices],
                     elites_identical_across_ranks=bool(same), scores_sha=shas[0], scores_sha_per_rank=shas,
-                    best=float(np.min(out['plan_stat']['scores_itr%d' % (self.iters - 1)])))
+                    best=float(np.min(out['plan_stat']['scores_itr%d' % (self.iters - 1)])), outputs=last)
 
     def collective_report(self, pred, avg_launch_us=None):
         """What the process group actually was - backend, world size, every rank's device - and what the one
@@ -606,6 +624,8 @@ class Bench(object):
         T, iters = self.T, self.iters
         primary = a.precision
         m = self.measure(primary)
+        if a.dump_outputs and self.rank == 0:
+            dump_outputs(m['outputs'], a.dump_outputs)
         frames_total = self.M * max(self.draws, 1) * T * self.ncam * iters * a.steps
         shared_gpus = self.world > 1 and self.backend != 'nccl'
         result = {
@@ -650,7 +670,7 @@ class Bench(object):
         }
         self.attach_traffic(result['roofline'], primary)
 
-        if not a.no_alt and not ((self.draws and a.network == 'savp2') or a.network == 'savp3'):   # (arch 2 / 3 are built for exact fp32 only)
+        if a.full and not a.no_alt and not ((self.draws and a.network == 'savp2') or a.network == 'savp3'):   # (arch 2 / 3 are built for exact fp32 only)
             other = 'bf16x6' if primary == 'fp32' else 'fp32'
             am = self.measure(other)
             result['alt_precision'] = {
@@ -666,7 +686,7 @@ class Bench(object):
                 'best_score_last_plan': am['best'],
             }
 
-        if self.rank == 0 and self.world == 1 and not a.no_cpu_baseline:
+        if self.rank == 0 and self.world == 1 and a.full and not a.no_cpu_baseline:
             result['cpu_baseline'] = cpu_baseline()
         elif self.rank == 0:
             result['cpu_baseline'] = None
@@ -674,6 +694,13 @@ class Bench(object):
             print(json.dumps(result), flush=True)
         if self.world > 1:
             self.dist.destroy_process_group()
+
+
+def dump_outputs(outputs, dirname):
+    """--dump-outputs: one DIR/<name>.npy per array, float32 arrays as they are and everything else as float64."""
+    os.makedirs(dirname, exist_ok=True)
+    for name, v in sorted(outputs.items()):
+        np.save(os.path.join(dirname, name + '.npy'), v.astype(np.float32 if v.dtype == np.float32 else np.float64))
 
 
 def compare_lines(a, b):

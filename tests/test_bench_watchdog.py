@@ -33,6 +33,23 @@ def test_metric_label_names_the_workload():
     assert 'workload c5' in b.metric_label() and '125-sample' in b.metric_label() and '5 latent draws' in b.metric_label()
 
 
+def test_plain_run_is_the_default_and_outputs_dump_as_float_arrays(tmp_path, monkeypatch):
+    """`--full` (alt_precision, CPU baseline) is opt-in; `--dump-outputs` writes one .npy per array in float32 / float64."""
+    import numpy as np
+    monkeypatch.setattr(bench.sys, 'argv', ['bench.py', '--gpus', '1', '--steps', '4', '--warmup', '1'])
+    a = bench.parse()
+    assert not a.full and a.dump_outputs is None and a.steps == 4 and a.warmup == 1
+    monkeypatch.setattr(bench.sys, 'argv', ['bench.py', '--full', '--dump-outputs', str(tmp_path)])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == str(tmp_path)
+    outputs = {'scores_itr0': np.arange(3, dtype=np.float32), 'actions': np.ones(4), 'elite_indices': np.array([2, 0])}
+    bench.dump_outputs(outputs, str(tmp_path / 'out'))
+    got = {p.stem: np.load(str(p)) for p in (tmp_path / 'out').glob('*.npy')}
+    assert sorted(got) == sorted(outputs)
+    assert got['scores_itr0'].dtype == np.float32 and got['actions'].dtype == np.float64
+    assert got['elite_indices'].dtype == np.float64 and list(got['elite_indices']) == [2.0, 0.0]
+
+
 def test_launcher_env_caps_host_threads_and_never_needs_torch():
     """The 8-GPU pre-flight: the self-launcher counts GPUs in a throw-away child (its own process stays GPU-free) and
     gives every rank one host math thread."""

@@ -8,6 +8,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -33,8 +34,17 @@ def _line(cmd, env=None):
 
 
 @pytest.fixture(scope='module')
-def single():
-    return _line([sys.executable, 'bench.py', '--gpus', '1'] + ARGS)
+def dumps(tmp_path_factory):
+    return tmp_path_factory.mktemp('bench_outputs')
+
+
+def _outputs(d):
+    return {p.stem: np.load(str(p)) for p in d.glob('*.npy')}
+
+
+@pytest.fixture(scope='module')
+def single(dumps):
+    return _line([sys.executable, 'bench.py', '--gpus', '1'] + ARGS + ['--dump-outputs', str(dumps / 'single')])
 
 
 def _check_common(r, n):
@@ -55,13 +65,18 @@ def test_single_rank_line(single):
 
 
 @pytest.mark.parametrize('launcher', ['self', 'torchrun'])
-def test_two_rank_line_and_collective_evidence(single, launcher):
+def test_two_rank_line_and_collective_evidence(single, dumps, launcher):
+    import bench
+    dump = ['--dump-outputs', str(dumps / launcher)]
     if launcher == 'self':
         env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK')}
-        r = _line([sys.executable, 'bench.py', '--gpus', '2'] + ARGS, env=env)
+        r = _line([sys.executable, 'bench.py', '--gpus', '2'] + ARGS + dump, env=env)
     else:       # exactly the driver's command line for N > 1
+        # (from an environment without thread caps of its own: bench.py only fills in the ones its launcher left unset)
+        env = {k: v for k, v in os.environ.items() if k not in bench.HOST_THREAD_CAPS}
         r = _line([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2',
-                   '--master-addr', '127.0.0.1', '--master-port', str(_free_port()), 'bench.py', '--gpus', '2'] + ARGS)
+                   '--master-addr', '127.0.0.1', '--master-port', str(_free_port()), 'bench.py', '--gpus', '2'] + ARGS + dump,
+                  env=env)
     _check_common(r, 2)
     c = r['collective']
     assert c['world_size'] == 2 and c['backend'] in ('nccl', 'gloo') and len(c['ranks']) == 2
@@ -80,13 +95,40 @@ def test_two_rank_line_and_collective_evidence(single, launcher):
     assert r['elites_identical_across_ranks'] is True
     assert r['scores_sha_per_rank'] == [r['scores_sha']] * 2
     assert r['scores_sha'] == single['scores_sha'], 'the 2-rank job planned something else than one GPU'
-    import bench
+    # ... and hands its caller the same arrays, bit for bit
+    mine, one = _outputs(dumps / launcher), _outputs(dumps / 'single')
+    assert sorted(mine) == sorted(one) and all(np.array_equal(mine[k], one[k]) for k in one)
     assert r['scores_sha_over'] == single['scores_sha_over'] and bench.compare_lines(r, single) == 'equal'
     assert c['rank_id_allgather_verified_on_every_rank'] is True
     assert (c['rccl_version'] is not None) == (c['backend'] == 'nccl')
     assert all(x['avg_launch_us'] > 0 for x in c['ranks'])
     lo, hi = c['avg_launch_us_min_max_over_ranks']
     assert 0 < lo <= hi
+
+
+def test_plain_line_is_lean_and_dumps_the_last_call(single, dumps):
+    """A plain run prints the headline line only (no alt_precision leg, no CPU baseline) and --dump-outputs holds what
+    its last timed planning call returned: the executed action, every CEM iteration's scores, the elite plans."""
+    assert 'alt_precision' not in single and single['cpu_baseline'] is None
+    got = _outputs(dumps / 'single')
+    assert sorted(got) == ['actions', 'elite_actions', 'elite_indices', 'scores_itr0', 'scores_itr1', 'scores_itr2']
+    assert all(v.dtype in (np.float32, np.float64) for v in got.values())
+    last = got['scores_itr2']
+    assert last.shape == (24,) and float(last.min()) == single['best_score_last_plan']
+    n_elite = len(got['elite_indices'])
+    assert np.array_equal(got['elite_indices'], np.argsort(last)[:n_elite])
+    assert got['elite_actions'].shape == (n_elite, 13, 4) and np.array_equal(got['actions'], got['elite_actions'][0, 0])
+
+
+def test_full_line_adds_the_alt_precision_leg(single):
+    """--full repeats the timed loop in the split-bf16 mode beside the unchanged primary measurement."""
+    r = _line([sys.executable, 'bench.py', '--gpus', '1', '--full', '--no-cpu-baseline'] +
+              [x for x in ARGS if x not in ('--no-alt', '--no-cpu-baseline')])
+    _check_common(r, 1)
+    assert r['scores_sha'] == single['scores_sha'] and r['cpu_baseline'] is None
+    alt = r['alt_precision']
+    assert alt['precision'] == 'bf16x6' and alt['value'] > 0 and alt['ms_per_step'] > 0
+    assert alt['roofline']['launches'] > 0
 
 
 def test_lines_with_different_warmups_are_not_comparable(single):

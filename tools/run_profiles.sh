@@ -8,7 +8,7 @@ O=$R/gpurun_out/prof_$tag
 mkdir -p $O
 cd $R
 # 1. the default bench line (fp32 primary, split-bf16 alt, CPU legs)
-python bench.py > $O/bench_default.json 2> $O/bench_default.err
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 python tools/bench_line.py $O/bench_default.json default
 # 2. kernel trace of the same workload
 cd /tmp
@@ -32,7 +32,7 @@ python bench.py --workload c3 --no-alt --no-cpu-baseline --steps 4 --warmup 1 2>
 python bench.py --workload c4 --samples 125 --no-alt --no-cpu-baseline --steps 8 --warmup 2 2>/dev/null | tail -1 > $O/bench_c4_shard125.json; python tools/bench_line.py $O/bench_c4_shard125.json c4-shard
 python bench.py --workload c4 --no-alt --no-cpu-baseline --steps 3 --warmup 1 2>/dev/null | tail -1 > $O/bench_c4_1gpu.json; python tools/bench_line.py $O/bench_c4_1gpu.json c4-1gpu
 python bench.py --samples 25 --no-alt --no-cpu-baseline --steps 10 --warmup 2 2>/dev/null | tail -1 > $O/bench_c2_shard25.json; python tools/bench_line.py $O/bench_c2_shard25.json c2-shard25
-python bench.py --workload c5 --samples 125 --no-cpu-baseline --steps 3 --warmup 1 2>/dev/null | tail -1 > $O/bench_c5_shard125.json; python tools/bench_line.py $O/bench_c5_shard125.json c5-shard
+python bench.py --workload c5 --samples 125 --full --no-cpu-baseline --steps 3 --warmup 1 2>/dev/null | tail -1 > $O/bench_c5_shard125.json; python tools/bench_line.py $O/bench_c5_shard125.json c5-shard
 python bench.py --ndesig 4 --no-alt --no-cpu-baseline --steps 8 --warmup 2 2>/dev/null | tail -1 > $O/bench_c2_nd4.json; python tools/bench_line.py $O/bench_c2_nd4.json c2-nd4
 python bench.py --samples 50 --no-alt --no-cpu-baseline --steps 8 --warmup 2 2>/dev/null | tail -1 > $O/bench_c2_shard50.json; python tools/bench_line.py $O/bench_c2_shard50.json c2-shard50
 # 5. phase statistics, two-rank dry run
