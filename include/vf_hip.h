@@ -148,6 +148,25 @@ int vf_rollout(vf_handle *h, const float *d_actions, int32_t B, const int32_t *g
                float finalweight, const float *task_weights, double *d_scores,
                double *d_scores_per_task, void *stream);
 
+/* Ensemble cost over independently trained predictors (reference
+ * visual_mpc/policy/cem_controllers/variants/ensemble_vidpred.py:32-61).  Scores the LAST vf_rollout of every member -
+ * n_members (1..16) handles of one vf_config, device included, that rolled the same sequences with the same goal pixels
+ * (same B).  Per (view c, pixel p, rolled sequence, step t) member m's expected distance x_m is the value its own
+ * vf_rollout scored with; the step cost is
+ *   c_t = mean_m x_m + lambda_variance * var_m x_m          (population variance, two passes, members in list order)
+ * and replaces x in vf_rollout's reduction: time-weighted mean with w = (1, ..., 1, finalweight), mean over the action's
+ * n_draws sequences, plain mean over tasks or the task_weights sum.  d_scores [B / n_draws] and d_scores_per_task
+ * [B / n_draws][ncam * ndesig] as vf_rollout's; d_cost_per_step (float64 [B / n_draws][ncam * ndesig][T], may be NULL)
+ * receives c_t averaged over the draws.  d_scores_per_task may be NULL.  If any member's device status is raised every
+ * output is NaN.  Enqueues one kernel on `stream` and never synchronises.
+ * Drive every member from ONE stream, one rollout after the other, and score on that stream: two persistent rollouts
+ * running at the same time can starve each other, their tiles give up waiting and every score becomes NaN.
+ * Returns VF_ERR_INVALID (nothing launched) for a NULL / empty / too long member list, differing configs, a member
+ * that has not rolled, differing B or differing goal pixels. */
+int vf_ensemble_scores(vf_handle *const *members, int32_t n_members, float lambda_variance, float finalweight,
+                       const float *task_weights, double *d_scores, double *d_scores_per_task,
+                       double *d_cost_per_step, void *stream);
+
 /* Copy the predictions of the last vf_rollout out in the reference's layout (camera axis,
  * normalised distributions).  Any destination may be NULL.  first/count select a range of rolled
  * sequences.  Replaces the gen_images/gen_distrib/gen_states fetch of

@@ -24,7 +24,8 @@ EXPORTS = ('vf_abi_version', 'vf_last_error', 'vf_weight_count', 'vf_create', 'v
            'vf_allgather_scores', 'vf_comm_init_all', 'vf_comm_destroy', 'vf_allgather_scores_group',
            'vf_macs_per_sample_step', 'vf_set_profiling', 'vf_get_profile',
            'vf_set_dedup', 'vf_set_persistent', 'vf_set_xcd_queues', 'vf_set_fuse_top', 'vf_device_status',
-           'vf_set_phase_stats', 'vf_debug_phase_stats', 'vf_debug_poison_status', 'vf_set_sched_option')
+           'vf_set_phase_stats', 'vf_debug_phase_stats', 'vf_debug_poison_status', 'vf_set_sched_option',
+           'vf_ensemble_scores')
 ABI_VERSION = 7
 
 
@@ -100,6 +101,8 @@ def load_library():
     lib.vf_set_context.argtypes = [P, P, P, P, P, P]
     lib.vf_rollout.argtypes = [P, P, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.c_float,
                                ctypes.POINTER(ctypes.c_float), P, P, P]
+    lib.vf_ensemble_scores.argtypes = [ctypes.POINTER(P), ctypes.c_int32, ctypes.c_float, ctypes.c_float,
+                                       ctypes.POINTER(ctypes.c_float), P, P, P, P]
     lib.vf_register.argtypes = [P, P, P, P, P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, P, P, P, P, P]
     lib.vf_allgather_scores.argtypes = [P, P, P, ctypes.c_int32, P, P]
     lib.vf_comm_init_all.argtypes = [ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(P)]
@@ -126,7 +129,7 @@ def load_library():
     lib.vf_device_status.argtypes = [P, ctypes.POINTER(ctypes.c_int32)]
     lib.vf_set_persistent.restype = lib.vf_device_status.restype = ctypes.c_int
     lib.vf_set_profiling.restype = lib.vf_get_profile.restype = ctypes.c_int
-    for name in ('vf_create', 'vf_destroy', 'vf_load_weights', 'vf_set_context', 'vf_rollout',
+    for name in ('vf_create', 'vf_destroy', 'vf_load_weights', 'vf_set_context', 'vf_rollout', 'vf_ensemble_scores',
                  'vf_export', 'vf_register', 'vf_allgather_scores', 'vf_comm_init_all', 'vf_comm_destroy',
                  'vf_allgather_scores_group', 'vf_set_phase_stats',
                  'vf_debug_phase_stats', 'vf_debug_poison_status'):

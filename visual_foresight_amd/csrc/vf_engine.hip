@@ -491,6 +491,7 @@ struct vf_handle {
     size_t blob_floats = 0;             // canonical floats per view
     bool have_weights = false, have_context = false;
     int last_B = 0;
+    std::vector<int32_t> last_goal;     // goal pixels [ncam][ND][2] of the last vf_rollout (vf_ensemble_scores compares them)
 
     // layers (geometry)
     ConvLayer enc0, lstm[7], enc1, enc2, enc3, convt1, convt2, convt3, fc;
@@ -2610,6 +2611,49 @@ int vf_rollout(vf_handle *h, const float *d_actions, int32_t B, const int32_t *g
                        h->d_status, d_scores, d_scores_per_task);
     VF_HIP_CHECK(hipGetLastError());
     h->last_B = B;
+    h->last_goal.assign(goal_pix, goal_pix + (size_t)h->ncam * h->ND * 2);
+    return VF_OK;
+    VF_API_CATCH(int)
+}
+
+int vf_ensemble_scores(vf_handle *const *members, int32_t n_members, float lambda_variance, float finalweight,
+                       const float *task_weights, double *d_scores, double *d_scores_per_task, double *d_cost_per_step,
+                       void *stream) {
+    VF_API_TRY
+    if (!members || n_members < 1) return fail(VF_ERR_INVALID, "empty member list");
+    if (n_members > kMaxMembers)
+        return fail(VF_ERR_INVALID, std::to_string(n_members) + " members, at most " + std::to_string(kMaxMembers));
+    if (!d_scores) return fail(VF_ERR_INVALID, "null argument");
+    const vf_handle *h0 = members[0];
+    for (int m = 0; m < n_members; ++m) {
+        const vf_handle *h = members[m];
+        const std::string who = "member " + std::to_string(m);
+        if (!h) return fail(VF_ERR_INVALID, who + " is NULL");
+        if (memcmp(&h->cfg, &h0->cfg, sizeof(vf_config)) != 0)
+            return fail(VF_ERR_INVALID, who + ": vf_config differs from member 0's (device included)");
+        if (h->last_B < 1) return fail(VF_ERR_INVALID, who + " has not rolled");
+        if (h->last_B != h0->last_B)
+            return fail(VF_ERR_INVALID, who + " rolled " + std::to_string(h->last_B) + " sequences, member 0 " +
+                                            std::to_string(h0->last_B));
+        if (h->last_goal != h0->last_goal) return fail(VF_ERR_INVALID, who + " rolled with other goal pixels");
+    }
+    VF_HIP_CHECK(hipSetDevice(h0->cfg.device));
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    EnsembleMembers em;
+    memset(&em, 0, sizeof(em));
+    em.n = n_members;
+    for (int m = 0; m < n_members; ++m) { em.sums[m] = members[m]->sums; em.status[m] = members[m]->d_status; }
+    TaskWeights tw;
+    memset(&tw, 0, sizeof(tw));
+    if (task_weights) {
+        tw.use = 1;
+        for (int i = 0; i < h0->ncam * h0->ND; ++i) tw.w[i] = task_weights[i];
+    }
+    const int n_actions = h0->last_B / h0->n_draws;
+    hipLaunchKernelGGL(ensemble_scores_kernel, dim3(n_actions), dim3(64), 0, st, em, h0->sums_step_stride,
+                       h0->sums_view_stride, n_actions, h0->n_draws, h0->T, h0->ND, h0->ncam, h0->nblocks,
+                       lambda_variance, finalweight, tw, d_scores, d_scores_per_task, d_cost_per_step);
+    VF_HIP_CHECK(hipGetLastError());
     return VF_OK;
     VF_API_CATCH(int)
 }

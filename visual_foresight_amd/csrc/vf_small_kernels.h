@@ -6,6 +6,7 @@
 //                    frame and designated-pixel distributions + expected-distance partial sums
 //   scores / export  reduce per-step sums to costs (mean over tasks or trade-off weights, mean over
 //                    latent draws); hand predictions out in the reference layout (camera axis)
+//   ensemble_scores  the same reduction over E engines' sums, per step mean + lambda * variance over the members
 //   register         bilinear warp by a flow field + designated-pixel re-localisation + warp error
 #pragma once
 #include <hip/hip_runtime.h>
@@ -606,6 +607,77 @@ VF_GLOBAL void scores_kernel(const double *sums, long long step_stride, long lon
             }
             const double sc = over_draws / n_draws;
             const int col = v * ND + d;
+            if (scores_per_task && lane == 0)
+                scores_per_task[(long long)a * ntask + col] = poisoned ? __builtin_nan("") : sc;
+            total += tw.use ? (double)tw.w[col] * sc : sc;
+        }
+    const double out = tw.use ? total : total / ntask;
+    if (lane == 0) scores[a] = poisoned ? __builtin_nan("") : out;
+}
+
+// ------------------------------------------------------------------------------------------
+// Ensemble cost (reference policy/cem_controllers/variants/ensemble_vidpred.py:32-61).  E engines of one config have
+// rolled the same sequences; per (view v, pixel d, rolled sequence r, step t) member m's expected distance is
+//     x_m = (S1/S0)_m(t, v, r, d)                         (the value that member's own scores_kernel used)
+//     mean = sum_m x_m / E,  var = sum_m (x_m - mean)^2 / E   (two passes, population variance, members 0 .. E-1)
+//     c_t = mean + lambda * var
+// and c_t takes the place of S1/S0 in scores_kernel's reduction: time-weighted mean, mean over the action's draws,
+// plain mean over tasks or the trade-off weighted sum.  The second pass re-reads the sums instead of holding E values
+// per lane, so no member count costs registers or scratch.  cost_per_step (optional) [A][ncam*ND][T] gets c_t averaged
+// over the draws.  A non-zero status of ANY member poisons every output with NaN.
+constexpr int kMaxMembers = 16;
+struct EnsembleMembers { const double *sums[kMaxMembers]; const int *status[kMaxMembers]; int n; };
+
+__device__ __forceinline__ double member_step_cost(const double *pp, int ntiles, int lane) {
+    double s0 = 0.0, s1 = 0.0;
+    for (int k = lane; k < ntiles; k += 64) { s0 += pp[2 * k]; s1 += pp[2 * k + 1]; }
+    s0 = wave_sum(s0); s1 = wave_sum(s1);
+    return s1 / s0;
+}
+
+// One WAVE per action, as scores_kernel.
+VF_GLOBAL void ensemble_scores_kernel(const EnsembleMembers em, long long step_stride, long long view_stride,
+                                       int n_actions, int n_draws, int T, int ND, int ncam, int ntiles,
+                                       float lambda_variance, float finalweight, const TaskWeights tw,
+                                       double *scores, double *scores_per_task, double *cost_per_step) {
+    const int a = blockIdx.x, lane = threadIdx.x;
+    if (a >= n_actions) return;
+    const int ntask = ncam * ND, E = em.n;
+    bool poisoned = false;
+    for (int m = 0; m < E; ++m) poisoned = poisoned || (em.status[m] && *em.status[m] != 0);
+    const double lam = (double)lambda_variance;
+    double total = 0.0;
+    for (int v = 0; v < ncam; ++v)
+        for (int d = 0; d < ND; ++d) {
+            const int col = v * ND + d;
+            double *cps = cost_per_step ? cost_per_step + ((long long)a * ntask + col) * T : nullptr;
+            double over_draws = 0.0;
+            for (int j = 0; j < n_draws; ++j) {
+                const long long b = (long long)a * n_draws + j;
+                const long long off0 = (long long)v * view_stride + (b * ND + d) * ntiles * 2;
+                double acc = 0.0, wsum = 0.0;
+                for (int t = 0; t < T; ++t) {
+                    const long long off = (long long)t * step_stride + off0;
+                    double sum = 0.0;
+                    for (int m = 0; m < E; ++m) sum += member_step_cost(em.sums[m] + off, ntiles, lane);
+                    const double mean = sum / (double)E;
+                    double sq = 0.0;
+                    for (int m = 0; m < E; ++m) {
+                        const double dev = member_step_cost(em.sums[m] + off, ntiles, lane) - mean;
+                        sq += dev * dev;
+                    }
+                    const double c = mean + lam * (sq / (double)E);
+                    const double w = (t == T - 1) ? (double)finalweight : 1.0;
+                    acc += w * c;
+                    wsum += w;
+                    if (cps && lane == 0) {     // (the same lane reads back what it wrote for the earlier draws)
+                        const double s = j == 0 ? c : cps[t] + c;
+                        cps[t] = poisoned ? __builtin_nan("") : (j == n_draws - 1 ? s / n_draws : s);
+                    }
+                }
+                over_draws += acc / wsum;
+            }
+            const double sc = over_draws / n_draws;
             if (scores_per_task && lane == 0)
                 scores_per_task[(long long)a * ntask + col] = poisoned ? __builtin_nan("") : sc;
             total += tw.use ? (double)tw.w[col] * sc : sc;

@@ -40,7 +40,7 @@ class PixelCostController(CEMBaseController):
         }
         predictor_class = self._hp.predictor_class
         if predictor_class is None:
-            predictor_class = _default_predictor_class(ag_params.get('ncam', 1))
+            predictor_class = self._default_predictor_class(ag_params)
         if getattr(predictor_class, 'wants_agent_params', False):
             # the HIP predictor is shape-specialised at construction (no checkpoint json to read
             # adim/sdim/size/T from), so it is told what the controller will ask of it
@@ -67,6 +67,10 @@ class PixelCostController(CEMBaseController):
         self._images = None
         if self._hp.predictor_propagation:
             self._chosen_distrib = None     # distributions of the executed plan
+
+    def _default_predictor_class(self, ag_params):
+        """The predictor built when ``predictor_class`` is None (variants override this)."""
+        return _default_predictor_class(ag_params.get('ncam', 1))
 
     def _plan_horizon(self):
         """Number of predicted steps the sampler will produce (nactions * repeat)."""
