@@ -27,6 +27,41 @@
 
 namespace vf {
 
+// ---- Pad skip.  The tile stages exact zeros for the halo outside the image, so at stride 1 / pad 2 a kernel row ky
+// multiplies only zeros for every GEMM row whose input row y + ky - 2 lies outside [0, Hin).  A 32-row block (two image
+// rows of the 8 x 16 tile) in which that holds for every pixel - the top block of a top tile for ky = 0, the bottom block
+// of a bottom tile for ky = 4 - or which holds no output pixel at all (rows below the image, images past the batch) can
+// leave the kernel row out: acc + 0 * w == acc for finite w, and the accumulators start at +0 and never become -0, so
+// the bits of every stored output are the same.  The mask depends only on the layer geometry and the tile, so it is
+// wave-uniform, and it holds for both input segments (h(s-1) and the layer input are padded alike).
+//
+// live kernel rows (bit ky) of the GEMM row at (image img, position rem inside the image's rows) of a tile at (ty0, tx0)
+__host__ __device__ inline unsigned gs_live_rows(const int img, const int rem, const int yy, const int n_here,
+                                                 const int TH, const int TW, const int ty0, const int tx0, const int Hout,
+                                                 const int Wout, const int Hin) {
+    const int y = ty0 + yy, x = tx0 + rem - yy * TW;
+    if (img >= n_here || rem >= TH * TW || y >= Hout || x >= Wout) return 0u;
+    unsigned bits = 0u;
+    for (int ky = 0; ky < 5; ++ky) bits |= ((unsigned)(y + ky - 2) < (unsigned)Hin ? 1u : 0u) << ky;
+    return bits;
+}
+// Which row blocks the K loop of kernel row ky runs, from the 4-bit mask of its live blocks (a dead block left in the range
+// multiplies zeros, as before).  At stride 1 only the edge rows lose blocks in a full-height tile - ky = 0 the top block,
+// ky = 4 the bottom one(s) - so only they have reduced variants: blocks 1-3 or none for ky = 0, blocks 0-2, 0-1 or none for
+// ky = 4; rows 1-3 always run all four.  (A variant choice at every row, measured in the ISA: the compiler then moves the
+// accumulators between registers at the join behind every kernel row, ~40 VALU moves per row on the full path too.)
+enum GsRowVariant { GS_ROW_ALL = 0, GS_ROW_FROM1, GS_ROW_TO3, GS_ROW_TO2, GS_ROW_NONE };
+__host__ __device__ constexpr int gs_row_variant(const unsigned live4, const int ky) {
+    return ky == 0 ? (live4 == 0u ? GS_ROW_NONE : (!(live4 & 1u) ? GS_ROW_FROM1 : GS_ROW_ALL))
+                   : (ky == 4 ? (live4 == 0u ? GS_ROW_NONE : (!(live4 & 12u) ? GS_ROW_TO2 : (!(live4 & 8u) ? GS_ROW_TO3 : GS_ROW_ALL)))
+                              : GS_ROW_ALL);
+}
+__host__ __device__ constexpr int gs_row_first(const int v) { return v == GS_ROW_FROM1 ? 1 : 0; }
+__host__ __device__ constexpr int gs_row_end(const int v) {
+    return v == GS_ROW_NONE ? 0 : (v == GS_ROW_TO3 ? 3 : (v == GS_ROW_TO2 ? 2 : 4));
+}
+template <int M0_, int M1_> struct GsBlocks { static constexpr int M0 = M0_, M1 = M1_; };
+
 // MR = 4: 128 rows per workgroup (MR = 2, 64 rows, compiles too).  5 x 5 kernel, stride 1, 32-channel chunks of whole
 // channel quads (vf_engine.hip plans this tile only then).
 // RAW (arch 3): the tile ends with the GEMM and stores the raw gate pre-activations (gates_raw_epilogue)
@@ -71,6 +106,7 @@ __device__ __forceinline__ void conv_lstm_gsplit2_tile(const PT &p, const int bx
 
     // ---- this lane's A rows (GEMM rows m * 32 + n), in float4 units inside an operand tile
     int ab4[MR];
+    unsigned live_rows = 0u;            // bit 4 ky + m: row block m holds a pixel whose kernel row ky reads the image (pad skip)
     {
         const int px_per_img = p.TH * p.TW;
         const TileDiv div_rpi(p.RPI), div_tw(p.TW);
@@ -81,7 +117,17 @@ __device__ __forceinline__ void conv_lstm_gsplit2_tile(const PT &p, const int bx
             const bool ok = img < p.NI && rem < px_per_img;
             const int y = div_tw.div(rem), x = rem - y * p.TW;
             ab4[m] = ((ok ? (img * tile_px + y * LW + x) * KCpad : 0) + kh * 4) >> 2;
+            if constexpr (MR == 4) {
+                if (p.pad_skip) {
+                    const unsigned bits = gs_live_rows(img, rem, y, min(p.NI, p.B - bimg0), p.TH, p.TW, ty0, tx0, p.Hout,
+                                                       p.Wout, p.Hin);
+#pragma unroll
+                    for (int ky = 0; ky < 5; ++ky)
+                        if (__builtin_amdgcn_ballot_w64(((bits >> ky) & 1u) != 0u) != 0ull) live_rows |= 1u << (4 * ky + m);
+                }
+            }
         }
+        live_rows = (MR != 4 || !p.pad_skip) ? 0xFFFFFu : (unsigned)__builtin_amdgcn_readfirstlane((int)live_rows);
     }
     f32x16 acc[MR][1];
 #pragma unroll
@@ -216,23 +262,26 @@ __device__ __forceinline__ void conv_lstm_gsplit2_tile(const PT &p, const int bx
     constexpr int GSZ = MR < 4 ? MR : 4, NG = MR / GSZ, NS = 4 * NG;
     const f32x4 *ar[MR];
     f32x4 aP4[GSZ], aQ4[GSZ];
-    auto gs_fetch = [&](f32x4 (&A_)[GSZ], const int kx, const int sub) {
+    // (blk: the row blocks [M0, M1) of each group this kernel row multiplies - all of them but where pad skip drops some)
+    auto gs_fetch = [&](auto blk, f32x4 (&A_)[GSZ], const int kx, const int sub) {
+        using BLK = decltype(blk);
 #pragma unroll
-        for (int m_ = 0; m_ < GSZ; ++m_) A_[m_] = ar[(sub % NG) * GSZ + m_][kx * 9 + (sub / NG) * 2];
+        for (int m_ = BLK::M0; m_ < BLK::M1; ++m_) A_[m_] = ar[(sub % NG) * GSZ + m_][kx * 9 + (sub / NG) * 2];
     };
-    auto gs_tap = [&](auto kxc, const int gt_next) {
+    auto gs_tap = [&](auto blk, auto kxc, const int gt_next) {
+        using BLK = decltype(blk);
         constexpr int KX = decltype(kxc)::value;
         static_for<NS>([&](auto sc) {
             constexpr int S = decltype(sc)::value;
             f32x4 (&a_cur)[GSZ] = (S & 1) ? aQ4 : aP4;
             f32x4 (&a_nxt)[GSZ] = (S & 1) ? aP4 : aQ4;
-            if constexpr (S + 1 < NS) gs_fetch(a_nxt, KX, S + 1);
-            else if constexpr (KX < 4) gs_fetch(a_nxt, KX + 1, 0);
+            if constexpr (S + 1 < NS) gs_fetch(blk, a_nxt, KX, S + 1);
+            else if constexpr (KX < 4) gs_fetch(blk, a_nxt, KX + 1, 0);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int j_ = 0; j_ < 4; ++j_) {
 #pragma unroll
-                for (int m_ = 0; m_ < GSZ; ++m_)
+                for (int m_ = BLK::M0; m_ < BLK::M1; ++m_)
                     acc[(S % NG) * GSZ + m_][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(
                         a_cur[m_][j_], gsW[S / NG][j_], acc[(S % NG) * GSZ + m_][0], 0, 0, 0);
                 if constexpr (KX == 0 && S == 0) {
@@ -255,16 +304,32 @@ __device__ __forceinline__ void conv_lstm_gsplit2_tile(const PT &p, const int bx
     };
     bool ychunk = false;                // this chunk is a recurrent chunk of a yielding item
     unsigned yseen = 0;                 // the partner's state word, requested one check ago
-    auto gs_row = [&](const int gt_row) {
-        gs_fetch(aP4, 0, 0);
-        gs_tap(std::integral_constant<int, 0>{}, gt_row + 1);
-        gs_tap(std::integral_constant<int, 1>{}, gt_row + 2);
-        gs_tap(std::integral_constant<int, 2>{}, gt_row + 3);
-        gs_tap(std::integral_constant<int, 3>{}, gt_row + 4);
-        gs_tap(std::integral_constant<int, 4>{}, gt_row + 5);
+    auto gs_row = [&](auto blk, const int gt_row) {
+        gs_fetch(blk, aP4, 0, 0);
+        gs_tap(blk, std::integral_constant<int, 0>{}, gt_row + 1);
+        gs_tap(blk, std::integral_constant<int, 1>{}, gt_row + 2);
+        gs_tap(blk, std::integral_constant<int, 2>{}, gt_row + 3);
+        gs_tap(blk, std::integral_constant<int, 3>{}, gt_row + 4);
+        gs_tap(blk, std::integral_constant<int, 4>{}, gt_row + 5);
     };
-
-    if constexpr (kInLaunch) VF_TRACE_EVT(TR_MFMAS, (unsigned long long)(25 * K8 * 4 * MR));
+    // pad skip: the variants of the edge kernel rows (wave-uniform; the first and last row are peeled off the loop of full
+    // rows, so that loop stays the single straight-line body it was).  (readfirstlane: keeps the row counter - and through it
+    // the weight loads' scalar offset - provably uniform for the compiler)
+    const int v_top = __builtin_amdgcn_readfirstlane(MR == 4 ? gs_row_variant(live_rows & 15u, 0) : GS_ROW_ALL);
+    const int v_bot = __builtin_amdgcn_readfirstlane(MR == 4 ? gs_row_variant((live_rows >> 16) & 15u, 4) : GS_ROW_ALL);
+    const int ky_begin = __builtin_amdgcn_readfirstlane(v_top == GS_ROW_ALL ? 0 : 1);
+    const int ky_end = __builtin_amdgcn_readfirstlane(v_bot == GS_ROW_ALL ? 5 : 4);
+#ifdef VF_TRACE
+    if constexpr (kInLaunch) {
+        unsigned blocks = 0;            // row blocks x kernel rows this item multiplies per chunk
+#pragma unroll
+        for (int ky = 0; ky < 5; ++ky) {
+            const int v = gs_row_variant((live_rows >> (4 * ky)) & 15u, ky);
+            blocks += MR == 4 ? (unsigned)(gs_row_end(v) - gs_row_first(v)) : (unsigned)MR;
+        }
+        VF_TRACE_EVT(TR_MFMAS, (unsigned long long)(5 * K8 * 4 * blocks));
+    }
+#endif
     __builtin_amdgcn_s_setprio(0);
     const f32x4 *a4 = reinterpret_cast<const f32x4 *>(smem);
     bool pf = false;                    // batch 0 of this chunk was requested under the previous K loop
@@ -293,12 +358,29 @@ __device__ __forceinline__ void conv_lstm_gsplit2_tile(const PT &p, const int bx
         if (pf) issue_batch(chunk_src(ci + 1), 0, pv);
         if constexpr (kInLaunch) VF_TRACE_EVT(TR_KLOOP);
         ychunk = yielding && ci < p.seg[0].nchunk;
-        for (int ky = 0; ky < 5; ++ky) {
+        // kernel row ky on the row blocks blk; with none, only the weight slice of the next row's first tap is requested
+        // (the first three k8 blocks, in place of the slice of this row that the last row requested; the fourth is
+        // requested inside the next row, as always)
+        auto row = [&](const int ky, auto blk) {
             if (ychunk) yseen = yield_peek_issue(yword);
 #pragma unroll
             for (int m = 0; m < MR; ++m) ar[m] = a4 + ab4[m] + ky * LW * 9;
-            gs_row(ci * 25 + ky * 5);
+            if constexpr (decltype(blk)::M1 > decltype(blk)::M0) gs_row(blk, ci * 25 + ky * 5);
+            else {
+#pragma unroll
+                for (int q_ = 0; q_ < 3; ++q_) gs_loadq(q_, ci * 25 + ky * 5 + 5);
+            }
             if (ychunk) yield_to_partner(yword, yseen, ybudget);
+        };
+        if constexpr (MR == 4) {
+            if (v_top == GS_ROW_FROM1) row(0, GsBlocks<1, 4>{});
+            else if (v_top == GS_ROW_NONE) row(0, GsBlocks<0, 0>{});
+        }
+        for (int ky = ky_begin; ky < ky_end; ++ky) row(ky, GsBlocks<0, GSZ>{});
+        if constexpr (MR == 4) {
+            if (v_bot == GS_ROW_TO3) row(4, GsBlocks<0, 3>{});
+            else if (v_bot == GS_ROW_TO2) row(4, GsBlocks<0, 2>{});
+            else if (v_bot == GS_ROW_NONE) row(4, GsBlocks<0, 0>{});
         }
     }
     __builtin_amdgcn_s_setprio(2);

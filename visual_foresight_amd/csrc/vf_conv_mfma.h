@@ -192,6 +192,9 @@ struct ConvParams {
     // gate-split tile only: first channel chunk of the K loop.  A conv-LSTM's recurrent input is all zeros at the first step
     // of a rollout - its chunks (segment 0) contribute nothing and are skipped (arch 3; 0 = every chunk)
     int chunk_begin;
+    // gate-split 128-row tile only: skip the row blocks of a kernel row whose every product multiplies zero padding
+    // (vf_conv_gsplit.h, "pad skip"; vf_handle::pad_skip, VF_PAD_SKIP=0 turns it off)
+    int pad_skip;
 };
 
 constexpr unsigned kLateSpinLimit = 1u << 26;   // polls before a mid-item wait gives up (as kSpinLimit)

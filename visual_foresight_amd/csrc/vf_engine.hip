@@ -567,6 +567,8 @@ struct vf_handle {
     bool fuse_top = true;               // vf_set_fuse_top: top transposed conv + compositing as one item (vf_fused_top.h)
     bool fuse_pair = true;              // ... and enc2 + enc3 as one item (conv_pair_epilogue); follows vf_set_fuse_top
     bool wt_publish = VF_WT_DEFAULT != 0;   // conv-LSTM tiles publish write-through (ConvParams::wt_out, no release fence)
+    bool pad_skip = true;               // the gate-split tile leaves out kernel rows that read only padding (ConvParams::pad_skip;
+                                        // VF_PAD_SKIP=0 at vf_create runs the full K loop - same bits, for A/B runs and tests)
     int yield_budget = -1;              // cooperative CU priority ("yielding", vf_conv_mfma.h): polls an early-started conv-LSTM
                                         // item may spend yielding to its CU partner; 0 = off, -1 = by batch size (yield_for)
     bool pair_allowed = true;           // (-DVF_DEBUG_KNOBS: VF_FUSE_PAIR=0, read once in vf_create)
@@ -827,7 +829,7 @@ struct SegArg {
     const float *gamma, *beta; int gamma_mod; int relu;
 };
 
-static ConvParams make_params(const ConvLayer &l, const LayerW &w, int B, const SegArg &s0, const SegArg *s1) {
+static ConvParams make_params(const ConvLayer &l, const LayerW &w, int B, const SegArg &s0, const SegArg *s1, bool pad_skip) {
     ConvParams p;
     memset(&p, 0, sizeof(p));
     const SegArg *sa[2] = {&s0, s1};
@@ -849,7 +851,43 @@ static ConvParams make_params(const ConvLayer &l, const LayerW &w, int B, const 
     p.chunks_per_split = l.chunks_per_split; p.n_valid = l.n_valid;
     p.stats_nparts = l.stats_nparts;    // row stride of p.stats; the conv-LSTM plans overwrite it with st_rows[k]
     p.tile_variant = l.prec == 1 ? 1 : 0;
+    p.pad_skip = pad_skip ? 1 : 0;
     return p;
+}
+
+// Products the gate-split tile leaves out per rollout phase of B samples (pad skip, vf_conv_gsplit.h): the in-image output
+// pixels of the row blocks a kernel row skips, times that row's five taps - the same ballots and variant choice as the
+// device, per workgroup.  Counted as (pixel, kernel row) pairs; every pair is 5 x (input channels) x 4 Cout products.
+static double gs_pad_skipped_pairs(const ConvLayer &l, int B) {
+    if (!l.gs_v2) return 0.0;
+    auto per_wg = [&](int n_here, int ty0, int tx0) {
+        unsigned bits[128], live[5] = {0, 0, 0, 0, 0};
+        for (int row = 0; row < 128; ++row) {
+            const int img = row / l.RPI, rem = row - img * l.RPI;
+            bits[row] = vf::gs_live_rows(img, rem, rem / l.TW, n_here, l.TH, l.TW, ty0, tx0, l.Hout, l.Wout, l.Hin);
+            for (int ky = 0; ky < 5; ++ky)
+                if ((bits[row] >> ky) & 1u) live[ky] |= 1u << (row / 32);
+        }
+        double pairs = 0.0;
+        for (int ky = 0; ky < 5; ++ky) {
+            const int v = vf::gs_row_variant(live[ky], ky);
+            for (int row = 0; row < 128; ++row) {
+                const int m = row / 32;
+                // (a pixel of the image reads it at kernel row 2 at least: bits != 0 is "in the image")
+                if (bits[row] != 0u && (m < vf::gs_row_first(v) || m >= vf::gs_row_end(v))) pairs += 1.0;
+            }
+        }
+        return pairs;
+    };
+    double pairs = 0.0;
+    if (l.NI == 1) {
+        for (int ty = 0; ty < l.tilesY; ++ty)
+            for (int tx = 0; tx < l.tilesX; ++tx) pairs += B * per_wg(1, ty * l.TH, tx * l.TW);
+    } else {
+        pairs += (B / l.NI) * per_wg(l.NI, 0, 0);
+        if (B % l.NI) pairs += per_wg(B % l.NI, 0, 0);
+    }
+    return pairs;
 }
 
 }  // namespace vf
@@ -1146,6 +1184,7 @@ int vf_create(const vf_config *cfg, vf_handle **out) {
     vf_handle *h = new vf_handle();
     made = h;
     h->cfg = *cfg;
+    if (const char *e = getenv("VF_PAD_SKIP")) h->pad_skip = atoi(e) != 0;     // (A/B and bit-identity tests; read once)
     h->ncam = std::max(1, cfg->ncam);
     h->n_draws = std::max(1, cfg->n_draws);
     h->cfg.ncam = h->ncam; h->cfg.n_draws = h->n_draws;
@@ -1445,7 +1484,8 @@ struct LaunchSink {
                 int r = launch_conv_t<4, EPI_LSTM>(l, p, st);
                 VF_HIP_CHECK(hipEventRecord(h->ev_pool[h->ev_used + 1], st));
                 h->ev_used += 2;
-                h->prof_flops += 2.0 * p.B * l.Hout * l.Wout * 25.0 * (l.segC[0] + l.segC[1]) * 4.0 * l.Cout;
+                h->prof_flops += 2.0 * (p.B * l.Hout * l.Wout * 25.0 - (p.pad_skip ? 5.0 * gs_pad_skipped_pairs(l, p.B) : 0.0)) *
+                                 (l.segC[0] + l.segC[1]) * 4.0 * l.Cout;
                 return r;
             }
             case PH_CONV_RELU: return launch_conv_t<1, EPI_BIAS_RELU>(l, p, st);
@@ -1618,8 +1658,10 @@ struct ScheduleSink {
         max_lds = std::max(max_lds, l.lds_bytes);
         const double rows = (double)p.B * l.Hout * l.Wout;
         const double taps = l.mode == PACK_CONVT ? 9.0 / 4.0 * 4.0 : (double)l.KH * l.KW;   // real taps
+        // (executed products: less the kernel rows the gate-split tile skips, ConvParams::pad_skip)
+        const double skipped = p.pad_skip && (type == PH_LSTM || type == PH_GATES_RAW) ? 5.0 * gs_pad_skipped_pairs(l, p.B) : 0.0;
         if (!l.first_valu)      // (the first conv runs on the vector ALUs: not matrix work, not counted)
-            flops += 2.0 * rows * taps * (l.segC[0] + (l.nseg > 1 ? l.segC[1] : 0) - p.chunk_begin * l.KC) *
+            flops += 2.0 * (rows * taps - skipped) * (l.segC[0] + (l.nseg > 1 ? l.segC[1] : 0) - p.chunk_begin * l.KC) *
                      (l.mode == PACK_LSTM ? 4.0 : (l.mode == PACK_PLAIN ? (double)l.G : 1.0)) * l.Cout;
         return add(P, P.gx * P.gy * l.nsplit, P.whole ? 1 : p.B, deps);
     }
@@ -1718,7 +1760,7 @@ static int emit_rollout(vf_handle *h, int view, const BatchView &v, const BatchV
     const int *L = kLstmSizes;
     const int lh[7] = {H2, H2, H4, H4, H8, H4, H2}, lw[7] = {W2, W2, W4, W4, W8, W4, W2};
     auto params = [&](const ConvLayer &l, int Bp, const SegArg &s0, const SegArg *s1) {
-        return make_params(l, vd.lw[l.id], Bp, s0, s1);
+        return make_params(l, vd.lw[l.id], Bp, s0, s1, h->pad_skip);
     };
 
     // tile plan of conv-LSTM k for a phase of Bp samples: the 256-row plan once the phase has many more items than

@@ -563,7 +563,7 @@ static int emit_rollout_s3(vf_handle *h, int view, int B, const float *d_actions
     auto plain = [](const float *ptr, long long bs) {
         SegArg a; memset(&a, 0, sizeof(a)); a.ptr = ptr; a.bstride = bs; a.gamma_mod = 1; return a;
     };
-    auto params = [&](const ConvLayer &l, const SegArg &s0, const SegArg *s1) { return make_params(l, vd.lw[l.id], B, s0, s1); };
+    auto params = [&](const ConvLayer &l, const SegArg &s0, const SegArg *s1) { return make_params(l, vd.lw[l.id], B, s0, s1, h->pad_skip); };
     auto ew_base = [&](int op, int gx, int spi) {
         EwParams e; memset(&e, 0, sizeof(e)); e.op = op; e.B = B; e.gx = gx; e.spi = spi; return e;
     };
