@@ -114,10 +114,10 @@ def test_chunking_permutation_and_determinism():
 
 
 def test_tile_plans_are_invisible_in_the_results():
-    """The conv-LSTM tile plan follows the batch size (64 / 128 / 256 rows per workgroup: DESIGN.md 4.1).  Exact
+    """The conv-LSTM tile plan follows the batch size (32 / 64 / 128 rows per workgroup: DESIGN.md 4.1).  Exact
     LayerNorm statistics and a common K order make the choice invisible: the same 160 candidates rolled as one
-    batch (256-row tiles on the two widest layers), in chunks of 70 (128-row tiles) and in chunks of 30 (64-row
-    tiles) give identical bits, for scores and for the materialised predictions."""
+    batch, in chunks of 70 (128-row tiles) and in chunks of 30 (64-row tiles) give identical bits, for scores and
+    for the materialised predictions."""
     H = W = 64
     T, M = 3, 160
     rs = np.random.RandomState(17)

@@ -1,6 +1,6 @@
 #!/bin/bash
 # GPU box, -DVF_DEBUG_KNOBS build (build/ab/knobs.so): conv-LSTM tile plans forced per layer (VF_LSTM_MREP: one
-# character per conv-LSTM, 2 / 1 / h / q = 256 / 128 / 64 / 32 rows, anything else = automatic).
+# character per conv-LSTM, 1 / h / q = 128 / 64 / 32 rows, anything else = automatic).
 # usage: tools/sweep_plans.sh <samples> <workload> <plan> [<plan> ...]
 n=$1; wl=$2; shift 2
 export VF_LIBRARY=build/ab/knobs.so

@@ -1,8 +1,8 @@
 // vf_conv_gsplit.h - the gate-split 128-row conv-LSTM tile of the persistent rollout (round 3, final form).
 //
 // Wave w multiplies gate w's weight slice with all four row blocks of the workgroup's 128 GEMM rows (vf_conv_mfma.h has the
-// machine model and the first version, conv_tile<4, EPI_LSTM, MREP, PT, 0>, which still serves the 64-row plan and the
-// debug-only 256-row variant).  This version differs in three ways:
+// machine model and the gate-split K loop of the first version, which still serves the 64-row plan: conv_tile<4, EPI_LSTM,
+// 1, PT, -2>).  This version differs from that first version in three ways:
 //   * ONE register set for the weight slice: the k8 block q of the NEXT tap is requested into its registers as soon as
 //     this tap's MFMAs on block q have been issued (~3000 cycles before its first use) - 16 VGPRs and the two parity
 //     copies of the unrolled kernel row are gone (248 VGPRs, no spills, half the code);

@@ -702,79 +702,6 @@ __device__ __forceinline__ void conv_epilogue(const PT &p, f32x16 (&acc)[MREP][G
     }
 }
 
-// Epilogue of the row-split conv-LSTM tiles (conv_tile<4, EPI_LSTM, 1, PT, RB> with RB = 2 or 1 row blocks
-// per workgroup): wave w holds GA = RB gates (2: {i,j} or {f,o}; 1: a single gate) of row block w % RB, so
-// the gate pre-activations cross through LDS (xch: [RB][4 gates][16][64 lanes] floats, the idle weight
-// buffers) and every wave finishes 4 * RB of its row block's 16 accumulator rows with all four gates at hand.
-// Same expressions on the same values, hence the same bits, as conv_epilogue.
-template <int RB, class PT>
-__device__ __forceinline__ void lstm_split_epilogue(const PT &p, f32x16 (&acc)[1][RB], const int bx, const int by,
-                                                    long long *red, float *xch) {
-    constexpr int GA = RB;                  // gates per wave
-    constexpr int RSTEP = 4 * RB;           // accumulator rows finished per wave
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int n = lane & 31, kh = lane >> 5;
-    const int rb = wave % RB, gg = wave / RB;       // row block, gate group
-    const int cg = by;
-    const int tiles_per_img = p.tilesY * p.tilesX;
-    int bimg0, ty0, tx0, tile_id;
-    if (p.NI == 1) {
-        bimg0 = bx / tiles_per_img;
-        tile_id = bx % tiles_per_img;
-        ty0 = (tile_id / p.tilesX) * p.TH;
-        tx0 = (tile_id % p.tilesX) * p.TW;
-    } else {
-        bimg0 = bx * p.NI;
-        tile_id = 0; ty0 = 0; tx0 = 0;
-    }
-    const int ch = cg * 32 + n;
-    __syncthreads();                        // the operand tiles are no longer read: their LDS becomes xch
-#pragma unroll
-    for (int g = 0; g < GA; ++g) {
-        const int gate = gg * GA + g;
-        const float bias = p.bias[(cg * 4 + gate) * 32 + n];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) xch[((rb * 4 + gate) * 16 + r) * 64 + lane] = acc[0][g][r] + bias;
-    }
-    __syncthreads();
-    StatSumD hstat;
-    const long long img_elems = (long long)p.Hout * p.Wout * p.Cout;
-    const TileDiv div_rpi(p.RPI), div_tw(p.TW);
-    auto cells = [&](auto ni1) {
-#pragma unroll
-        for (int rr = 0; rr < RSTEP; ++rr) {
-            const int r = gg * RSTEP + rr;
-            const int row = rb * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh;
-            const LstmRowAddr a = lstm_row_addr<decltype(ni1)::value>(p, row, ch, bimg0, ty0, tx0, img_elems, div_rpi,
-                                                                      div_tw);
-            if (!a.ok) continue;
-            const float gi = xch[((rb * 4 + 0) * 16 + r) * 64 + lane], gj = xch[((rb * 4 + 1) * 16 + r) * 64 + lane];
-            const float gf = xch[((rb * 4 + 2) * 16 + r) * 64 + lane], go = xch[((rb * 4 + 3) * 16 + r) * 64 + lane];
-            float c_new, h_new;
-            lstm_cell(gi, gj, gf, go, a.cin[a.off], c_new, h_new);
-            a.cst[a.off] = c_new;
-            a.hout[a.off] = h_new;
-            hstat.add(h_new);
-        }
-    };
-    if (p.NI == 1) cells(std::true_type{}); else cells(std::false_type{});
-    const long long wsum = wave_sum(hstat.sum()), wsq = wave_sum(hstat.sumsq());
-    if (lane == 0) { red[2 * wave] = wsum; red[2 * wave + 1] = wsq; }
-    __syncthreads();
-    if (tid == 0) {
-        // wave w carries part of row block w % RB, which lies in image slot (w % RB) * 32 / RPI
-        for (int img = 0; img < p.NI; ++img) {
-            if (bimg0 + img >= p.B) continue;
-            long long su = 0, sq = 0;
-            for (int w = 0; w < 4; ++w)
-                if (((w % RB) * 32) / p.RPI == img) { su += red[2 * w]; sq += red[2 * w + 1]; }
-            long long *dst = p.stats + ((long long)(bimg0 + img) * p.stats_nparts +
-                                        (p.NI == 1 ? tile_id * p.ncg + cg : cg)) * 2;
-            dst[0] = su; dst[1] = sq;
-        }
-    }
-}
-
 // compile-time loop: f(std::integral_constant<int, 0>{}) ... f(std::integral_constant<int, N - 1>{})
 template <class F, int... I>
 __device__ __forceinline__ void static_for_impl(F &&f, std::integer_sequence<int, I...>) {
@@ -783,11 +710,11 @@ __device__ __forceinline__ void static_for_impl(F &&f, std::integer_sequence<int
 template <int N, class F>
 __device__ __forceinline__ void static_for(F &&f) { static_for_impl(f, std::make_integer_sequence<int, N>{}); }
 
-// Epilogue of the gate-split 128-row conv-LSTM tile (conv_tile<4, EPI_LSTM, 1, PT, 0>): wave w holds gate w of all four
-// row blocks.  The gate pre-activations cross through LDS (xch: [4 row blocks][4 gates][16][64 lanes] floats = 64 KiB
-// over the dead operand tile) and wave w finishes row block w with all four gates at hand; the reduction scratch lies
-// behind xch.  Same expressions on the same values, hence the same bits, as conv_epilogue.
-// (MR = 8, the 256-row tile: the same in two rounds of four row blocks - wave w finishes row blocks w and 4 + w)
+// Epilogue of the gate-split conv-LSTM tiles (vf_conv_gsplit.h: MR = 4 row blocks; conv_tile<4, EPI_LSTM, 1, PT, -2>: 2;
+// the 32-row tile: 1): wave w holds gate w of all MR row blocks.  The gate pre-activations cross through LDS (xch: [MR row
+// blocks][4 gates][16][64 lanes] floats = 64 KiB at MR 4, over the dead operand tile) and every wave finishes its part of
+// the row blocks with all four gates at hand; the reduction scratch lies behind xch.  Same expressions on the same values,
+// hence the same bits, as conv_epilogue.
 constexpr int kGsXchFloats = 4 * 4 * 16 * 64;
 // arch 2: LDS floats of a 128-row gate-split tile whose epilogue adds the conditioning biases through its class tables
 // (exchange buffer, reduction scratch, [25][128] values, [128] classes)
@@ -811,8 +738,8 @@ __device__ __forceinline__ void lstm_gsplit_epilogue(const PT &p, f32x16 (&acc)[
     }
     const int ch = cg * 32 + n;
     float *xch = smem;
-    // (the reduction scratch lies behind the part of xch this tile height uses: 16 KiB per row block of a round)
-    long long *red = reinterpret_cast<long long *>(smem + (MR < 4 ? MR : 4) * 4 * 16 * 64);
+    // (the reduction scratch lies behind the part of xch this tile height uses: 16 KiB per row block)
+    long long *red = reinterpret_cast<long long *>(smem + MR * 4 * 16 * 64);
     const bool wt = p.wt_out != 0;          // write-through publish: sc1 stores, no release fence behind them
 
     // ---- Wave w finishes row block w: 32 pixels x 32 channels.  After the exchange a lane owns FOUR pixels x FOUR
@@ -841,14 +768,15 @@ __device__ __forceinline__ void lstm_gsplit_epilogue(const PT &p, f32x16 (&acc)[
     const bool ni1 = p.NI == 1;
     const float bias = p.bias[(cg * 4 + wave) * 32 + n];
     StatSumD hstat;
-    // rounds of RBR row blocks through xch; in a round a wave finishes NK of the four 8-pixel groups of ONE row block:
-    // MR 4 / 8: row block (round * 4 + wave), all four groups; MR 2: row block (wave & 1), groups 2 (wave >> 1) + {0, 1}
-    constexpr int RBR = MR < 4 ? MR : 4, NK = RBR, ROUNDS = MR / RBR;
+    // a wave finishes NK = MR of the four 8-pixel groups of ONE row block: MR 4: row block wave, all four groups; MR 2:
+    // row block (wave & 1), groups 2 (wave >> 1) + {0, 1}; MR 1: row block 0, group wave
+    constexpr int NK = MR;
+    // (a one-pass loop: this is the loop form the tile was measured in - written straight-line, the same statements compile
+    // to a different instruction stream)
 #pragma unroll
-    for (int half = 0; half < ROUNDS; ++half) {
-        const int rbl = MR < 4 ? (wave & (RBR - 1)) : wave;                 // row block within the round
-        const int k0 = MR < 4 ? NK * (wave / RBR) : 0;                      // first pixel group of this wave
-        const int rb = half * RBR + rbl;                 // the row block this wave finishes in this round
+    for (int pass = 0; pass < 1; ++pass) {
+        const int rb = MR < 4 ? (wave & (MR - 1)) : wave;                   // the row block this wave finishes
+        const int k0 = MR < 4 ? NK * (wave / MR) : 0;                       // its first pixel group
         unsigned off_o[NK];
         f32x4 c_old[NK];
 #pragma unroll
@@ -864,7 +792,7 @@ __device__ __forceinline__ void lstm_gsplit_epilogue(const PT &p, f32x16 (&acc)[
             const unsigned off_c = ok ? (unsigned)img * cin_step + in_img : 0xFFFFFFFFu;
             c_old[k] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r_cin, off_c, 0, 0));
         }
-        __syncthreads();                    // the operand tile / the previous round's gates are no longer read
+        __syncthreads();                    // the operand tile is no longer read
         if (MR == 4 && ni1 && p.cond_bias != nullptr) {
             // arch 2, one image per 128-row tile: + the conditioning bias of each row's border class through two small LDS
             // tables behind the exchange buffer (kGsCondFloats, planned by init_layer) - this lane's 25 class values of its
@@ -885,12 +813,12 @@ __device__ __forceinline__ void lstm_gsplit_epilogue(const PT &p, f32x16 (&acc)[
             }
             __syncthreads();
 #pragma unroll
-            for (int m = 0; m < RBR; ++m)
+            for (int m = 0; m < MR; ++m)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int cl = ccls[(half * RBR + m) * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh];
+                    const int cl = ccls[m * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh];
                     const float add = cl >= 0 ? ctab[cl * 128 + wave * 32 + n] : 0.f;
-                    acc[half * RBR + m][0][r] = acc[half * RBR + m][0][r] + add;
+                    acc[m][0][r] = acc[m][0][r] + add;
                 }
         } else if (p.cond_bias != nullptr) {
             // arch 2: + the conditioning bias of each row's border class (lane = gate column wave * Cout + ch; the class
@@ -898,10 +826,10 @@ __device__ __forceinline__ void lstm_gsplit_epilogue(const PT &p, f32x16 (&acc)[
             const int C4 = 4 * p.Cout, col = wave * p.Cout + ch;
             const float *cb = p.cond_bias + (long long)bimg0 * (25 * C4) + col;
 #pragma unroll
-            for (int m = 0; m < RBR; ++m)
+            for (int m = 0; m < MR; ++m)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int row = (half * RBR + m) * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh;
+                    const int row = m * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh;
                     int img = 0, rem = row;
                     if (!ni1) { img = div_rpi.div(row); rem = row - img * p.RPI; }
                     const int yy = div_tw.div(rem);
@@ -910,16 +838,16 @@ __device__ __forceinline__ void lstm_gsplit_epilogue(const PT &p, f32x16 (&acc)[
                     const int cy = y < 2 ? y : (y >= p.Hout - 2 ? y - (p.Hout - 5) : 2);
                     const int cx = x < 2 ? x : (x >= p.Wout - 2 ? x - (p.Wout - 5) : 2);
                     const float add = ok ? cb[(long long)(img * 25 + cy * 5 + cx) * C4] : 0.f;
-                    acc[half * RBR + m][0][r] = acc[half * RBR + m][0][r] + add;
+                    acc[m][0][r] = acc[m][0][r] + add;
                 }
         }
 #pragma unroll
-        for (int m = 0; m < RBR; ++m)
+        for (int m = 0; m < MR; ++m)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) xch[((m * 4 + wave) * 16 + r) * 64 + lane] = acc[half * RBR + m][0][r] + bias;
+            for (int r = 0; r < 16; ++r) xch[((m * 4 + wave) * 16 + r) * 64 + lane] = acc[m][0][r] + bias;
         __syncthreads();
         // GEMM row R = pl + 8 k of the block sits in accumulator row r = (R & 3) + 4 (R >> 3) of lane half (R >> 2) & 1
-        const float *xw = xch + ((rbl * 4) * 16 + (pl & 3)) * 64 + 32 * ((pl >> 2) & 1) + 4 * cq;
+        const float *xw = xch + ((rb * 4) * 16 + (pl & 3)) * 64 + 32 * ((pl >> 2) & 1) + 4 * cq;
 #pragma unroll
         for (int k = 0; k < NK; ++k) {
             f32x4 gate[4], cn, hn;
@@ -942,8 +870,7 @@ __device__ __forceinline__ void lstm_gsplit_epilogue(const PT &p, f32x16 (&acc)[
             }
         }
     }
-    // exact integer reduction (the 256-row tile always holds ONE image - plan_geometry - so only the per-tile total is
-    // needed there; otherwise wave w finished (part of) row block w, or w & 1 in the 64-row tile)
+    // exact integer reduction (wave w finished (part of) row block w, w & 1 in the 64-row tile, 0 in the 32-row tile)
     const long long wsum = wave_sum(hstat.sum()), wsq = wave_sum(hstat.sumsq());
     if (lane == 0) { red[2 * wave] = wsum; red[2 * wave + 1] = wsq; }
     __syncthreads();
@@ -1123,9 +1050,9 @@ __device__ __forceinline__ void conv_pair_epilogue(const PT &p, f32x16 (&acc)[1]
 // persistent rollout kernel (vf_persistent.h).
 // MREP = MFMA row blocks (of 32 GEMM rows) per wave: the workgroup covers 4 * MREP * 32 rows.
 // PT = ConvParams (kernel argument) or ConvParams in the constant address space (persistent kernel).
-// RB < 4 (conv-LSTM, B through LDS only): the workgroup covers RB row blocks of 32 - 64 or 32 rows instead of
-// 128 - and wave w takes row block w % RB and RB of the four gates, for batches so small that the per-sample
-// dependency chain, not the throughput, bounds a rollout; same chunking and K order, i.e. the same bits.
+// RB != 4 (conv-LSTM): the tiles for batches so small that the per-sample dependency chain, not the throughput, bounds a
+// rollout - RB 1: 32 rows (one row block, wave w = gate w), RB -2: the gate-split 64-row tile (two row blocks, wave w =
+// gate w of both); same chunking and K order, i.e. the same bits.
 // epilogue of EPI_CONVT_FUSED, defined in vf_fused_top.h (it needs the compositing code)
 template <int ND, bool FIRST, int K, class PT>
 __device__ __forceinline__ void convt_fused_epilogue(const PT &p, f32x16 (&acc)[1][4], int bx, long long *red, float *smem);
@@ -1138,36 +1065,32 @@ __device__ __forceinline__ void conv_tile(const PT &p, const int bx_, const int 
     // instructions do not overlap with the issuing wave's MFMAs - tools/ubench/mfma_shadow.hip - so they are not free)
     const int bx = __builtin_amdgcn_readfirstlane(bx_), by = __builtin_amdgcn_readfirstlane(by_),
               bz = __builtin_amdgcn_readfirstlane(bz_);
-    constexpr bool SPLIT = RB == 1 || RB == 2;
     [[maybe_unused]] constexpr bool kInLaunch = !std::is_same<PT, ConvParams>::value;     // tile of the persistent rollout
-    // gate-split conv-LSTM tiles: wave w = gate w of ALL row blocks of the workgroup - RB 0: 4 * MREP row blocks (128 /
-    // 256 rows), RB -2: two row blocks (64 rows, the plan of narrow phases)
-    constexpr bool GSPLIT = RB <= 0;
-    static_assert(RB == 4 || (G == 4 && EPI == EPI_LSTM && ((SPLIT && MREP == 1) || RB == 0 || (RB == -2 && MREP == 1))),
-                  "the row-split and gate-split tiles are conv-LSTM tiles");
-    constexpr int MR = RB == 0 ? 4 * MREP : (RB < 0 ? -RB : MREP);  // MFMA row blocks (accumulator tiles along the rows) per wave
+    constexpr bool ROW32 = RB == 1;     // the 32-row conv-LSTM tile
+    constexpr bool GSPLIT = RB == -2;   // the gate-split 64-row conv-LSTM tile
+    static_assert(RB == 4 || (G == 4 && EPI == EPI_LSTM && MREP == 1 && (ROW32 || GSPLIT)),
+                  "the 32- and 64-row tiles are conv-LSTM tiles");
+    static_assert(EPI != EPI_LSTM || MREP == 1, "the conv-LSTM tiles have one row block per wave");
+    constexpr int MR = GSPLIT ? 2 : MREP;   // MFMA row blocks (accumulator tiles along the rows) per wave
     constexpr int WROWS = MR * 32;      // GEMM rows per wave
-    constexpr int GA = GSPLIT ? 1 : (SPLIT ? RB : G);   // gates (accumulator tiles along the columns) per wave
+    constexpr int GA = (GSPLIT || ROW32) ? 1 : G;   // gates (accumulator tiles along the columns) per wave
     // Where the weight operand B comes from:
-    //  * 128- and 64-row conv-LSTM tiles: through LDS - wave w fetches gate w's slice one tap ahead, all four waves
+    //  * 128-row conv-LSTM tile (RB 4): through LDS - wave w fetches gate w's slice one tap ahead, all four waves
     //    read all four gates, one barrier per tap (a quarter of the L2 loads of the direct path);
     //  * 32-row conv-LSTM tile (RB 1): every wave multiplies only ITS gate's slice, so LDS staging shares nothing
     //    and costs a barrier per tap, while a tap's 16 MFMAs are too short to cover the L2 latency of a one-tap
     //    look-ahead.  B goes straight from L2 into a register ring of one kernel ROW (5 taps x K8 float4): every
-    //    load is issued five taps before its use, no barrier inside a chunk, same K order (same bits).  (For the
-    //    64-row tile the ring measured 1-3 % slower than LDS: profiles/r03_tile_plan_sweep.txt.)
-    //  * 256-row conv-LSTM tile: straight from L2 with a one-step look-ahead (its input tile needs the LDS, and it
-    //    must keep the 32-channel chunks of the other plans so that every plan accumulates in the same K order);
+    //    load is issued five taps before its use, no barrier inside a chunk, same K order (same bits).
     //  * light layers: straight from L2 through a ring of 4 (5) K steps, see kGRing below.
-    //  * gate-split 128-row conv-LSTM tile (RB 0): wave w multiplies gate w's slice with all 128 rows, so nothing
-    //    is shared and a tap is long (64 MFMAs): the slice of the NEXT tap goes straight from L2 into registers, no
-    //    LDS staging, no barrier and no VALU instruction inside a kernel row (see the K loop).
-    constexpr bool kBRing = SPLIT && RB == 1;
-    constexpr bool kBLds = (EPI == EPI_LSTM) && MREP == 1 && !kBRing && !GSPLIT;
+    //  * gate-split 64-row conv-LSTM tile (RB -2): wave w multiplies gate w's slice with both row blocks, so nothing
+    //    is shared: the slice of the NEXT tap goes straight from L2 into registers, no LDS staging, no barrier and no
+    //    VALU instruction inside a kernel row (see the K loop).
+    constexpr bool kBRing = ROW32;
+    constexpr bool kBLds = EPI == EPI_LSTM && RB == 4;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int n = lane & 31, kh = lane >> 5;
-    const int wrow0 = GSPLIT ? 0 : (SPLIT ? (wave % RB) * 32 : wave * WROWS);     // first GEMM row of this wave
-    const int gbase = GSPLIT ? wave : (SPLIT ? (wave / RB) * GA : 0);            // first gate of this wave
+    const int wrow0 = (GSPLIT || ROW32) ? 0 : wave * WROWS;     // first GEMM row of this wave
+    const int gbase = (GSPLIT || ROW32) ? wave : 0;             // first gate of this wave
     const int KC = p.KC, KCpad = KC + 4, K8 = KC >> 3;
     const int LH = (p.TH - 1) * p.stride + p.KH, LW = (p.TW - 1) * p.stride + p.KW;
     const int tile_px = LH * LW;
@@ -1204,7 +1127,7 @@ __device__ __forceinline__ void conv_tile(const PT &p, const int bx_, const int 
     ln_table(p, bimg0, lnTab, 0, late ? 1 : 2);
     // (yielding, above: the recurrent chunks of an early-started conv-LSTM item step aside for chain-critical work of the
     // CU's other workgroup - once per kernel row, bounded per item; the small-shard tiles only)
-    [[maybe_unused]] const bool yielding = kInLaunch && EPI == EPI_LSTM && (GSPLIT || (SPLIT && RB == 1)) && late &&
+    [[maybe_unused]] const bool yielding = kInLaunch && EPI == EPI_LSTM && (GSPLIT || ROW32) && late &&
                                            p.cu_state != nullptr && p.yield_budget > 0;
     [[maybe_unused]] int ybudget = p.yield_budget;
     [[maybe_unused]] const int *yword = yielding ? cu_partner_word(p) : nullptr;
@@ -1380,14 +1303,14 @@ __device__ __forceinline__ void conv_tile(const PT &p, const int bx_, const int 
         // channel range and LayerNorm gain / offset are loop invariants.  The light layers load them once per chunk
         // (no per-element modulo and loads: -1.5 % at the C5 shard); in the conv-LSTM tiles the up-front loads cost
         // more than they save (+1.2 % at C2, measured), so those keep fetching them per element.
-        constexpr bool kHoistLn = EPI != EPI_LSTM || MREP > 1;
+        constexpr bool kHoistLn = EPI != EPI_LSTM;
         const int q = tid & (q4 - 1);
         const int c = c0 + 4 * q;
         const int nvalid = min(4, sg.C - c);
         const bool lean = vec_ok && sg.C % KC == 0;     // whole channel quads in whole chunks: the lean loop below
         [[maybe_unused]] float gam[4] = {1.f, 1.f, 1.f, 1.f}, bet[4] = {0.f, 0.f, 0.f, 0.f};
         if constexpr (kHoistLn) {
-            if (sg.ln_part && c < sg.C && !(kGbTab && lean)) {
+            if (sg.ln_part && c < sg.C) {
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const int cc = (c + j) % sg.gamma_mod;
@@ -1574,22 +1497,16 @@ __device__ __forceinline__ void conv_tile(const PT &p, const int bx_, const int 
 
         if constexpr (GSPLIT) {
             // ---- K loop of the gate-split tile (5x5 kernel, 32-channel chunks): one kernel ROW = 5 taps = 20 k8 steps
-            // of 16 MFMAs, statically unrolled.  Per step the wave reads its four A row blocks (one ds_read_b128 each,
-            // immediate offsets off four row pointers that are set up once per kernel row), one step ahead of the
-            // MFMAs that use them and across tap boundaries; per tap it issues the four buffer loads of the NEXT tap's
-            // weight slice into the idle one of two register sets (a tap is 64 MFMAs = 4096 cycles, several times the
-            // L2 latency).  No barrier, no LDS store, no VALU instruction inside a row: what a K loop costs the matrix
-            // pipe besides its MFMAs is 4 VMEM + 16 LDS issues per tap.  Same (chunk, tap, k8, j) order per output as
-            // every other plan: the same bits.
-            // (MREP 2: eight row blocks per wave, worked through in two groups of four per k8 step - a "substep" is one
-            // group's 16 MFMAs; the operands of substep s + 1 are fetched before the MFMAs of substep s are issued)
-            constexpr int GSZ = MR < 4 ? MR : 4;            // row blocks per group (the 64-row tile has one group of two)
-            constexpr int NG = MR / GSZ, NS = 4 * NG;       // row-block groups, substeps per tap
+            // of 4 x MR MFMAs, statically unrolled.  Per step the wave reads its MR A row blocks (one ds_read_b128 each,
+            // immediate offsets off MR row pointers that are set up once per kernel row), one step ahead of the MFMAs
+            // that use them and across tap boundaries; per tap it issues the four buffer loads of the NEXT tap's weight
+            // slice into the idle one of two register sets.  No barrier, no LDS store, no VALU instruction inside a row.
+            // Same (chunk, tap, k8, j) order per output as every other plan: the same bits.
             const f32x4 *ar[MR];
-            f32x4 aP4[GSZ], aQ4[GSZ];
-            auto gs_fetch = [&](f32x4 (&A_)[GSZ], const int kx, const int sub) {
+            f32x4 aP4[MR], aQ4[MR];
+            auto gs_fetch = [&](f32x4 (&A_)[MR], const int kx, const int q) {
 #pragma unroll
-                for (int m_ = 0; m_ < GSZ; ++m_) A_[m_] = ar[(sub % NG) * GSZ + m_][kx * 9 + (sub / NG) * 2];
+                for (int m_ = 0; m_ < MR; ++m_) A_[m_] = ar[m_][kx * 9 + q * 2];
             };
             auto gs_loadb = [&](f32x4 (&D_)[4], const int gt) {
                 // (unconditional: behind the item's last tap the last slice is simply fetched again - a branch around
@@ -1600,27 +1517,26 @@ __device__ __forceinline__ void conv_tile(const PT &p, const int bx_, const int 
                     D_[q_] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
                         gs_rsrc, gs_loff, so_ + (unsigned)q_ * gs_wstep_b, 0));
             };
-            // one tap: the operands of its substep 0 are already in aP; cur = this tap's weight slice, nxt <- the next tap's
+            // one tap: the operands of its k8 step 0 are already in aP; cur = this tap's weight slice, nxt <- the next tap's
             auto gs_tap = [&](auto kxc, f32x4 (&cur)[4], f32x4 (&nxt)[4], const int gt_next) {
                 constexpr int KX = decltype(kxc)::value;
-                static_for<NS>([&](auto sc) {
-                    constexpr int S = decltype(sc)::value;
-                    f32x4 (&a_cur)[GSZ] = (S & 1) ? aQ4 : aP4;
-                    f32x4 (&a_nxt)[GSZ] = (S & 1) ? aP4 : aQ4;
-                    if constexpr (S + 1 < NS) gs_fetch(a_nxt, KX, S + 1);
+                static_for<4>([&](auto qc) {
+                    constexpr int Q = decltype(qc)::value;
+                    f32x4 (&a_cur)[MR] = (Q & 1) ? aQ4 : aP4;
+                    f32x4 (&a_nxt)[MR] = (Q & 1) ? aP4 : aQ4;
+                    if constexpr (Q + 1 < 4) gs_fetch(a_nxt, KX, Q + 1);
                     else if constexpr (KX < 4) gs_fetch(a_nxt, KX + 1, 0);
                     __builtin_amdgcn_sched_barrier(0);
-                    if constexpr (S == 0) {
+                    if constexpr (Q == 0) {
                         gs_loadb(nxt, gt_next);
                         __builtin_amdgcn_sched_barrier(0);
                     }
-                    const f32x4 bq = cur[S / NG];
+                    const f32x4 bq = cur[Q];
 #pragma unroll
                     for (int j_ = 0; j_ < 4; ++j_) {
 #pragma unroll
-                        for (int m_ = 0; m_ < GSZ; ++m_)
-                            acc[(S % NG) * GSZ + m_][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(
-                                a_cur[m_][j_], bq[j_], acc[(S % NG) * GSZ + m_][0], 0, 0, 0);
+                        for (int m_ = 0; m_ < MR; ++m_)
+                            acc[m_][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a_cur[m_][j_], bq[j_], acc[m_][0], 0, 0, 0);
                     }
                     __builtin_amdgcn_sched_barrier(0);
                 });
@@ -1646,7 +1562,7 @@ __device__ __forceinline__ void conv_tile(const PT &p, const int bx_, const int 
             }
         } else if constexpr (kBLds) {
           if (K8 == 4) {
-            // ---- K loop, B through LDS, 32-channel chunks (every conv-LSTM plan of vf_engine.hip): the k8 steps are
+            // ---- K loop, B through LDS, 32-channel chunks (the 128-row conv-LSTM plans of vf_engine.hip): the k8 steps are
             // unrolled with immediate LDS offsets and the next tap's weight slice comes through a raw buffer load
             // (lane offset in one VGPR, tap offset in an SGPR), so a tap costs three VALU instructions besides its 64
             // MFMAs.  A wave's own VALU / VMEM instructions do not overlap with its MFMAs (each costs the matrix pipe
@@ -1740,7 +1656,7 @@ __device__ __forceinline__ void conv_tile(const PT &p, const int bx_, const int 
 #undef VF_FETCH_L
           }
         } else if constexpr (kBRing) {
-            // ---- K loop of the row-split tiles: B from the register ring, A double-buffered from LDS, no barrier
+            // ---- K loop of the 32-row tile: B from the register ring, A double-buffered from LDS, no barrier
             f32x4 aC[4], aN[4];
             const int a0 = ab4[0];
 #pragma unroll
@@ -1883,12 +1799,9 @@ __device__ __forceinline__ void conv_tile(const PT &p, const int bx_, const int 
     if constexpr (EPI == EPI_LSTM) __builtin_amdgcn_s_setprio(2);
     if constexpr (kInLaunch) VF_TRACE_EVT(TR_EPI);
     [[maybe_unused]] const unsigned long long ts2 = VF_TS_NOW();
-    // (xch = the double-buffered B area: 32 KiB at 32-channel chunks, disjoint from lnTab / red)
-    if constexpr (GSPLIT) lstm_gsplit_epilogue<MR>(p, acc, bx, by, smem);
-    // (the 32-row tile: wave w = gate w of its one row block - the gate-split exchange with one row block per round, and
-    // with it the vectorised cell update: 16-byte loads and stores instead of 48 scalar ones per lane)
-    else if constexpr (SPLIT && RB == 1) lstm_gsplit_epilogue<1>(p, acc, bx, by, smem);
-    else if constexpr (SPLIT) lstm_split_epilogue<RB>(p, acc, bx, by, red, reinterpret_cast<float *>(bsm));
+    // (the 32-row tile: wave w = gate w of its one row block - the gate-split exchange with one row block, and with it the
+    // vectorised cell update: 16-byte loads and stores instead of 48 scalar ones per lane)
+    if constexpr (GSPLIT || ROW32) lstm_gsplit_epilogue<MR>(p, acc, bx, by, smem);
     else if constexpr (is_top_fused(EPI))
         convt_fused_epilogue<((EPI - EPI_CONVT_FUSED) & 7) / 2 + 1, ((EPI - EPI_CONVT_FUSED) & 1) != 0,
                              (EPI - EPI_CONVT_FUSED) >= 8 ? 6 : 10>(p, acc, bx, red, smem);
@@ -1910,24 +1823,16 @@ VF_GLOBAL VF_LAUNCH_BOUNDS(kConvThreads, 2) void conv_mfma_kernel(const ConvPara
     conv_tile<G, EPI, MREP>(p, blockIdx.x, blockIdx.y, blockIdx.z, smem);
 }
 
-// RB = 2 / 1: the 64- / 32-row tiles
-template <int RB>
-VF_GLOBAL VF_LAUNCH_BOUNDS(kConvThreads, 2) void conv_lstm_split_kernel(const ConvParams p) {
+// the 32-row tile
+VF_GLOBAL VF_LAUNCH_BOUNDS(kConvThreads, 2) void conv_lstm_row32_kernel(const ConvParams p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    conv_tile<4, EPI_LSTM, 1, ConvParams, RB>(p, blockIdx.x, blockIdx.y, 0, smem);
+    conv_tile<4, EPI_LSTM, 1, ConvParams, 1>(p, blockIdx.x, blockIdx.y, 0, smem);
 }
 
 // the gate-split 64-row tile
 VF_GLOBAL VF_LAUNCH_BOUNDS(kConvThreads, 2) void conv_lstm_gsplit64_kernel(const ConvParams p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     conv_tile<4, EPI_LSTM, 1, ConvParams, -2>(p, blockIdx.x, blockIdx.y, 0, smem);
-}
-
-// the gate-split tiles: 128 (MREP 1) / 256 (MREP 2) rows per workgroup
-template <int MREP>
-VF_GLOBAL VF_LAUNCH_BOUNDS(kConvThreads, 2) void conv_lstm_gsplit_kernel(const ConvParams p) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    conv_tile<4, EPI_LSTM, MREP, ConvParams, 0>(p, blockIdx.x, blockIdx.y, 0, smem);
 }
 
 }  // namespace vf

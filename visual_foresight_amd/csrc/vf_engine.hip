@@ -215,14 +215,9 @@ struct ConvLayer {          // geometry only: shared by every view; the packed w
                                     // recurrent input h, which sits BEHIND the layer input x in the canonical
                                     // [x | h] channel order - the recurrent chunks lead the K order of every plan)
     int KC, nchunk[2];
-    int mrep;                       // MFMA row blocks per wave: the workgroup covers 128 * mrep rows;
-                                    // 0 / -1 = the 64- / 32-row conv-LSTM tiles (waves split rows x gates)
+    TileKind tile = TILE_CONV;      // the tile body (plan_geometry / init_layer; vf_persistent.h)
+    int mrep = 1;                   // TILE_CONV: MFMA row blocks per wave - the workgroup covers 128 * mrep rows
     int prec = 0;                   // 1: split-bf16 tile (conv-LSTM only)
-    bool first_valu = false;        // the 5 x 5 / 2 conv on the 3-channel frame as a vector-ALU tile (vf_conv_first.h; mrep 8):
-                                    // 16 x 16 output pixels per item, canonical [tap][channel][Cout] weights
-    bool gs_v2 = false;              // ... in its final form (vf_conv_gsplit.h: one rolling weight register set)
-    bool gsplit = false;            // 128-row fp32 conv-LSTM tile with 32-channel chunks: the gate-split tile (wave w =
-                                    // gate w of all four row blocks, weights from L2 into registers, no barrier per tap)
     int NI, TH, TW, RPI, tilesY, tilesX;
     int ni_cap = 0;                 // > 0: at most this many whole images per workgroup (plans for narrow phases)
     int kc_cap = 0;                 // > 0: chunk size at most this (a narrow-phase plan that shares the regular plan's packed weights)
@@ -231,7 +226,7 @@ struct ConvLayer {          // geometry only: shared by every view; the packed w
     int stats_nparts;               // partial sums this layer's epilogue writes per sample
     size_t lds_bytes;
     size_t packed_w() const {       // floats of the packed fp32 weights (pack_weights)
-        if (first_valu) return (size_t)KH * KW * segC[0] * Cout;
+        if (tile == TILE_FIRST_VALU) return (size_t)KH * KW * segC[0] * Cout;   // canonical [tap][channel][Cout]
         return (size_t)(nchunk[0] + nchunk[1]) * KH * KW * (KC / 8) * 2 * ((size_t)ncg * G * 32) * 4;
     }
     size_t packed_w16() const {     // bf16 values of the 3-plane split weights (pack_weights_bf16x3)
@@ -256,7 +251,7 @@ static size_t conv_lds_bytes(const ConvLayer &l, int KC) {
     const int LH = (l.TH - 1) * l.stride + l.KH, LW = (l.TW - 1) * l.stride + l.KW;
     // A tile + LayerNorm table + reduction scratch (+ for 4-gate layers the double-buffered
     // per-tap B blocks: 2 x KC/8 x [4 gates][64 lanes] float4)
-    const size_t b_lds = (l.mode == PACK_LSTM && l.mrep <= 1) ? (size_t)2 * (KC / 8) * 4 * 64 * 16 : 0;
+    const size_t b_lds = l.mode == PACK_LSTM ? (size_t)2 * (KC / 8) * 4 * 64 * 16 : 0;
     // conv-LSTM tiles: LayerNorm gain / offset of every input channel (conv_tile's gbTab)
     const size_t gb_lds = l.mode == PACK_LSTM ? (size_t)2 * round_up(l.segC[0] + (l.nseg > 1 ? l.segC[1] : 0), 4) * 4 : 0;
     const size_t need = ((size_t)l.NI * LH * LW * (KC + 4) + 4 * (size_t)l.NI) * 4 + 64 + gb_lds + b_lds;
@@ -264,19 +259,23 @@ static size_t conv_lds_bytes(const ConvLayer &l, int KC) {
     return std::max(need, (size_t)vf::kEpiVecFloats * 4 + 64);
 }
 
-// choose tile shape and chunk size for a layer whose GEMM row grid is Hout x Wout
-static void plan_geometry(ConvLayer &l, bool needs_stats, bool one_pixel_images) {
-    const int rows = l.mrep == 0 ? 64 : (l.mrep < 0 ? 32 : 128 * l.mrep), wrows = l.mrep <= 0 ? 32 : 32 * l.mrep;
+// choose tile body, tile shape and chunk size for a layer whose GEMM row grid is Hout x Wout and whose workgroups cover
+// `rows` GEMM rows: 128 or 256 (the generic tile, one or two row blocks per wave); a conv-LSTM 128, 64 or 32
+static void plan_geometry(ConvLayer &l, int rows, bool needs_stats, bool one_pixel_images) {
+    l.tile = TILE_CONV; l.mrep = rows / 128;
+    if (l.mode == PACK_LSTM) {
+        l.mrep = 1;
+        if (l.prec == 1) { l.tile = TILE_LSTM_BF16X6; rows = 128; }
+        else l.tile = rows == 64 ? TILE_LSTM_GS64 : (rows == 32 ? TILE_LSTM_ROW32 : TILE_LSTM_GS128);
+    }
+    const int wrows = std::max(32, rows / 4);
     if (one_pixel_images) {         // FC: every sample is a 1x1 image with many channels
         l.TH = l.TW = 1; l.tilesY = l.tilesX = 1; l.RPI = 1; l.NI = rows;
     } else {
         l.TW = std::min(l.Wout, 32);
         // the gate-split 128-row conv-LSTM tile (vf_conv_gsplit.h): 8 x 16 output pixels have a smaller halo than 4 x 32
         // (240 instead of 288 staged pixels per chunk)
-        if (l.mode == PACK_LSTM && l.prec == 0 && l.mrep == 1 && l.KH == 5 && l.KW == 5) l.TW = std::min(l.Wout, 16);
-#ifdef VF_DEBUG_KNOBS
-        if (const char *e = getenv("VF_TILE_W")) l.TW = std::min(l.Wout, std::max(8, atoi(e)));
-#endif
+        if (l.tile == TILE_LSTM_GS128 && l.KH == 5 && l.KW == 5) l.TW = std::min(l.Wout, 16);
         l.TH = std::min(l.Hout, rows / l.TW);
         l.tilesX = (l.Wout + l.TW - 1) / l.TW;
         l.tilesY = (l.Hout + l.TH - 1) / l.TH;
@@ -295,45 +294,24 @@ static void plan_geometry(ConvLayer &l, bool needs_stats, bool one_pixel_images)
     while (KC > 8 && (KC > round_up(maxC, 8) || conv_lds_bytes(l, KC) > 78 * 1024 || (l.kc_cap > 0 && KC > l.kc_cap) ||
                       l.segC[0] % KC || (l.nseg > 1 && l.segC[1] % KC)))
         KC >>= 1;
-    if (l.prec == 1) KC = kBfKC;        // the split-bf16 tile stages 16-channel chunks
+    if (l.tile == TILE_LSTM_BF16X6) KC = kBfKC;        // the split-bf16 tile stages 16-channel chunks
     l.KC = KC;
     for (int s = 0; s < 2; ++s) l.nchunk[s] = s < l.nseg ? (l.segC[s] + KC - 1) / KC : 0;
     l.lds_bytes = conv_lds_bytes(l, KC);
-    // (the device code also has the 256-row variant - conv_lstm_gsplit_kernel<2>, eight row blocks per wave - but its
-    // 128 accumulator registers + two weight sets + two operand sets spill inside the K loop: 75.1 vs 67.1 ms at C2,
-    // so 256-row plans keep the weights-from-L2 tile; VF_GSPLIT256=1 in a -DVF_DEBUG_KNOBS build selects it)
-    bool gs256 = false;
-#ifdef VF_DEBUG_KNOBS
-    if (const char *e = getenv("VF_GSPLIT256")) gs256 = atoi(e) != 0;
-#endif
-    bool gs64 = true;
-#ifdef VF_DEBUG_KNOBS
-    if (const char *e = getenv("VF_GSPLIT64")) gs64 = atoi(e) != 0;
-#endif
-    l.gsplit = l.mode == PACK_LSTM && (l.mrep == 1 || (gs64 && l.mrep == 0) || (gs256 && l.mrep == 2 && l.NI == 1)) &&
-               l.prec == 0 && KC == 32 && l.KH == 5 && l.KW == 5;
-    l.gs_v2 = false;
-    if (l.gsplit) {
+    const int LH = (l.TH - 1) * l.stride + l.KH, LW = (l.TW - 1) * l.stride + l.KW;
+    // the gate-split tiles (wave w = gate w of all row blocks, weights from L2 into registers, no barrier per tap) take
+    // 32-channel chunks of a 5 x 5 kernel, and the 128-row one stages ten elements per thread at most: a 128-row plan it
+    // cannot stage (none of the shipped networks has one) takes the tile with its weights through LDS.  (The 64- and
+    // 32-row plans are only used with 32-channel chunks: half_ok / quarter_ok in cdna_create.)
+    const bool gs_ok = KC == 32 && l.KH == 5 && l.KW == 5;
+    if (l.tile == TILE_LSTM_GS128 && !(gs_ok && l.stride == 1 && (size_t)l.NI * LH * LW <= 320)) l.tile = TILE_LSTM_LDS;
+    if (gs_ok && (l.tile == TILE_LSTM_GS128 || l.tile == TILE_LSTM_GS64)) {
         // no weight buffers in LDS, but the epilogue's gate exchange (64 KiB over the dead operand tile; 32 KiB for the
         // 64-row tile) + its scratch
-        const size_t b_lds = l.mrep <= 1 ? (size_t)2 * (KC / 8) * 4 * 64 * 16 : 0;
-        const int LH = (l.TH - 1) * l.stride + l.KH, LW = (l.TW - 1) * l.stride + l.KW;
-        // the final form of the 128-row tile (vf_conv_gsplit.h) stages ten elements per thread at most
-        l.gs_v2 = l.mrep == 1 && l.stride == 1 && (size_t)l.NI * LH * LW <= 320;
-#ifdef VF_DEBUG_KNOBS
-        if (const char *e = getenv("VF_GSPLIT_V2")) l.gs_v2 = l.gs_v2 && atoi(e) != 0;
-#else
-        // production builds carry ONE 128-row gate-split tile (vf_conv_gsplit.h); a geometry it cannot stage (none of
-        // the shipped networks has one) falls back to the weights-through-LDS tile instead of the first-generation
-        // gate-split tile, which only exists in -DVF_DEBUG_KNOBS builds
-        if (l.mrep == 1 && !l.gs_v2) l.gsplit = false;
-#endif
-        if (l.gsplit) l.lds_bytes = std::max(l.lds_bytes - b_lds, (size_t)vf::kGsXchFloats * 4 + 64);
+        const size_t b_lds = (size_t)2 * (KC / 8) * 4 * 64 * 16;
+        l.lds_bytes = std::max(l.lds_bytes - b_lds, (size_t)vf::kGsXchFloats * 4 + 64);
     }
-    if (l.prec == 1) {
-        const int LH = (l.TH - 1) * l.stride + l.KH, LW = (l.TW - 1) * l.stride + l.KW;
-        l.lds_bytes = bf16x6_lds_bytes(l.NI, LH, LW);
-    }
+    if (l.tile == TILE_LSTM_BF16X6) l.lds_bytes = bf16x6_lds_bytes(l.NI, LH, LW);
     l.stats_nparts = (l.NI == 1 ? l.tilesY * l.tilesX : 1) * l.ncg;
 }
 
@@ -502,19 +480,14 @@ struct vf_handle {
     // items, each shorter - for batches whose phases do not fill the workgroup slots anyway (same packed weights,
     // same arithmetic per output)
     ConvLayer enc2_one, enc3_one, convt1_one;
-    // Second tile plan of every conv-LSTM (256 GEMM rows per workgroup, weights read straight from L2 so that
-    // the larger input tile fits the LDS with the SAME 32-channel chunks): fewer, longer items - better per
-    // FLOP once a phase has far more items than workgroup slots, worse for the per-sample dependency chain of
-    // a small batch.  Both plans accumulate every output in the same K order and LayerNorm statistics are
-    // exact integers (vf_conv_mfma.h), so the choice is invisible in the results and may follow the batch size.
-    ConvLayer lstm_big[7];
-    bool have_big = false, big_ok[7] = {false};
-    // Third and fourth plan: 64 and 32 GEMM rows per workgroup (conv_tile<..., RB = 2 / 1>), for batches so
-    // small that a rollout is bound by the per-sample dependency chain: more items, each shorter.
+    // Second and third tile plan of every conv-LSTM: 64 and 32 GEMM rows per workgroup (TILE_LSTM_GS64 / ROW32), for
+    // batches so small that a rollout is bound by the per-sample dependency chain: more items, each shorter.  Every plan
+    // accumulates every output in the same K order and LayerNorm statistics are exact integers (vf_conv_mfma.h), so the
+    // choice is invisible in the results and may follow the batch size.
     ConvLayer lstm_half[7], lstm_quarter[7];
-    bool half_ok[7] = {false}, quarter_ok[7] = {false};
+    bool small_plans = false, half_ok[7] = {false}, quarter_ok[7] = {false};
     int st_rows[7] = {0};               // LayerNorm partial-sum slots per sample of lstm k (max over its plans)
-    int mrep_override[7] = {0};         // VF_DEBUG_KNOBS: 1 / 2 / 3 (64 rows) forces a plan, 0 = automatic
+    int mrep_override[7] = {0};         // VF_DEBUG_KNOBS: 1 (128 rows) / 3 (64) / 4 (32) forces a plan, 0 = automatic
     std::vector<ConvLayer *> layers;    // in slot order
     std::vector<ViewData> views;
 
@@ -674,8 +647,8 @@ static int validate(const vf_config *c) {
 
 static void init_layer(ConvLayer &l, const char *name, PackMode mode, int Hin, int Win, int Hout, int Wout,
                        int KH, int KW, int stride, int pad, int c0, int c1, int Cout, bool stats,
-                       bool fc = false, int mrep = 1, int prec = 0, bool second_first = false, int cond_ch = 0) {
-    l.name = name; l.mode = mode; l.G = (mode == PACK_PLAIN) ? 1 : 4; l.mrep = prec == 1 ? 1 : mrep; l.prec = prec;
+                       bool fc = false, int rows = 128, int prec = 0, bool second_first = false, int cond_ch = 0) {
+    l.name = name; l.mode = mode; l.G = (mode == PACK_PLAIN) ? 1 : 4; l.prec = prec;
     l.Hin = Hin; l.Win = Win; l.Hout = Hout; l.Wout = Wout;
     l.KH = KH; l.KW = KW; l.stride = stride; l.pad = pad;
     l.segC[0] = c0; l.segC[1] = c1; l.nseg = c1 > 0 ? 2 : 1;
@@ -688,10 +661,10 @@ static void init_layer(ConvLayer &l, const char *name, PackMode mode, int Hin, i
     }                                                       //  part of the GEMM: CondParams, vf_small_kernels.h)
     l.Cout = Cout; l.ncg = (Cout + 31) / 32;
     l.nsplit = 1; l.n_valid = Cout;
-    plan_geometry(l, stats, fc);
+    plan_geometry(l, rows, stats, fc);
     l.chunks_per_split = l.nchunk[0] + l.nchunk[1];
     // (arch 2: the 128-row gate-split tile adds the conditioning biases through two LDS tables behind its exchange buffer)
-    if (cond_ch > 0 && l.gs_v2) l.lds_bytes = std::max(l.lds_bytes, (size_t)vf::kGsCondFloats * 4 + 64);
+    if (cond_ch > 0 && l.tile == TILE_LSTM_GS128) l.lds_bytes = std::max(l.lds_bytes, (size_t)vf::kGsCondFloats * 4 + 64);
     // the first conv of the encoder (3-channel frame in, exact statistics out): one thread per output pixel on the vector
     // ALUs instead of a K = 75 GEMM padded to 200 on the matrix pipe (vf_conv_first.h)
     bool first = mode == PACK_PLAIN && !fc && stats && l.nseg == 1 && c0 == vf::kFirstCin && KH == vf::kFirstK &&
@@ -700,7 +673,7 @@ static void init_layer(ConvLayer &l, const char *name, PackMode mode, int Hin, i
     if (const char *e = getenv("VF_FIRST_VALU")) first = first && atoi(e) != 0;
 #endif
     if (first) {
-        l.first_valu = true; l.mrep = 8;
+        l.tile = TILE_FIRST_VALU;
         l.TW = std::min(Wout, 16); l.TH = std::min(Hout, vf::kConvThreads / l.TW);
         l.tilesX = (Wout + l.TW - 1) / l.TW; l.tilesY = (Hout + l.TH - 1) / l.TH;
         l.NI = 1; l.RPI = l.TH * l.TW;
@@ -727,12 +700,6 @@ static int configure_kernels(vf_handle *h) {
     const size_t n = h->max_lds;
     int rc;
     if ((rc = allow_lds(&conv_mfma_kernel<4, EPI_LSTM, 1>, n))) return rc;
-#ifdef VF_DEBUG_KNOBS
-    if ((rc = allow_lds(&conv_mfma_kernel<4, EPI_LSTM, 2>, n))) return rc;
-    if ((rc = allow_lds(&conv_lstm_gsplit_kernel<1>, n))) return rc;
-    if ((rc = allow_lds(&conv_lstm_gsplit_kernel<2>, n))) return rc;
-    if ((rc = allow_lds(&conv_lstm_split_kernel<2>, n))) return rc;
-#endif
     if ((rc = allow_lds(&conv_mfma_kernel<1, EPI_BIAS_RELU, 1>, n))) return rc;
     if ((rc = allow_lds(&conv_mfma_kernel<1, EPI_RAW_STATS, 1>, n))) return rc;
     if ((rc = allow_lds(&conv_mfma_kernel<4, EPI_CONVT_RELU, 1>, n))) return rc;
@@ -741,7 +708,7 @@ static int configure_kernels(vf_handle *h) {
     if ((rc = allow_lds(&conv_lstm_bf16x6_kernel<1>, n))) return rc;
     if ((rc = allow_lds(&conv_lstm_gsplit64_kernel, n))) return rc;
     if ((rc = allow_lds(&conv_lstm_gsplit2_kernel<4>, n))) return rc;
-    if ((rc = allow_lds(&conv_lstm_split_kernel<1>, n))) return rc;
+    if ((rc = allow_lds(&conv_lstm_row32_kernel, n))) return rc;
     if ((rc = allow_lds(&conv_mfma_kernel<1, EPI_RAW, 1>, n))) return rc;
     if ((rc = allow_lds(&conv_gates_raw_kernel, n))) return rc;
     if ((rc = allow_lds(&conv_mfma_kernel<2, EPI_RAW, 1>, n))) return rc;
@@ -769,57 +736,27 @@ static int launch_conv_m(const ConvLayer &l, const ConvParams &p, hipStream_t st
     return VF_OK;
 }
 
-static int launch_lstm_split(const ConvLayer &l, const ConvParams &p, hipStream_t st) {
+// the conv-LSTM tile bodies
+static int launch_lstm(const ConvLayer &l, const ConvParams &p, hipStream_t st) {
     const int tiles = l.NI == 1 ? p.B * l.tilesY * l.tilesX : (p.B + l.NI - 1) / l.NI;
-    // (tiles no production plan selects - the first-generation gate-split tiles and the 64-row tile with its weights
-    // through LDS - are compiled into -DVF_DEBUG_KNOBS builds only; plan_geometry / vf_create never plan them otherwise)
-    if (l.gs_v2)
-        hipLaunchKernelGGL(conv_lstm_gsplit2_kernel<4>, dim3(tiles, l.ncg), dim3(kConvThreads), l.lds_bytes, st, p);
-    else if (l.gsplit && l.mrep == 0)
-        hipLaunchKernelGGL(conv_lstm_gsplit64_kernel, dim3(tiles, l.ncg), dim3(kConvThreads), l.lds_bytes, st, p);
-#ifdef VF_DEBUG_KNOBS
-    else if (l.gsplit && l.mrep == 2)
-        hipLaunchKernelGGL(conv_lstm_gsplit_kernel<2>, dim3(tiles, l.ncg), dim3(kConvThreads), l.lds_bytes, st, p);
-    else if (l.gsplit)
-        hipLaunchKernelGGL(conv_lstm_gsplit_kernel<1>, dim3(tiles, l.ncg), dim3(kConvThreads), l.lds_bytes, st, p);
-    else if (l.mrep == 0)
-        hipLaunchKernelGGL(conv_lstm_split_kernel<2>, dim3(tiles, l.ncg), dim3(kConvThreads), l.lds_bytes, st, p);
-#else
-    else if (l.gsplit || l.mrep == 0)
-        return fail(VF_ERR_INVALID, "conv-LSTM tile plan not compiled into this build (needs -DVF_DEBUG_KNOBS)");
-#endif
-    else
-        hipLaunchKernelGGL(conv_lstm_split_kernel<1>, dim3(tiles, l.ncg), dim3(kConvThreads), l.lds_bytes, st, p);
+    const dim3 grid(tiles, l.ncg);
+    switch (l.tile) {
+        case TILE_LSTM_LDS: return launch_conv_m<4, EPI_LSTM, 1>(l, p, st);
+        case TILE_LSTM_GS128: hipLaunchKernelGGL(conv_lstm_gsplit2_kernel<4>, grid, dim3(kConvThreads), l.lds_bytes, st, p); break;
+        case TILE_LSTM_GS64: hipLaunchKernelGGL(conv_lstm_gsplit64_kernel, grid, dim3(kConvThreads), l.lds_bytes, st, p); break;
+        case TILE_LSTM_ROW32: hipLaunchKernelGGL(conv_lstm_row32_kernel, grid, dim3(kConvThreads), l.lds_bytes, st, p); break;
+        case TILE_LSTM_BF16X6: hipLaunchKernelGGL(conv_lstm_bf16x6_kernel<1>, grid, dim3(kConvThreads), l.lds_bytes, st, p); break;
+        default: return fail(VF_ERR_INVALID, "internal: " + l.name + " is planned without a conv-LSTM tile");
+    }
     VF_HIP_CHECK(hipGetLastError());
     return VF_OK;
 }
 
-template <int MREP>
-static int launch_lstm_bf16x6(const ConvLayer &l, const ConvParams &p, hipStream_t st) {
-    const int tiles = l.NI == 1 ? p.B * l.tilesY * l.tilesX : (p.B + l.NI - 1) / l.NI;
-    hipLaunchKernelGGL((conv_lstm_bf16x6_kernel<MREP>), dim3(tiles, l.ncg), dim3(kConvThreads), l.lds_bytes, st, p);
-    VF_HIP_CHECK(hipGetLastError());
-    return VF_OK;
-}
-
-// which (G, EPI, MREP) instances exist: LSTM in both tile heights, the FC with 256 rows (it has
-// few rows and a long K), every other layer with 128-row tiles
+// which (G, EPI, MREP) instances of the light layers exist: the FC with 256 rows (it has few rows and a long K), every
+// other layer with 128-row tiles
 template <int G, int EPI>
 static int launch_conv_t(const ConvLayer &l, const ConvParams &p, hipStream_t st) {
-    if constexpr (EPI == EPI_LSTM) {
-        if (l.prec == 1) return launch_lstm_bf16x6<1>(l, p, st);        // 128-row tiles only
-        if (l.mrep <= 0 || l.gsplit) return launch_lstm_split(l, p, st);
-#ifdef VF_DEBUG_KNOBS
-        if (l.mrep == 2) return launch_conv_m<G, EPI, 2>(l, p, st);
-#else
-        if (l.mrep == 2) return fail(VF_ERR_INVALID, "256-row conv-LSTM plan not compiled into this build");
-#endif
-        return launch_conv_m<G, EPI, 1>(l, p, st);
-    } else if constexpr (EPI == EPI_PARTIAL) {
-        return launch_conv_m<G, EPI, 2>(l, p, st);
-    } else {
-        return launch_conv_m<G, EPI, 1>(l, p, st);
-    }
+    return launch_conv_m<G, EPI, EPI == EPI_PARTIAL ? 2 : 1>(l, p, st);
 }
 
 #endif  // VF_HOST_SELFTEST
@@ -859,7 +796,7 @@ static ConvParams make_params(const ConvLayer &l, const LayerW &w, int B, const 
 // pixels of the row blocks a kernel row skips, times that row's five taps - the same ballots and variant choice as the
 // device, per workgroup.  Counted as (pixel, kernel row) pairs; every pair is 5 x (input channels) x 4 Cout products.
 static double gs_pad_skipped_pairs(const ConvLayer &l, int B) {
-    if (!l.gs_v2) return 0.0;
+    if (l.tile != TILE_LSTM_GS128) return 0.0;
     auto per_wg = [&](int n_here, int ty0, int tx0) {
         unsigned bits[128], live[5] = {0, 0, 0, 0, 0};
         for (int row = 0; row < 128; ++row) {
@@ -947,13 +884,10 @@ static int cdna_create(vf_handle *h) {
     const int Hc = h->Hc, Wc = h->Wc;           // the three-scale core works on Hc x Wc
     const int H2 = Hc / 2, W2 = Wc / 2, H4 = Hc / 4, W4 = Wc / 4, H8 = Hc / 8, W8 = Wc / 8;
     const int *L = kLstmSizes;
-    // rows per LSTM workgroup: 128 (mrep 1) keeps items short - the per-sample dependency chain,
-    // not the MFMA rate, bounds a 200-sample rollout
-    const int lstm_mrep[7] = {1, 1, 1, 1, 1, 1, 1};
 #ifdef VF_DEBUG_KNOBS
     if (const char *e = getenv("VF_LSTM_MREP"))
-        for (int k = 0; k < 7 && e[k]; ++k)         // per layer: h = 64 rows, 1 = 128, 2 = 256, anything else automatic
-            h->mrep_override[k] = e[k] == '2' ? 2 : (e[k] == '1' ? 1 : (e[k] == 'h' ? 3 : (e[k] == 'q' ? 4 : 0)));
+        for (int k = 0; k < 7 && e[k]; ++k)         // per layer: 1 = 128 rows, h = 64, q = 32, anything else automatic
+            h->mrep_override[k] = e[k] == '1' ? 1 : (e[k] == 'h' ? 3 : (e[k] == 'q' ? 4 : 0));
 #endif
 #ifdef VF_DEBUG_KNOBS
     if (const char *e = getenv("VF_YIELD")) h->yield_budget = atoi(e);
@@ -966,17 +900,17 @@ static int cdna_create(vf_handle *h) {
     const int ccond = h->cond ? cfg->adim + cfg->sdim : 0;     // conditioning rows in every conv-LSTM's canonical weights
     if (h->savp) {
         init_layer(h->enc00, "enc00", PACK_PLAIN, H, W, Hc, Wc, 5, 5, 2, 1, 3, 0, kEnc00Ch, true);
-        init_layer(h->convt4, "convt4", PACK_CONVT, Hc, Wc, Hc, Wc, 2, 2, 1, 1, 32, kEnc00Ch, 32, true, false, 1, 0, true);
+        init_layer(h->convt4, "convt4", PACK_CONVT, Hc, Wc, Hc, Wc, 2, 2, 1, 1, 32, kEnc00Ch, 32, true, false, 128, 0, true);
     }
     init_layer(h->enc0, "enc0", PACK_PLAIN, Hc, Wc, H2, W2, 5, 5, 2, 1, h->savp ? kEnc00Ch : 3, 0, 32, true);
-    init_layer(h->lstm[0], "lstm1", PACK_LSTM, H2, W2, H2, W2, 5, 5, 1, 2, 32, L[0], L[0], true, false, lstm_mrep[0], cfg->precision, false, ccond);
-    init_layer(h->lstm[1], "lstm2", PACK_LSTM, H2, W2, H2, W2, 5, 5, 1, 2, L[0], L[1], L[1], true, false, lstm_mrep[1], cfg->precision, false, ccond);
+    init_layer(h->lstm[0], "lstm1", PACK_LSTM, H2, W2, H2, W2, 5, 5, 1, 2, 32, L[0], L[0], true, false, 128, cfg->precision, false, ccond);
+    init_layer(h->lstm[1], "lstm2", PACK_LSTM, H2, W2, H2, W2, 5, 5, 1, 2, L[0], L[1], L[1], true, false, 128, cfg->precision, false, ccond);
     init_layer(h->enc1, "enc1", PACK_PLAIN, H2, W2, H4, W4, 3, 3, 2, 0, L[1], 0, L[1], false);
-    init_layer(h->lstm[2], "lstm3", PACK_LSTM, H4, W4, H4, W4, 5, 5, 1, 2, L[1], L[2], L[2], true, false, lstm_mrep[2], cfg->precision, false, ccond);
-    init_layer(h->lstm[3], "lstm4", PACK_LSTM, H4, W4, H4, W4, 5, 5, 1, 2, L[2], L[3], L[3], true, false, lstm_mrep[3], cfg->precision, false, ccond);
+    init_layer(h->lstm[2], "lstm3", PACK_LSTM, H4, W4, H4, W4, 5, 5, 1, 2, L[1], L[2], L[2], true, false, 128, cfg->precision, false, ccond);
+    init_layer(h->lstm[3], "lstm4", PACK_LSTM, H4, W4, H4, W4, 5, 5, 1, 2, L[2], L[3], L[3], true, false, 128, cfg->precision, false, ccond);
     init_layer(h->enc2, "enc2", PACK_PLAIN, H4, W4, H8, W8, 3, 3, 2, 0, L[3], 0, L[3], false);
     init_layer(h->enc3, "enc3", PACK_PLAIN, H8, W8, H8, W8, 1, 1, 1, 0, L[3], 0, L[3], false);
-    init_layer(h->lstm[4], "lstm5", PACK_LSTM, H8, W8, H8, W8, 5, 5, 1, 2, L[3], L[4], L[4], true, false, lstm_mrep[4], cfg->precision, false, ccond);
+    init_layer(h->lstm[4], "lstm5", PACK_LSTM, H8, W8, H8, W8, 5, 5, 1, 2, L[3], L[4], L[4], true, false, 128, cfg->precision, false, ccond);
     init_layer(h->convt1, "convt1", PACK_CONVT, H8, W8, H8, W8, 2, 2, 1, 1, L[4], 0, L[4], false);
     h->enc2_one.ni_cap = h->enc3_one.ni_cap = h->convt1_one.ni_cap = 1;
     h->enc2_one.kc_cap = h->enc2.KC;   // the one-image plan of enc2 chunks like the regular one: it shares its packed weights,
@@ -985,15 +919,15 @@ static int cdna_create(vf_handle *h) {
     h->enc2_one.lds_bytes = std::max(h->enc2_one.lds_bytes, (size_t)2 * 128 * 36 * 4);     // (room for the pair's hand-over tile)
     init_layer(h->enc3_one, "enc3", PACK_PLAIN, H8, W8, H8, W8, 1, 1, 1, 0, L[3], 0, L[3], false);
     init_layer(h->convt1_one, "convt1", PACK_CONVT, H8, W8, H8, W8, 2, 2, 1, 1, L[4], 0, L[4], false);
-    init_layer(h->lstm[5], "lstm6", PACK_LSTM, H4, W4, H4, W4, 5, 5, 1, 2, L[4], L[5], L[5], true, false, lstm_mrep[5], cfg->precision, false, ccond);
+    init_layer(h->lstm[5], "lstm6", PACK_LSTM, H4, W4, H4, W4, 5, 5, 1, 2, L[4], L[5], L[5], true, false, 128, cfg->precision, false, ccond);
     const bool pub = cfg->arch == 0 && cfg->layer_spec == 1;
     h->c_t2 = pub ? L[5] + L[1] : L[5];
     h->c_top = pub ? L[6] + 32 : 32;
-    init_layer(h->convt2, "convt2", PACK_CONVT, H4, W4, H4, W4, 2, 2, 1, 1, L[5], L[1], h->c_t2, false, false, 1, 0, true);
-    init_layer(h->lstm[6], "lstm7", PACK_LSTM, H2, W2, H2, W2, 5, 5, 1, 2, h->c_t2, L[6], L[6], true, false, lstm_mrep[6], cfg->precision, false, ccond);
-    init_layer(h->convt3, "convt3", PACK_CONVT, H2, W2, H2, W2, 2, 2, 1, 1, L[6], 32, h->c_top, true, false, 1, 0, true);
+    init_layer(h->convt2, "convt2", PACK_CONVT, H4, W4, H4, W4, 2, 2, 1, 1, L[5], L[1], h->c_t2, false, false, 128, 0, true);
+    init_layer(h->lstm[6], "lstm7", PACK_LSTM, H2, W2, H2, W2, 5, 5, 1, 2, h->c_t2, L[6], L[6], true, false, 128, cfg->precision, false, ccond);
+    init_layer(h->convt3, "convt3", PACK_CONVT, H2, W2, H2, W2, 2, 2, 1, 1, L[6], 32, h->c_top, true, false, 128, 0, true);
     // CDNA FC as a K-split GEMM over 1x1 "images"
-    init_layer(h->fc, "cdna", PACK_PLAIN, 1, 1, 1, 1, 1, 1, 1, 0, H8 * W8 * L[4], 0, kTaps * h->K, false, true, 2);
+    init_layer(h->fc, "cdna", PACK_PLAIN, 1, 1, 1, 1, 1, 1, 1, 0, H8 * W8 * L[4], 0, kTaps * h->K, false, true, 256);
     {
         ConvLayer &f = h->fc;
         const int total = f.nchunk[0];
@@ -1003,35 +937,24 @@ static int cdna_create(vf_handle *h) {
         f.n_valid = kTaps * h->K;
         // the persistent schedule's plan: same packed weights, same chunks and splits, 128 rows x all column groups
         h->fc_wide = f;
-        h->fc_wide.mrep = 7; h->fc_wide.NI = kFcRows; h->fc_wide.lds_bytes = fc_wide_lds_bytes();
+        h->fc_wide.tile = TILE_FC_WIDE; h->fc_wide.NI = kFcRows; h->fc_wide.lds_bytes = fc_wide_lds_bytes();
         h->fc_wide_ok = f.KC == 32 && f.ncg <= kFcGroups && f.nseg == 1 && f.segC[0] % 32 == 0;
     }
     h->layers = {&h->enc0, &h->lstm[0], &h->lstm[1], &h->enc1, &h->lstm[2], &h->lstm[3], &h->enc2, &h->enc3,
                  &h->lstm[4], &h->convt1, &h->lstm[5], &h->convt2, &h->lstm[6], &h->convt3, &h->fc};
     if (h->savp) { h->layers.push_back(&h->enc00); h->layers.push_back(&h->convt4); }
-    h->have_big = cfg->precision == 0;      // the split-bf16 tile has 128 rows only
+    h->small_plans = cfg->precision == 0;   // the split-bf16 tile has 128 rows only
     for (int k = 0; k < 7; ++k) {
         h->st_rows[k] = h->lstm[k].stats_nparts;
-        if (!h->have_big) continue;
+        if (!h->small_plans) continue;
         const ConvLayer &sm = h->lstm[k];
-        init_layer(h->lstm_big[k], sm.name.c_str(), PACK_LSTM, sm.Hin, sm.Win, sm.Hout, sm.Wout, 5, 5, 1, 2, sm.segC[1],
-                   sm.segC[0], sm.Cout, true, false, 2, 0, false, ccond);
         // same chunking = same K order per output (bit-identical results) and the same packed weights
-#ifdef VF_DEBUG_KNOBS
-        h->big_ok[k] = h->lstm_big[k].KC == sm.KC;
-#else
-        h->big_ok[k] = false;       // the 256-row tile lost to the 128-row gate-split tile at every batch size (round 3): debug builds only
-#endif
-        if (h->big_ok[k]) h->st_rows[k] = std::max(h->st_rows[k], h->lstm_big[k].stats_nparts);
         init_layer(h->lstm_half[k], sm.name.c_str(), PACK_LSTM, sm.Hin, sm.Win, sm.Hout, sm.Wout, 5, 5, 1, 2, sm.segC[1],
-                   sm.segC[0], sm.Cout, true, false, 0, 0, false, ccond);
+                   sm.segC[0], sm.Cout, true, false, 64, 0, false, ccond);
         h->half_ok[k] = h->lstm_half[k].KC == sm.KC && sm.KC == 32;
-#ifndef VF_DEBUG_KNOBS
-        h->half_ok[k] = h->half_ok[k] && h->lstm_half[k].gsplit;     // the only 64-row tile of a production build
-#endif
         if (h->half_ok[k]) h->st_rows[k] = std::max(h->st_rows[k], h->lstm_half[k].stats_nparts);
         init_layer(h->lstm_quarter[k], sm.name.c_str(), PACK_LSTM, sm.Hin, sm.Win, sm.Hout, sm.Wout, 5, 5, 1, 2,
-                   sm.segC[1], sm.segC[0], sm.Cout, true, false, -1, 0, false, ccond);
+                   sm.segC[1], sm.segC[0], sm.Cout, true, false, 32, 0, false, ccond);
         h->quarter_ok[k] = h->lstm_quarter[k].KC == sm.KC && sm.KC == 32;
         if (h->quarter_ok[k]) h->st_rows[k] = std::max(h->st_rows[k], h->lstm_quarter[k].stats_nparts);
     }
@@ -1043,9 +966,8 @@ static int cdna_create(vf_handle *h) {
     h->enc2_one.id = h->enc2.id; h->enc3_one.id = h->enc3.id; h->convt1_one.id = h->convt1.id;   // shared packed weights
     h->fc_wide.id = h->fc.id;
     for (int k = 0; k < 7; ++k)
-        if (h->have_big) {
-            h->lstm_big[k].id = h->lstm_half[k].id = h->lstm_quarter[k].id = h->lstm[k].id;    // shared packed weights
-            if (h->big_ok[k]) h->max_lds = std::max(h->max_lds, h->lstm_big[k].lds_bytes);
+        if (h->small_plans) {
+            h->lstm_half[k].id = h->lstm_quarter[k].id = h->lstm[k].id;    // shared packed weights
             if (h->half_ok[k]) h->max_lds = std::max(h->max_lds, h->lstm_half[k].lds_bytes);
             if (h->quarter_ok[k]) h->max_lds = std::max(h->max_lds, h->lstm_quarter[k].lds_bytes);
         }
@@ -1306,7 +1228,7 @@ int vf_load_weights(vf_handle *h, const float *blob_all, size_t n_floats) {
                 // only the enc2 rows go through the GEMM; the action/state rows become a per-sample bias
                 wp = pack_weights(l, blob + w->offset, 1, 1, w->shape[2], w->shape[3]);
                 bp = pack_bias(l, blob + b->offset);
-            } else if (l.first_valu) {      // canonical [5][5][3][Cout] as it is
+            } else if (l.tile == TILE_FIRST_VALU) {      // canonical [5][5][3][Cout] as it is
                 wp.assign(blob + w->offset, blob + w->offset + w->size());
                 bp = pack_bias(l, blob + b->offset);
             } else {
@@ -1474,14 +1396,14 @@ struct LaunchSink {
     int conv(int type, const ConvLayer &l, const ConvParams &p, std::initializer_list<int>) {
         switch (type) {
             case PH_LSTM: {
-                if (!h->profiling) return launch_conv_t<4, EPI_LSTM>(l, p, st);
+                if (!h->profiling) return launch_lstm(l, p, st);
                 while (h->ev_pool.size() < h->ev_used + 2) {
                     hipEvent_t e;
                     VF_HIP_CHECK(hipEventCreate(&e));
                     h->ev_pool.push_back(e);
                 }
                 VF_HIP_CHECK(hipEventRecord(h->ev_pool[h->ev_used], st));
-                int r = launch_conv_t<4, EPI_LSTM>(l, p, st);
+                int r = launch_lstm(l, p, st);
                 VF_HIP_CHECK(hipEventRecord(h->ev_pool[h->ev_used + 1], st));
                 h->ev_used += 2;
                 h->prof_flops += 2.0 * (p.B * l.Hout * l.Wout * 25.0 - (p.pad_skip ? 5.0 * gs_pad_skipped_pairs(l, p.B) : 0.0)) *
@@ -1490,7 +1412,7 @@ struct LaunchSink {
             }
             case PH_CONV_RELU: return launch_conv_t<1, EPI_BIAS_RELU>(l, p, st);
             case PH_CONV_RAW:
-                if (l.first_valu) {
+                if (l.tile == TILE_FIRST_VALU) {
                     const dim3 grid(p.B * l.tilesY * l.tilesX);
                     if (l.Cout == 16) hipLaunchKernelGGL(conv_first_kernel<16>, grid, dim3(kConvThreads), l.lds_bytes, st, p);
                     else hipLaunchKernelGGL(conv_first_kernel<32>, grid, dim3(kConvThreads), l.lds_bytes, st, p);
@@ -1651,16 +1573,16 @@ struct ScheduleSink {
         P.NI = l.NI; P.tiles_per_img = l.tilesY * l.tilesX;
         P.gx = l.NI == 1 ? p.B * P.tiles_per_img : (p.B + l.NI - 1) / l.NI;
         P.gy = l.ncg;
-        if (type == PH_FC_PARTIAL && l.mrep == 7) P.gy = 1;     // all column groups in one item (vf_fc_tile.h)
+        if (l.tile == TILE_FC_WIDE) P.gy = 1;     // all column groups in one item (vf_fc_tile.h)
         P.whole = type == PH_FC_PARTIAL;
-        P.mrep = l.gsplit ? (l.mrep == 2 ? 4 : (l.mrep == 0 ? 5 : (l.gs_v2 ? 6 : 3))) : l.mrep;
+        P.tile = l.tile; P.mrep = l.mrep;
         P.prec = p.tile_variant;
         max_lds = std::max(max_lds, l.lds_bytes);
         const double rows = (double)p.B * l.Hout * l.Wout;
         const double taps = l.mode == PACK_CONVT ? 9.0 / 4.0 * 4.0 : (double)l.KH * l.KW;   // real taps
         // (executed products: less the kernel rows the gate-split tile skips, ConvParams::pad_skip)
         const double skipped = p.pad_skip && (type == PH_LSTM || type == PH_GATES_RAW) ? 5.0 * gs_pad_skipped_pairs(l, p.B) : 0.0;
-        if (!l.first_valu)      // (the first conv runs on the vector ALUs: not matrix work, not counted)
+        if (l.tile != TILE_FIRST_VALU)      // (the first conv runs on the vector ALUs: not matrix work, not counted)
             flops += 2.0 * (rows * taps - skipped) * (l.segC[0] + (l.nseg > 1 ? l.segC[1] : 0) - p.chunk_begin * l.KC) *
                      (l.mode == PACK_LSTM ? 4.0 : (l.mode == PACK_PLAIN ? (double)l.G : 1.0)) * l.Cout;
         return add(P, P.gx * P.gy * l.nsplit, P.whole ? 1 : p.B, deps);
@@ -1763,28 +1685,22 @@ static int emit_rollout(vf_handle *h, int view, const BatchView &v, const BatchV
         return make_params(l, vd.lw[l.id], Bp, s0, s1, h->pad_skip);
     };
 
-    // tile plan of conv-LSTM k for a phase of Bp samples: the 256-row plan once the phase has many more items than
-    // the chip has workgroup slots (everything from ~500 64x64-samples on; the two widest layers from ~150)
+    // tile plan of conv-LSTM k for a phase of Bp samples: the 64- or 32-row plan once the phase has too few items to fill
+    // the chip's workgroup slots, the 128-row plan otherwise
     auto lstm_plan = [&](int k, int Bp) -> const ConvLayer & {
-        if (!h->have_big) return h->lstm[k];
+        if (!h->small_plans) return h->lstm[k];
         // Cost model of one phase on S = 2 x n_cu workgroup slots, fitted to the per-item times of the persistent
         // launch (profiles/r02_phase_stats_*.txt, r03_tile_plan_sweep.txt): an item of a plan with `rows` GEMM rows
         // costs d = fixed + slope * K microseconds (K = taps x input channels), a phase of n items takes about
         // max(d, n * d / S) - the per-sample chain, or the slot time.  The plan with the smallest estimate wins; within
-        // 15 % the larger tile is kept (fewer items: less scheduling, staging and epilogue work per FLOP).  With the
-        // early start of the conv-LSTM items (recurrent half under the previous layer) the larger tiles pay off at
-        // smaller batches than they used to: at 125 samples lstm1/2/7 take 256 rows (500 items, one round of slots)
-        // instead of 128 (1000 items), 55.5 -> 52.6 ms per rollout.
+        // 15 % the larger tile is kept (fewer items: less scheduling, staging and epilogue work per FLOP).  (A 256-row
+        // plan lost to the 128-row gate-split tile at every batch size from 100 to 1000 samples,
+        // profiles/r03_plan_sweep_gsplit.txt, and is retired: EXPERIMENTS.md.)
         const ConvLayer &mid = h->lstm[k];
         const double K = 25.0 * (mid.segC[0] + mid.segC[1]);
         const double S = 2.0 * h->n_cu;
         struct Cand { int want; const ConvLayer *l; double fixed, slope; };
-        // (round 3: the 128-row tile is the gate-split one now - 0.91 of the matrix pipe with the CU to itself against
-        // 0.84 for the 256-row tile, tools/trace_cu.py - and wins at every batch size from 100 to 1000 samples,
-        // profiles/r03_plan_sweep_gsplit.txt; the 256-row entry is priced so that the 15 % preference for the larger tile below
-        // no longer selects it)
-        const Cand cands[4] = {{2, h->big_ok[k] ? &h->lstm_big[k] : nullptr, 50.0, 0.300},
-                               {1, &mid, 33.0, 0.114},
+        const Cand cands[3] = {{1, &mid, 33.0, 0.114},
                                {3, h->half_ok[k] ? &h->lstm_half[k] : nullptr, 30.0, 0.057},
                                {4, h->quarter_ok[k] ? &h->lstm_quarter[k] : nullptr, 28.0, 0.030}};
         int want = 1;
@@ -1798,7 +1714,6 @@ static int emit_rollout(vf_handle *h, int view, const BatchView &v, const BatchV
             if (best == 0.0 || t < 0.85 * best) { best = t; want = c.want; }
         }
         if (h->mrep_override[k]) want = h->mrep_override[k];
-        if (want == 2 && h->big_ok[k]) return h->lstm_big[k];
         if (want == 4 && h->quarter_ok[k]) return h->lstm_quarter[k];
         if (want >= 3 && h->half_ok[k]) return h->lstm_half[k];
         return h->lstm[k];
@@ -2086,7 +2001,7 @@ static int emit_rollout(vf_handle *h, int view, const BatchView &v, const BatchV
 
 // Write-through publish (ConvParams::wt_out: the item bumps its completion counters WITHOUT a release fence) is only sound
 // for a tile ALL of whose global stores are sc1 / agent-scope atomic stores.  This is the one place that knows which
-// (phase type, tile plan, output width) combinations dispatch such an epilogue on the device (vf_persistent.h's switch,
+// (phase type, tile kind, output width) combinations dispatch such an epilogue on the device (vf_persistent.h's switch,
 // conv_epilogue's kVec predicate, lstm_gsplit_epilogue / gates_raw_epilogue): build_schedule derives wt_out from it - never
 // from the phase type alone - and vf_selftest_schedule re-checks every phase against the restated conditions.
 static bool wt_epilogue(const PhaseDesc &P) {
@@ -2097,15 +2012,17 @@ static bool wt_epilogue(const PhaseDesc &P) {
             if (P.ew.op == EW_INORM || P.ew.op == EW_INCELL || P.ew.op == EW_UPSAMPLE) return true;
             return P.ew.op == EW_TOP3 && P.ew.top.H % kSumBlockH == 0 && P.ew.top.W % kSumBlockW == 0;
         case PH_LSTM:           // gate-split 128- / 64-row tiles and the 32-row tile (lstm_gsplit_epilogue), exact fp32
-            return P.prec == 0 && (P.mrep == 6 || P.mrep == 5 || P.mrep == -1);
+            return (VF_WT_DEFAULT & 1) != 0 &&
+                   (P.tile == TILE_LSTM_GS128 || P.tile == TILE_LSTM_GS64 || P.tile == TILE_LSTM_ROW32);
         case PH_CONV_RELU: case PH_CONV_RAW: case PH_CONVT_RELU: case PH_CONVT_RAW:
             // conv_epilogue's vectorised form: one row block per wave, whole channel quads; the vector-ALU first conv
-            // (mrep 8, vf_conv_first.h: Cout / 4 16-byte stores per pixel + an atomic-store partial)
-            return (VF_WT_DEFAULT & 2) != 0 && (P.mrep == 1 || (P.type == PH_CONV_RAW && P.mrep == 8)) && P.conv.Cout % 4 == 0;
+            // (vf_conv_first.h: Cout / 4 16-byte stores per pixel + an atomic-store partial)
+            return (VF_WT_DEFAULT & 2) != 0 && P.conv.Cout % 4 == 0 &&
+                   ((P.tile == TILE_CONV && P.mrep == 1) || (P.type == PH_CONV_RAW && P.tile == TILE_FIRST_VALU));
         case PH_CONV_RAW3: case PH_CONV_RAW3G2: case PH_CONV_RAW3G4:     // EPI_RAW is vectorised for one and two row blocks per wave
-            return (VF_WT_DEFAULT & 2) != 0 && (P.mrep == 1 || P.mrep == 2) && P.conv.Cout % 4 == 0;
-        case PH_GATES_RAW:      // gates_raw_epilogue: sixteen 16-byte stores per lane, nothing else
-            return true;
+            return (VF_WT_DEFAULT & 2) != 0 && P.tile == TILE_CONV && (P.mrep == 1 || P.mrep == 2) && P.conv.Cout % 4 == 0;
+        case PH_GATES_RAW:      // gates_raw_epilogue (the gate-split 128-row tile): sixteen 16-byte stores per lane, nothing else
+            return (VF_WT_DEFAULT & 1) != 0;
         case PH_TOP_FUSED:      // fused_top_body: blocks turned over in LDS into 16-byte stores, partials and sums as atomic stores
             return (VF_WT_DEFAULT & 2) != 0;
         default:
@@ -2150,13 +2067,6 @@ static int build_schedule(vf_handle *h, int B, bool skip_shared, BuiltSchedule &
     int ticket = 0;
     for (PhaseDesc &P : out.phases) { P.first_ticket = ticket; ticket += P.n_items; }
     out.items = ticket;
-#ifndef VF_DEBUG_KNOBS
-    // the persistent kernel of a production build carries the tiles 6 / 5 / -1 / 1 only (vf_persistent.h)
-    for (const PhaseDesc &P : out.phases)
-        if (P.type == PH_LSTM && P.prec == 0 && !(P.mrep == 6 || P.mrep == 5 || P.mrep == -1 || P.mrep == 1))
-            return fail(VF_ERR_INVALID, "conv-LSTM tile plan " + std::to_string(P.mrep) +
-                                            " is not compiled into this build (needs -DVF_DEBUG_KNOBS)");
-#endif
     // Deal every phase's items to the XCD queues (vf_persistent.h): item = (unit * q_inner + inner) * q_gy + cg
     // goes to queue (unit % (nq / q_gy)) * q_gy + cg.  unit = sample (or sample group) of the item, inner = its
     // tile within the sample, cg = output-channel group.  Launches too small to occupy every XCD keep one queue.
@@ -2269,11 +2179,13 @@ extern "C" int vf_selftest_schedule(vf_handle *h, int32_t B, int32_t skip_shared
         }
         // a write-through item must be one whose every store is a 16-byte sc1 store (restated here, not read from wt_epilogue)
         if (P.conv.wt_out != 0) {
-            const bool lstm_vec = P.type == PH_LSTM && P.prec == 0 && (P.mrep == 6 || P.mrep == 5 || P.mrep == -1);
+            const bool lstm_vec = P.type == PH_LSTM &&
+                                  (P.tile == TILE_LSTM_GS128 || P.tile == TILE_LSTM_GS64 || P.tile == TILE_LSTM_ROW32);
             const bool light_vec = P.type >= PH_CONV_RELU && P.type <= PH_CONVT_RAW && P.conv.Cout % 4 == 0 &&
-                                   (P.mrep == 1 || (P.mrep == 8 && P.type == PH_CONV_RAW && (P.conv.Cout == 16 || P.conv.Cout == 32)));
+                                   ((P.tile == TILE_CONV && P.mrep == 1) ||
+                                    (P.tile == TILE_FIRST_VALU && P.type == PH_CONV_RAW && (P.conv.Cout == 16 || P.conv.Cout == 32)));
             const bool raw3_vec = (P.type == PH_CONV_RAW3 || P.type == PH_CONV_RAW3G2 || P.type == PH_CONV_RAW3G4) &&
-                                  (P.mrep == 1 || P.mrep == 2) && P.conv.Cout % 4 == 0;
+                                  P.tile == TILE_CONV && (P.mrep == 1 || P.mrep == 2) && P.conv.Cout % 4 == 0;
             if (!(lstm_vec || light_vec || raw3_vec || P.type == PH_GATES_RAW || P.type == PH_TOP_FUSED))
                 return fail(VF_ERR_INVALID, "phase " + std::to_string(i) + ": write-through publish on a tile with plain stores");
         }

@@ -185,9 +185,9 @@ static int s3_cpi(int HW, int C) {
 }
 
 // 256-row tiles (two MFMA row blocks per wave: every weight load feeds two blocks) for every conv whose image supplies the rows
-static int s3_mrep(int ho, int wo, int C) {
+static int s3_rows(int ho, int wo, int C) {
     (void)C;
-    return ho * wo >= 256 ? 2 : 1;
+    return ho * wo >= 256 ? 256 : 128;
 }
 
 static int s3_create(vf_handle *h) {
@@ -206,20 +206,20 @@ static int s3_create(vf_handle *h) {
         // Layers with few channels at 64 x 64 pixels and more (the first encoder conv, the last decoder conv, the heads) are
         // dominated by per-item overhead - a 128-row item is ~4 us of MFMAs in 11 - 27 us: they take 256-row tiles (two row
         // blocks per wave, conv_tile<.., EPI_RAW, 2>): half the items, the same arithmetic per output
-        int mrep = s3_mrep(l.ho, l.wo, l.C);
+        const int rows = s3_rows(l.ho, l.wo, l.C);
         if (!l.dec) {
             // conv k x k / 1 + 2x2 average pool = ONE (k + 1) x (k + 1) / 2 convolution with the box-filtered kernel
             // (its stride-2 input tile is four times the output tile: the 256-row plan only where it keeps the chunk size)
             const int p = (l.k - 1) / 2;
-            auto plan = [&](const int mr) {
-                if (i == 0) init_layer(l.conv, nm.c_str(), PACK_PLAIN, l.hi, l.wi, l.ho, l.wo, l.k + 1, l.k + 1, 2, p, 3, 3, l.C, false, false, mr);
-                else init_layer(l.conv, nm.c_str(), PACK_PLAIN, l.hi, l.wi, l.ho, l.wo, l.k + 1, l.k + 1, 2, p, l.cin, 0, l.C, false, false, mr);
+            auto plan = [&](const int r) {
+                if (i == 0) init_layer(l.conv, nm.c_str(), PACK_PLAIN, l.hi, l.wi, l.ho, l.wo, l.k + 1, l.k + 1, 2, p, 3, 3, l.C, false, false, r);
+                else init_layer(l.conv, nm.c_str(), PACK_PLAIN, l.hi, l.wi, l.ho, l.wo, l.k + 1, l.k + 1, 2, p, l.cin, 0, l.C, false, false, r);
             };
-            plan(1);
+            plan(128);
             const int kc1 = l.conv.KC;
-            if (mrep == 2) { plan(2); if (l.conv.KC != kc1) plan(1); }
+            if (rows == 256) { plan(256); if (l.conv.KC != kc1) plan(128); }
         } else {
-            init_layer(l.conv, nm.c_str(), PACK_PLAIN, l.ho, l.wo, l.ho, l.wo, 3, 3, 1, 1, l.cin, 0, l.C, false, false, mrep);
+            init_layer(l.conv, nm.c_str(), PACK_PLAIN, l.ho, l.wo, l.ho, l.wo, 3, 3, 1, 1, l.cin, 0, l.C, false, false, rows);
             const int cq = l.cin / 4;
             l.up_rows = std::max(1, std::min(l.ho, 24576 / (l.wo * cq)));
             l.up_items = (l.ho + l.up_rows - 1) / l.up_rows;
@@ -236,9 +236,9 @@ static int s3_create(vf_handle *h) {
             if (G == 4 && l.conv.mrep != 1) {       // four accumulator tiles per row block: 128-row items
                 if (!l.dec) {
                     const int p = (l.k - 1) / 2;
-                    init_layer(l.conv, nm.c_str(), PACK_PLAIN, l.hi, l.wi, l.ho, l.wo, l.k + 1, l.k + 1, 2, p, l.cin, 0, l.C, false, false, 1);
+                    init_layer(l.conv, nm.c_str(), PACK_PLAIN, l.hi, l.wi, l.ho, l.wo, l.k + 1, l.k + 1, 2, p, l.cin, 0, l.C, false, false, 128);
                 } else {
-                    init_layer(l.conv, nm.c_str(), PACK_PLAIN, l.ho, l.wo, l.ho, l.wo, 3, 3, 1, 1, l.cin, 0, l.C, false, false, 1);
+                    init_layer(l.conv, nm.c_str(), PACK_PLAIN, l.ho, l.wo, l.ho, l.wo, 3, 3, 1, 1, l.cin, 0, l.C, false, false, 128);
                 }
                 if (l.conv.KC != l.conv_pack.KC) l.conv = l.conv_pack, G = 2;      // (keep the packed chunking)
                 else l.conv_pack = l.conv;
@@ -253,9 +253,9 @@ static int s3_create(vf_handle *h) {
         l.cpi_n = s3_cpi(l.ho * l.wo, l.C);
         if (l.rnn) {
             const std::string ln = "h" + std::to_string(i) + "l";
-            init_layer(l.lstm, ln.c_str(), PACK_LSTM, l.ho, l.wo, l.ho, l.wo, 5, 5, 1, 2, l.C, l.C, l.C, true, false, 1, 0,
+            init_layer(l.lstm, ln.c_str(), PACK_LSTM, l.ho, l.wo, l.ho, l.wo, 5, 5, 1, 2, l.C, l.C, l.C, true, false, 128, 0,
                        false, s->ncond);
-            if (!l.lstm.gs_v2 || l.lstm.KC != 32)
+            if (l.lstm.tile != TILE_LSTM_GS128 || l.lstm.KC != 32)
                 return fail(VF_ERR_INVALID, "arch 3: conv-LSTM " + ln + " does not fit the gate-split tile");
             h->layers.push_back(&l.lstm);
             l.cpi_c = s3_cpi(l.ho * l.wo, l.C);
@@ -263,17 +263,17 @@ static int s3_create(vf_handle *h) {
         if (l.cin % 4 && i > 0) return fail(VF_ERR_INVALID, "arch 3: channel counts must be multiples of 4");
     }
     const int top = s->L[s->nl - 1].C;
-    const int mrep_top = s3_mrep(H, W, kS3Ngf);
-    init_layer(s->hmhs_pack, "hmhs", PACK_PLAIN, H, W, H, W, 3, 3, 1, 1, top, 0, 2 * kS3Ngf, false, false, mrep_top);
+    const int rows_top = s3_rows(H, W, kS3Ngf);
+    init_layer(s->hmhs_pack, "hmhs", PACK_PLAIN, H, W, H, W, 3, 3, 1, 1, top, 0, 2 * kS3Ngf, false, false, rows_top);
     s->hmhs = s->hmhs_pack;
     s->hmhs.G = 2; s->hmhs.ncg = 1; s->hmhs.Cout = kS3Ngf; s->hmhs.n_valid = kS3Ngf;
     if ((s->hmhs.KH * s->hmhs.KW * (s->hmhs.KC / 8)) % 2)
         return fail(VF_ERR_INVALID, "arch 3: the fused head conv needs an even number of K steps per chunk");
-    init_layer(s->scratch, "scratch", PACK_PLAIN, H, W, H, W, 3, 3, 1, 1, kS3Ngf, 0, kScrCh, false, false, mrep_top);
-    init_layer(s->masks, "masks", PACK_PLAIN, H, W, H, W, 3, 3, 1, 1, kS3Ngf, kTransCh, kMaskCh, false, false, mrep_top);
+    init_layer(s->scratch, "scratch", PACK_PLAIN, H, W, H, W, 3, 3, 1, 1, kS3Ngf, 0, kScrCh, false, false, rows_top);
+    init_layer(s->masks, "masks", PACK_PLAIN, H, W, H, W, 3, 3, 1, 1, kS3Ngf, kTransCh, kMaskCh, false, false, rows_top);
     for (ConvLayer *l : {&s->hmhs, &s->scratch, &s->masks}) h->layers.push_back(l);
     const S3Layer &bot = s->L[s->n_enc - 1];
-    init_layer(h->fc, "cdna", PACK_PLAIN, 1, 1, 1, 1, 1, 1, 1, 0, bot.ho * bot.wo * bot.C, 0, kTaps * h->K, false, true, 2);
+    init_layer(h->fc, "cdna", PACK_PLAIN, 1, 1, 1, 1, 1, 1, 1, 0, bot.ho * bot.wo * bot.C, 0, kTaps * h->K, false, true, 256);
     {
         ConvLayer &f = h->fc;
         const int total = f.nchunk[0];
@@ -282,7 +282,7 @@ static int s3_create(vf_handle *h) {
         f.nsplit = (total + f.chunks_per_split - 1) / f.chunks_per_split;
         f.n_valid = kTaps * h->K;
         h->fc_wide = f;
-        h->fc_wide.mrep = 7; h->fc_wide.NI = kFcRows; h->fc_wide.lds_bytes = fc_wide_lds_bytes();
+        h->fc_wide.tile = TILE_FC_WIDE; h->fc_wide.NI = kFcRows; h->fc_wide.lds_bytes = fc_wide_lds_bytes();
         h->fc_wide_ok = f.KC == 32 && f.ncg <= kFcGroups && f.nseg == 1 && f.segC[0] % 32 == 0;
     }
     h->layers.push_back(&h->fc);
@@ -297,7 +297,7 @@ static int s3_create(vf_handle *h) {
     for (int i = 0; i < s->nl; ++i) s->L[i].conv_pack.id = s->L[i].conv.id;
     h->max_lds = std::max(h->max_lds, h->fc_wide.lds_bytes) + 16;
     h->dedup = false;               // every sample runs every step (no context de-duplication in arch 3)
-    h->have_big = false;
+    h->small_plans = false;
     s->top_tiles = h->ntiles;
 
 #define S3_ALLOC(ptr, n)                           \

@@ -47,6 +47,21 @@ __host__ __device__ constexpr bool ph_is_conv(const int t) {
     return t <= PH_CONVT_RAW || t == PH_CONV_RAW3 || t == PH_GATES_RAW || t == PH_CONV_RAW3G2 || t == PH_CONV_RAW3G4;
 }
 
+// The tile body of a conv phase, one kind per compiled body; decided once per layer plan (plan_geometry / init_layer in
+// vf_engine.hip), read by the dispatch below, the per-layer launches and the write-through rule (wt_epilogue).
+enum TileKind : int {
+    TILE_CONV = 0,          // conv_tile<G, EPI, MREP> (vf_conv_mfma.h) with MREP = ConvLayer::mrep / PhaseDesc::mrep row blocks
+                            // per wave: every layer type but the ones below
+    TILE_LSTM_LDS,          // conv-LSTM, 128 rows, weights through LDS (conv_tile<4, EPI_LSTM, 1>): a geometry the gate-split
+                            // tile cannot stage
+    TILE_LSTM_GS128,        // conv-LSTM, gate-split 128 rows (vf_conv_gsplit.h)
+    TILE_LSTM_GS64,         // conv-LSTM, gate-split 64 rows (conv_tile<4, EPI_LSTM, 1, PT, -2>)
+    TILE_LSTM_ROW32,        // conv-LSTM, 32 rows, weights from a register ring (conv_tile<4, EPI_LSTM, 1, PT, 1>)
+    TILE_LSTM_BF16X6,       // conv-LSTM, split-bf16, 128 rows (vf_conv_bf16x6.h)
+    TILE_FC_WIDE,           // CDNA FC: all column groups in one item per (row tile, K split) (vf_fc_tile.h)
+    TILE_FIRST_VALU         // first conv of the encoder (3-channel frame, 5 x 5 / 2) on the vector ALUs (vf_conv_first.h)
+};
+
 constexpr int kMaxDeps = 3;
 constexpr int kQueues = 8;                  // one ticket queue per XCD
 constexpr int kTicketStride = 32;           // ints between ticket heads (128 B)
@@ -77,10 +92,8 @@ struct PhaseDesc {
     int B;                  // samples this phase covers
     int NI, tiles_per_img;  // conv phases: how an item maps to samples
     int whole;              // 1: completion is counted once per item on counter 0
-    int mrep;               // MFMA row blocks per wave of this conv phase (1 or 2; 0 / -1: the 64- / 32-row conv-LSTM
-                            // tiles; 3 / 4 / 5: the gate-split 128- / 256- / 64-row conv-LSTM tiles of vf_conv_mfma.h;
-                            // 6: the gate-split 128-row tile of vf_conv_gsplit.h)
-    int prec;               // conv-LSTM tile: 0 exact fp32, 1 split-bf16
+    TileKind tile;          // conv phases: the tile body
+    int prec;               // conv-LSTM tile: 0 exact fp32, 1 split-bf16 (TILE_LSTM_BF16X6)
     int view;               // camera view this phase belongs to (selects the goal pixels of PH_COMPOSITE)
     int cnt_base;
     int aux_base;           // PH_TOP_FUSED: first of the per-sample "LayerNorm partial published" counters
@@ -88,6 +101,7 @@ struct PhaseDesc {
     PhaseDep dep[kMaxDeps];
     int has_late;           // two-input conv phases: the producer of segment 1 is awaited INSIDE the item, after the chunks
     PhaseDep late;          // of segment 0 (ConvParams::late_cnt, "early start"); dep[] then only holds segment 0's producer
+    int mrep;               // TILE_CONV: MFMA row blocks per wave (1 or 2)
     ConvParams conv;
     ConvParams conv2;       // PH_CONV_PAIR: the 1x1 conv behind `conv` (conv.fuse_next points here, on the device)
     SaParams sa;
@@ -172,13 +186,8 @@ template <int G, int EPI, int MREP>
 static __device__ __noinline__ __attribute__((not_tail_called)) void conv_tile_call(const ConvParams *p, int bx, int by, int bz) {
     conv_tile<G, EPI, MREP>(const_params(p), bx, by, bz, tile_lds());
 }
-template <int RB>
-static __device__ __noinline__ __attribute__((not_tail_called)) void lstm_split_tile_call(const ConvParams *p, int bx, int by) {
-    conv_tile<4, EPI_LSTM, 1, const VF_CONST_AS ConvParams, RB>(const_params(p), bx, by, 0, tile_lds());
-}
-template <int MREP>
-static __device__ __noinline__ __attribute__((not_tail_called)) void lstm_gsplit_tile_call(const ConvParams *p, int bx, int by) {
-    conv_tile<4, EPI_LSTM, MREP, const VF_CONST_AS ConvParams, 0>(const_params(p), bx, by, 0, tile_lds());
+static __device__ __noinline__ __attribute__((not_tail_called)) void lstm_row32_tile_call(const ConvParams *p, int bx, int by) {
+    conv_tile<4, EPI_LSTM, 1, const VF_CONST_AS ConvParams, 1>(const_params(p), bx, by, 0, tile_lds());
 }
 template <int MR>
 static __device__ __noinline__ __attribute__((not_tail_called)) void lstm_gsplit2_tile_call(const ConvParams *p, int bx, int by) {
@@ -410,35 +419,26 @@ VF_GLOBAL VF_LAUNCH_BOUNDS(kConvThreads, 2) void rollout_persistent_kernel(
             const int by = local % P.gy, bx = local / P.gy;
             switch (P.type) {
                 case PH_LSTM:
-                    // Production plans (lstm_plan / plan_geometry in vf_engine.hip) select four fp32 tiles: the 128- and
-                    // 64-row gate-split tiles, the 32-row tile, and - only for a geometry the gate-split tile cannot stage
-                    // - the 128-row tile with its weights through LDS.  The tiles that lost in rounds 2-3 (first-generation
-                    // gate-split 128 / 256 rows, 256 rows from L2, 64 rows through LDS) are A/B material of
-                    // -DVF_DEBUG_KNOBS builds: compiled in here they cost the launch 33 spilled VGPRs and 924 B of scratch.
-                    if (P.prec == 1) lstm_bf16x6_tile_call<1>(&P.conv, bx, by);         // 128-row tiles only
-                    else if (P.mrep == 6) lstm_gsplit2_tile_call<4>(&P.conv, bx, by);    // gate-split 128-row tile, final form
-                    else if (P.mrep == 5) lstm_gsplit64_tile_call(&P.conv, bx, by);        // gate-split 64-row tile
-                    else if (P.mrep < 0) lstm_split_tile_call<1>(&P.conv, bx, by);
-#ifdef VF_DEBUG_KNOBS
-                    else if (P.mrep == 0) lstm_split_tile_call<2>(&P.conv, bx, by);
-                    else if (P.mrep == 3) lstm_gsplit_tile_call<1>(&P.conv, bx, by);       // gate-split 128-row tile, first form
-                    else if (P.mrep == 4) lstm_gsplit_tile_call<2>(&P.conv, bx, by);       // gate-split 256-row tile
-                    else if (P.mrep == 2) conv_tile_call<4, EPI_LSTM, 2>(&P.conv, bx, by, 0);
-#endif
-                    else conv_tile_call<4, EPI_LSTM, 1>(&P.conv, bx, by, 0);
+                    // (the conv-LSTM plans of lstm_plan / plan_geometry in vf_engine.hip: the 128- and 64-row gate-split
+                    // tiles, the 32-row tile, the split-bf16 tile and - only for a geometry the gate-split tile cannot
+                    // stage - the 128-row tile with its weights through LDS)
+                    if (P.tile == TILE_LSTM_BF16X6) lstm_bf16x6_tile_call<1>(&P.conv, bx, by);
+                    else if (P.tile == TILE_LSTM_GS128) lstm_gsplit2_tile_call<4>(&P.conv, bx, by);
+                    else if (P.tile == TILE_LSTM_GS64) lstm_gsplit64_tile_call(&P.conv, bx, by);
+                    else if (P.tile == TILE_LSTM_ROW32) lstm_row32_tile_call(&P.conv, bx, by);
+                    else conv_tile_call<4, EPI_LSTM, 1>(&P.conv, bx, by, 0);        // TILE_LSTM_LDS
                     break;
                 case PH_CONV_RELU: conv_tile_call<1, EPI_BIAS_RELU, 1>(&P.conv, bx, by, 0); break;
                 case PH_CONV_RAW:
-                    // (mrep 8: the first conv of the encoder - 3-channel frame, 5 x 5 / 2 - on the vector ALUs, vf_conv_first.h)
-                    if (P.mrep == 8) { if (P.conv.Cout == 16) conv_first_tile_call<16>(&P.conv, bx); else conv_first_tile_call<32>(&P.conv, bx); }
+                    if (P.tile == TILE_FIRST_VALU) { if (P.conv.Cout == 16) conv_first_tile_call<16>(&P.conv, bx); else conv_first_tile_call<32>(&P.conv, bx); }
                     else conv_tile_call<1, EPI_RAW_STATS, 1>(&P.conv, bx, by, 0);
                     break;
                 case PH_CONVT_RELU: conv_tile_call<4, EPI_CONVT_RELU, 1>(&P.conv, bx, by, 0); break;
                 case PH_CONVT_RAW: conv_tile_call<4, EPI_CONVT_RAW_STATS, 1>(&P.conv, bx, by, 0); break;
                 case PH_FC_PARTIAL:
-                    // (mrep 7: all eight column groups in one item per (row tile, K split), vf_fc_tile.h - the plan of
-                    // every persistent schedule; the generic tile serves a geometry that one cannot hold)
-                    if (P.mrep == 7) fc_wide_tile_call(&P.conv, bx % P.gx, bx / P.gx);
+                    // (TILE_FC_WIDE is the plan of every persistent schedule; the generic tile serves a geometry that one
+                    // cannot hold)
+                    if (P.tile == TILE_FC_WIDE) fc_wide_tile_call(&P.conv, bx % P.gx, bx / P.gx);
                     else conv_tile_call<1, EPI_PARTIAL, 2>(&P.conv, bx % P.gx, by, bx / P.gx);
                     break;
                 case PH_CONV_PAIR: conv_tile_call<2, EPI_CONV_PAIR, 1>(&P.conv, bx, 0, 0); break;
