@@ -167,6 +167,24 @@ int vf_ensemble_scores(vf_handle *const *members, int32_t n_members, float lambd
                        const float *task_weights, double *d_scores, double *d_scores_per_task,
                        double *d_cost_per_step, void *stream);
 
+/* Goal-image cost (reference visual_mpc/policy/cem_controllers/goal_im_controller.py:93: CEM on the mean squared error
+ * between a predicted frame and a goal picture).  Scores the frames of the handle's LAST vf_rollout where they lie -
+ * nothing is exported or copied.  d_goal: DEVICE float32 [ncam][H][W][3], 16-byte aligned, in the scale the host wants
+ * compared with the predicted frames (which are in [0,1]).  Per rolled sequence b, view c, step t
+ *   mse[b][c][t] = mean over (row, col, channel) of (frame[b][t][c] - goal[c])^2       (float64)
+ * steps_mode 0: e[b][c] = mse[b][c][T-1], only the last predicted frames are read (unless d_cost_per_step asks for all);
+ * steps_mode 1: e[b][c] = sum_t w_t mse[b][c][t] / sum_t w_t, w = (1, ..., 1, finalweight), the weighting of vf_rollout.
+ * Then the mean over each action's n_draws sequences; score = e[.][0] if first_view_only, else the plain mean over views.
+ * d_scores float64 [B / n_draws]; d_scores_per_view float64 [B / n_draws][ncam] (may be NULL); d_cost_per_step float64
+ * [B / n_draws][ncam][T] = mse averaged over the draws (may be NULL).  The summation order of an image depends on H and W
+ * alone: a sequence's cost has the same bits in any batch, chunk or rank.  If the handle's device status is raised every
+ * output is NaN.  Enqueues two kernels on `stream` and never synchronises.  Returns VF_ERR_INVALID (nothing launched) for
+ * a NULL handle / d_goal / d_scores, a misaligned d_goal, a steps_mode other than 0 or 1, or a handle that has not
+ * rolled. */
+int vf_goal_image_scores(vf_handle *h, const float *d_goal, int32_t steps_mode, float finalweight,
+                         int32_t first_view_only, double *d_scores, double *d_scores_per_view,
+                         double *d_cost_per_step, void *stream);
+
 /* Copy the predictions of the last vf_rollout out in the reference's layout (camera axis,
  * normalised distributions).  Any destination may be NULL.  first/count select a range of rolled
  * sequences.  Replaces the gen_images/gen_distrib/gen_states fetch of

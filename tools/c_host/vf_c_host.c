@@ -4,6 +4,7 @@
  * points a non-Python maintainer of the reference's planner would bind:
  *
  *     vf_create -> vf_load_weights -> vf_set_persistent -> vf_set_context -> vf_rollout -> vf_device_status -> vf_export
+ *     -> vf_goal_image_scores (printed only)
  *
  * i.e. what `self.predictor = predictor_class(...)`, `.restore()` and `self.predictor(context, {'actions'})` +
  * `_eval_pixel_cost` do in visual_mpc/policy/cem_controllers/pixel_cost_controller.py:29-36,83-84,135-166 of the
@@ -102,7 +103,18 @@ int main(int argc, char **argv) {
     VF_CALL(vf_device_status(h, &status));
     if (status != 0) { fprintf(stderr, "device status %d\n", status); return 5; }
     if (nex > 0) VF_CALL(vf_export(h, 0, nex, d_of, d_od, d_os, st));
+    /* the goal-image cost of the same rollout (goal_im_controller.py:93), with the first context frame as the goal */
+    const size_t n_img = (size_t)H * W * 3;
+    float *goal_img = malloc(n_img * 4);
+    if (!goal_img) return 4;
+    for (size_t i = 0; i < n_img; ++i) goal_img[i] = (float)frames[i] / 255.0f;
+    void *d_gi, *d_gs;
+    if (to_device(&d_gi, goal_img, n_img * 4)) return 2;
+    HIP_OK(hipMalloc(&d_gs, (size_t)B * 8));
+    VF_CALL(vf_goal_image_scores(h, d_gi, 0, *fw, 0, d_gs, NULL, NULL, st));
     HIP_OK(hipStreamSynchronize(st));
+    double goal_score0 = 0.0;
+    HIP_OK(hipMemcpy(&goal_score0, d_gs, 8, hipMemcpyDeviceToHost));
 
     double *scores = malloc((size_t)B * 8), *per_task = malloc((size_t)B * nd * 8);
     float *of = malloc(n_of * 4 + 4), *od = malloc(n_od * 4 + 4), *os = malloc(n_os * 4 + 4);
@@ -119,6 +131,7 @@ int main(int argc, char **argv) {
     fclose(o);
     printf("vf_c_host: %d sequences x %d steps rolled through the C ABI (version %d); score[0] = %.17g\n", B, T,
            vf_abi_version(), scores[0]);
+    printf("vf_c_host: goal-image score[0] = %.17g (last predicted frame against the first context frame)\n", goal_score0);
     VF_CALL(vf_destroy(h));
     return 0;
 }

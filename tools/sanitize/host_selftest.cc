@@ -143,6 +143,21 @@ int main() {
                 std::fprintf(stderr, "schedule after failure: %s\n", vf_last_error()); rc = 1;
             }
         }
+        // vf_goal_image_scores refuses before it touches the device: NULL arguments, a bad steps_mode, a handle that has not rolled
+        if (hh) {
+            alignas(16) float goal[4];
+            double score = 0.0;
+            struct { vf_handle *h; const float *g; int mode; double *out; const char *msg; } refusals[] = {
+                {nullptr, goal, 0, &score, "null argument"}, {hh, nullptr, 0, &score, "null argument"},
+                {hh, goal, 0, nullptr, "null argument"},     {hh, goal, 2, &score, "steps_mode"},
+                {hh, goal, -1, &score, "steps_mode"},        {hh, goal, 1, &score, "not rolled"}};
+            for (const auto &c : refusals) {
+                const int r = vf_goal_image_scores(c.h, c.g, c.mode, 10.f, 0, c.out, nullptr, nullptr, nullptr);
+                if (r != VF_ERR_INVALID || std::string(vf_last_error()).find(c.msg) == std::string::npos) {
+                    std::fprintf(stderr, "vf_goal_image_scores: want refusal '%s', got rc %d '%s'\n", c.msg, r, vf_last_error()); rc = 1;
+                }
+            }
+        }
         if (hh && vf_destroy(hh)) { std::fprintf(stderr, "vf_destroy after the injected failures failed\n"); rc = 1; }
         std::printf("  injected failures (bad_alloc, std::exception, foreign) in vf_create / vf_load_weights / build_schedule: %s\n",
                     rc ? "FAILED" : "status codes returned, handle reusable");

@@ -35,6 +35,7 @@
 #include "../../include/vf_hip.h"
 #include "vf_conv_mfma.h"
 #include "vf_small_kernels.h"
+#include "vf_goal_image.h"
 #include "vf_conv_bf16x6.h"
 #include "vf_persistent.h"
 
@@ -507,6 +508,7 @@ struct vf_handle {
     float *frames_all = nullptr, *distrib_all = nullptr, *states_all = nullptr;
     double *sums = nullptr;
     long long sums_step_stride = 0, sums_view_stride = 0;
+    double *goal_mse = nullptr;         // [max_batch][ncam][T] per-image goal cost of vf_goal_image_scores (vf_goal_image.h)
 
     std::vector<AllocRec> allocs;
 
@@ -1050,6 +1052,7 @@ static int cdna_create(vf_handle *h) {
     h->sums_view_stride = (long long)Bc * ND * h->nblocks * 2;
     h->sums_step_stride = h->sums_view_stride * NV;
     VF_ALLOC(h->sums, (size_t)h->T * h->sums_step_stride);
+    VF_ALLOC(h->goal_mse, BV * h->T);
     VF_ALLOC(h->actions_buf, (size_t)Bc * h->T * cfg->adim);
     h->sched_capacity = ((size_t)h->S * 32 + 8) * NV;       // (arch 2: up to 29 phases per step)
     h->counter_capacity = ((size_t)h->S * 32 + 8) * ((size_t)Bc + 1) * NV;
@@ -2117,6 +2120,16 @@ static int build_schedule(vf_handle *h, int B, bool skip_shared, BuiltSchedule &
     return VF_OK;
 }
 
+// the refusals of vf_goal_image_scores (host work only: shared by the device build and the host self-test)
+static int goal_image_check(const vf_handle *h, const float *d_goal, int32_t steps_mode, const double *d_scores) {
+    if (!h || !d_goal || !d_scores) return fail(VF_ERR_INVALID, "null argument");
+    if (steps_mode != 0 && steps_mode != 1)
+        return fail(VF_ERR_INVALID, "steps_mode " + std::to_string(steps_mode) + " is neither 0 (last step) nor 1 (weighted)");
+    if (h->last_B < 1) return fail(VF_ERR_INVALID, "the handle has not rolled");
+    if (reinterpret_cast<uintptr_t>(d_goal) % 16) return fail(VF_ERR_INVALID, "the goal image must be 16-byte aligned");
+    return VF_OK;
+}
+
 #ifdef VF_HOST_SELFTEST
 // ------------------------------------------------------------------ host self-test hooks
 // (tools/host_selftest.cc; ASan/UBSan build).  Checks the invariants the device relies on.
@@ -2330,6 +2343,13 @@ extern "C" int vf_set_fuse_top(vf_handle *h, int32_t enable) {      // (the devi
     h->fuse_top = enable != 0;
     h->fuse_pair = enable != 0;
     return VF_OK;
+    VF_API_CATCH(int)
+}
+extern "C" int vf_goal_image_scores(vf_handle *h, const float *d_goal, int32_t steps_mode, float, int32_t, double *d_scores,
+                                    double *, double *, void *) {      // (refusal paths only: this build never rolls)
+    VF_API_TRY
+    if (int rc = goal_image_check(h, d_goal, steps_mode, d_scores)) return rc;
+    return fail(VF_ERR_HIP, "the host self-test build launches nothing");
     VF_API_CATCH(int)
 }
 #else   // ------------------------------------------------------------------ device execution
@@ -2607,6 +2627,30 @@ int vf_ensemble_scores(vf_handle *const *members, int32_t n_members, float lambd
     hipLaunchKernelGGL(ensemble_scores_kernel, dim3(n_actions), dim3(64), 0, st, em, h0->sums_step_stride,
                        h0->sums_view_stride, n_actions, h0->n_draws, h0->T, h0->ND, h0->ncam, h0->nblocks,
                        lambda_variance, finalweight, tw, d_scores, d_scores_per_task, d_cost_per_step);
+    VF_HIP_CHECK(hipGetLastError());
+    return VF_OK;
+    VF_API_CATCH(int)
+}
+
+int vf_goal_image_scores(vf_handle *h, const float *d_goal, int32_t steps_mode, float finalweight, int32_t first_view_only,
+                         double *d_scores, double *d_scores_per_view, double *d_cost_per_step, void *stream) {
+    VF_API_TRY
+    if (int rc = goal_image_check(h, d_goal, steps_mode, d_scores)) return rc;
+    VF_HIP_CHECK(hipSetDevice(h->cfg.device));
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const int B = h->last_B, T = h->T, NV = h->ncam;
+    const int n4 = h->H * h->W * 3 / 4;         // (H, W multiples of 8: an image is a whole number of 16-byte loads)
+    // only the steps the cost needs are read: the last one, unless the weighting or the per-step output wants them all
+    const bool all_steps = steps_mode == 1 || d_cost_per_step;
+    const int t0 = all_steps ? 0 : T - 1, n_steps = all_steps ? T : 1;
+    const long long view_stride = (long long)h->cfg.max_batch * T * h->H * h->W * 3;
+    hipLaunchKernelGGL(goal_mse_kernel, dim3((unsigned)(B * NV * n_steps)), dim3(kGoalThreads), 0, st, h->frames_all,
+                       view_stride, d_goal, NV, T, n4, t0, n_steps, h->goal_mse);
+    VF_HIP_CHECK(hipGetLastError());
+    const int n_actions = B / h->n_draws;
+    hipLaunchKernelGGL(goal_scores_kernel, dim3((unsigned)((n_actions + 63) / 64)), dim3(64), 0, st, h->goal_mse, n_actions,
+                       h->n_draws, NV, T, steps_mode, finalweight, first_view_only != 0, h->d_status, d_scores,
+                       d_scores_per_view, d_cost_per_step);
     VF_HIP_CHECK(hipGetLastError());
     return VF_OK;
     VF_API_CATCH(int)

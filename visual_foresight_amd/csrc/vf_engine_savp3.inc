@@ -373,6 +373,7 @@ static int s3_create(vf_handle *h) {
     h->sums_view_stride = (long long)Bc * ND * h->nblocks * 2;
     h->sums_step_stride = h->sums_view_stride * NV;
     S3_ALLOC(h->sums, (size_t)h->T * h->sums_step_stride);
+    S3_ALLOC(h->goal_mse, BV * h->T);
     S3_ALLOC(h->actions_buf, (size_t)Bc * h->T * c.adim);
     h->sched_capacity = ((size_t)h->S * 80 + 8) * NV;
     h->counter_capacity = ((size_t)h->S * 80 + 8) * ((size_t)Bc + 1) * NV;

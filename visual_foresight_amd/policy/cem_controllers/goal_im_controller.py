@@ -1,0 +1,148 @@
+"""CEM controller scoring rollouts by the mean squared error between predicted frames and a goal image.
+
+Restates the reference's ``visual_mpc/policy/cem_controllers/goal_im_controller.py`` (ctor :15-45, defaults :47-59,
+``evaluate_rollouts`` :77-143 with the cost at :93, ``act`` :229-245) at the same import path, with the same
+four-argument constructor.  Hyper-parameters: the reference's five (``verbose_img_height``, ``predictor_propagation``,
+``only_take_first_view``, ``state_append``, ``finalweight``, same defaults), the predictor ones of ``PixelCostController``
+(``predictor_class``, ``model_path``, ``vpred_batch_size``) and two of this project: ``goal_cost_steps`` (``'last'``: the
+last predicted frame, as the reference; ``'weighted'``: the time-weighted mean over all steps, ``w = (1, ..., 1,
+finalweight)``) and ``goal_image_raw`` (below).
+
+The default predictor is ``HipVPredEvaluation``: its ``score_goal_image`` reduces the frames resident on the GPU and only
+the score rows come back.  A predictor without ``score_goal_image`` is scored on the host from the ``predicted_frames``
+its ``__call__`` returns (``goal_image_cost`` below).  ``predictor_propagation`` is accepted so that reference configs
+load, and has no effect: no designated pixel is tracked (the reference's own propagation code is commented out).
+
+Departures from the reference:
+
+(a) The reference reads the goal from a hard-coded JPEG path and resizes it with OpenCV (:87-90).  Here the goal is the
+    ``goal_image`` argument of ``act`` - ``get_policy_args`` fills it by name from the observation or the agent's step
+    data - and must already have the predictor's image size: ``[ncam, H, W, 3]`` or, with one view, ``[H, W, 3]``.
+(b) The reference subtracts the goal as raw 0..255 bytes from frames in [0, 1] (:87-93, no ``/ 255``), which makes its
+    score nearly linear in ``-2 * frame * goal``.  The default here compares both in [0, 1] (a uint8 goal is scaled by
+    1/255 as context frames are); ``goal_image_raw=True`` reproduces the reference's literal arithmetic - the host simply
+    does not scale the goal, the device kernel is the same.
+(c) The reference indexes view 0 whatever ``only_take_first_view`` says (its goal-image models are single-view, where
+    both readings coincide).  Here ``only_take_first_view=False``, the reference's default, means the plain mean over
+    views, as in ``PixelCostController``.
+
+With one view and the default hyper-parameters the score is the reference's: the MSE of the last predicted frame.
+"""
+import numpy as np
+
+from .cem_base_controller import CEMBaseController
+from .pixel_cost_controller import _default_predictor_class, build_predictor
+
+
+def prepare_goal_image(goal_image, ncam, height, width, raw=False):
+    """-> ``[ncam, H, W, 3]`` in the scale it is compared in: uint8 / 255 as float32 (``raw``: the bytes' values as
+    float32, the reference's literal arithmetic); floating-point goals are taken as they are."""
+    g = np.asarray(goal_image)
+    if g.ndim == 3 and ncam == 1:
+        g = g[None]
+    if g.shape != (ncam, height, width, 3):
+        raise ValueError('goal_image must be [%d, %d, %d, 3], got %s' % (ncam, height, width, g.shape))
+    if g.dtype == np.uint8:
+        g = g.astype(np.float32)
+        return g if raw else g / np.float32(255.)
+    if not np.issubdtype(g.dtype, np.floating):
+        raise ValueError('goal_image must be uint8 or floating point, got %s' % g.dtype)
+    return g.astype(np.float32)
+
+
+def goal_image_cost(gen_images, goal, steps='last', finalweight=10., first_view_only=False):
+    """Host scoring of materialised frames ``[M, T, ncam, H, W, 3]`` against ``goal [ncam, H, W, 3]`` in float64
+    (reference :93) -> (scores [M], per view [M, ncam], per step [M, ncam, T])."""
+    if steps not in ('last', 'weighted'):
+        raise ValueError("goal_cost_steps must be 'last' or 'weighted', got %r" % (steps,))
+    diff = np.asarray(gen_images, dtype=np.float64) - np.asarray(goal, dtype=np.float64)[None, None]
+    per_step = np.transpose((diff ** 2).mean(axis=(3, 4, 5)), (0, 2, 1))                # [M, ncam, T]
+    if steps == 'last':
+        per_view = per_step[:, :, -1]
+    else:
+        t_mult = np.ones(per_step.shape[2])
+        t_mult[-1] = finalweight
+        per_view = np.sum(per_step * t_mult, axis=2) / np.sum(t_mult)
+    scores = per_view[:, 0].copy() if first_view_only else per_view.mean(axis=1)
+    return scores, per_view, per_step
+
+
+class GoalImController(CEMBaseController):
+    def __init__(self, ag_params, policyparams, gpu_id, ngpu):
+        """
+        :param ag_params: agent parameter dict (needs adim, sdim, image_height, image_width)
+        :param policyparams: policy parameter dict (overrides of the HParams defaults)
+        :param gpu_id: first GPU to use
+        :param ngpu: number of GPUs to use
+        """
+        CEMBaseController.__init__(self, ag_params, policyparams)
+        predictor_class = self._hp.predictor_class
+        if predictor_class is None:
+            predictor_class = _default_predictor_class(ag_params.get('ncam', 1))
+        horizon = self._hp.nactions * self._hp.get('repeat', 1)
+        # no designated pixel is planned on: the network carries one distribution channel, switched on at the centre
+        self.predictor = build_predictor(self, predictor_class, ag_params, gpu_id, ngpu, 1, horizon)
+        self._net_context = self.predictor.n_context
+        self._img_height, self._img_width = [ag_params['image_height'], ag_params['image_width']]
+        self._n_cam = getattr(self.predictor, 'n_cam', 1)
+        self._images = None
+        self._goal_image = None
+        self.cost_perstep = None        # [M, ncam, T] MSE of the last scoring call
+
+    def _default_hparams(self):
+        defaults = [
+            ('predictor_class', None),      # None -> HipVPredEvaluation
+            ('model_path', ''),
+            ('vpred_batch_size', 200),
+            ('verbose_img_height', 128),
+            ('predictor_propagation', False),   # accepted for config compatibility; nothing is propagated
+            ('only_take_first_view', False),
+            ('state_append', None),
+            ('finalweight', 10.),
+            ('goal_cost_steps', 'last'),        # 'last' | 'weighted'
+            ('goal_image_raw', False),          # True: the reference's unscaled 0..255 goal
+        ]
+        params = super(GoalImController, self)._default_hparams()
+        for name, value in defaults:
+            params.add_hparam(name, value)
+        return params
+
+    def evaluate_rollouts(self, actions, cem_itr):
+        hp = self._hp
+        context = {
+            "context_frames": self._images,
+            "context_actions": self._sampler.chosen_actions,
+            "context_states": self._state,
+        }
+        if hasattr(self.predictor, 'score_goal_image'):
+            scores, per_view = self.predictor.score_goal_image(
+                context, {'actions': actions}, self._goal_image, steps=hp.goal_cost_steps,
+                finalweight=hp.finalweight, first_view_only=hp.only_take_first_view)
+            self.cost_perstep = self.predictor.last_goal_cost_per_step
+        else:
+            one_hot = np.zeros((self._net_context, self._n_cam, self._img_height, self._img_width, 1), np.float32)
+            one_hot[:, :, self._img_height // 2, self._img_width // 2, :] = 1.
+            prediction = self.predictor(dict(context, context_pixel_distributions=one_hot), {'actions': actions})
+            scores, per_view, self.cost_perstep = goal_image_cost(
+                prediction['predicted_frames'], self._goal_image, hp.goal_cost_steps, hp.finalweight,
+                hp.only_take_first_view)
+        bestind = scores.argsort()[0]
+        for icam in range(per_view.shape[1]):
+            self._logger.log('best goal-image score cam{}  :{}'.format(icam, np.min(per_view[:, icam])))
+            self._logger.log('goal-image score of best traj cam{} :{}'.format(icam, per_view[bestind, icam]))
+        if self._verbose_condition(cem_itr):
+            self._logger.log('best scores itr {}: {}'.format(cem_itr, np.sort(scores)[:10]))
+        return scores
+
+    def act(self, t, i_tr, images, state, goal_image, verbose_worker=None):
+        """
+        :param t: the controller's time step
+        :param images: uint8 history ``[t+1, ncam, H, W, 3]``
+        :param state: state history ``[t+1, sdim]``
+        :param goal_image: ``[ncam, H, W, 3]`` or ``[H, W, 3]`` (one view), uint8 or float, at the predictor's size
+        """
+        self._goal_image = prepare_goal_image(goal_image, self._n_cam, self._img_height, self._img_width,
+                                              raw=self._hp.goal_image_raw)
+        self._images = images
+        self._verbose_worker = verbose_worker
+        return super(GoalImController, self).act(t, i_tr, state)

@@ -25,6 +25,30 @@ def _default_predictor_class(ncam=1):
     return HipVPredEvaluation
 
 
+def build_predictor(ctrl, predictor_class, ag_params, gpu_id, ngpu, designated_pixel_count, horizon):
+    """Construct and restore the video predictor of a CEM controller (reference ``pixel_cost_controller.py:29-36``) and
+    raise the controller's ``start_planning`` to the network's context.  Shared by the controllers that plan on
+    predicted videos (``PixelCostController`` and its variants, ``GoalImController``)."""
+    hp = ctrl._hp
+    predictor_hparams = {
+        'designated_pixel_count': designated_pixel_count,
+        'run_batch_size': min(hp.vpred_batch_size, hp.num_samples),
+    }
+    if getattr(predictor_class, 'wants_agent_params', False):
+        # the HIP predictor is shape-specialised at construction (no checkpoint json to read
+        # adim/sdim/size/T from), so it is told what the controller will ask of it
+        predictor_hparams.update(
+            adim=ctrl._adim, sdim=ctrl._sdim,
+            image_height=ag_params['image_height'], image_width=ag_params['image_width'],
+            ncam=ag_params.get('ncam', 1),
+            sequence_length=horizon + predictor_class.n_context_default)
+    predictor = predictor_class(hp.model_path, predictor_hparams, n_gpus=ngpu, first_gpu=gpu_id)
+    predictor.restore()
+    if hp.start_planning < predictor.n_context - 1:
+        hp.start_planning = predictor.n_context - 1
+    return predictor
+
+
 class PixelCostController(CEMBaseController):
     def __init__(self, ag_params, policyparams, gpu_id, ngpu):
         """
@@ -34,28 +58,12 @@ class PixelCostController(CEMBaseController):
         :param ngpu: number of GPUs to use
         """
         CEMBaseController.__init__(self, ag_params, policyparams)
-        predictor_hparams = {
-            'designated_pixel_count': self._hp.designated_pixel_count,
-            'run_batch_size': min(self._hp.vpred_batch_size, self._hp.num_samples),
-        }
         predictor_class = self._hp.predictor_class
         if predictor_class is None:
             predictor_class = self._default_predictor_class(ag_params)
-        if getattr(predictor_class, 'wants_agent_params', False):
-            # the HIP predictor is shape-specialised at construction (no checkpoint json to read
-            # adim/sdim/size/T from), so it is told what the controller will ask of it
-            predictor_hparams.update(
-                adim=self._adim, sdim=self._sdim,
-                image_height=ag_params['image_height'], image_width=ag_params['image_width'],
-                ncam=ag_params.get('ncam', 1),
-                sequence_length=self._plan_horizon() + predictor_class.n_context_default)
-        self.predictor = predictor_class(self._hp.model_path, predictor_hparams,
-                                         n_gpus=ngpu, first_gpu=gpu_id)
-        self.predictor.restore()
-
+        self.predictor = build_predictor(self, predictor_class, ag_params, gpu_id, ngpu,
+                                         self._hp.designated_pixel_count, self._plan_horizon())
         self._net_context = self.predictor.n_context
-        if self._hp.start_planning < self._net_context - 1:
-            self._hp.start_planning = self._net_context - 1
 
         self._n_desig = self._hp.designated_pixel_count
         self._img_height, self._img_width = [ag_params['image_height'], ag_params['image_width']]

@@ -138,6 +138,7 @@ class HipVPredEvaluation(object):
         self._last_M = 0
         self._last_lo = 0
         self._last_prepared = None      # (engine context, sequences, M) of the last score() / __call__
+        self.last_goal_cost_per_step = None     # [M, ncam, T] of the last score_goal_image()
         # in-process multi-GPU: this object is lane 0, the others are plain engines on the following devices
         self.gather = str(hp.get('gather', 'auto'))         # 'auto' | 'rccl' | 'host'
         if self.gather not in ('auto', 'rccl', 'host'):
@@ -328,11 +329,13 @@ class HipVPredEvaluation(object):
         """(context, actions[n]) -> (engine context, sequences[n * n_draws])."""
         return context, actions
 
-    def _score_prepared(self, context, seqs, n, goal_pix, finalweight, index_base=0, task_weights=None):
+    def _score_prepared(self, context, seqs, n, goal_pix, finalweight, index_base=0, task_weights=None,
+                        after_chunk=None):
         """Roll ``seqs [n * n_draws, T, engine adim]`` (as ``_prepare`` returns them) on this engine -> device tensors
         (scores[n], per_task[n, ncam*nd]).  ``index_base`` is the global index of the first action (what
         ``fetch_pixel_distributions`` is asked for).  Only enqueues work on this engine's device (the uploads of
-        pageable host arrays aside)."""
+        pageable host arrays aside).  ``after_chunk(c0, c1)`` runs after the rollout of actions ``[c0, c1)``, while
+        their predictions are resident (``score_goal_image`` reduces them there)."""
         torch = self._torch
         ntask = self.n_cam * self.cfg.ndesig
         nd = self.n_draws
@@ -346,6 +349,8 @@ class HipVPredEvaluation(object):
             self._rollout_chunk(local[c0 * nd:c1 * nd], goal_pix, finalweight, scores[c0:c1], per_task[c0:c1],
                                 task_weights)
             self._last_lo, self._last_M = index_base + c0, c1 - c0
+            if after_chunk is not None:
+                after_chunk(c0, c1)
         return scores, per_task
 
     def score(self, context, inputs, goal_pix, finalweight=10., only_take_first_view=False, task_weights=None):
@@ -385,6 +390,100 @@ class HipVPredEvaluation(object):
             scores_np = per_task_np[:, 0].copy()
         return scores_np, per_task_np
 
+    # ------------------------------------------------------------------ goal-image cost
+    def _check_goal_image(self, goal_image):
+        """-> float32 ``[ncam, H, W, 3]``: uint8 is scaled by 1/255 as ``get_context`` scales context frames (reference
+        ``video_prediction/pred_util.py:4-13``), floating point is taken as it is."""
+        c = self.cfg
+        g = np.asarray(goal_image)
+        if g.ndim == 3 and self.n_cam == 1:
+            g = g[None]
+        if g.shape != (self.n_cam, c.height, c.width, 3):
+            raise ValueError('goal_image must be [%d, %d, %d, 3]%s, got %s'
+                             % (self.n_cam, c.height, c.width, ' or [H, W, 3]' if self.n_cam == 1 else '', g.shape))
+        if g.dtype == np.uint8:
+            return np.ascontiguousarray(g.astype(np.float32) / np.float32(255.))
+        if not np.issubdtype(g.dtype, np.floating):
+            raise ValueError('goal_image must be uint8 or floating point, got %s' % g.dtype)
+        return np.ascontiguousarray(g, dtype=np.float32)
+
+    def _goal_rows(self, context, seqs, n, index_base, goal, mode, finalweight, first_view_only):
+        """Roll ``n`` actions on this engine and reduce every chunk's resident frames against ``goal`` ->
+        device rows ``[n, 1 + ncam + ncam * T]`` = [score | per view | cost per step]."""
+        torch, ncam, c = self._torch, self.n_cam, self.cfg
+        T = self.sequence_length - self.n_context
+        goal_dev = torch.from_numpy(goal).to(self.device)
+        rows = torch.empty((n, 1 + ncam + ncam * T), dtype=torch.float64, device=self.device)
+        bs = self.run_batch_size // self.n_draws
+        c_s = torch.empty(bs, dtype=torch.float64, device=self.device)
+        c_pv = torch.empty((bs, ncam), dtype=torch.float64, device=self.device)
+        c_cps = torch.empty((bs, ncam * T), dtype=torch.float64, device=self.device)
+
+        def reduce_chunk(c0, c1):
+            _lib.check(self._libh.vf_goal_image_scores(
+                self._handle, goal_dev.data_ptr(), mode, ctypes.c_float(finalweight), int(bool(first_view_only)),
+                c_s.data_ptr(), c_pv.data_ptr(), c_cps.data_ptr(), self._stream()))
+            k = c1 - c0
+            rows[c0:c1, 0], rows[c0:c1, 1:1 + ncam], rows[c0:c1, 1 + ncam:] = c_s[:k], c_pv[:k], c_cps[:k]
+
+        centre = np.tile(np.array([c.height // 2, c.width // 2], np.int32), (ncam, c.ndesig, 1))
+        self._score_prepared(context, seqs, n, centre, 1.0, index_base=index_base, after_chunk=reduce_chunk)
+        return rows
+
+    def score_goal_image(self, context, inputs, goal_image, steps='last', finalweight=10., first_view_only=False):
+        """Fused rollout + goal-image cost (reference ``policy/cem_controllers/goal_im_controller.py:93``): the mean
+        squared error between predicted frames and ``goal_image``, reduced on the GPU from the frames resident in the
+        engine.  Returns (scores[M], scores_per_view[M, ncam]) float64; ``last_goal_cost_per_step`` ``[M, ncam, T]``
+        keeps the per-step MSE (averaged over latent draws).
+
+        ``goal_image``: ``[ncam, H, W, 3]`` (or ``[H, W, 3]`` with one view); uint8 is scaled by 1/255 like the
+        context frames, floating point is compared as it is.  ``steps='last'`` scores the last predicted frame,
+        ``'weighted'`` the time-weighted mean with ``w = (1, ..., 1, finalweight)``.  ``first_view_only`` takes view 0's
+        cost as the score instead of the mean over views (``scores_per_view`` keeps every view).
+
+        Sharding, chunking, lanes and latent draws are those of ``score``.  The rollout entry still wants goal pixels
+        and a distribution context: the image centre is passed for both (``context_pixel_distributions`` of
+        ``context`` is not read) and its pixel scores are dropped - the price is the ``ndesig`` distribution
+        channels the network carries anyway."""
+        goal = self._check_goal_image(goal_image)
+        if steps not in ('last', 'weighted'):
+            raise ValueError("steps must be 'last' or 'weighted', got %r" % (steps,))
+        mode = 1 if steps == 'weighted' else 0
+        actions = self._check_actions(inputs['actions'])
+        M = actions.shape[0]
+        ncam, c, nd = self.n_cam, self.cfg, self.n_draws
+        T = self.sequence_length - self.n_context
+        centre = np.zeros((self.n_context, ncam, c.height, c.width, c.ndesig), np.float32)
+        centre[:, :, c.height // 2, c.width // 2, :] = 1.0
+        ctx_p, seqs = self._prepare(dict(context, context_pixel_distributions=centre), actions)
+        self._last_prepared = (ctx_p, seqs, M)
+        rank, world = _dist_info()
+        torch = self._torch
+        if self._lanes:
+            packed = []
+            for i, lane in enumerate(self._lanes):
+                lo, hi = shard_bounds(M, i, len(self._lanes))
+                with torch.cuda.device(lane.device):
+                    if hi > lo:
+                        packed.append(lane._goal_rows(ctx_p, seqs[lo * nd:hi * nd], hi - lo, lo, goal, mode, finalweight,
+                                                      first_view_only))
+                    else:
+                        lane._last_lo, lane._last_M = lo, 0
+                        packed.append(torch.empty((0, 1 + ncam + ncam * T), dtype=torch.float64, device=lane.device))
+            rows_np = self._gather_lane_rows(packed, M)
+        else:
+            lo, hi = shard_bounds(M, rank, world)
+            with torch.cuda.device(self.device):
+                rows = self._goal_rows(ctx_p, seqs[lo * nd:hi * nd], hi - lo, lo, goal, mode, finalweight,
+                                       first_view_only)
+                if world > 1:
+                    rows = all_gather_rows(rows, M)
+                rows_np = rows.cpu().numpy()
+        scores_np = np.ascontiguousarray(rows_np[:, 0])
+        self._check_scores(scores_np)
+        self.last_goal_cost_per_step = np.ascontiguousarray(rows_np[:, 1 + ncam:]).reshape(M, ncam, T)
+        return scores_np, np.ascontiguousarray(rows_np[:, 1:1 + ncam])
+
     # ------------------------------------------------------------------ in-process multi-GPU (n_gpus > 1)
     def _score_lanes(self, context, seqs, M, goal_pix, finalweight, task_weights):
         """Lane i rolls the contiguous shard ``shard_bounds(M, i, n_gpus)`` of the prepared sequences on its own
@@ -404,6 +503,11 @@ class HipVPredEvaluation(object):
                     lane._last_lo, lane._last_M = lo, 0
                     packed.append(torch.empty((0, 1 + self.n_cam * self.cfg.ndesig), dtype=torch.float64,
                                               device=lane.device))
+        rows = self._gather_lane_rows(packed, M)
+        return np.ascontiguousarray(rows[:, 0]), np.ascontiguousarray(rows[:, 1:])
+
+    def _gather_lane_rows(self, packed, M):
+        """The lanes' device rows (lane order, any width) -> all ``M`` rows on the host."""
         rows = None
         if self._use_rccl:
             try:
@@ -417,7 +521,7 @@ class HipVPredEvaluation(object):
                 self._use_rccl = False
         if rows is None:
             rows = np.concatenate([p.cpu().numpy() for p in packed], axis=0)
-        return np.ascontiguousarray(rows[:, 0]), np.ascontiguousarray(rows[:, 1:])
+        return rows
 
     def _gather_rccl(self, packed, M):
         """One grouped RCCL all-gather over the lanes' devices (padded to equal rows); lane 0's copy goes to the host."""

@@ -74,3 +74,13 @@ class StochasticHipPredictor(HipVPredEvaluation):
                 task_weights=task_weights)
         finally:
             self._z = None
+
+    def score_goal_image(self, context, inputs, goal_image, steps='last', finalweight=10., first_view_only=False):
+        T = np.asarray(inputs['actions']).shape[1]
+        self._z = self.draw_latents(T)          # as score(): one set of draws per scoring call
+        self._calls += 1
+        try:
+            return super(StochasticHipPredictor, self).score_goal_image(
+                context, inputs, goal_image, steps=steps, finalweight=finalweight, first_view_only=first_view_only)
+        finally:
+            self._z = None
