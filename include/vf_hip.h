@@ -185,6 +185,21 @@ int vf_goal_image_scores(vf_handle *h, const float *d_goal, int32_t steps_mode, 
                          int32_t first_view_only, double *d_scores, double *d_scores_per_view,
                          double *d_cost_per_step, void *stream);
 
+/* Plan visualisation (reference visual_mpc/policy/cem_controllers/pixel_cost_controller.py:88-131: the ten best plans of
+ * a CEM iteration as movies).  Renders K rolled sequences of the handle's LAST vf_rollout where they lie, so that only
+ * bytes leave the device.  d_seq: DEVICE int32 [K], indices into the rolled batch (an entry outside [0, B) is clamped
+ * into it - the host validates before the upload).  d_lut: DEVICE uint8 [256][3], any colour table.  Outputs (either
+ * may be NULL), one movie contiguous:
+ *   d_frames_u8  [K][ncam][T][H][W][3]          = (uint8) trunc(frame * 255.0f)                          (:123)
+ *   d_distrib_u8 [K][ncam][ndesig][T][H][W][3]  per plane, p the normalised distribution vf_export gives:
+ *       mx = max over the plane of p;  q = p / (mx + 1e-6f)  (float32 add, IEEE float32 division);
+ *       pixel = d_lut[min((int)(q * 256.0f), 255)]                                                       (:114-115)
+ * Enqueues at most two kernels on `stream`, allocates nothing, never synchronises.  Returns VF_ERR_INVALID (nothing
+ * launched) for a NULL handle / d_seq, both outputs NULL, d_distrib_u8 without d_lut, K < 1 or K > max_batch, or a
+ * handle that has not rolled. */
+int vf_render_plans(vf_handle *h, const int32_t *d_seq, int32_t K, const uint8_t *d_lut, uint8_t *d_frames_u8,
+                    uint8_t *d_distrib_u8, void *stream);
+
 /* Copy the predictions of the last vf_rollout out in the reference's layout (camera axis,
  * normalised distributions).  Any destination may be NULL.  first/count select a range of rolled
  * sequences.  Replaces the gen_images/gen_distrib/gen_states fetch of

@@ -4,7 +4,7 @@
  * points a non-Python maintainer of the reference's planner would bind:
  *
  *     vf_create -> vf_load_weights -> vf_set_persistent -> vf_set_context -> vf_rollout -> vf_device_status -> vf_export
- *     -> vf_goal_image_scores (printed only)
+ *     -> vf_goal_image_scores, vf_render_plans (printed only)
  *
  * i.e. what `self.predictor = predictor_class(...)`, `.restore()` and `self.predictor(context, {'actions'})` +
  * `_eval_pixel_cost` do in visual_mpc/policy/cem_controllers/pixel_cost_controller.py:29-36,83-84,135-166 of the
@@ -112,9 +112,25 @@ int main(int argc, char **argv) {
     if (to_device(&d_gi, goal_img, n_img * 4)) return 2;
     HIP_OK(hipMalloc(&d_gs, (size_t)B * 8));
     VF_CALL(vf_goal_image_scores(h, d_gi, 0, *fw, 0, d_gs, NULL, NULL, st));
+    /* the plan page's pictures of the first sequence (pixel_cost_controller.py:107-126), through a grey colour table */
+    const int32_t first_seq = 0;
+    uint8_t grey[256 * 3];
+    for (int i = 0; i < 256 * 3; ++i) grey[i] = (uint8_t)(i / 3);
+    const size_t n_movie = (size_t)T * H * W * 3;
+    void *d_sq, *d_lu, *d_rf, *d_rd;
+    if (to_device(&d_sq, &first_seq, 4) || to_device(&d_lu, grey, sizeof grey)) return 2;
+    HIP_OK(hipMalloc(&d_rf, n_movie));
+    HIP_OK(hipMalloc(&d_rd, n_movie * nd));
+    VF_CALL(vf_render_plans(h, d_sq, 1, d_lu, d_rf, d_rd, st));
     HIP_OK(hipStreamSynchronize(st));
     double goal_score0 = 0.0;
     HIP_OK(hipMemcpy(&goal_score0, d_gs, 8, hipMemcpyDeviceToHost));
+    uint8_t *movie = malloc(n_movie * (1 + nd));
+    if (!movie) return 4;
+    HIP_OK(hipMemcpy(movie, d_rf, n_movie, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(movie + n_movie, d_rd, n_movie * nd, hipMemcpyDeviceToHost));
+    unsigned brightest = 0;
+    for (size_t i = 0; i < n_movie * (1 + nd); ++i) brightest = movie[i] > brightest ? movie[i] : brightest;
 
     double *scores = malloc((size_t)B * 8), *per_task = malloc((size_t)B * nd * 8);
     float *of = malloc(n_of * 4 + 4), *od = malloc(n_od * 4 + 4), *os = malloc(n_os * 4 + 4);
@@ -132,6 +148,8 @@ int main(int argc, char **argv) {
     printf("vf_c_host: %d sequences x %d steps rolled through the C ABI (version %d); score[0] = %.17g\n", B, T,
            vf_abi_version(), scores[0]);
     printf("vf_c_host: goal-image score[0] = %.17g (last predicted frame against the first context frame)\n", goal_score0);
+    printf("vf_c_host: rendered sequence 0 as %zu bytes of frames and %zu of distributions; brightest byte %u\n", n_movie,
+           n_movie * nd, brightest);
     VF_CALL(vf_destroy(h));
     return 0;
 }

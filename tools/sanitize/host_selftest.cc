@@ -158,6 +158,22 @@ int main() {
                 }
             }
         }
+        // vf_render_plans likewise: NULL arguments, nothing to render, no colour table, a bad K, a handle that has not rolled
+        if (hh) {
+            int32_t seq[1] = {0};
+            uint8_t lut[768] = {0}, out[4] = {0};
+            struct { vf_handle *h; const int32_t *seq; int K; const uint8_t *lut; uint8_t *f, *d; const char *msg; } refusals[] = {
+                {nullptr, seq, 1, lut, out, out, "null argument"},  {hh, nullptr, 1, lut, out, out, "null argument"},
+                {hh, seq, 1, lut, nullptr, nullptr, "both outputs"}, {hh, seq, 1, nullptr, out, out, "colour table"},
+                {hh, seq, 0, lut, out, out, "at least one"},          {hh, seq, 1 << 20, lut, out, nullptr, "max_batch"},
+                {hh, seq, 1, nullptr, out, nullptr, "not rolled"}};
+            for (const auto &c : refusals) {
+                const int r = vf_render_plans(c.h, c.seq, c.K, c.lut, c.f, c.d, nullptr);
+                if (r != VF_ERR_INVALID || std::string(vf_last_error()).find(c.msg) == std::string::npos) {
+                    std::fprintf(stderr, "vf_render_plans: want refusal '%s', got rc %d '%s'\n", c.msg, r, vf_last_error()); rc = 1;
+                }
+            }
+        }
         if (hh && vf_destroy(hh)) { std::fprintf(stderr, "vf_destroy after the injected failures failed\n"); rc = 1; }
         std::printf("  injected failures (bad_alloc, std::exception, foreign) in vf_create / vf_load_weights / build_schedule: %s\n",
                     rc ? "FAILED" : "status codes returned, handle reusable");

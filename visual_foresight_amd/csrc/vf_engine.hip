@@ -36,6 +36,7 @@
 #include "vf_conv_mfma.h"
 #include "vf_small_kernels.h"
 #include "vf_goal_image.h"
+#include "vf_plan_render.h"
 #include "vf_conv_bf16x6.h"
 #include "vf_persistent.h"
 
@@ -2130,6 +2131,20 @@ static int goal_image_check(const vf_handle *h, const float *d_goal, int32_t ste
     return VF_OK;
 }
 
+// the refusals of vf_render_plans (host work only, as above; the handle is not read before the argument checks are through)
+static int render_plans_check(const vf_handle *h, const int32_t *d_seq, int32_t K, const uint8_t *d_lut,
+                              const uint8_t *d_frames_u8, const uint8_t *d_distrib_u8) {
+    if (!h || !d_seq) return fail(VF_ERR_INVALID, "null argument");
+    if (!d_frames_u8 && !d_distrib_u8) return fail(VF_ERR_INVALID, "both outputs are null: nothing to render");
+    if (d_distrib_u8 && !d_lut) return fail(VF_ERR_INVALID, "distributions need a colour table");
+    if (K < 1) return fail(VF_ERR_INVALID, "K = " + std::to_string(K) + " plans, need at least one");
+    if (K > h->cfg.max_batch)
+        return fail(VF_ERR_INVALID, "K = " + std::to_string(K) + " plans exceed max_batch = " +
+                                        std::to_string(h->cfg.max_batch));
+    if (h->last_B < 1) return fail(VF_ERR_INVALID, "the handle has not rolled");
+    return VF_OK;
+}
+
 #ifdef VF_HOST_SELFTEST
 // ------------------------------------------------------------------ host self-test hooks
 // (tools/host_selftest.cc; ASan/UBSan build).  Checks the invariants the device relies on.
@@ -2349,6 +2364,13 @@ extern "C" int vf_goal_image_scores(vf_handle *h, const float *d_goal, int32_t s
                                     double *, double *, void *) {      // (refusal paths only: this build never rolls)
     VF_API_TRY
     if (int rc = goal_image_check(h, d_goal, steps_mode, d_scores)) return rc;
+    return fail(VF_ERR_HIP, "the host self-test build launches nothing");
+    VF_API_CATCH(int)
+}
+extern "C" int vf_render_plans(vf_handle *h, const int32_t *d_seq, int32_t K, const uint8_t *d_lut, uint8_t *d_frames_u8,
+                               uint8_t *d_distrib_u8, void *) {        // (refusal paths only, as above)
+    VF_API_TRY
+    if (int rc = render_plans_check(h, d_seq, K, d_lut, d_frames_u8, d_distrib_u8)) return rc;
     return fail(VF_ERR_HIP, "the host self-test build launches nothing");
     VF_API_CATCH(int)
 }
@@ -2652,6 +2674,39 @@ int vf_goal_image_scores(vf_handle *h, const float *d_goal, int32_t steps_mode, 
                        h->n_draws, NV, T, steps_mode, finalweight, first_view_only != 0, h->d_status, d_scores,
                        d_scores_per_view, d_cost_per_step);
     VF_HIP_CHECK(hipGetLastError());
+    return VF_OK;
+    VF_API_CATCH(int)
+}
+
+int vf_render_plans(vf_handle *h, const int32_t *d_seq, int32_t K, const uint8_t *d_lut, uint8_t *d_frames_u8,
+                    uint8_t *d_distrib_u8, void *stream) {
+    VF_API_TRY
+    if (int rc = render_plans_check(h, d_seq, K, d_lut, d_frames_u8, d_distrib_u8)) return rc;
+    VF_HIP_CHECK(hipSetDevice(h->cfg.device));
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const int T = h->T, NV = h->ncam, HW = h->H * h->W;
+    const long long view_rows = (long long)h->cfg.max_batch * T;
+    if (d_frames_u8) {
+        const int n4 = T * HW * 3 / 4;          // (H, W multiples of 8: a movie is a whole number of 16-byte loads)
+        hipLaunchKernelGGL(render_frames_kernel, dim3((unsigned)((n4 + kRenderThreads - 1) / kRenderThreads), (unsigned)(K * NV)),
+                           dim3(kRenderThreads), 0, st, h->frames_all, view_rows * HW * 3, d_seq, h->last_B, NV, n4,
+                           reinterpret_cast<uint32_t *>(d_frames_u8));
+        VF_HIP_CHECK(hipGetLastError());
+    }
+    if (d_distrib_u8) {
+        auto launch = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, dim3((unsigned)(K * NV * T)), dim3(kRenderThreads), 0, st, h->distrib_all,
+                               view_rows * HW * h->ND, h->sums, h->sums_step_stride, h->sums_view_stride, h->nblocks, d_seq,
+                               h->last_B, NV, T, HW, d_lut, reinterpret_cast<uint32_t *>(d_distrib_u8));
+        };
+        switch (h->ND) {
+            case 1: launch(render_distrib_kernel<1>); break;
+            case 2: launch(render_distrib_kernel<2>); break;
+            case 3: launch(render_distrib_kernel<3>); break;
+            default: launch(render_distrib_kernel<4>); break;
+        }
+        VF_HIP_CHECK(hipGetLastError());
+    }
     return VF_OK;
     VF_API_CATCH(int)
 }

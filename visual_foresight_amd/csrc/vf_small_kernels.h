@@ -701,6 +701,15 @@ VF_GLOBAL void export_frames_kernel(const float *src, long long view_stride, int
     dst[i] = src[(long long)v * view_stride + ((long long)(first + bb) * T + t) * HWC + e];
 }
 
+// The normalisation every reader of a predicted distribution shares (vf_export, vf_render_plans): S0 of a plane is its
+// block sums pp[2 * k] added in block order, a value leaves as (float)((double)src / S0).
+__device__ __forceinline__ double distrib_s0(const double *pp, int ntiles) {
+    double s0 = 0.0;
+    for (int k = 0; k < ntiles; ++k) s0 += pp[2 * k];
+    return s0;
+}
+__device__ __forceinline__ float distrib_normalised(float src, double s0) { return (float)((double)src / s0); }
+
 // normalised distributions out: dst[bb][t][view][hw][d] = src[view][b][t][hw][d] / S0(t, view, b, d)
 VF_GLOBAL void export_distrib_kernel(const float *src, long long view_stride, const double *sums,
                                       long long step_stride, long long sums_view_stride, int first, int count,
@@ -717,9 +726,8 @@ VF_GLOBAL void export_distrib_kernel(const float *src, long long view_stride, co
     const int b = first + bb;
     const double *pp = sums + (long long)t * step_stride + (long long)v * sums_view_stride +
                        ((long long)b * ND + d) * ntiles * 2;
-    double s0 = 0.0;
-    for (int k = 0; k < ntiles; ++k) s0 += pp[2 * k];
-    dst[i] = (float)((double)src[(long long)v * view_stride + ((long long)b * T + t) * HW * ND + e] / s0);
+    dst[i] = distrib_normalised(src[(long long)v * view_stride + ((long long)b * T + t) * HW * ND + e],
+                                distrib_s0(pp, ntiles));
 }
 
 // ------------------------------------------------------------------------------------------

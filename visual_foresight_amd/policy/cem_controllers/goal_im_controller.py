@@ -120,9 +120,8 @@ class GoalImController(CEMBaseController):
                 finalweight=hp.finalweight, first_view_only=hp.only_take_first_view)
             self.cost_perstep = self.predictor.last_goal_cost_per_step
         else:
-            one_hot = np.zeros((self._net_context, self._n_cam, self._img_height, self._img_width, 1), np.float32)
-            one_hot[:, :, self._img_height // 2, self._img_width // 2, :] = 1.
-            prediction = self.predictor(dict(context, context_pixel_distributions=one_hot), {'actions': actions})
+            context = self._with_centre_distribution(context)
+            prediction = self.predictor(context, {'actions': actions})
             scores, per_view, self.cost_perstep = goal_image_cost(
                 prediction['predicted_frames'], self._goal_image, hp.goal_cost_steps, hp.finalweight,
                 hp.only_take_first_view)
@@ -132,7 +131,28 @@ class GoalImController(CEMBaseController):
             self._logger.log('goal-image score of best traj cam{} :{}'.format(icam, per_view[bestind, icam]))
         if self._verbose_condition(cem_itr):
             self._logger.log('best scores itr {}: {}'.format(cem_itr, np.sort(scores)[:10]))
+            if self._verbose_worker is not None:
+                self._put_plan_page(cem_itr, scores, context, actions)
         return scores
+
+    def _with_centre_distribution(self, context):
+        """``context`` plus the one distribution channel the network carries, switched on at the image centre."""
+        one_hot = np.zeros((self._net_context, self._n_cam, self._img_height, self._img_width, 1), np.float32)
+        one_hot[:, :, self._img_height // 2, self._img_width // 2, :] = 1.
+        return dict(context, context_pixel_distributions=one_hot)
+
+    def _put_plan_page(self, cem_itr, scores, context, actions):
+        """The reference's page (:101-141): start and goal images, the predicted frames of the ten best plans, their
+        scores - rendered by the predictor's ``render_plans`` where the last rollout lies, else on the host."""
+        from .visualizer import plan_page
+        self.visualize_indices = scores.argsort()[:plan_page.N_PLANS]
+        rendered = plan_page.render_for_page(self.predictor, self.visualize_indices,
+                                             self._with_centre_distribution(context), actions, want_distributions=False)
+        for message in plan_page.build_plan_messages(
+                self._t, cem_itr, self._images[-1], scores[self.visualize_indices], rendered['frames'],
+                goal_images=self._goal_bytes, img_height=self._hp.verbose_img_height,
+                extensions=plan_page.asset_extensions(self._verbose_worker)):
+            self._verbose_worker.put(message)
 
     def act(self, t, i_tr, images, state, goal_image, verbose_worker=None):
         """
@@ -145,4 +165,7 @@ class GoalImController(CEMBaseController):
                                               raw=self._hp.goal_image_raw)
         self._images = images
         self._verbose_worker = verbose_worker
+        if verbose_worker is not None:      # the goal as the plan page shows it: the caller's bytes, or a float goal's
+            g = np.asarray(goal_image).reshape(self._goal_image.shape)
+            self._goal_bytes = g if g.dtype == np.uint8 else (np.clip(g, 0., 1.) * 255.).astype(np.uint8)
         return super(GoalImController, self).act(t, i_tr, state)

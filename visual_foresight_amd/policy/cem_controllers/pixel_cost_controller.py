@@ -136,20 +136,30 @@ class PixelCostController(CEMBaseController):
             scores = self._eval_pixel_cost(cem_itr, gen_distrib, gen_images)
 
         if self._verbose_condition(cem_itr):
-            self._visualize(cem_itr, scores)
+            self._visualize(cem_itr, scores, context, actions)
         return scores
 
     def _task_weights(self):
         """Per-(camera, designated pixel) score weights, or None for the reference's plain mean."""
         return None
 
-    def _visualize(self, cem_itr, scores):
-        """Hook for plan visualisation (the reference renders an HTML/GIF page, :88-131).
-
-        Rendering is debug tooling outside the planner hot path; subclasses may override this
-        and pull videos with ``self.predictor(context, ...)``.
-        """
+    def _visualize(self, cem_itr, scores, context=None, actions=None):
+        """Plan visualisation (reference :88-131).  Without a ``verbose_worker`` (or without the rollout's inputs) the
+        ten best scores are logged.  With one, the plans ``scores.argsort()[:10]`` are rendered - by the predictor's
+        ``render_plans`` where the last rollout lies, or on the host from ``self.predictor(context, ...)`` of those
+        plans - and the page's messages (``visualizer/plan_page.py``) are ``put`` on the worker."""
         self._logger.log('best scores itr {}: {}'.format(cem_itr, np.sort(scores)[:10]))
+        worker = getattr(self, '_verbose_worker', None)
+        if worker is None or context is None:
+            return
+        from .visualizer import plan_page
+        self.visualize_indices = scores.argsort()[:plan_page.N_PLANS]
+        rendered = plan_page.render_for_page(self.predictor, self.visualize_indices, context, actions)
+        for message in plan_page.build_plan_messages(
+                self._t, cem_itr, self._images[-1], scores[self.visualize_indices], rendered['frames'],
+                rendered['distributions'], desig_pix=self._desig_pix, goal_pix=self._goal_pix,
+                img_height=self._hp.verbose_img_height, extensions=plan_page.asset_extensions(worker)):
+            worker.put(message)
 
     def _log_task_scores(self, scores, scores_per_task):
         bestind = scores.argsort()[0]

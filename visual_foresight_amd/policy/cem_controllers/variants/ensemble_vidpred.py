@@ -74,6 +74,10 @@ class CEM_Controller_Ensemble_Vidpred(PixelCostController):
             self._visualize(cem_itr, scores)
         return scores
 
+    def _visualize(self, cem_itr, scores, context=None, actions=None):
+        """The reference's ensemble controller has no plan page: the best scores are logged."""
+        self._logger.log('best scores itr {}: {}'.format(cem_itr, np.sort(scores)[:10]))
+
     def _eval_pixel_cost(self, cem_itr, gen_distrib, gen_images):
         """Host scoring of member-major distributions ``[E, M, T, ncam, H, W, ndesig]``."""
         E, M, T = gen_distrib.shape[:3]

@@ -36,6 +36,11 @@ class SyntheticAgent(object):
         self._hyperparams.setdefault('adim', self.env.adim)
         self._hyperparams.setdefault('sdim', self.env.sdim)
         self.T = hyperparams['T']
+        # optional 'verbose_dir': the plan pages of verbose policies are written below it (default: no file worker)
+        self._save_worker = None
+        if hyperparams.get('verbose_dir'):
+            from visual_foresight_amd.utils.plan_page_writer import PlanPageWriter
+            self._save_worker = PlanPageWriter(hyperparams['verbose_dir'])
 
     def sample(self, policy, i_tr):
         return self.rollout(policy, i_tr)
@@ -45,10 +50,12 @@ class SyntheticAgent(object):
         history = {'images': [obs['images']], 'state': [obs['state']]}
         agent_data = {'traj_ok': True}
         policy_outs = []
+        if self._save_worker is not None:
+            self._save_worker.put(('path', os.path.join(self._hyperparams['verbose_dir'], 'traj%d' % i_tr)))
         for t in range(self.T):
             agent_data['desig_pix'] = self.env.get_desig_pix()
             agent_data['goal_pix'] = self.env.get_goal_pix()
-            agent_data['verbose_worker'] = None
+            agent_data['verbose_worker'] = self._save_worker
             obs_hist = {k: np.stack(v, 0) for k, v in history.items()}
             pi_t = policy.act(**get_policy_args(policy, obs_hist, t, i_tr, agent_data))
             policy_outs.append(pi_t)

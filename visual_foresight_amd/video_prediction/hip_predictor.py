@@ -629,25 +629,96 @@ class HipVPredEvaluation(object):
                              % (sample_index, self._last_lo, self._last_lo + self._last_M))
         return self._reroll_one(sample_index, out)
 
-    def _reroll_one(self, sample_index, out):
-        """Roll action ``sample_index`` of the last scoring call again (its ``n_draws`` sequences, alone) and export
-        the first draw's distributions into ``out``."""
+    def _reroll(self, indices):
+        """Roll the actions ``indices`` of the last scoring call again as ONE batch (``len(indices) * n_draws`` sequences of
+        ``_last_prepared``, at most ``run_batch_size``) -> their device scores.  Row ``i * n_draws`` of the resident batch is
+        then the first draw of ``indices[i]``.  Call under this engine's device."""
         torch, nd = self._torch, self.n_draws
         ctx_p, seqs, _ = self._last_prepared
         ntask = self.n_cam * self.cfg.ndesig
-        with torch.cuda.device(self.device):
-            self._set_context(ctx_p)
-            seq = torch.from_numpy(np.ascontiguousarray(seqs[sample_index * nd:(sample_index + 1) * nd],
-                                                        dtype=np.float32)).to(self.device)
-            scores = torch.empty(1, dtype=torch.float64, device=self.device)
-            per_task = torch.empty((1, ntask), dtype=torch.float64, device=self.device)
-            self._rollout_chunk(seq, np.zeros((self.n_cam, self.cfg.ndesig, 2), np.int32), 1.0, scores, per_task)
-            # under torch.distributed EVERY rank has just rolled it: nobody may claim to be "the" holder afterwards
-            # (the fetch's all-reduce adds the holders' copies), so the ranks keep nothing resident
-            self._last_lo, self._last_M = sample_index, (1 if _dist_info()[1] == 1 else 0)
+        n = len(indices)
+        rows = (np.asarray(indices, dtype=np.int64)[:, None] * nd + np.arange(nd)[None]).reshape(-1)
+        self._set_context(ctx_p)
+        seq = torch.from_numpy(np.ascontiguousarray(np.asarray(seqs)[rows], dtype=np.float32)).to(self.device)
+        scores = torch.empty(n, dtype=torch.float64, device=self.device)
+        per_task = torch.empty((n, ntask), dtype=torch.float64, device=self.device)
+        self._rollout_chunk(seq, np.zeros((self.n_cam, self.cfg.ndesig, 2), np.int32), 1.0, scores, per_task)
+        # what is resident now is not a range of the scoring call, unless it is one action.  Under torch.distributed
+        # EVERY rank may have just rolled it: nobody may claim to be "the" holder afterwards (the fetch's all-reduce
+        # adds the holders' copies), so the ranks keep nothing resident
+        alone = n == 1 and _dist_info()[1] == 1
+        self._last_lo, self._last_M = int(indices[0]), (1 if alone else 0)
+        return scores
+
+    def _reroll_one(self, sample_index, out):
+        """Roll action ``sample_index`` of the last scoring call again (its ``n_draws`` sequences, alone) and export
+        the first draw's distributions into ``out``."""
+        with self._torch.cuda.device(self.device):
+            scores = self._reroll([sample_index])
             _lib.check(self._libh.vf_export(self._handle, 0, 1, None, out.data_ptr(), None, self._stream()))
             self._check_scores(scores.cpu().numpy())
             return out.cpu().numpy()
+
+    # ------------------------------------------------------------------ plan visualisation
+    def _render_resident(self, rows, lut_dev, frames, distributions):
+        """``vf_render_plans`` on the rolled sequences ``rows`` of this engine's resident batch -> device uint8 tensors
+        (frames ``[K, ncam, T, H, W, 3]`` or None, distributions ``[K, ncam, ndesig, T, H, W, 3]`` or None)."""
+        torch, c = self._torch, self.cfg
+        T, K = self.sequence_length - self.n_context, len(rows)
+        seq = torch.from_numpy(np.ascontiguousarray(rows, dtype=np.int32)).to(self.device)
+        f = torch.empty((K, self.n_cam, T, c.height, c.width, 3), dtype=torch.uint8, device=self.device) if frames else None
+        d = torch.empty((K, self.n_cam, c.ndesig, T, c.height, c.width, 3), dtype=torch.uint8,
+                        device=self.device) if distributions else None
+        _lib.check(self._libh.vf_render_plans(self._handle, seq.data_ptr(), K, lut_dev.data_ptr(),
+                                              f.data_ptr() if frames else None, d.data_ptr() if distributions else None,
+                                              self._stream()))
+        return f, d
+
+    def render_plans(self, indices, lut=None, frames=True, distributions=True):
+        """The plan page's pictures (reference ``pixel_cost_controller.py:107-126``) of K actions of the last ``score()``
+        / ``score_goal_image()`` call (with latent draws: their first draw), rendered on the GPU: ``{'frames': uint8
+        [K, ncam, T, H, W, 3], 'distributions': uint8 [K, ncam, ndesig, T, H, W, 3]}`` (the keys asked for).  Frames are
+        ``trunc(frame * 255)``, every distribution plane is coloured against its own maximum through ``lut`` (uint8
+        ``[256, 3]``, default viridis) - the arithmetic of ``visualizer/colormap.py``, bit for bit.
+
+        When this engine still holds all K (one engine and ``M <= run_batch_size``: the reference default) nothing is
+        rolled.  Otherwise - chunked calls, lanes, ``torch.distributed`` ranks - the K actions are rolled again as one
+        batch: a sample's arithmetic does not depend on its batch, so the bytes are the same, and every rank does it
+        locally without a collective."""
+        from visual_foresight_amd.policy.cem_controllers.visualizer.colormap import check_lut
+        torch, nd = self._torch, self.n_draws
+        prepared = self._last_prepared
+        if prepared is None:
+            raise IndexError('render_plans follows a score() / score_goal_image() call')
+        idx = np.asarray(indices)
+        if idx.ndim != 1 or idx.size == 0 or not np.issubdtype(idx.dtype, np.integer):
+            raise ValueError('indices must be a non-empty 1-d integer sequence, got %r' % (indices,))
+        if not (frames or distributions):
+            raise ValueError('nothing to render: frames and distributions are both off')
+        if idx.min() < 0 or idx.max() >= prepared[2]:
+            raise IndexError('indices %s outside the last scoring call (%d actions)' % (idx.tolist(), prepared[2]))
+        if len(np.unique(idx)) != idx.size:
+            raise ValueError('indices repeat: %s' % (idx.tolist(),))
+        parts = []
+        with torch.cuda.device(self.device):
+            lut_dev = torch.from_numpy(np.array(check_lut(lut))).to(self.device)
+            local = idx - self._last_lo
+            if local.min() >= 0 and local.max() < self._last_M:
+                parts.append(self._render_resident(local * nd, lut_dev, frames, distributions))
+            else:
+                bs = self.run_batch_size // nd
+                rolled = []
+                for g0 in range(0, idx.size, bs):
+                    group = idx[g0:g0 + bs]
+                    rolled.append(self._reroll(group))
+                    parts.append(self._render_resident(np.arange(group.size) * nd, lut_dev, frames, distributions))
+                self._check_scores(torch.cat(rolled).cpu().numpy())
+            out = {}
+            if frames:
+                out['frames'] = torch.cat([p[0] for p in parts]).cpu().numpy()
+            if distributions:
+                out['distributions'] = torch.cat([p[1] for p in parts]).cpu().numpy()
+        return out
 
     # ------------------------------------------------------------------ registration
     def register(self, current, reference, flow, pix, region=0, clip_sub=1, want_warped=False):
