@@ -200,6 +200,58 @@ int vf_goal_image_scores(vf_handle *h, const float *d_goal, int32_t steps_mode, 
 int vf_render_plans(vf_handle *h, const int32_t *d_seq, int32_t K, const uint8_t *d_lut, uint8_t *d_frames_u8,
                     uint8_t *d_distrib_u8, void *stream);
 
+/* Learned-cost planning: a frame scorer on the device (reference
+ * visual_mpc/policy/cem_controllers/variants/classifier_controller.py:34-36,94-105 and nce_cost_controller.py:33-35,90-103:
+ * control_embedding.deploy_simple_model / deploy_model on a GPU of its own, every predicted frame copied to the host and
+ * through that network).  The scorer package is not part of the reference snapshot; the network is this project's
+ * (visual_foresight_amd/video_prediction/frame_scorer_arch.py: four 3x3 / 2 convolutions 32-64-128-128 with ReLU, mean
+ * over the positions, FC to D values), one weight set per view.  head 0 = classifier (D = 2 logits; embed_dim ignored),
+ * head 1 = embedding (D = embed_dim) with a second tower (tower 1, six input channels: concat[goal image, start image],
+ * nce_cost_controller.py:94-99).  height and width are multiples of 16, width <= 128; max_frames = the most images
+ * (per view) one call scores, e.g. the handle's max_batch * T.  Images are multiplied by input_scale (float32) on the way
+ * in (classifier_controller.py:94,98: 1; nce_cost_controller.py:90,95: 255).  Every device buffer is allocated in
+ * vf_scorer_create; vf_scorer_load_weights is the one blocking call.  The activations, head outputs and raw costs of a
+ * pass are scratch of the scorer: like a handle, a scorer is driven from ONE stream at a time - two scoring or embedding calls
+ * on the same scorer from different streams would overwrite each other's scratch (use one scorer per stream). */
+typedef struct vf_scorer_config {
+    int32_t height, width;
+    int32_t ncam;               /* views (1..4; 0 = 1) */
+    int32_t head;               /* 0 = classifier, 1 = embedding */
+    int32_t embed_dim;          /* head 1: D (1..1024) */
+    int32_t max_frames;
+    int32_t device;             /* HIP device ordinal */
+    float input_scale;
+} vf_scorer_config;
+
+typedef struct vf_scorer vf_scorer;
+
+/* float32 values of ONE view's weights of `tower` (0: frames, 1: goal / start pair, head 1 only), the canonical table of
+ * frame_scorer_arch.py concatenated in table order; 0 + vf_last_error() for a bad config or tower. */
+size_t vf_scorer_weight_count(const vf_scorer_config *cfg, int32_t tower);
+int vf_scorer_create(const vf_scorer_config *cfg, vf_scorer **out);
+int vf_scorer_destroy(vf_scorer *s);
+/* HOST blob, ncam views back to back; re-packs the convolution weights for the MFMA kernel into the buffers
+ * vf_scorer_create allocated (replaces restore_path of deploy_simple_model / deploy_model). */
+int vf_scorer_load_weights(vf_scorer *s, int32_t tower, const float *host_blob, size_t n_floats);
+/* Any images: d_images DEVICE float32 [n][ncam][H][W][Cin] (Cin = 3 for tower 0, 6 for tower 1; 16-byte aligned; in the
+ * scale of predicted frames, multiplied by input_scale like them) -> d_out [n][ncam][D].  n <= max_frames.  The goal /
+ * start pair of nce_cost_controller.py:94-98 ('goal_enc'), and the tests. */
+int vf_scorer_embed(vf_scorer *s, int32_t tower, const float *d_images, int32_t n, float *d_out, void *stream);
+/* Scores the frames of h's LAST vf_rollout where they lie (nothing is exported or copied).  Per rolled sequence b and
+ * step t:  raw[b][t] = sum over views c of x[b][t][c]                     (classifier_controller.py:104, nce_...:102)
+ *   head 0: x = -log(p1 + 1e-5), p = softmax(logits) in float64 from the float32 logits                 (:10,102)
+ *   head 1: x = -sum_d d_goal_enc[c][d] * enc[b][t][c][d], float64 products, d ascending        (nce_...:100,160-164)
+ * then _weight_scores (classifier_controller.py:135-142): finalweight >= 0: (sum_{t<T-1} raw + fw * raw[T-1]) / (T-1+fw);
+ * finalweight < 0: raw[T-1] (only the last frames are scored unless an optional output wants all); then the mean over
+ * each action's n_draws sequences.  d_scores float64 [B / n_draws]; d_cost_per_step float64 [B / n_draws][T] = raw
+ * averaged over the draws (NULL ok); d_head_out float32 [B][T][ncam][D] (NULL ok); d_goal_enc DEVICE float32 [ncam][D]
+ * (head 1; ignored for head 0).  A frame's head output has the same bits in any batch, chunk or rank.  If the handle's
+ * device status is raised every output is NaN.  Enqueues on `stream`, never synchronises, allocates nothing.
+ * VF_ERR_INVALID (nothing launched): NULL s / h / d_scores, scorer and handle of different size / ncam / device, a handle
+ * that has not rolled, more frames than max_frames, head 1 without d_goal_enc, weights not loaded. */
+int vf_scorer_scores(vf_scorer *s, vf_handle *h, const float *d_goal_enc, float finalweight, double *d_scores,
+                     double *d_cost_per_step, float *d_head_out, void *stream);
+
 /* Copy the predictions of the last vf_rollout out in the reference's layout (camera axis,
  * normalised distributions).  Any destination may be NULL.  first/count select a range of rolled
  * sequences.  Replaces the gen_images/gen_distrib/gen_states fetch of

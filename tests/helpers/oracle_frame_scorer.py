@@ -1,0 +1,167 @@
+"""PyTorch-CPU restatement of the frame scorer (``visual_foresight_amd/video_prediction/frame_scorer_arch.py``: four 3x3 / 2
+convolutions with zero padding 1, bias, ReLU; mean over the positions; FC) in float32 AND float64, and the learned-cost
+arithmetic (reference ``classifier_controller.py:94-105,135-142``, ``nce_cost_controller.py:90-103,160-164``) in NumPy
+float64.  Plus two slower restatements the tests use as yardsticks: naive loops (``naive_*``), and a float32 forward pass
+that adds each output's products as ONE ``fmaf`` chain in the device's K order (``forward_device_order``).  Test
+infrastructure only."""
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+LOG_SHIFT = 1e-5
+
+
+def conv_block(x, w, b):
+    """x ``[n, H, W, Cin]``, w ``[3, 3, Cin, Cout]`` -> relu(conv 3x3 / 2, zero pad 1, + b) ``[n, H/2, W/2, Cout]``."""
+    y = F.conv2d(x.permute(0, 3, 1, 2), w.permute(3, 2, 0, 1), b, stride=2, padding=1)
+    return F.relu(y).permute(0, 2, 3, 1)
+
+
+def pool_block(x):
+    return x.mean(dim=(1, 2))
+
+
+def fc_block(x, w, b):
+    return x @ w + b
+
+
+def forward(weights, images, input_scale, dtype=torch.float64):
+    """One view's tower on ``images [n, H, W, Cin]`` (float32 values, in [0, 1]) -> head outputs ``[n, D]`` in ``dtype``.
+    The input scaling is the float32 multiply of the spec in both precisions."""
+    x = torch.from_numpy(np.ascontiguousarray(images, dtype=np.float32)) * torch.tensor(input_scale, dtype=torch.float32)
+    x = x.to(dtype)
+    t = {k: torch.from_numpy(v).to(dtype) for k, v in weights.tensors.items()}
+    with torch.no_grad():
+        for i in range(1, 5):
+            x = conv_block(x, t['c%d/w' % i], t['c%d/b' % i])
+        return fc_block(pool_block(x), t['fc/w'], t['fc/b']).numpy()
+
+
+def forward_views(weight_views, images, input_scale, dtype=torch.float64, batch=128):
+    """``images [n, ncam, H, W, Cin]`` -> ``[n, ncam, D]``."""
+    images = np.asarray(images)
+    out = []
+    for c, w in enumerate(weight_views):
+        out.append(np.concatenate([forward(w, images[i:i + batch, c], input_scale, dtype)
+                                   for i in range(0, images.shape[0], batch)]))
+    return np.stack(out, axis=1)
+
+
+# ----------------------------------------------------------------------------------------------- naive loops (tiny shapes)
+def naive_conv_block(x, w, b):
+    x, w, b = [np.asarray(a, dtype=np.float64) for a in (x, w, b)]
+    n, H, W, Cin = x.shape
+    Cout = w.shape[3]
+    out = np.zeros((n, H // 2, W // 2, Cout))
+    for i in range(n):
+        for oy in range(H // 2):
+            for ox in range(W // 2):
+                acc = b.copy()
+                for ky in range(3):
+                    for kx in range(3):
+                        iy, ix = 2 * oy + ky - 1, 2 * ox + kx - 1
+                        if 0 <= iy < H and 0 <= ix < W:
+                            acc += x[i, iy, ix] @ w[ky, kx]
+                out[i, oy, ox] = np.maximum(acc, 0.)
+    return out
+
+
+def naive_pool_block(x):
+    x = np.asarray(x, dtype=np.float64)
+    n, H, W, C = x.shape
+    out = np.zeros((n, C))
+    for r in range(H):
+        for c in range(W):
+            out += x[:, r, c]
+    return out / (H * W)
+
+
+# --------------------------------------------------------------------- the device's summation order, float32 fmaf chains
+def _fma32(a, b, acc):
+    """float32 fused multiply-add, elementwise: the float64 product of two float32 values is exact, the sum is rounded to
+    float64 and then to float32 - double rounding differs from one rounding only in half-way cases of measure ~2^-29, far
+    below what this yardstick resolves."""
+    return (a.astype(np.float64) * b.astype(np.float64) + acc.astype(np.float64)).astype(np.float32)
+
+
+def device_k_order(cin, first_layer):
+    """The order in which the device adds one tap's input channels: ascending in c1; in c2..c4 steps of eight channels,
+    inside a step 0, 4, 1, 5, 2, 6, 3, 7 (csrc/vf_frame_scorer.h)."""
+    if first_layer:
+        return list(range(cin))
+    return [8 * s + q + 4 * h for s in range(cin // 8) for q in range(4) for h in range(2)]
+
+
+def forward_device_order(weights, images, input_scale):
+    """float32 forward pass of one view's tower in the device's own order of additions."""
+    x = np.ascontiguousarray(images, dtype=np.float32) * np.float32(input_scale)
+    for i in range(1, 5):
+        w, b = weights.tensors['c%d/w' % i], weights.tensors['c%d/b' % i]
+        n, H, W, Cin = x.shape
+        xp = np.zeros((n, H + 2, W + 2, Cin), np.float32)
+        xp[:, 1:-1, 1:-1] = x
+        acc = np.zeros((n, H // 2, W // 2, w.shape[3]), np.float32)
+        order = device_k_order(Cin, i == 1)
+        for ky in range(3):
+            for kx in range(3):
+                patch = xp[:, ky:ky + H:2, kx:kx + W:2]             # [n, H/2, W/2, Cin]
+                for ci in order:
+                    acc = _fma32(patch[..., ci:ci + 1], w[ky, kx, ci][None, None, None], acc)
+        x = np.maximum(acc + b, np.float32(0.))
+    n, H, W, C = x.shape
+    s = np.zeros((n, C), np.float32)
+    for r in range(H):
+        for c in range(W):
+            s = s + x[:, r, c]
+    pooled = s / np.float32(H * W)
+    wf, bf = weights.tensors['fc/w'], weights.tensors['fc/b']
+    acc = np.zeros((n, wf.shape[1]), np.float32)
+    for k in range(C):
+        acc = _fma32(pooled[:, k:k + 1], wf[k][None], acc)
+    return acc + bf
+
+
+# ------------------------------------------------------------------------------------------------------- cost arithmetic
+def classifier_raw(logits):
+    """``[..., ncam, 2]`` -> ``-log(softmax[1] + 1e-5)`` summed over views."""
+    z = np.asarray(logits, dtype=np.float64)
+    z = z - z.max(axis=-1, keepdims=True)
+    p = np.exp(z) / np.exp(z).sum(axis=-1, keepdims=True)
+    return (-np.log(p[..., 1] + LOG_SHIFT)).sum(axis=-1)
+
+
+def embedding_raw(goal_enc, enc):
+    """``goal_enc [ncam, D]``, ``enc [..., ncam, D]`` -> ``-<goal, enc>`` summed over views."""
+    return -(np.asarray(goal_enc, dtype=np.float64) * np.asarray(enc, dtype=np.float64)).sum(axis=-1).sum(axis=-1)
+
+
+def weight_scores(raw, finalweight):
+    raw = np.asarray(raw, dtype=np.float64)
+    if finalweight >= 0:
+        w = np.ones(raw.shape[1])
+        w[-1] = finalweight
+        return (raw * w).sum(axis=1) / w.sum()
+    return raw[:, -1].copy()
+
+
+def learned_cost(head, head_out, goal_enc=None, finalweight=100., n_draws=1):
+    """Head outputs ``[B, T, ncam, D]`` (draw-minor) -> (scores [A], cost_per_step [A, T])."""
+    raw = classifier_raw(head_out) if head == 'classifier' else embedding_raw(goal_enc, head_out)
+    A = raw.shape[0] // n_draws
+    scores = weight_scores(raw, finalweight).reshape(A, n_draws).mean(axis=1)
+    return scores, raw.reshape(A, n_draws, -1).mean(axis=1)
+
+
+class OracleFrameScorer(object):
+    """The float64 oracle behind the scorer duck-type of the controllers (``embed`` / ``goal_enc``): what drives a
+    controller together with the oracle predictor in the elite-parity test."""
+
+    def __init__(self, weights, cfg, ncam=1, dtype=torch.float64):
+        self.weights, self.cfg, self.n_cam, self.dtype = weights, cfg, ncam, dtype
+
+    def embed(self, images, tower='frames'):
+        return forward_views(self.weights[tower], np.asarray(images), self.cfg.input_scale, self.dtype)
+
+    def goal_enc(self, goal_image, start_image):
+        pair = np.concatenate([np.asarray(goal_image, np.float32), np.asarray(start_image, np.float32)], axis=-1)
+        return self.embed(pair[None], 'goal')[0]

@@ -174,6 +174,82 @@ int main() {
                 }
             }
         }
+        // the frame scorer (learned-cost planning): table, buffers and packer for both heads and the three sizes; injected
+        // failures in vf_scorer_create / vf_scorer_load_weights; the refusals of vf_scorer_scores / vf_scorer_embed
+        {
+            const int sizes[3][2] = {{64, 64}, {48, 64}, {128, 128}};
+            for (int head = 0; head < 2; ++head)
+                for (const auto &sz : sizes) {
+                    vf_scorer_config sc = {sz[0], sz[1], 2, head, 24, 50, 0, head ? 255.f : 1.f};
+                    vf_scorer *s = nullptr;
+                    if (vf_scorer_create(&sc, &s)) { std::fprintf(stderr, "vf_scorer_create: %s\n", vf_last_error()); rc = 1; continue; }
+                    for (int tower = 0; tower <= head; ++tower) {
+                        const size_t n = vf_scorer_weight_count(&sc, tower) * 2;
+                        std::vector<float> w(n, 0.01f);
+                        if (n == 0 || vf_scorer_load_weights(s, tower, w.data(), n) || vf_scorer_load_weights(s, tower, w.data(), n)) {
+                            std::fprintf(stderr, "vf_scorer_load_weights: %s\n", vf_last_error()); rc = 1;
+                        }
+                        if (vf_scorer_load_weights(s, tower, w.data(), n - 1) == 0) { std::fprintf(stderr, "short scorer blob accepted\n"); rc = 1; }
+                    }
+                    if (vf_scorer_load_weights(s, head + 1, nullptr, 0) == 0) { std::fprintf(stderr, "bad tower accepted\n"); rc = 1; }
+                    if (vf_scorer_destroy(s)) rc = 1;
+                }
+            vf_scorer_config bad_sc = {40, 64, 1, 0, 2, 10, 0, 1.f};
+            vf_scorer *s = nullptr;
+            if (vf_scorer_create(&bad_sc, &s) == 0 || vf_scorer_weight_count(&bad_sc, 0) != 0) { std::fprintf(stderr, "scorer at 40x64 accepted\n"); rc = 1; }
+            vf_scorer_config sc = {64, 64, 1, 1, 16, 100, 0, 255.f};
+            for (int kind = 0; kind < 3; ++kind) {
+                vf_selftest_inject(4, kind);
+                s = reinterpret_cast<vf_scorer *>(1);
+                const int r = vf_scorer_create(&sc, &s);
+                if (r != want_code[kind] || s != nullptr || std::string(vf_last_error()) != want_msg[kind]) {
+                    std::fprintf(stderr, "vf_scorer_create under injected failure %d: rc %d, '%s'\n", kind, r, vf_last_error()); rc = 1;
+                }
+            }
+            if (vf_scorer_create(&sc, &s)) { std::fprintf(stderr, "vf_scorer_create after the injected failures: %s\n", vf_last_error()); rc = 1; s = nullptr; }
+            const size_t n0 = vf_scorer_weight_count(&sc, 0);
+            std::vector<float> w(n0, 0.01f);
+            double score = 0.0;
+            alignas(16) float img[4];
+            if (s && hh) {
+                if (vf_scorer_scores(s, hh, img, 100.f, &score, nullptr, nullptr, nullptr) != VF_ERR_INVALID ||
+                    std::string(vf_last_error()).find("not loaded") == std::string::npos) { std::fprintf(stderr, "scores before weights: '%s'\n", vf_last_error()); rc = 1; }
+                for (int kind = 0; kind < 3; ++kind) {
+                    vf_selftest_inject(5, kind);
+                    const int r = vf_scorer_load_weights(s, 0, w.data(), n0);
+                    if (r != want_code[kind] || std::string(vf_last_error()) != want_msg[kind]) {
+                        std::fprintf(stderr, "vf_scorer_load_weights under injected failure %d: rc %d, '%s'\n", kind, r, vf_last_error()); rc = 1;
+                    }
+                    if (vf_scorer_load_weights(s, 0, w.data(), n0)) { std::fprintf(stderr, "scorer reload after failure: %s\n", vf_last_error()); rc = 1; }
+                }
+                struct { vf_scorer *s; vf_handle *h; const float *g; double *out; const char *msg; } refusals[] = {
+                    {nullptr, hh, img, &score, "null argument"}, {s, nullptr, img, &score, "null argument"},
+                    {s, hh, img, nullptr, "null argument"},      {s, hh, nullptr, &score, "d_goal_enc"},
+                    {s, hh, img, &score, "not rolled"}};
+                for (const auto &c : refusals) {
+                    const int r = vf_scorer_scores(c.s, c.h, c.g, 100.f, c.out, nullptr, nullptr, nullptr);
+                    if (r != VF_ERR_INVALID || std::string(vf_last_error()).find(c.msg) == std::string::npos) {
+                        std::fprintf(stderr, "vf_scorer_scores: want refusal '%s', got rc %d '%s'\n", c.msg, r, vf_last_error()); rc = 1;
+                    }
+                }
+                vf_scorer_config sc48 = {48, 64, 1, 0, 2, 100, 0, 1.f};
+                vf_scorer *s48 = nullptr;
+                if (vf_scorer_create(&sc48, &s48) == 0) {
+                    if (vf_scorer_scores(s48, hh, nullptr, 100.f, &score, nullptr, nullptr, nullptr) != VF_ERR_INVALID ||
+                        std::string(vf_last_error()).find("image size") == std::string::npos) { std::fprintf(stderr, "size mismatch: '%s'\n", vf_last_error()); rc = 1; }
+                    vf_scorer_destroy(s48);
+                } else rc = 1;
+                float out4[4];
+                if (vf_scorer_embed(s, 1, img, 1, out4, nullptr) != VF_ERR_INVALID || std::string(vf_last_error()).find("not loaded") == std::string::npos) rc = 1;
+                if (vf_scorer_embed(s, 2, img, 1, out4, nullptr) != VF_ERR_INVALID || std::string(vf_last_error()).find("tower") == std::string::npos) rc = 1;
+                if (vf_scorer_embed(s, 0, img, 101, out4, nullptr) != VF_ERR_INVALID || std::string(vf_last_error()).find("max_frames") == std::string::npos) rc = 1;
+                if (vf_scorer_embed(s, 0, img + 1, 1, out4, nullptr) != VF_ERR_INVALID || std::string(vf_last_error()).find("aligned") == std::string::npos) rc = 1;
+                if (vf_scorer_embed(s, 0, nullptr, 1, out4, nullptr) != VF_ERR_INVALID) rc = 1;
+            }
+            if (s && vf_scorer_destroy(s)) { std::fprintf(stderr, "vf_scorer_destroy failed\n"); rc = 1; }
+            std::printf("  frame scorer: both heads at 64x64 / 48x64 / 128x128, injected failures in vf_scorer_create / vf_scorer_load_weights, refusals: %s\n",
+                        rc ? "FAILED" : "ok");
+        }
         if (hh && vf_destroy(hh)) { std::fprintf(stderr, "vf_destroy after the injected failures failed\n"); rc = 1; }
         std::printf("  injected failures (bad_alloc, std::exception, foreign) in vf_create / vf_load_weights / build_schedule: %s\n",
                     rc ? "FAILED" : "status codes returned, handle reusable");

@@ -14,7 +14,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(_HERE)
 LIB_PATH = os.environ.get('VF_LIBRARY') or os.path.join(_HERE, 'libvf_hip.so')     # override: experiments only
 SOURCES = [os.path.join(_HERE, 'csrc', f) for f in
-           ('vf_engine.hip', 'vf_conv_mfma.h', 'vf_conv_gsplit.h', 'vf_small_kernels.h', 'vf_goal_image.h', 'vf_plan_render.h', 'vf_persistent.h',
+           ('vf_engine.hip', 'vf_conv_mfma.h', 'vf_conv_gsplit.h', 'vf_small_kernels.h', 'vf_goal_image.h', 'vf_plan_render.h', 'vf_frame_scorer.h',
+            'vf_engine_scorer.inc', 'vf_persistent.h',
             'vf_conv_bf16x6.h', 'vf_fused_top.h', 'vf_fc_tile.h', 'vf_conv_first.h', 'vf_savp3.h', 'vf_engine_savp3.inc')] + \
           [os.path.join(REPO, 'include', 'vf_hip.h')]
 
@@ -25,7 +26,9 @@ EXPORTS = ('vf_abi_version', 'vf_last_error', 'vf_weight_count', 'vf_create', 'v
            'vf_macs_per_sample_step', 'vf_set_profiling', 'vf_get_profile',
            'vf_set_dedup', 'vf_set_persistent', 'vf_set_xcd_queues', 'vf_set_fuse_top', 'vf_device_status',
            'vf_set_phase_stats', 'vf_debug_phase_stats', 'vf_debug_poison_status', 'vf_set_sched_option',
-           'vf_ensemble_scores', 'vf_goal_image_scores', 'vf_render_plans')
+           'vf_ensemble_scores', 'vf_goal_image_scores', 'vf_render_plans',
+           'vf_scorer_weight_count', 'vf_scorer_create', 'vf_scorer_destroy', 'vf_scorer_load_weights', 'vf_scorer_embed',
+           'vf_scorer_scores')
 ABI_VERSION = 7
 
 
@@ -37,6 +40,11 @@ class VfConfig(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in
                 ('height', 'width', 'adim', 'sdim', 'ndesig', 'n_context', 'sequence_length',
                  'num_masks', 'max_batch', 'device', 'precision', 'ncam', 'n_draws', 'arch', 'zdim', 'layer_spec')]
+
+
+class VfScorerConfig(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ('height', 'width', 'ncam', 'head', 'embed_dim', 'max_frames', 'device')] + \
+               [('input_scale', ctypes.c_float)]
 
 
 def _hipcc():
@@ -105,6 +113,13 @@ def load_library():
                                        ctypes.POINTER(ctypes.c_float), P, P, P, P]
     lib.vf_goal_image_scores.argtypes = [P, P, ctypes.c_int32, ctypes.c_float, ctypes.c_int32, P, P, P, P]
     lib.vf_render_plans.argtypes = [P, P, ctypes.c_int32, P, P, P, P]
+    lib.vf_scorer_weight_count.restype = ctypes.c_size_t
+    lib.vf_scorer_weight_count.argtypes = [ctypes.POINTER(VfScorerConfig), ctypes.c_int32]
+    lib.vf_scorer_create.argtypes = [ctypes.POINTER(VfScorerConfig), ctypes.POINTER(P)]
+    lib.vf_scorer_destroy.argtypes = [P]
+    lib.vf_scorer_load_weights.argtypes = [P, ctypes.c_int32, P, ctypes.c_size_t]
+    lib.vf_scorer_embed.argtypes = [P, ctypes.c_int32, P, ctypes.c_int32, P, P]
+    lib.vf_scorer_scores.argtypes = [P, P, P, ctypes.c_float, P, P, P, P]
     lib.vf_register.argtypes = [P, P, P, P, P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, P, P, P, P, P]
     lib.vf_allgather_scores.argtypes = [P, P, P, ctypes.c_int32, P, P]
     lib.vf_comm_init_all.argtypes = [ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(P)]
@@ -132,7 +147,8 @@ def load_library():
     lib.vf_set_persistent.restype = lib.vf_device_status.restype = ctypes.c_int
     lib.vf_set_profiling.restype = lib.vf_get_profile.restype = ctypes.c_int
     for name in ('vf_create', 'vf_destroy', 'vf_load_weights', 'vf_set_context', 'vf_rollout', 'vf_ensemble_scores',
-                 'vf_goal_image_scores', 'vf_render_plans',
+                 'vf_goal_image_scores', 'vf_render_plans', 'vf_scorer_create', 'vf_scorer_destroy',
+                 'vf_scorer_load_weights', 'vf_scorer_embed', 'vf_scorer_scores',
                  'vf_export', 'vf_register', 'vf_allgather_scores', 'vf_comm_init_all', 'vf_comm_destroy',
                  'vf_allgather_scores_group', 'vf_set_phase_stats',
                  'vf_debug_phase_stats', 'vf_debug_poison_status'):

@@ -36,6 +36,7 @@
 #include "vf_conv_mfma.h"
 #include "vf_small_kernels.h"
 #include "vf_goal_image.h"
+#include "vf_frame_scorer.h"
 #include "vf_plan_render.h"
 #include "vf_conv_bf16x6.h"
 #include "vf_persistent.h"
@@ -3051,3 +3052,5 @@ int vf_get_profile(vf_handle *h, double *kernel_ms, int64_t *launches, double *f
 
 }  // extern "C"
 #endif  // VF_HOST_SELFTEST
+
+#include "vf_engine_scorer.inc"

@@ -139,6 +139,8 @@ class HipVPredEvaluation(object):
         self._last_lo = 0
         self._last_prepared = None      # (engine context, sequences, M) of the last score() / __call__
         self.last_goal_cost_per_step = None     # [M, ncam, T] of the last score_goal_image()
+        self.last_frame_cost_per_step = None    # [M, T] of the last score_frames()
+        self._lane_scorers = {}                 # id(scorer) -> (scorer, its copy on this lane's device); one entry per scorer seen
         # in-process multi-GPU: this object is lane 0, the others are plain engines on the following devices
         self.gather = str(hp.get('gather', 'auto'))         # 'auto' | 'rccl' | 'host'
         if self.gather not in ('auto', 'rccl', 'host'):
@@ -483,6 +485,117 @@ class HipVPredEvaluation(object):
         self._check_scores(scores_np)
         self.last_goal_cost_per_step = np.ascontiguousarray(rows_np[:, 1 + ncam:]).reshape(M, ncam, T)
         return scores_np, np.ascontiguousarray(rows_np[:, 1:1 + ncam])
+
+    # ------------------------------------------------------------------ learned cost (frame scorer)
+    def _scorer_here(self, scorer):
+        """``scorer`` if it lives on this engine's device, else its cached copy here (one scorer per lane device)."""
+        if scorer.device == self.device:
+            return scorer
+        hit = self._lane_scorers.get(id(scorer))
+        if hit is None or hit[0] is not scorer:         # (the entry keeps the scorer alive, so its id stays its own)
+            hit = (scorer, scorer.clone_to(self.device))
+            self._lane_scorers[id(scorer)] = hit
+            while len(self._lane_scorers) > 4:          # a handful of scorers (two heads, a swap); older copies are freed
+                self._lane_scorers.pop(next(iter(self._lane_scorers)))
+        return hit[1]
+
+    def _frame_rows(self, context, seqs, n, index_base, scorer, goal_enc, finalweight):
+        """Roll ``n`` actions on this engine and score every chunk's resident frames -> device rows ``[n, 1 + T]`` =
+        [score | cost per step]."""
+        torch, ncam, c = self._torch, self.n_cam, self.cfg
+        T = self.sequence_length - self.n_context
+        scorer = self._scorer_here(scorer)
+        goal_dev = None if goal_enc is None else torch.from_numpy(goal_enc).to(self.device)
+        rows = torch.empty((n, 1 + T), dtype=torch.float64, device=self.device)
+        bs = self.run_batch_size // self.n_draws
+        c_s = torch.empty(bs, dtype=torch.float64, device=self.device)
+        c_cps = torch.empty((bs, T), dtype=torch.float64, device=self.device)
+
+        def reduce_chunk(c0, c1):
+            _lib.check(self._libh.vf_scorer_scores(
+                scorer._handle, self._handle, None if goal_dev is None else goal_dev.data_ptr(),
+                ctypes.c_float(finalweight), c_s.data_ptr(), c_cps.data_ptr(), None, self._stream()))
+            k = c1 - c0
+            rows[c0:c1, 0], rows[c0:c1, 1:] = c_s[:k], c_cps[:k]
+
+        centre = np.tile(np.array([c.height // 2, c.width // 2], np.int32), (ncam, c.ndesig, 1))
+        self._score_prepared(context, seqs, n, centre, 1.0, index_base=index_base, after_chunk=reduce_chunk)
+        return rows
+
+    def score_resident_frames(self, scorer, goal_enc=None, finalweight=100.):
+        """Score the frames of this engine's LAST rollout chunk again, head outputs included -> (scores [A], cost per
+        step [A, T], head outputs [B, T, ncam, D]) on the host; A = B / n_draws.  For tests and measurements."""
+        torch = self._torch
+        T = self.sequence_length - self.n_context
+        A, B = self._last_M, self._last_M * self.n_draws
+        scorer = self._scorer_here(scorer)
+        with torch.cuda.device(self.device):
+            goal_dev = None if goal_enc is None else torch.from_numpy(np.ascontiguousarray(goal_enc, np.float32)).to(self.device)
+            s = torch.empty(A, dtype=torch.float64, device=self.device)
+            cps = torch.empty((A, T), dtype=torch.float64, device=self.device)
+            out = torch.empty((B, T, self.n_cam, scorer.cfg.out_dim), dtype=torch.float32, device=self.device)
+            _lib.check(self._libh.vf_scorer_scores(
+                scorer._handle, self._handle, None if goal_dev is None else goal_dev.data_ptr(),
+                ctypes.c_float(finalweight), s.data_ptr(), cps.data_ptr(), out.data_ptr(), self._stream()))
+            return s.cpu().numpy(), cps.cpu().numpy(), out.cpu().numpy()
+
+    def score_frames(self, context, inputs, scorer, goal_enc=None, finalweight=100.):
+        """Fused rollout + learned cost (reference ``policy/cem_controllers/variants/classifier_controller.py:94-105``,
+        ``nce_cost_controller.py:90-103``): every predicted frame goes through ``scorer`` (a ``HipFrameScorer``) where
+        it lies in the engine, and only score rows leave the GPU.  Returns ``scores[M]`` float64;
+        ``last_frame_cost_per_step`` ``[M, T]`` keeps the per-step cost summed over views (averaged over latent draws).
+
+        Classifier head: ``-log(p_success + 1e-5)``; embedding head: ``-<goal_enc, frame embedding>`` with ``goal_enc
+        [ncam, D]`` from ``scorer.goal_enc(goal, start)``.  Both are SUMMED over views, then weighted over time by
+        ``_weight_scores`` (``finalweight >= 0``: ``w = (1, ..., 1, finalweight)``; ``< 0``: the last step alone).
+
+        Sharding, chunking, lanes and latent draws are those of ``score`` (with ``n_gpus > 1`` the scorer is copied to
+        every lane's device once).  As in ``score_goal_image`` the image centre stands in for the goal pixels and
+        the distribution context the rollout entry wants."""
+        c, ncam, nd = self.cfg, self.n_cam, self.n_draws
+        T = self.sequence_length - self.n_context
+        if (scorer.cfg.height, scorer.cfg.width, scorer.n_cam) != (c.height, c.width, ncam):
+            raise ValueError('the scorer is built for %dx%d, %d view(s); the predictor rolls %dx%d, %d view(s)'
+                             % (scorer.cfg.height, scorer.cfg.width, scorer.n_cam, c.height, c.width, ncam))
+        if scorer.cfg.head == 'embedding':
+            if goal_enc is None:
+                raise ValueError('the embedding head needs goal_enc [ncam, D]')
+            goal_enc = np.ascontiguousarray(goal_enc, dtype=np.float32)
+            if goal_enc.shape != (ncam, scorer.cfg.out_dim):
+                raise ValueError('goal_enc must be [%d, %d], got %s' % (ncam, scorer.cfg.out_dim, goal_enc.shape))
+        else:
+            goal_enc = None
+        actions = self._check_actions(inputs['actions'])
+        M = actions.shape[0]
+        centre = np.zeros((self.n_context, ncam, c.height, c.width, c.ndesig), np.float32)
+        centre[:, :, c.height // 2, c.width // 2, :] = 1.0
+        ctx_p, seqs = self._prepare(dict(context, context_pixel_distributions=centre), actions)
+        self._last_prepared = (ctx_p, seqs, M)
+        rank, world = _dist_info()
+        torch = self._torch
+        if self._lanes:
+            packed = []
+            for i, lane in enumerate(self._lanes):
+                lo, hi = shard_bounds(M, i, len(self._lanes))
+                with torch.cuda.device(lane.device):
+                    if hi > lo:
+                        packed.append(lane._frame_rows(ctx_p, seqs[lo * nd:hi * nd], hi - lo, lo, scorer, goal_enc,
+                                                       finalweight))
+                    else:
+                        lane._last_lo, lane._last_M = lo, 0
+                        packed.append(torch.empty((0, 1 + T), dtype=torch.float64, device=lane.device))
+            rows_np = self._gather_lane_rows(packed, M)
+        else:
+            lo, hi = shard_bounds(M, rank, world)
+            with torch.cuda.device(self.device):
+                rows = self._frame_rows(ctx_p, seqs[lo * nd:hi * nd], hi - lo, lo, scorer, goal_enc, finalweight)
+                if world > 1:
+                    rows = all_gather_rows(rows, M)
+                rows_np = rows.cpu().numpy()
+        scores_np = np.ascontiguousarray(rows_np[:, 0])
+        self._check_scores(scores_np)
+        self.last_frame_cost_per_step = np.ascontiguousarray(rows_np[:, 1:])
+        return scores_np
 
     # ------------------------------------------------------------------ in-process multi-GPU (n_gpus > 1)
     def _score_lanes(self, context, seqs, M, goal_pix, finalweight, task_weights):

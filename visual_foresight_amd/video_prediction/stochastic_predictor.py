@@ -84,3 +84,13 @@ class StochasticHipPredictor(HipVPredEvaluation):
                 context, inputs, goal_image, steps=steps, finalweight=finalweight, first_view_only=first_view_only)
         finally:
             self._z = None
+
+    def score_frames(self, context, inputs, scorer, goal_enc=None, finalweight=100.):
+        T = np.asarray(inputs['actions']).shape[1]
+        self._z = self.draw_latents(T)          # as score(): one set of draws per scoring call
+        self._calls += 1
+        try:
+            return super(StochasticHipPredictor, self).score_frames(context, inputs, scorer, goal_enc=goal_enc,
+                                                                    finalweight=finalweight)
+        finally:
+            self._z = None
