@@ -69,6 +69,7 @@ int main() {
     rc |= run_case(48, 64, 3, 3, 2, 2, 2, 37, 1, 1, 1, b_small, 4);
     rc |= run_case(64, 64, 4, 5, 1, 1, 2, 16, 0, 1, 1, b_small, 3);
     rc |= run_case(64, 64, 4, 5, 1, 2, 13, 200, 0, 1, 1, b_c2, 3);
+    rc |= run_case(64, 64, 4, 5, 1, 1, 2, 200, 0, 1, 1, b_c2, 3);    // one context frame at batches that take the 64- / 128-row plans
     rc |= run_case(64, 64, 4, 5, 2, 2, 13, 600, 0, 2, 1, b_c3, 2);
     rc |= run_case(128, 128, 12, 5, 1, 2, 15, 50, 1, 1, 5, b_c5, 2);
     rc |= run_case(40, 56, 5, 5, 4, 2, 2, 16, 0, 3, 1, b_small, 3);

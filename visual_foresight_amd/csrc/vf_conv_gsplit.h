@@ -134,6 +134,10 @@ __device__ __forceinline__ void conv_lstm_gsplit2_tile(const PT &p, const int bx
     for (int m = 0; m < MR; ++m)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[m][0][r] = 0.f;
+    // (the recurrent chunks' sums come from the shared partial, ConvParams::acc_init; chunk_begin points behind them)
+    if constexpr (!RAW) {
+        if (p.acc_init != nullptr) gs_acc_init<MR>(p, acc, cg, ty0, tx0);
+    }
 
     const int Ntot = p.ncg * G * 32;
     const int total_chunks = p.seg[0].nchunk + (p.nseg > 1 ? p.seg[1].nchunk : 0);

@@ -189,12 +189,20 @@ struct ConvParams {
     // arch 2: the per-sample border-class biases of the tiled conditioning vector, [B][25][4 Cout] (cond_bias_sample,
     // vf_small_kernels.h), added to the gate pre-activations in the conv-LSTM epilogue; null: none
     const float *cond_bias;
-    // gate-split tile only: first channel chunk of the K loop.  A conv-LSTM's recurrent input is all zeros at the first step
-    // of a rollout - its chunks (segment 0) contribute nothing and are skipped (arch 3; 0 = every chunk)
+    // gate-split tiles only (vf_conv_gsplit.h and the 64-row conv_tile<4, EPI_LSTM, 1, PT, -2>; every other body runs every
+    // chunk): first channel chunk of the K loop, 0 = every chunk.  The chunks in front of it are segment 0, the recurrent
+    // input: all zeros at the first step of a rollout, where they contribute nothing (arch 3), or already summed in acc_init
+    // (arch 0-2, the shared recurrent partial)
     int chunk_begin;
     // gate-split 128-row tile only: skip the row blocks of a kernel row whose every product multiplies zero padding
     // (vf_conv_gsplit.h, "pad skip"; vf_handle::pad_skip, VF_PAD_SKIP=0 turns it off)
     int pad_skip;
+    // gate-split 128- and 64-row tiles, one image per tile: the accumulators start from this image of raw gate sums,
+    // [pixel][4 Cout] with gate-major columns as gates_raw_epilogue stores it, instead of from zero (gs_acc_init).  Set
+    // together with chunk_begin = seg[0].nchunk at the step where the recurrent input is still one image for every sample:
+    // the sums of the recurrent chunks are computed once for all of them (vf_engine.hip, "shared recurrent partial").
+    // null: start from zero
+    const float *acc_init;
 };
 
 constexpr unsigned kLateSpinLimit = 1u << 26;   // polls before a mid-item wait gives up (as kSpinLimit)
@@ -710,6 +718,37 @@ __device__ __forceinline__ void static_for_impl(F &&f, std::integer_sequence<int
 template <int N, class F>
 __device__ __forceinline__ void static_for(F &&f) { static_for_impl(f, std::make_integer_sequence<int, N>{}); }
 
+// Accumulator start of a gate-split conv-LSTM tile (ConvParams::acc_init; one image per tile): wave w holds gate w, lane
+// (n, kh) column cg * 32 + n of it, and accumulator r of row block m belongs to GEMM row m * 32 + (r & 3) + 8 (r >> 2) +
+// 4 kh (the MFMA layout lstm_gsplit_epilogue reads too).  The four rows of an r >> 2 group are four consecutive pixels of
+// one image row (the host plans this only for tile and image widths that are multiples of 4), so a lane works out four
+// pixel offsets per row block and the 32 lanes of a half wave read 128 consecutive bytes per load.  Rows
+// outside the tile or the image read pixel 0: their accumulators are never stored.  fp32 out, fp32 back in: the item
+// continues the fma chain the partial's producer stopped at, bit for bit.
+template <int MR, class PT>
+__device__ __forceinline__ void gs_acc_init(const PT &p, f32x16 (&acc)[MR][1], const int cg, const int ty0, const int tx0) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int n = lane & 31, kh = lane >> 5;
+    const unsigned px_b = (unsigned)(4 * p.Cout) * 4u;                      // bytes per pixel
+    const unsigned col_b = (unsigned)(wave * p.Cout + cg * 32 + n) * 4u;
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<float *>(p.acc_init), 0, (int)((unsigned)(p.Hout * p.Wout) * px_b), 0x00020000);
+    const TileDiv div_tw(p.TW);
+#pragma unroll
+    for (int m = 0; m < MR; ++m)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int rem = m * 32 + 8 * j + 4 * kh;
+            const int yy = div_tw.div(rem);
+            const int y = ty0 + yy, x = tx0 + rem - yy * p.TW;
+            const bool ok = rem < p.TH * p.TW && y < p.Hout && x < p.Wout;
+            const unsigned off = (ok ? (unsigned)(y * p.Wout + x) * px_b : 0u) + col_b;
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                acc[m][0][4 * j + i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, off, (unsigned)i * px_b, 0));
+        }
+}
+
 // Epilogue of the gate-split conv-LSTM tiles (vf_conv_gsplit.h: MR = 4 row blocks; conv_tile<4, EPI_LSTM, 1, PT, -2>: 2;
 // the 32-row tile: 1): wave w holds gate w of all MR row blocks.  The gate pre-activations cross through LDS (xch: [MR row
 // blocks][4 gates][16][64 lanes] floats = 64 KiB at MR 4, over the dead operand tile) and every wave finishes its part of
@@ -1154,11 +1193,16 @@ __device__ __forceinline__ void conv_tile(const PT &p, const int bx_, const int 
         for (int g = 0; g < GA; ++g)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[m][g][r] = 0.f;
+    // (the 64-row gate-split tile: the recurrent chunks' sums come from the shared partial, ConvParams::acc_init, and
+    // the K loop starts behind them)
+    if constexpr (GSPLIT) {
+        if (p.acc_init != nullptr) gs_acc_init<MR>(p, acc, cg, ty0, tx0);
+    }
 
     const int ntaps = p.KH * p.KW;
     const int Ntot = p.ncg * G * 32;
     const int total_chunks = p.seg[0].nchunk + (p.nseg > 1 ? p.seg[1].nchunk : 0);
-    const int ch_begin = bz * p.chunks_per_split;
+    const int ch_begin = bz * p.chunks_per_split + (GSPLIT ? p.chunk_begin : 0);
     const int ch_end = min(ch_begin + p.chunks_per_split, total_chunks);
     const float *wlane = p.Wp + ((long long)kh * Ntot + (cg * G) * 32 + n) * 4;
     const long long wstep = (long long)2 * Ntot * 4;        // floats per (chunk, tap, k8) block

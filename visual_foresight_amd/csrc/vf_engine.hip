@@ -434,6 +434,8 @@ struct BatchView {
     float *c_state[7], *h_state[7][2];
     long long *st_enc0, *st_h[7], *st_enc6, *st_enc00, *st_enc7;
     float *sbias, *fc_part, *kern;
+    float *rec_part[7];                 // shared views only: raw gate sums of lstm k's recurrent chunks, [pixel][4C] (emit_rollout,
+                                        // "shared recurrent partial")
     float *cond_bias[7][2];             // (two buffers, by step parity: the biases of step s + 1 are computed while the
                                         //  epilogues of step s still read theirs)
     float *frames_all, *distrib_all, *states_all;
@@ -546,6 +548,9 @@ struct vf_handle {
     bool wt_publish = VF_WT_DEFAULT != 0;   // conv-LSTM tiles publish write-through (ConvParams::wt_out, no release fence)
     bool pad_skip = true;               // the gate-split tile leaves out kernel rows that read only padding (ConvParams::pad_skip;
                                         // VF_PAD_SKIP=0 at vf_create runs the full K loop - same bits, for A/B runs and tests)
+    bool share_recurrent = true;        // the recurrent gate sums on a still shared h(s-1) are computed once for every sample
+                                        // (emit_rollout, "shared recurrent partial"; VF_SHARE_RECURRENT=0 at vf_create: every
+                                        // sample computes them itself - same bits, for A/B runs and tests)
     int yield_budget = -1;              // cooperative CU priority ("yielding", vf_conv_mfma.h): polls an early-started conv-LSTM
                                         // item may spend yielding to its CU partner; 0 = off, -1 = by batch size (yield_for)
     bool pair_allowed = true;           // (-DVF_DEBUG_KNOBS: VF_FUSE_PAIR=0, read once in vf_create)
@@ -1078,6 +1083,8 @@ static int cdna_create(vf_handle *h) {
             VF_ALLOC(sv.h_state[k][0], per);
             VF_ALLOC(sv.h_state[k][1], per);
             VF_ALLOC(sv.st_h[k], (size_t)h->st_rows[k] * 2);
+            // (the shared recurrent partial's image: only where a unit can be emitted - emit_rollout)
+            if (h->share_recurrent && h->lstm[k].tile == TILE_LSTM_GS128) VF_ALLOC(sv.rec_part[k], 4 * per);
         }
         VF_ALLOC(sv.st_enc0, (size_t)h->enc0.stats_nparts * 2);
         if (h->savp) {
@@ -1112,6 +1119,7 @@ int vf_create(const vf_config *cfg, vf_handle **out) {
     made = h;
     h->cfg = *cfg;
     if (const char *e = getenv("VF_PAD_SKIP")) h->pad_skip = atoi(e) != 0;     // (A/B and bit-identity tests; read once)
+    if (const char *e = getenv("VF_SHARE_RECURRENT")) h->share_recurrent = atoi(e) != 0;   // (likewise)
     h->ncam = std::max(1, cfg->ncam);
     h->n_draws = std::max(1, cfg->n_draws);
     h->cfg.ncam = h->ncam; h->cfg.n_draws = h->n_draws;
@@ -1398,23 +1406,27 @@ struct LaunchSink {
     hipStream_t st;
     static int skipped() { return VF_OK; }
 
+    // a conv-LSTM gate GEMM of arch 0-2 (the cell's item, or the shared recurrent partial): with profiling on, bracketed by
+    // two events and counted with the products it executes
+    template <class F>
+    int profiled_lstm(const ConvLayer &l, const ConvParams &p, F launch) {
+        if (!h->profiling) return launch();
+        while (h->ev_pool.size() < h->ev_used + 2) {
+            hipEvent_t e;
+            VF_HIP_CHECK(hipEventCreate(&e));
+            h->ev_pool.push_back(e);
+        }
+        VF_HIP_CHECK(hipEventRecord(h->ev_pool[h->ev_used], st));
+        int r = launch();
+        VF_HIP_CHECK(hipEventRecord(h->ev_pool[h->ev_used + 1], st));
+        h->ev_used += 2;
+        h->prof_flops += 2.0 * (p.B * l.Hout * l.Wout * 25.0 - (p.pad_skip ? 5.0 * gs_pad_skipped_pairs(l, p.B) : 0.0)) *
+                         (l.segC[0] + (l.nseg > 1 ? l.segC[1] : 0) - p.chunk_begin * l.KC) * 4.0 * l.Cout;
+        return r;
+    }
     int conv(int type, const ConvLayer &l, const ConvParams &p, std::initializer_list<int>) {
         switch (type) {
-            case PH_LSTM: {
-                if (!h->profiling) return launch_lstm(l, p, st);
-                while (h->ev_pool.size() < h->ev_used + 2) {
-                    hipEvent_t e;
-                    VF_HIP_CHECK(hipEventCreate(&e));
-                    h->ev_pool.push_back(e);
-                }
-                VF_HIP_CHECK(hipEventRecord(h->ev_pool[h->ev_used], st));
-                int r = launch_lstm(l, p, st);
-                VF_HIP_CHECK(hipEventRecord(h->ev_pool[h->ev_used + 1], st));
-                h->ev_used += 2;
-                h->prof_flops += 2.0 * (p.B * l.Hout * l.Wout * 25.0 - (p.pad_skip ? 5.0 * gs_pad_skipped_pairs(l, p.B) : 0.0)) *
-                                 (l.segC[0] + l.segC[1]) * 4.0 * l.Cout;
-                return r;
-            }
+            case PH_LSTM: return profiled_lstm(l, p, [&] { return launch_lstm(l, p, st); });
             case PH_CONV_RELU: return launch_conv_t<1, EPI_BIAS_RELU>(l, p, st);
             case PH_CONV_RAW:
                 if (l.tile == TILE_FIRST_VALU) {
@@ -1431,10 +1443,14 @@ struct LaunchSink {
             case PH_CONV_RAW3G2: return l.mrep == 2 ? launch_conv_m<2, EPI_RAW, 2>(l, p, st) : launch_conv_m<2, EPI_RAW, 1>(l, p, st);
             case PH_CONV_RAW3G4: return launch_conv_m<4, EPI_RAW, 1>(l, p, st);
             case PH_GATES_RAW: {
-                const int tiles = l.NI == 1 ? p.B * l.tilesY * l.tilesX : (p.B + l.NI - 1) / l.NI;
-                hipLaunchKernelGGL(conv_gates_raw_kernel, dim3(tiles, l.ncg), dim3(kConvThreads), l.lds_bytes, st, p);
-                VF_HIP_CHECK(hipGetLastError());
-                return VF_OK;
+                auto launch = [&]() -> int {
+                    const int tiles = l.NI == 1 ? p.B * l.tilesY * l.tilesX : (p.B + l.NI - 1) / l.NI;
+                    hipLaunchKernelGGL(conv_gates_raw_kernel, dim3(tiles, l.ncg), dim3(kConvThreads), l.lds_bytes, st, p);
+                    VF_HIP_CHECK(hipGetLastError());
+                    return VF_OK;
+                };
+                // (arch 3's gate GEMMs are not part of the conv-LSTM profile; the shared recurrent partial of arch 0-2 is)
+                return h->cfg.arch == 3 ? launch() : profiled_lstm(l, p, launch);
             }
             default: return launch_conv_t<1, EPI_PARTIAL>(l, p, st);
         }
@@ -1675,6 +1691,16 @@ struct ScheduleSink {
 // rollouts: the CEM iterations of one planning call keep the same context, and every rollout
 // after the first skips them (`skip_shared`) and reads the shared buffers of the first.
 //
+// Shared recurrent partial: at the first step at which conv-LSTM k is per-sample (lstm5-7: n_context - 1, lstm1-4: one
+// step later; arch 2: all seven at n_context - 1) its recurrent input h(s-1) is still the one shared image.  The recurrent chunks lead the K order of every plan
+// and every output is one fma chain, so all samples reach the same accumulator bits before their first per-sample chunk.
+// One batch-1 unit runs those chunks alone and stores the raw fp32 sums ([pixel][4C], the layout of gates_raw_epilogue,
+// which does not depend on the tile plan); the per-sample items start their accumulators from it (ConvParams::acc_init)
+// and their K loop behind the recurrent chunks (chunk_begin).  fp32 stored and reloaded is the same fp32, the rest of the
+// chain is the same products in the same order: bit-identical.  The unit depends on (context, weights) only and is
+// cached across rollouts like every shared unit.  Consumers are the gate-split 128- and 64-row tiles with one image per
+// tile; every other plan keeps its ordinary item.
+//
 // goal_pix: this view's [ND][2] goal pixels (only the per-layer composite kernel reads them from
 // its parameters; the persistent kernel receives all goals as launch arguments).
 template <class Sink>
@@ -1780,6 +1806,27 @@ static int emit_rollout(vf_handle *h, int view, const BatchView &v, const BatchV
         sp.sbias = D.sbias;
         VF_EMIT_SH(u_sa, all_sh, sink.sa(sp, {last}))
 
+        // ---- shared recurrent partials (above) of the conv-LSTMs that turn per-sample at this step, at the head of the
+        // step: their only producer is the same cell of the previous step
+        bool rec_sh[7];
+        int u_part[7];
+        for (int k = 0; k < 7; ++k) {
+            rec_sh[k] = false; u_part[k] = -1;
+            // (rec_part is null with the switch off or a layer without the 128-row gate-split plan.  One context frame: lstm1-4
+            // read a shared h(0) at step 1 as well, but nothing is emitted - that case is not measured, EXPERIMENTS.md S)
+            if (!sh.rec_part[k] || nc < 2 || s < 1 || !lstm_shared(k, s - 1) || lstm_shared(k, s)) continue;
+            const ConvLayer &cl = lstm_plan(k, B);
+            ConvLayer pl = h->lstm[k];          // the recurrent segment alone, on the 128-row gate-split tile
+            if (pl.tile != TILE_LSTM_GS128 || (cl.tile != TILE_LSTM_GS128 && cl.tile != TILE_LSTM_GS64) || cl.NI != 1 ||
+                cl.TW % 4 || cl.Wout % 4 || cl.KC != pl.KC || cl.nchunk[0] != pl.nchunk[0] || pl.segC[0] % pl.KC)
+                continue;
+            pl.nseg = 1; pl.segC[1] = 0; pl.nchunk[1] = 0; pl.chunks_per_split = pl.nchunk[0];
+            ConvParams q = params(pl, 1, plain(sh.h_state[k][cur], 0), nullptr);
+            q.out = sh.rec_part[k];
+            VF_EMIT_SH(u_p, true, sink.conv(PH_GATES_RAW, pl, q, {u_prev[k]}))
+            rec_sh[k] = true; u_part[k] = u_p;
+        }
+
         // ---- arch 2: the conditioning biases of the seven conv-LSTMs of step `sc` (inputs: that step's action / latent and
         // the state the state FC of step sc - 1 produced; two buffers by step parity).  Step 0's are emitted here; those of
         // step s + 1 are emitted in the MIDDLE of step s, behind lstm5 (below): their only producer, this step's state FC, is
@@ -1862,16 +1909,27 @@ static int emit_rollout(vf_handle *h, int view, const BatchView &v, const BatchV
 #endif
             return q;
         };
-        VF_EMIT_SH(u_l1, lstm_shared(0, s), sink.lstm(lstm_plan(0, lstm_shared(0, s) ? 1 : B), lstm_params(0, enc0_n), u_prev[0], u_enc0, u_cond[0]))
-        VF_EMIT_SH(u_l2, lstm_shared(1, s), sink.lstm(lstm_plan(1, lstm_shared(1, s) ? 1 : B), lstm_params(1, h_normed(0)), u_prev[1], u_l1, u_cond[1]))
+        // conv-LSTM k of this step on layer input x (produced by u_x).  With a shared recurrent partial the item starts
+        // from it and needs no early start: the partial's unit (which waited for u_prev[k] itself), the layer input and
+        // the conditioning biases are ordinary dependencies
+        auto emit_lstm = [&](int k, const SegArg &x, int u_x) -> int {
+            const bool shd = lstm_shared(k, s);
+            if (shd && skip_shared) return Sink::skipped();
+            const ConvLayer &l = lstm_plan(k, shd ? 1 : B);
+            ConvParams q = lstm_params(k, x);
+            if (!rec_sh[k]) return sink.lstm(l, q, u_prev[k], u_x, u_cond[k]);
+            q.chunk_begin = q.seg[0].nchunk; q.acc_init = sh.rec_part[k];
+            return sink.conv(PH_LSTM, l, q, {u_part[k], u_x, u_cond[k]});
+        };
+        VF_EMIT(u_l1, emit_lstm(0, enc0_n, u_enc0))
+        VF_EMIT(u_l2, emit_lstm(1, h_normed(0), u_l1))
 
         p = params(h->enc1, BE, h_normed(1), nullptr);
         p.out = E.enc1_o;
         VF_EMIT_SH(u_enc1, enc_sh, sink.conv(PH_CONV_RELU, h->enc1, p, {u_l2}))
 
-        VF_EMIT_SH(u_l3, lstm_shared(2, s), sink.lstm(lstm_plan(2, lstm_shared(2, s) ? 1 : B),
-                                lstm_params(2, plain(E.enc1_o, bs(enc_sh, (long long)H4 * W4 * L[1]))), u_prev[2], u_enc1, u_cond[2]))
-        VF_EMIT_SH(u_l4, lstm_shared(3, s), sink.lstm(lstm_plan(3, lstm_shared(3, s) ? 1 : B), lstm_params(3, h_normed(2)), u_prev[3], u_l3, u_cond[3]))
+        VF_EMIT(u_l3, emit_lstm(2, plain(E.enc1_o, bs(enc_sh, (long long)H4 * W4 * L[1])), u_enc1))
+        VF_EMIT(u_l4, emit_lstm(3, h_normed(2), u_l3))
 
         const ConvLayer &enc2_l = light_plan(h->enc2, h->enc2_one, BE);
         const ConvLayer &enc3_l = light_plan(h->enc3, h->enc3_one, BD);
@@ -1899,8 +1957,7 @@ static int emit_rollout(vf_handle *h, int view, const BatchView &v, const BatchV
             u_enc3 = u_enc3_;
         }
 
-        VF_EMIT_SH(u_l5, lstm_shared(4, s), sink.lstm(lstm_plan(4, lstm_shared(4, s) ? 1 : B),
-                                lstm_params(4, plain(D.enc3_o, bs(all_sh, (long long)H8 * W8 * L[3]))), u_prev[4], u_enc3, u_cond[4]))
+        VF_EMIT(u_l5, emit_lstm(4, plain(D.enc3_o, bs(all_sh, (long long)H8 * W8 * L[3])), u_enc3))
         SegArg h5n = h_normed(4);
 
         // ---- decoder
@@ -1912,8 +1969,7 @@ static int emit_rollout(vf_handle *h, int view, const BatchView &v, const BatchV
             if (Sink::failed(rcn)) return rcn;
         }
         VF_EMIT_SH(u_t1, all_sh, sink.conv(PH_CONVT_RELU, convt1_l, p, {u_l5}))
-        VF_EMIT_SH(u_l6, lstm_shared(5, s), sink.lstm(lstm_plan(5, lstm_shared(5, s) ? 1 : B),
-                                lstm_params(5, plain(D.enc4_o, bs(all_sh, (long long)H4 * W4 * L[4]))), u_prev[5], u_t1, u_cond[5]))
+        VF_EMIT(u_l6, emit_lstm(5, plain(D.enc4_o, bs(all_sh, (long long)H4 * W4 * L[4])), u_t1))
 
         // ---- CDNA kernels (only needed when this step's prediction is used).  The FC needs lstm5 of EVERY sample
         // and its only consumer is the compositing at the end of the step: it is emitted here, behind lstm6, where
@@ -1933,8 +1989,7 @@ static int emit_rollout(vf_handle *h, int view, const BatchView &v, const BatchV
         p = params(h->convt2, BD, enc1_s, &h6n);        // the skip tensor first: it exists since the encoder (early start)
         p.out = D.enc5_o;
         VF_EMIT_SH(u_t2, all_sh, sink.conv_late(PH_CONVT_RELU, h->convt2, p, u_enc1, u_l6))
-        VF_EMIT_SH(u_l7, lstm_shared(6, s), sink.lstm(lstm_plan(6, lstm_shared(6, s) ? 1 : B),
-                                lstm_params(6, plain(D.enc5_o, bs(all_sh, (long long)H2 * W2 * h->c_t2))), u_prev[6], u_t2, u_cond[6]))
+        VF_EMIT(u_l7, emit_lstm(6, plain(D.enc5_o, bs(all_sh, (long long)H2 * W2 * h->c_t2)), u_t2))
         last = u_l7;
         {
             const int now[7] = {u_l1, u_l2, u_l3, u_l4, u_l5, u_l6, u_l7};
@@ -2205,6 +2260,17 @@ extern "C" int vf_selftest_schedule(vf_handle *h, int32_t B, int32_t skip_shared
             }
             ok = ok && in_allocs(h, c.Wp, 16) && in_allocs(h, c.bias, 4) && in_allocs(h, c.out, 4);
             ok = ok && in_allocs(h, c.cstate, 4) && in_allocs(h, c.cstate_in, 4) && in_allocs(h, c.stats, 8);
+            // the shared recurrent partial: one image of raw gate sums, written by a batch-1 PH_GATES_RAW unit and read by
+            // items that skip exactly the recurrent chunks
+            const size_t gates_bytes = (size_t)c.Hout * c.Wout * 4 * c.Cout * 4;
+            if (P.type == PH_GATES_RAW) ok = ok && in_allocs(h, c.out, (size_t)P.B * gates_bytes);
+            // a K loop that starts behind chunk 0 exists in the gate-split bodies only (every other body ignores chunk_begin)
+            if (c.chunk_begin != 0)
+                ok = ok && (P.type == PH_GATES_RAW ||
+                            (P.type == PH_LSTM && (P.tile == TILE_LSTM_GS128 || P.tile == TILE_LSTM_GS64)));
+            if (c.acc_init)
+                ok = ok && in_allocs(h, c.acc_init, gates_bytes) && P.type == PH_LSTM && P.NI == 1 && !P.has_late &&
+                     (P.tile == TILE_LSTM_GS128 || P.tile == TILE_LSTM_GS64) && c.chunk_begin == c.seg[0].nchunk;
         }
         // a write-through item must be one whose every store is a 16-byte sc1 store (restated here, not read from wt_epilogue)
         if (P.conv.wt_out != 0) {
