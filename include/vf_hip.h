@@ -252,6 +252,41 @@ int vf_scorer_embed(vf_scorer *s, int32_t tower, const float *d_images, int32_t 
 int vf_scorer_scores(vf_scorer *s, vf_handle *h, const float *d_goal_enc, float finalweight, double *d_scores,
                      double *d_cost_per_step, float *d_head_out, void *stream);
 
+/* Registration network: the flow field of designated-pixel registration on the device (reference
+ * visual_mpc/policy/cem_controllers/register_gtruth_controller.py:7,21,64-66: setup_gdn(gdnconf, gpu_id) builds the
+ * warper, which is called once per registration target and planning call).  The registration_network package is not part
+ * of the reference snapshot; the network is this project's
+ * (visual_foresight_amd/video_prediction/registration_net_arch.py: 3x3 convolutions with ReLU, three with 2x2 max-pool
+ * 6 -> 32m -> 64m -> 128m, three with bilinear x2 up-sampling -> 64m -> 32m -> 16m, a 5x5 flow head; m = ch_mult), one
+ * weight set per view.  height and width are multiples of 8 in 16..128, ch_mult is 1, 2 or 4, max_pairs the most
+ * (current, reference) pairs of one call.  Every device buffer is allocated in vf_regnet_create; vf_regnet_load_weights is
+ * the one blocking call.  The activations are scratch of the net: like a scorer, a net is driven from ONE stream at a
+ * time.  A pair's flow has the same bits whatever n, slot or call it is computed in. */
+typedef struct vf_regnet_config {
+    int32_t height, width;
+    int32_t ncam;               /* views (1..4; 0 = 1) */
+    int32_t ch_mult;            /* 1, 2 or 4 */
+    int32_t max_pairs;
+    int32_t device;             /* HIP device ordinal */
+} vf_regnet_config;
+
+typedef struct vf_regnet vf_regnet;
+
+/* float32 values of ONE view's weights, the canonical table of registration_net_arch.py concatenated in table order;
+ * 0 + vf_last_error() for a bad config. */
+size_t vf_regnet_weight_count(const vf_regnet_config *cfg);
+int vf_regnet_create(const vf_regnet_config *cfg, vf_regnet **out);
+int vf_regnet_destroy(vf_regnet *r);
+/* HOST blob, ncam views back to back; re-packs the convolution weights for the MFMA kernel into the buffers
+ * vf_regnet_create allocated (replaces gdnconf['pretrained_model']). */
+int vf_regnet_load_weights(vf_regnet *r, const float *host_blob, size_t n_floats);
+/* d_current, d_reference: DEVICE float32 [n][ncam][H][W][3] in [0, 1], 16-byte aligned, n <= max_pairs; d_flow: DEVICE
+ * float32 [n][ncam][H][W][2] = (dx, dy), 8-byte aligned.  d_flow + i * ncam * H * W * 2 is what vf_register takes for pair
+ * i.  Enqueues on `stream`, never synchronises, allocates nothing.  VF_ERR_INVALID (nothing launched): a NULL pointer, a
+ * misaligned pointer, n < 1 or n > max_pairs, weights not loaded. */
+int vf_regnet_flow(vf_regnet *r, const float *d_current, const float *d_reference, int32_t n, float *d_flow,
+                   void *stream);
+
 /* Copy the predictions of the last vf_rollout out in the reference's layout (camera axis,
  * normalised distributions).  Any destination may be NULL.  first/count select a range of rolled
  * sequences.  Replaces the gen_images/gen_distrib/gen_states fetch of
@@ -261,8 +296,8 @@ int vf_export(vf_handle *h, int32_t first, int32_t count, float *d_frames, float
 
 /* Designated-pixel registration (reference
  * visual_mpc/policy/cem_controllers/register_gtruth_controller.py:54-173, get_warp_err).  The
- * registration NETWORK is not part of the reference snapshot; this entry point takes its output,
- * a flow field d_flow [ncam][H][W][2] = (dx, dy) that maps reference pixel (r, c) to the point
+ * registration network is vf_regnet above (or any other source of a flow field); this entry point
+ * takes its output, a flow field d_flow [ncam][H][W][2] = (dx, dy) that maps reference pixel (r, c) to the point
  * (x, y) = (c + dx, r + dy) of the current frame, and does the rest on the device:
  *   d_warp_pts [ncam][H][W][2] = (x, y)                        (optional, may be NULL)
  *   d_warped   [ncam][H][W][3] = bilinear sample of d_current at warp_pts, border-clamped (opt.)

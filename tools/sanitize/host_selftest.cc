@@ -9,6 +9,7 @@
 // invariants the device relies on (contiguous tickets, dependencies on earlier phases only,
 // counters in range, every pointer of every phase inside a buffer of the handle).
 // Never built for or run on a GPU (GPU sanitizers are not available on this pool).
+#include <array>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -250,6 +251,33 @@ int main() {
             if (s && vf_scorer_destroy(s)) { std::fprintf(stderr, "vf_scorer_destroy failed\n"); rc = 1; }
             std::printf("  frame scorer: both heads at 64x64 / 48x64 / 128x128, injected failures in vf_scorer_create / vf_scorer_load_weights, refusals: %s\n",
                         rc ? "FAILED" : "ok");
+        }
+        // the registration network: table, buffers and packer (u3 at ch_mult 1 pads 16 channels to a 32-wide tile) for every
+        // ch_mult at three sizes, two views; the refusals of vf_regnet_flow
+        {
+            alignas(16) static float img[8];
+            float flow2[2];
+            for (int m : {1, 2, 4})
+                for (const auto &sz : {std::array<int, 2>{64, 64}, {48, 64}, {128, 128}}) {
+                    vf_regnet_config rc_cfg = {sz[0], sz[1], 2, m, 2, 0};
+                    vf_regnet *r = nullptr;
+                    if (vf_regnet_create(&rc_cfg, &r)) { std::fprintf(stderr, "vf_regnet_create: %s\n", vf_last_error()); rc = 1; continue; }
+                    const size_t n = vf_regnet_weight_count(&rc_cfg) * 2;
+                    std::vector<float> w(n, 0.5f);
+                    if (vf_regnet_flow(r, img, img, 1, flow2, nullptr) != VF_ERR_INVALID || std::string(vf_last_error()).find("not loaded") == std::string::npos) rc = 1;
+                    if (n == 0 || vf_regnet_load_weights(r, w.data(), n) || vf_regnet_load_weights(r, w.data(), n)) {
+                        std::fprintf(stderr, "vf_regnet_load_weights: %s\n", vf_last_error()); rc = 1;
+                    }
+                    if (vf_regnet_load_weights(r, w.data(), n - 1) == 0) { std::fprintf(stderr, "short regnet blob accepted\n"); rc = 1; }
+                    if (vf_regnet_flow(r, img, img, 3, flow2, nullptr) != VF_ERR_INVALID || std::string(vf_last_error()).find("max_pairs") == std::string::npos) rc = 1;
+                    if (vf_regnet_flow(r, img + 1, img, 1, flow2, nullptr) != VF_ERR_INVALID || std::string(vf_last_error()).find("aligned") == std::string::npos) rc = 1;
+                    if (vf_regnet_flow(r, img, nullptr, 1, flow2, nullptr) != VF_ERR_INVALID) rc = 1;
+                    if (vf_regnet_destroy(r)) rc = 1;
+                }
+            vf_regnet_config bad_rn = {64, 136, 1, 1, 2, 0};
+            vf_regnet *r = nullptr;
+            if (vf_regnet_create(&bad_rn, &r) == 0 || vf_regnet_weight_count(&bad_rn) != 0) { std::fprintf(stderr, "regnet at 64x136 accepted\n"); rc = 1; }
+            std::printf("  registration net: ch_mult 1 / 2 / 4 at 64x64 / 48x64 / 128x128, refusals: %s\n", rc ? "FAILED" : "ok");
         }
         if (hh && vf_destroy(hh)) { std::fprintf(stderr, "vf_destroy after the injected failures failed\n"); rc = 1; }
         std::printf("  injected failures (bad_alloc, std::exception, foreign) in vf_create / vf_load_weights / build_schedule: %s\n",

@@ -37,6 +37,7 @@
 #include "vf_small_kernels.h"
 #include "vf_goal_image.h"
 #include "vf_frame_scorer.h"
+#include "vf_registration_net.h"
 #include "vf_plan_render.h"
 #include "vf_conv_bf16x6.h"
 #include "vf_persistent.h"
@@ -3120,3 +3121,4 @@ int vf_get_profile(vf_handle *h, double *kernel_ms, int64_t *launches, double *f
 #endif  // VF_HOST_SELFTEST
 
 #include "vf_engine_scorer.inc"
+#include "vf_engine_regnet.inc"

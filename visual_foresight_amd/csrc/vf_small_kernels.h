@@ -732,7 +732,7 @@ VF_GLOBAL void export_distrib_kernel(const float *src, long long view_stride, co
 
 // ------------------------------------------------------------------------------------------
 // Registration (reference register_gtruth_controller.py:54-173).  A flow field (dx, dy) per
-// reference pixel - the output of the plug-in registration network - maps reference pixel
+// reference pixel - the output of the registration network (vf_registration_net.h) - maps reference pixel
 // (r, c) to the point (x, y) = (c + dx, r + dy) of the current frame ("warp_pts", :64-66).
 __device__ __forceinline__ float bilinear_clamped(const float *img, int H, int W, float x, float y, int ch) {
     x = fminf(fmaxf(x, 0.f), (float)(W - 1));

@@ -22,8 +22,10 @@ With a predictor that offers ``register()`` (``HipVPredEvaluation``) the arithme
 ``get_warp_err`` - bilinear warp of the current frame by the registration network's flow field,
 window median of the warp points, photometric warp error - runs on the GPU (``vf_register``,
 ``include/vf_hip.h``) and the trade-off weights are applied inside the fused score kernel; the
-plug-in only has to supply the flow field.  Any other predictor takes the NumPy path of
-``registration.py`` on the plug-in's own ``(warped, flow, warp_pts)``.
+warper only has to supply the flow field.  With ``HipRegistrationNet``
+(``video_prediction/registration_net.py``) as the warper the flow fields of all registrations come
+from one ``flow_device`` call on the predictor's device and never visit the host.  Any other
+predictor takes the NumPy path of ``registration.py`` on the warper's own ``(warped, flow, warp_pts)``.
 """
 import numpy as np
 
@@ -54,6 +56,7 @@ class RegisterGtruthController(PixelCostController):
     # ------------------------------------------------------------------ registration
     def register_gtruth(self, start_image, current_image):
         """-> (tracked desig pixels [ncam, ndesig, 2], trade-off [ncam, ndesig]) for this frame."""
+        # (registration runs where predictor.register runs: on the first lane's device of an in-process multi-GPU predictor)
         if self.goal_image_warper is None:
             raise ValueError("RegisterGtruthController needs the 'registration_warper' hyper-parameter")
         regs = self._hp.register_gtruth
@@ -61,14 +64,26 @@ class RegisterGtruthController(PixelCostController):
         if hasattr(self.predictor, 'register') and self._hp.registration_on_device:
             region = (5 if H >= 96 else 2) if self._hp.register_region else 0
             per_reg = []
-            if 'start' in regs:
-                _, flow, _ = self.goal_image_warper(current_image, start_image)
-                per_reg.append(self.predictor.register(current_image, start_image, flow, self.desig_pix_t0,
-                                                       region=region, clip_sub=1))
-            if 'goal' in regs:
-                _, flow, _ = self.goal_image_warper(current_image, self.goal_image)
-                per_reg.append(self.predictor.register(current_image, self.goal_image, flow, self.goal_pix_sel,
-                                                       region=region, clip_sub=0))
+            targets = [(ref, pix, clip) for name, ref, pix, clip in
+                       (('start', start_image, self.desig_pix_t0, 1), ('goal', self.goal_image, self.goal_pix_sel, 0))
+                       if name in regs]
+            if hasattr(self.goal_image_warper, 'flow_device'):
+                # a registration network on the device: one call for all registrations, the flow stays on the card
+                net, pred_dev = self.goal_image_warper, getattr(self.predictor, 'device', None)
+                if pred_dev is not None and net.device != pred_dev:
+                    raise ValueError('the registration net lives on %s, the predictor registers on %s (use clone_to)'
+                                     % (net.device, pred_dev))
+                # every image is uploaded once: the net and predictor.register both read the device copies
+                import torch
+                d_cur = torch.from_numpy(np.ascontiguousarray(current_image, dtype=np.float32)).to(net.device)
+                d_refs = torch.from_numpy(np.stack([np.asarray(ref, dtype=np.float32) for ref, _, _ in targets])).to(net.device)
+                flows = net.flow_device(d_cur.expand_as(d_refs), d_refs)
+                for i, (_, pix, clip) in enumerate(targets):
+                    per_reg.append(self.predictor.register(d_cur, d_refs[i], flows[i], pix, region=region, clip_sub=clip))
+            else:
+                for ref, pix, clip in targets:
+                    _, flow, _ = self.goal_image_warper(current_image, ref)
+                    per_reg.append(self.predictor.register(current_image, ref, flow, pix, region=region, clip_sub=clip))
             desig = [np.stack([d[icam] for d, _ in per_reg], axis=1) for icam in range(self._n_cam)]   # [ntask, nreg, 2]
             errs = [np.stack([e[icam] for _, e in per_reg], axis=1) for icam in range(self._n_cam)]    # [ntask, nreg]
         else:

@@ -7,7 +7,9 @@ frame (the first frame of the episode and/or the goal image), re-localise every 
 in the current frame and derive per-(camera, registration) trade-off weights from the warp error.
 
 The registration *network* (``visual_mpc.registration_network``, ``:7,32``) is not part of the
-reference snapshot, so the warper is a plug-in:
+reference snapshot; this project ships its own (``video_prediction/registration_net.py``:
+``HipRegistrationNet`` on the device, ``HostRegistrationNet`` on the CPU).  The warper stays a
+plug-in, so any other source of a flow field fits too:
 
     warper(current [ncam,H,W,3] float32, reference [ncam,H,W,3] float32)
         -> warped [ncam,H,W,3], flow (ignored), warp_pts [ncam,H,W,2]
@@ -80,3 +82,32 @@ def tradeoff_weights(warperrs):
     """
     inv = 1.0 / warperrs
     return inv / np.sum(np.sum(inv, 0, keepdims=True), 2, keepdims=True)
+
+
+def bilinear_warp(current, flow):
+    """``current [ncam, H, W, 3]``, ``flow [ncam, H, W, 2]`` (dx, dy) -> ``(warped, warp_pts)``: the frame sampled
+    bilinearly at ``warp_pts[c, r, col] = (col + dx, r + dy)``, border-clamped.  Vectorised; the same float32
+    operations in the same order as ``oracle.registration.bilinear_warp_loops`` and ``bilinear_clamped`` of
+    ``csrc/vf_small_kernels.h``, so all three agree bit for bit."""
+    cur = np.asarray(current, dtype=np.float32)
+    fl = np.asarray(flow, dtype=np.float32)
+    ncam, H, W = cur.shape[:3]
+    f32, f64 = np.float32, np.float64
+    x = np.arange(W, dtype=f32)[None, None, :] + fl[..., 0]
+    y = np.arange(H, dtype=f32)[None, :, None] + fl[..., 1]
+    pts = np.stack([x, y], axis=-1).astype(f32)
+    xc = np.minimum(np.maximum(x, f32(0)), f32(W - 1))
+    yc = np.minimum(np.maximum(y, f32(0)), f32(H - 1))
+    x0, y0 = np.floor(xc).astype(np.int64), np.floor(yc).astype(np.int64)
+    x1, y1 = np.minimum(x0 + 1, W - 1), np.minimum(y0 + 1, H - 1)
+    fx = (xc - x0.astype(f32)).astype(f32).astype(f64)[..., None]
+    fy = (yc - y0.astype(f32)).astype(f32).astype(f64)[..., None]
+    cam = np.arange(ncam)[:, None, None]
+    a, b = cur[cam, y0, x0].astype(f64), cur[cam, y0, x1].astype(f64)
+    c, d = cur[cam, y1, x0].astype(f64), cur[cam, y1, x1].astype(f64)
+
+    def lerp(t, lo, hi):        # fmaf(t, hi - lo, lo): the difference rounded to float32, the fma exact then rounded
+        return (t * (hi - lo).astype(f32).astype(f64) + lo).astype(f32).astype(f64)
+
+    top, bot = lerp(fx, a, b), lerp(fx, c, d)
+    return lerp(fy, top, bot).astype(f32), pts

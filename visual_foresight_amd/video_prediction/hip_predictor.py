@@ -837,22 +837,30 @@ class HipVPredEvaluation(object):
     def register(self, current, reference, flow, pix, region=0, clip_sub=1, want_warped=False):
         """Device side of ``get_warp_err`` (reference ``register_gtruth_controller.py:113-173``).
 
-        current, reference ``[ncam, H, W, 3]`` float images, flow ``[ncam, H, W, 2]`` (dx, dy) of the plug-in
-        registration network, pix ``[ncam, ntask, 2]`` (row, col) in the reference image.  Returns
+        current, reference ``[ncam, H, W, 3]`` float images, flow ``[ncam, H, W, 2]`` (dx, dy) of the
+        registration network - each a NumPy array or a float tensor on this predictor's device, which is used
+        without a host round trip (``HipRegistrationNet.flow_device``) - pix ``[ncam, ntask, 2]`` (row, col) in the reference image.  Returns
         ``desig [ncam, ntask, 2]`` (row, col in the current frame), ``err [ncam, ntask]`` and, on request,
         the warped frame ``[ncam, H, W, 3]`` and the warp points ``[ncam, H, W, 2]`` (x, y).
         """
         torch, c = self._torch, self.cfg
-        cur = np.ascontiguousarray(current, dtype=np.float32)
-        ref = np.ascontiguousarray(reference, dtype=np.float32)
-        fl = np.ascontiguousarray(flow, dtype=np.float32)
+
+        def as_input(a):        # device tensors (a registration net's flow) are used where they lie, the rest becomes NumPy
+            if torch.is_tensor(a) and a.is_cuda:
+                if a.device != self.device:
+                    raise ValueError('register: a tensor on %s was given, the predictor registers on %s' % (a.device, self.device))
+                return a.to(torch.float32).contiguous()
+            return np.ascontiguousarray(a, dtype=np.float32)
+
+        cur, ref, fl = as_input(current), as_input(reference), as_input(flow)
         px = np.ascontiguousarray(pix, dtype=np.int32).reshape(self.n_cam, -1, 2)
-        if cur.shape != (self.n_cam, c.height, c.width, 3) or ref.shape != cur.shape or \
-                fl.shape != (self.n_cam, c.height, c.width, 2):
+        if tuple(cur.shape) != (self.n_cam, c.height, c.width, 3) or tuple(ref.shape) != tuple(cur.shape) or \
+                tuple(fl.shape) != (self.n_cam, c.height, c.width, 2):
             raise ValueError('register: need [ncam, H, W, 3] images and a [ncam, H, W, 2] flow field')
         ntask = px.shape[1]
         with torch.cuda.device(self.device):
-            d_cur, d_ref, d_fl, d_px = (torch.from_numpy(a).to(self.device) for a in (cur, ref, fl, px))
+            d_cur, d_ref, d_fl, d_px = (a if torch.is_tensor(a) else torch.from_numpy(a).to(self.device)
+                                        for a in (cur, ref, fl, px))
             desig = torch.empty((self.n_cam, ntask, 2), dtype=torch.float32, device=self.device)
             err = torch.empty((self.n_cam, ntask), dtype=torch.float32, device=self.device)
             warped = torch.empty_like(d_cur) if want_warped else None
