@@ -86,7 +86,7 @@ def _fma32(a, b, acc):
 
 def device_k_order(cin, first_layer):
     """The order in which the device adds one tap's input channels: ascending in c1; in c2..c4 steps of eight channels,
-    inside a step 0, 4, 1, 5, 2, 6, 3, 7 (csrc/vf_frame_scorer.h)."""
+    inside a step 0, 4, 1, 5, 2, 6, 3, 7 (csrc/vf_net_conv.h)."""
     if first_layer:
         return list(range(cin))
     return [8 * s + q + 4 * h for s in range(cin // 8) for q in range(4) for h in range(2)]

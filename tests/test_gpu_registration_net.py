@@ -41,7 +41,7 @@ def flow_errors(weights, cur, ref, device_flow):
 
 @pytest.mark.parametrize('H,W,m,ncam,n', [(48, 64, 1, 1, 1), (48, 64, 4, 2, 2), (64, 64, 1, 2, 2), (64, 64, 4, 1, 1),
                                           (64, 64, 4, 2, 2), (64, 64, 2, 2, 2), (96, 128, 1, 2, 1), (96, 128, 4, 2, 2), (128, 128, 1, 1, 2),
-                                          (128, 128, 4, 2, 1)])
+                                          (128, 128, 4, 2, 1), (40, 56, 1, 2, 2)])
 def test_flow_against_the_float64_restatement(H, W, m, ncam, n):
     torch.set_num_threads(min(16, torch.get_num_threads()))
     net = HipRegistrationNet('', _hp(H, W, m, ncam)).restore()

@@ -3120,5 +3120,6 @@ int vf_get_profile(vf_handle *h, double *kernel_ms, int64_t *launches, double *f
 }  // extern "C"
 #endif  // VF_HOST_SELFTEST
 
+#include "vf_engine_sidenet.inc"
 #include "vf_engine_scorer.inc"
 #include "vf_engine_regnet.inc"

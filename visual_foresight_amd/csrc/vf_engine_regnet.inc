@@ -1,13 +1,13 @@
 // vf_engine_regnet.inc - host side of the registration network (vf_registration_net.h; include/vf_hip.h "Registration
-// network"): tensor table, buffers, weight re-packing, the launch sequence.  Included at the end of vf_engine.hip.  Under
-// -DVF_HOST_SELFTEST allocations are address reservations and uploads are dropped (as in vf_engine_scorer.inc).
+// network"): tensor table, buffers, the launch sequence.  Included at the end of vf_engine.hip, after vf_engine_sidenet.inc
+// (allocation, upload, weight packing, also under -DVF_HOST_SELFTEST).
 
 struct vf_regnet {
     vf_regnet_config cfg;
     int H = 0, W = 0, ncam = 1, m = 1, n_img = 0;      // n_img = max_pairs * ncam
     size_t blob_floats = 0;                             // canonical floats per view
     float *w1 = nullptr, *b1 = nullptr;                 // d1 as in the blob, [ncam][54 * 32m], [ncam][32m]
-    float *wp[5] = {nullptr}, *b[5] = {nullptr};        // d2, d3, u1, u2, u3 packed for regnet_conv_kernel, biases
+    float *wp[5] = {nullptr}, *b[5] = {nullptr};        // d2, d3, u1, u2, u3 packed for vf_net_conv.h, biases
     float *wf = nullptr, *bf = nullptr;                 // flow head [ncam][25 * 16m * 2], [ncam][2]
     float *down[3] = {nullptr};                         // outputs of d1 .. d3 (pooled)
     float *conv = nullptr;                              // output of the convolution of u1 .. u3 before up-sampling
@@ -42,42 +42,6 @@ static size_t regnet_blob_floats(int m) {
     return n + (size_t)25 * 16 * m * 2 + 2;
 }
 
-template <typename T>
-static int regnet_alloc(vf_regnet *r, T **p, size_t n) {
-    const size_t bytes = std::max<size_t>(n, 1) * sizeof(T);
-    void *q = nullptr;
-#ifdef VF_HOST_SELFTEST
-    q = mmap(nullptr, bytes, PROT_NONE, MAP_PRIVATE | MAP_ANONYMOUS | MAP_NORESERVE, -1, 0);       // never dereferenced
-    if (q == MAP_FAILED) return fail(VF_ERR_NOMEM, "self-test address reservation failed");
-#else
-    if (hipMalloc(&q, bytes) != hipSuccess)
-        return fail(VF_ERR_NOMEM, "hipMalloc of " + std::to_string(bytes) + " bytes failed");
-#endif
-    r->allocs.push_back({q, bytes});
-    *p = reinterpret_cast<T *>(q);
-    return VF_OK;
-}
-
-// canonical [3][3][Cin][Cout] -> [step][half][ceil(Cout / 32)][32][4] (regnet_conv_kernel): step = tap * Cin / 8 + block;
-// the columns past Cout stay zero
-static void regnet_pack_conv(const float *w, int Cin, int Cout, std::vector<float> &out) {
-    const int blocks = Cin / 8, ntile = (Cout + 31) / 32;
-    out.assign((size_t)9 * Cin * ntile * 32, 0.f);
-    for (int tap = 0; tap < 9; ++tap)
-        for (int blk = 0; blk < blocks; ++blk)
-            for (int half = 0; half < 2; ++half)
-                for (int nt = 0; nt < ntile; ++nt)
-                    for (int j = 0; j < 32 && 32 * nt + j < Cout; ++j)
-                        for (int q = 0; q < 4; ++q) {
-                            const size_t step = (size_t)tap * blocks + blk;
-                            const size_t dst = ((((step * 2 + half) * ntile + nt) * 32 + j) * 4) + q;
-                            const size_t src = ((size_t)tap * Cin + 8 * blk + 4 * half + q) * Cout + 32 * nt + j;
-                            out.at(dst) = w[src];
-                        }
-}
-
-static size_t regnet_packed_floats(int Cin, int Cout) { return (size_t)9 * Cin * ((Cout + 31) / 32) * 32; }
-
 // the refusals of vf_regnet_flow (host work only: shared by the device build and the host self-test)
 static int regnet_flow_check(const vf_regnet *r, const float *d_current, const float *d_reference, int32_t n, const float *d_flow) {
     if (!r || !d_current || !d_reference || !d_flow) return fail(VF_ERR_INVALID, "null argument");
@@ -99,18 +63,16 @@ static void regnet_launch_conv(const float *in, int n_img, int ncam, int Hin, in
     const int tw = 1 << tw_shift, th = 32 >> tw_shift;
     const long long mtiles = (long long)((Win + tw - 1) / tw) * ((Hin + th - 1) / th);
     const int ntile = (Cout + 31) / 32;
-    const long long stride = (long long)regnet_packed_floats(Cin, Cout);
+    const long long stride = (long long)packed_floats(Cin, Cout);
     // two channel tiles per wave share the activation loads where one image alone still yields a wave per SIMD and more
-    // (the choice depends on the layer's shape only, and no output value's summation order depends on it)
-    const bool two = ntile % 2 == 0 && mtiles * (ntile / 2) >= 256;
-    const long long tasks = (long long)n_img * mtiles * (two ? ntile / 2 : ntile);
-    const dim3 grid((unsigned)((tasks + 3) / 4));
-    if (two)
-        hipLaunchKernelGGL((regnet_conv_kernel<2, POOL>), grid, dim3(kRnThreads), 0, st, in, n_img, ncam, Hin, Win, Cin, Cout,
-                           tw_shift, wp, bias, stride, out);
+    // (the choice depends on the layer's shape only, and no output value's summation order depends on it).  Pooling layers
+    // only: no other layer of a configuration regnet_validate accepts reaches the condition.
+    if (POOL && ntile % 2 == 0 && mtiles * (ntile / 2) >= 256)
+        launch_net_conv(regnet_conv_kernel<2, true>, n_img, mtiles, ntile / 2, st, in, n_img, ncam, Hin, Win, Cin, Cout, tw_shift,
+                        wp, bias, stride, out);
     else
-        hipLaunchKernelGGL((regnet_conv_kernel<1, POOL>), grid, dim3(kRnThreads), 0, st, in, n_img, ncam, Hin, Win, Cin, Cout,
-                           tw_shift, wp, bias, stride, out);
+        launch_net_conv(regnet_conv_kernel<1, POOL>, n_img, mtiles, ntile, st, in, n_img, ncam, Hin, Win, Cin, Cout, tw_shift,
+                        wp, bias, stride, out);
 }
 
 static int regnet_run(vf_regnet *r, const float *d_current, const float *d_reference, int n, float *d_flow, hipStream_t st) {
@@ -157,13 +119,7 @@ size_t vf_regnet_weight_count(const vf_regnet_config *cfg) {
 int vf_regnet_destroy(vf_regnet *r) {
     VF_API_TRY
     if (!r) return VF_OK;
-#ifdef VF_HOST_SELFTEST
-    for (const AllocRec &a : r->allocs) munmap(a.p, a.bytes);
-#else
-    (void)hipSetDevice(r->cfg.device);
-    (void)hipDeviceSynchronize();
-    for (const AllocRec &a : r->allocs) (void)hipFree(a.p);
-#endif
+    side_free_all(r->cfg.device, r->allocs);
     delete r;
     return VF_OK;
     VF_API_CATCH(int)
@@ -189,27 +145,23 @@ int vf_regnet_create(const vf_regnet_config *cfg, vf_regnet **out) {
     r->blob_floats = regnet_blob_floats(r->m);
     const int m = r->m, NV = r->ncam;
     const size_t HW = (size_t)r->H * r->W, N = (size_t)r->n_img;
-#define VF_RN_ALLOC(ptr, n)                            \
-    do {                                               \
-        rc = regnet_alloc(r, &(ptr), (size_t)(n));     \
-        if (rc) { vf_regnet_destroy(r); return rc; }   \
-    } while (0)
-    VF_RN_ALLOC(r->w1, (size_t)NV * 54 * 32 * m);
-    VF_RN_ALLOC(r->b1, (size_t)NV * 32 * m);
+    VF_SIDE_ALLOC(r, vf_regnet_destroy, r->w1, (size_t)NV * 54 * 32 * m);
+    VF_SIDE_ALLOC(r, vf_regnet_destroy, r->b1, (size_t)NV * 32 * m);
     for (int l = 0; l < 5; ++l) {
-        VF_RN_ALLOC(r->wp[l], (size_t)NV * regnet_packed_floats(kRnConv[l].cin * m, kRnConv[l].cout * m));
-        VF_RN_ALLOC(r->b[l], (size_t)NV * kRnConv[l].cout * m);
+        const int Cin = kRnConv[l].cin * m, Cout = kRnConv[l].cout * m;
+        VF_SIDE_ALLOC(r, vf_regnet_destroy, r->wp[l], NV * packed_floats(Cin, Cout));
+        VF_SIDE_ALLOC(r, vf_regnet_destroy, r->b[l], (size_t)NV * Cout);
     }
-    VF_RN_ALLOC(r->wf, (size_t)NV * 25 * 16 * m * 2);
-    VF_RN_ALLOC(r->bf, (size_t)NV * 2);
-    VF_RN_ALLOC(r->down[0], N * (HW / 4) * 32 * m);
-    VF_RN_ALLOC(r->down[1], N * (HW / 16) * 64 * m);
-    VF_RN_ALLOC(r->down[2], N * (HW / 64) * 128 * m);
-    VF_RN_ALLOC(r->conv, N * (HW / 4) * 16 * m);        // the largest of u1 (HW / 64 * 64m), u2 (HW / 16 * 32m), u3 (HW / 4 * 16m)
-    VF_RN_ALLOC(r->up[0], N * (HW / 16) * 64 * m);
-    VF_RN_ALLOC(r->up[1], N * (HW / 4) * 32 * m);
-    VF_RN_ALLOC(r->up[2], N * HW * 16 * m);
-#undef VF_RN_ALLOC
+    VF_SIDE_ALLOC(r, vf_regnet_destroy, r->wf, (size_t)NV * 25 * 16 * m * 2);
+    VF_SIDE_ALLOC(r, vf_regnet_destroy, r->bf, (size_t)NV * 2);
+    VF_SIDE_ALLOC(r, vf_regnet_destroy, r->down[0], N * (HW / 4) * 32 * m);
+    VF_SIDE_ALLOC(r, vf_regnet_destroy, r->down[1], N * (HW / 16) * 64 * m);
+    VF_SIDE_ALLOC(r, vf_regnet_destroy, r->down[2], N * (HW / 64) * 128 * m);
+    // (the largest of u1 (HW / 64 * 64m), u2 (HW / 16 * 32m), u3 (HW / 4 * 16m))
+    VF_SIDE_ALLOC(r, vf_regnet_destroy, r->conv, N * (HW / 4) * 16 * m);
+    VF_SIDE_ALLOC(r, vf_regnet_destroy, r->up[0], N * (HW / 16) * 64 * m);
+    VF_SIDE_ALLOC(r, vf_regnet_destroy, r->up[1], N * (HW / 4) * 32 * m);
+    VF_SIDE_ALLOC(r, vf_regnet_destroy, r->up[2], N * HW * 16 * m);
     *out = r;
     return VF_OK;
     VF_API_CATCH_CLEANUP(int, { if (made) vf_regnet_destroy(made); if (out) *out = nullptr; })
@@ -227,27 +179,17 @@ int vf_regnet_load_weights(vf_regnet *r, const float *host_blob, size_t n_floats
     VF_HIP_CHECK(hipDeviceSynchronize());       // (hot swap: calls in flight have finished)
 #endif
     const int m = r->m;
-    std::vector<float> packed;
     for (int v = 0; v < r->ncam; ++v) {
-        const float *p = host_blob + (size_t)v * r->blob_floats;
-        int rc = 0;
-        const size_t n1 = (size_t)54 * 32 * m;
-        if ((rc = scorer_upload(r->w1 + v * n1, p, n1 * sizeof(float)))) return rc;
-        p += n1;
-        if ((rc = scorer_upload(r->b1 + (size_t)v * 32 * m, p, (size_t)32 * m * sizeof(float)))) return rc;
-        p += 32 * m;
+        BlobCursor blob{host_blob + (size_t)v * r->blob_floats, v};
+        blob.upload(r->w1, (size_t)54 * 32 * m);
+        blob.upload(r->b1, 32 * m);
         for (int l = 0; l < 5; ++l) {
-            const int Cin = kRnConv[l].cin * m, Cout = kRnConv[l].cout * m;
-            regnet_pack_conv(p, Cin, Cout, packed);
-            if ((rc = scorer_upload(r->wp[l] + v * packed.size(), packed.data(), packed.size() * sizeof(float)))) return rc;
-            p += (size_t)9 * Cin * Cout;
-            if ((rc = scorer_upload(r->b[l] + (size_t)v * Cout, p, Cout * sizeof(float)))) return rc;
-            p += Cout;
+            blob.upload_packed(r->wp[l], kRnConv[l].cin * m, kRnConv[l].cout * m);
+            blob.upload(r->b[l], kRnConv[l].cout * m);
         }
-        const size_t nf = (size_t)25 * 16 * m * 2;
-        if ((rc = scorer_upload(r->wf + v * nf, p, nf * sizeof(float)))) return rc;
-        p += nf;
-        if ((rc = scorer_upload(r->bf + (size_t)v * 2, p, 2 * sizeof(float)))) return rc;
+        blob.upload(r->wf, (size_t)25 * 16 * m * 2);
+        blob.upload(r->bf, 2);
+        if (blob.rc) return blob.rc;
     }
     r->loaded = true;
     return VF_OK;

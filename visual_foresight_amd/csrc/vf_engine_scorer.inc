@@ -1,7 +1,6 @@
 // vf_engine_scorer.inc - host side of the frame scorer (vf_frame_scorer.h; include/vf_hip.h "Learned-cost planning"):
-// tensor table, buffers, weight re-packing, the launch sequence.  Included at the end of vf_engine.hip (it reads the
-// resident predictions of a vf_handle).  Under -DVF_HOST_SELFTEST allocations are address reservations and uploads are
-// dropped, so the table, the packer and every refusal run under the sanitizers without a GPU.
+// tensor table, buffers, the launch sequence.  Included at the end of vf_engine.hip (it reads the resident predictions of a
+// vf_handle), after vf_engine_sidenet.inc (allocation, upload, weight packing, also under -DVF_HOST_SELFTEST).
 
 struct vf_scorer {
     vf_scorer_config cfg;
@@ -12,7 +11,7 @@ struct vf_scorer {
         int cin = 3;
         size_t blob_floats = 0;         // canonical floats per view
         float *w1 = nullptr, *b1 = nullptr;             // c1 as in the blob, [ncam][9 * cin * 32], [ncam][32]
-        float *wp[3] = {nullptr}, *b[3] = {nullptr};    // c2 .. c4 packed for scorer_conv_kernel, biases
+        float *wp[3] = {nullptr}, *b[3] = {nullptr};    // c2 .. c4 packed for vf_net_conv.h, biases
         float *wfc = nullptr, *bfc = nullptr;           // [ncam][128][D], [ncam][D]
         bool loaded = false;
     } tower[2];
@@ -46,48 +45,6 @@ static size_t scorer_blob_floats(int cin, int D) {
     int c_in = cin;
     for (int l = 1; l <= 4; ++l) { n += (size_t)9 * c_in * kScCh[l] + kScCh[l]; c_in = kScCh[l]; }
     return n + (size_t)kScCh[4] * D + D;
-}
-
-template <typename T>
-static int scorer_alloc(vf_scorer *s, T **p, size_t n) {
-    const size_t bytes = std::max<size_t>(n, 1) * sizeof(T);
-    void *q = nullptr;
-#ifdef VF_HOST_SELFTEST
-    q = mmap(nullptr, bytes, PROT_NONE, MAP_PRIVATE | MAP_ANONYMOUS | MAP_NORESERVE, -1, 0);       // never dereferenced
-    if (q == MAP_FAILED) return fail(VF_ERR_NOMEM, "self-test address reservation failed");
-#else
-    if (hipMalloc(&q, bytes) != hipSuccess)
-        return fail(VF_ERR_NOMEM, "hipMalloc of " + std::to_string(bytes) + " bytes failed");
-#endif
-    s->allocs.push_back({q, bytes});
-    *p = reinterpret_cast<T *>(q);
-    return VF_OK;
-}
-
-static int scorer_upload(void *dst, const void *src, size_t bytes) {
-#ifdef VF_HOST_SELFTEST
-    (void)dst; (void)src; (void)bytes;
-#else
-    VF_HIP_CHECK(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice));
-#endif
-    return VF_OK;
-}
-
-// canonical [3][3][Cin][Cout] -> [step][half][Cout / 32][32][4] (scorer_conv_kernel): step = tap * Cin / 8 + block
-static void scorer_pack_conv(const float *w, int Cin, int Cout, std::vector<float> &out) {
-    const int blocks = Cin / 8, ntile = Cout / 32;
-    out.assign((size_t)9 * Cin * Cout, 0.f);
-    for (int tap = 0; tap < 9; ++tap)
-        for (int blk = 0; blk < blocks; ++blk)
-            for (int half = 0; half < 2; ++half)
-                for (int nt = 0; nt < ntile; ++nt)
-                    for (int j = 0; j < 32; ++j)
-                        for (int q = 0; q < 4; ++q) {
-                            const size_t step = (size_t)tap * blocks + blk;
-                            const size_t dst = ((((step * 2 + half) * ntile + nt) * 32 + j) * 4) + q;
-                            const size_t src = ((size_t)tap * Cin + 8 * blk + 4 * half + q) * Cout + 32 * nt + j;
-                            out.at(dst) = w[src];
-                        }
 }
 
 // the refusals of vf_scorer_scores / vf_scorer_embed (host work only: shared by the device build and the host self-test)
@@ -131,17 +88,13 @@ static int scorer_run(vf_scorer *s, int tw, const ScorerSrc &src, long long n_fv
         for (int l = 2; l <= 4; ++l) {
             const int Hin = H >> (l - 1), Win = W >> (l - 1), Cin = kScCh[l - 1], Cout = kScCh[l];
             const int P = (Hin / 2) * (Win / 2), mtiles = (P + 31) / 32;
-            const long long stride = (long long)9 * Cin * Cout;
-            if (l == 2) {           // NT = 2: all 64 output channels in one wave
-                const long long tasks = (long long)n * mtiles;
-                hipLaunchKernelGGL(scorer_conv_kernel<2>, dim3((unsigned)((tasks + 3) / 4)), dim3(kScThreads), 0, st, s->act[0], n,
-                                   (int)f0, s->ncam, Hin, Win, Cin, Cout, t.wp[0], t.b[0], stride, s->act[1]);
-            } else {                // NT = 1: four waves share a row tile (few positions are left, more tasks keep the CUs busy)
-                const long long tasks = (long long)n * mtiles * (Cout / 32);
-                hipLaunchKernelGGL(scorer_conv_kernel<1>, dim3((unsigned)((tasks + 3) / 4)), dim3(kScThreads), 0, st,
-                                   s->act[l - 2], n, (int)f0, s->ncam, Hin, Win, Cin, Cout, t.wp[l - 2], t.b[l - 2], stride,
-                                   s->act[l - 1]);
-            }
+            const long long stride = (long long)packed_floats(Cin, Cout);
+            if (l == 2)             // NT = 2: all 64 output channels in one wave
+                launch_net_conv(scorer_conv_kernel<2>, n, mtiles, 1, st, s->act[0], n, (int)f0, s->ncam, Hin, Win, Cin, Cout,
+                                t.wp[0], t.b[0], stride, s->act[1]);
+            else                    // NT = 1: four waves share a row tile (few positions are left, more tasks keep the CUs busy)
+                launch_net_conv(scorer_conv_kernel<1>, n, mtiles, Cout / 32, st, s->act[l - 2], n, (int)f0, s->ncam, Hin, Win,
+                                Cin, Cout, t.wp[l - 2], t.b[l - 2], stride, s->act[l - 1]);
             VF_HIP_CHECK(hipGetLastError());
         }
         hipLaunchKernelGGL(scorer_head_kernel, dim3((unsigned)n), dim3(kScHeadThreads), 0, st, s->act[3], (int)f0, s->ncam,
@@ -167,13 +120,7 @@ size_t vf_scorer_weight_count(const vf_scorer_config *cfg, int32_t tower) {
 int vf_scorer_destroy(vf_scorer *s) {
     VF_API_TRY
     if (!s) return VF_OK;
-#ifdef VF_HOST_SELFTEST
-    for (const AllocRec &a : s->allocs) munmap(a.p, a.bytes);
-#else
-    (void)hipSetDevice(s->cfg.device);
-    (void)hipDeviceSynchronize();
-    for (const AllocRec &a : s->allocs) (void)hipFree(a.p);
-#endif
+    side_free_all(s->cfg.device, s->allocs);
     delete s;
     return VF_OK;
     VF_API_CATCH(int)
@@ -202,28 +149,23 @@ int vf_scorer_create(const vf_scorer_config *cfg, vf_scorer **out) {
     // the activations of a pass stay within 256 MB (the last-level cache); the pass size is invisible in the results
     const long long total = (long long)cfg->max_frames * s->ncam;
     s->group = (int)std::max<long long>(1, std::min<long long>(total, ((long long)1 << 28) / (long long)(per_frame * sizeof(float))));
-#define VF_SC_ALLOC(ptr, n)                            \
-    do {                                               \
-        rc = scorer_alloc(s, &(ptr), (size_t)(n));     \
-        if (rc) { vf_scorer_destroy(s); return rc; }   \
-    } while (0)
-    for (int l = 1; l <= 4; ++l) VF_SC_ALLOC(s->act[l - 1], (size_t)s->group * scorer_act_floats(s->H, s->W, l));
+    for (int l = 1; l <= 4; ++l)
+        VF_SIDE_ALLOC(s, vf_scorer_destroy, s->act[l - 1], (size_t)s->group * scorer_act_floats(s->H, s->W, l));
     for (int tw = 0; tw < s->towers; ++tw) {
         vf_scorer::Tower &t = s->tower[tw];
         t.cin = tw == 1 ? 6 : 3;
         t.blob_floats = scorer_blob_floats(t.cin, s->D);
-        VF_SC_ALLOC(t.w1, (size_t)s->ncam * 9 * t.cin * kScCh[1]);
-        VF_SC_ALLOC(t.b1, (size_t)s->ncam * kScCh[1]);
+        VF_SIDE_ALLOC(s, vf_scorer_destroy, t.w1, (size_t)s->ncam * 9 * t.cin * kScCh[1]);
+        VF_SIDE_ALLOC(s, vf_scorer_destroy, t.b1, (size_t)s->ncam * kScCh[1]);
         for (int l = 2; l <= 4; ++l) {
-            VF_SC_ALLOC(t.wp[l - 2], (size_t)s->ncam * 9 * kScCh[l - 1] * kScCh[l]);
-            VF_SC_ALLOC(t.b[l - 2], (size_t)s->ncam * kScCh[l]);
+            VF_SIDE_ALLOC(s, vf_scorer_destroy, t.wp[l - 2], s->ncam * packed_floats(kScCh[l - 1], kScCh[l]));
+            VF_SIDE_ALLOC(s, vf_scorer_destroy, t.b[l - 2], (size_t)s->ncam * kScCh[l]);
         }
-        VF_SC_ALLOC(t.wfc, (size_t)s->ncam * kScCh[4] * s->D);
-        VF_SC_ALLOC(t.bfc, (size_t)s->ncam * s->D);
+        VF_SIDE_ALLOC(s, vf_scorer_destroy, t.wfc, (size_t)s->ncam * kScCh[4] * s->D);
+        VF_SIDE_ALLOC(s, vf_scorer_destroy, t.bfc, (size_t)s->ncam * s->D);
     }
-    VF_SC_ALLOC(s->enc, (size_t)total * s->D);
-    VF_SC_ALLOC(s->raw, (size_t)cfg->max_frames);
-#undef VF_SC_ALLOC
+    VF_SIDE_ALLOC(s, vf_scorer_destroy, s->enc, (size_t)total * s->D);
+    VF_SIDE_ALLOC(s, vf_scorer_destroy, s->raw, (size_t)cfg->max_frames);
     VF_INJECT(4);
     *out = s;
     return VF_OK;
@@ -243,28 +185,17 @@ int vf_scorer_load_weights(vf_scorer *s, int32_t tower, const float *host_blob, 
     VF_HIP_CHECK(hipSetDevice(s->cfg.device));
     VF_HIP_CHECK(hipDeviceSynchronize());       // (hot swap: passes in flight have finished)
 #endif
-    std::vector<float> packed;
     for (int v = 0; v < s->ncam; ++v) {
-        const float *p = host_blob + (size_t)v * t.blob_floats;
-        int rc = 0;
-        const size_t n1 = (size_t)9 * t.cin * kScCh[1];
-        if ((rc = scorer_upload(t.w1 + v * n1, p, n1 * sizeof(float)))) return rc;
-        p += n1;
-        if ((rc = scorer_upload(t.b1 + (size_t)v * kScCh[1], p, kScCh[1] * sizeof(float)))) return rc;
-        p += kScCh[1];
+        BlobCursor blob{host_blob + (size_t)v * t.blob_floats, v};
+        blob.upload(t.w1, (size_t)9 * t.cin * kScCh[1]);
+        blob.upload(t.b1, kScCh[1]);
         for (int l = 2; l <= 4; ++l) {
-            const int Cin = kScCh[l - 1], Cout = kScCh[l];
-            const size_t nw = (size_t)9 * Cin * Cout;
-            scorer_pack_conv(p, Cin, Cout, packed);
-            if ((rc = scorer_upload(t.wp[l - 2] + v * nw, packed.data(), nw * sizeof(float)))) return rc;
-            p += nw;
-            if ((rc = scorer_upload(t.b[l - 2] + (size_t)v * Cout, p, Cout * sizeof(float)))) return rc;
-            p += Cout;
+            blob.upload_packed(t.wp[l - 2], kScCh[l - 1], kScCh[l]);
+            blob.upload(t.b[l - 2], kScCh[l]);
         }
-        const size_t nfc = (size_t)kScCh[4] * s->D;
-        if ((rc = scorer_upload(t.wfc + v * nfc, p, nfc * sizeof(float)))) return rc;
-        p += nfc;
-        if ((rc = scorer_upload(t.bfc + (size_t)v * s->D, p, s->D * sizeof(float)))) return rc;
+        blob.upload(t.wfc, (size_t)kScCh[4] * s->D);
+        blob.upload(t.bfc, s->D);
+        if (blob.rc) return blob.rc;
     }
     t.loaded = true;
     return VF_OK;

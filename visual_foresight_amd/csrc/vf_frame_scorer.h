@@ -16,16 +16,14 @@
 //
 // Same bits everywhere: every output value of every layer is ONE fmaf chain whose order depends on the layer alone -
 //   c1:     (ky, kx, ci) ascending, then + bias;
-//   c2..c4: taps (ky, kx) ascending; inside a tap the input channels in steps of eight, a step's channels in the order
-//           0, 4, 1, 5, 2, 6, 3, 7 (lane half h of the MFMA supplies channels 4h .. 4h + 3); then + bias;
-//   gap:    positions in row-major order, then one division by their number;   fc: k ascending, then + bias
-// - and an MFMA row (an output position) does not see the other rows of its tile.  Padding taps multiply zeros (fmaf(0, w,
-// acc) == acc), so they change nothing.  A frame's head output is therefore the same whatever batch, chunk, group, lane or
-// rank it is scored in.
+//   c2..c4: the order of vf_net_conv.h (taps ascending, channels in steps of eight, K never split), then + bias;
+//   gap:    positions in row-major order, then one division by their number;   fc: k ascending, then + bias.
+// A frame's head output is therefore the same whatever batch, chunk, group, lane or rank it is scored in.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "vf_conv_mfma.h"
+#include "vf_net_conv.h"
 
 namespace vf {
 
@@ -105,54 +103,23 @@ scorer_c1_kernel(ScorerSrc src, int f0, int H, int W, float scale, const float *
 
 // c2 .. c4: in [n][Hin][Win][Cin] -> out [n][Hin/2][Win/2][Cout], 3x3 / 2, zero padding 1, + bias, ReLU.  One wave per task =
 // (frame fl, row tile of 32 output positions in row-major order, group of NT * 32 output channels); rows past the frame's
-// last position are idle (loaded as zeros, not stored).  wp: packed [step][half][Cout / 32][32][4] (vf_scorer_load_weights),
-// step = tap * Cin / 8 + channel block, element q of lane (j, half) = w[tap][8 * block + 4 * half + q][32 * ntile + j]: one
-// 16-byte load of each operand feeds four MFMAs.  MFMA lane layout (lane l: A[i = l & 31][k = l >> 5], B[k = l >> 5][j = l & 31],
-// D register r: row (r & 3) + 8 (r >> 2) + 4 (l >> 5), column l & 31) as in vf_fc_tile.h.
+// last position are idle (not stored).  wp: packed by vf_scorer_load_weights in the layout of vf_net_conv.h.
 template <int NT>
-VF_GLOBAL VF_LAUNCH_BOUNDS(kScThreads) void
+VF_GLOBAL VF_LAUNCH_BOUNDS(kNetConvThreads) void
 scorer_conv_kernel(const float *__restrict__ in, int n_frames, int f0, int ncam, int Hin, int Win, int Cin, int Cout,
                    const float *__restrict__ wp, const float *__restrict__ bias, long long wp_view_stride,
                    float *__restrict__ out) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int j = lane & 31, half = lane >> 5;
-    const int Ho = Hin / 2, Wo = Win / 2, P = Ho * Wo;
-    const int mtiles = (P + 31) / 32, ngroups = Cout / (32 * NT), ntile_all = Cout / 32;
-    const long long task = (long long)blockIdx.x * (kScThreads / 64) + wave;
-    if (task >= (long long)n_frames * mtiles * ngroups) return;             // (no barrier in this kernel)
-    const int ng = (int)(task % ngroups), mt = (int)((task / ngroups) % mtiles), fl = (int)(task / ((long long)ngroups * mtiles));
+    const int j = threadIdx.x & 31, half = (threadIdx.x & 63) >> 5;
+    const int Wo = Win / 2, P = (Hin / 2) * Wo;
+    int fl, mt, ng;
+    if (!net_conv_task(n_frames, (P + 31) / 32, Cout / (32 * NT), fl, mt, ng)) return;
     const int c = (f0 + fl) % ncam;
     const int p = mt * 32 + j;
-    const bool row_ok = p < P;
-    const int oy = p / Wo, ox = p % Wo;
-    const float *img = in + (long long)fl * Hin * Win * Cin;
-    const f32x4 *w4 = reinterpret_cast<const f32x4 *>(wp + c * wp_view_stride);
-    const int blocks = Cin / 8;
 
-    f32x16 acc[NT];
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[nt][r] = 0.f;
+    f32x16 acc[NT];         // (stride 2: position (oy, ox) is centred on input (2 oy, 2 ox))
+    net_conv3x3_mma<NT>(acc, in + (long long)fl * Hin * Win * Cin, Hin, Win, Cin, 2 * (p / Wo), 2 * (p % Wo), p < P,
+                        reinterpret_cast<const f32x4 *>(wp + c * wp_view_stride), Cout / 32, ng, j, half);
 
-    for (int tap = 0; tap < 9; ++tap) {
-        const int iy = 2 * oy + tap / 3 - 1, ix = 2 * ox + tap % 3 - 1;     // (iy <= Hin - 1, ix <= Win - 1 for p < P)
-        const bool ok = row_ok && iy >= 0 && ix >= 0;
-        const f32x4 *a4 = reinterpret_cast<const f32x4 *>(img + ((long long)(ok ? iy : 0) * Win + (ok ? ix : 0)) * Cin + 4 * half);
-        const f32x4 *b4 = w4 + ((long long)(tap * blocks * 2 + half) * ntile_all + ng * NT) * 32 + j;
-        for (int s = 0; s < blocks; ++s) {
-            f32x4 a = {0.f, 0.f, 0.f, 0.f};
-            if (ok) a = a4[2 * s];
-            f32x4 bq[NT];
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) bq[nt] = b4[((long long)s * 2 * ntile_all + nt) * 32];
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt)
-                    acc[nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[q], bq[nt][q], acc[nt], 0, 0, 0);
-        }
-    }
     const float *bv = bias + c * Cout;
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) {
@@ -160,7 +127,7 @@ scorer_conv_kernel(const float *__restrict__ in, int n_frames, int f0, int ncam,
         const float bc = bv[co];
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int po = mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+            const int po = mt * 32 + net_mma_row(r, half);
             if (po < P) out[((long long)fl * P + po) * Cout + co] = fmaxf(acc[nt][r] + bc, 0.f);
         }
     }

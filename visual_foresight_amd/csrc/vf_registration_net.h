@@ -17,19 +17,18 @@
 //
 // Same bits everywhere: every output value of every layer is ONE fmaf chain whose order depends on the layer alone -
 //   d1:        (ky, kx, ci) ascending with ci over concat[current, reference]; + bias; ReLU; max over the window;
-//   d2 .. u3:  taps (ky, kx) ascending; inside a tap the input channels in steps of eight, a step's channels in the order
-//              0, 4, 1, 5, 2, 6, 3, 7 (lane half h of the MFMA supplies channels 4h .. 4h + 3); + bias; ReLU (and the
-//              window maximum, which is exact, so max-then-bias equals bias-then-max);
+//   d2 .. u3:  the order of vf_net_conv.h (taps ascending, channels in steps of eight, K never split); + bias; ReLU (and
+//              the window maximum, which is exact, so max-then-bias equals bias-then-max);
 //   up-sample: the (at most four) contributing inputs in (ky, kx) ascending order of the transposed-convolution kernel,
 //              each an fmaf with the exactly representable weight k[ky] * k[kx];
 //   flow:      (ky, kx, ci) ascending; + bias
-// - and an MFMA row (an output position) does not see the other rows of its tile.  Padding taps multiply zeros or are
-// skipped (fmaf(0, w, acc) == acc).  K is never split.  A pair's flow is therefore the same whatever call, slot or number
-// of pairs it is computed with.
+// Padding taps multiply zeros or are skipped (fmaf(0, w, acc) == acc).  A pair's flow is therefore the same whatever call,
+// slot or number of pairs it is computed with.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "vf_conv_mfma.h"
+#include "vf_net_conv.h"
 
 namespace vf {
 
@@ -103,55 +102,26 @@ regnet_d1_kernel(const float *__restrict__ cur, const float *__restrict__ ref, i
 // d2 .. u3: in [n_img][Hin][Win][Cin] -> relu(conv 3x3 / 1, zero padding 1, + bias); POOL: the 2x2 maxima
 // [n_img][Hin / 2][Win / 2][Cout], else [n_img][Hin][Win][Cout].  One wave per task = (image, tile of 32 / tw rows x tw
 // columns, group of NT * 32 output channels), tw = 1 << tw_shift (16, or 8 for narrow maps; POOL needs 16 and even Hin, Win);
-// positions past the map are idle (loaded as zeros, not stored).  wp: packed [step][half][ceil(Cout / 32)][32][4]
-// (vf_regnet_load_weights; columns past Cout are zero), step = tap * Cin / 8 + channel block, element q of lane (j, half) =
-// w[tap][8 * block + 4 * half + q][32 * ntile + j]: one 16-byte load of each operand feeds four MFMAs.  MFMA lane layout as
-// in vf_frame_scorer.h (D register r of lane l: row (r & 3) + 8 (r >> 2) + 4 (l >> 5), column l & 31).
+// positions past the map are idle (not stored).  wp: packed by vf_regnet_load_weights in the layout of vf_net_conv.h.
 template <int NT, bool POOL>
-VF_GLOBAL VF_LAUNCH_BOUNDS(kRnThreads) void
+VF_GLOBAL VF_LAUNCH_BOUNDS(kNetConvThreads) void
 regnet_conv_kernel(const float *__restrict__ in, int n_img, int ncam, int Hin, int Win, int Cin, int Cout, int tw_shift,
                    const float *__restrict__ wp, const float *__restrict__ bias, long long wp_view_stride,
                    float *__restrict__ out) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int j = lane & 31, half = lane >> 5;
+    const int j = threadIdx.x & 31, half = (threadIdx.x & 63) >> 5;
     const int tw = 1 << tw_shift, th = 32 >> tw_shift;
-    const int tiles_x = (Win + tw - 1) >> tw_shift, tiles_y = (Hin + th - 1) / th, mtiles = tiles_x * tiles_y;
-    const int ntile_all = (Cout + 31) / 32, ngroups = ntile_all / NT;
-    const long long task = (long long)blockIdx.x * (kRnThreads / 64) + wave;
-    if (task >= (long long)n_img * mtiles * ngroups) return;                // (no barrier in this kernel)
-    const int ng = (int)(task % ngroups), mt = (int)((task / ngroups) % mtiles), img = (int)(task / ((long long)ngroups * mtiles));
+    const int tiles_x = (Win + tw - 1) >> tw_shift, tiles_y = (Hin + th - 1) / th;
+    const int ntile_all = (Cout + 31) / 32;
+    int img, mt, ng;
+    if (!net_conv_task(n_img, tiles_x * tiles_y, ntile_all / NT, img, mt, ng)) return;
     const int c = img % ncam;
     const int y0 = (mt / tiles_x) * th, x0 = (mt % tiles_x) << tw_shift;
     const int y = y0 + (j >> tw_shift), x = x0 + (j & (tw - 1));
-    const bool row_ok = y < Hin && x < Win;
-    const float *src = in + (long long)img * Hin * Win * Cin;
-    const f32x4 *w4 = reinterpret_cast<const f32x4 *>(wp + c * wp_view_stride);
-    const int blocks = Cin / 8;
 
     f32x16 acc[NT];
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[nt][r] = 0.f;
+    net_conv3x3_mma<NT>(acc, in + (long long)img * Hin * Win * Cin, Hin, Win, Cin, y, x, y < Hin && x < Win,
+                        reinterpret_cast<const f32x4 *>(wp + c * wp_view_stride), ntile_all, ng, j, half);
 
-    for (int tap = 0; tap < 9; ++tap) {
-        const int iy = y + tap / 3 - 1, ix = x + tap % 3 - 1;
-        const bool ok = row_ok && iy >= 0 && iy < Hin && ix >= 0 && ix < Win;
-        const f32x4 *a4 = reinterpret_cast<const f32x4 *>(src + ((long long)(ok ? iy : 0) * Win + (ok ? ix : 0)) * Cin + 4 * half);
-        const f32x4 *b4 = w4 + ((long long)(tap * blocks * 2 + half) * ntile_all + ng * NT) * 32 + j;
-        for (int s = 0; s < blocks; ++s) {
-            f32x4 a = {0.f, 0.f, 0.f, 0.f};
-            if (ok) a = a4[2 * s];
-            f32x4 bq[NT];
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) bq[nt] = b4[((long long)s * 2 * ntile_all + nt) * 32];
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt)
-                    acc[nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[q], bq[nt][q], acc[nt], 0, 0, 0);
-        }
-    }
     const float *bv = bias + c * Cout;
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) {
@@ -174,7 +144,7 @@ regnet_conv_kernel(const float *__restrict__ in, int n_img, int ncam, int Hin, i
         } else {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int i = (r & 3) + 8 * (r >> 2) + 4 * half;
+                const int i = net_mma_row(r, half);
                 const int yy = y0 + (i >> tw_shift), xx = x0 + (i & (tw - 1));
                 if (yy < Hin && xx < Win) out[(((long long)img * Hin + yy) * Win + xx) * Cout + co] = fmaxf(acc[nt][r] + bc, 0.f);
             }
