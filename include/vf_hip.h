@@ -287,6 +287,41 @@ int vf_regnet_load_weights(vf_regnet *r, const float *host_blob, size_t n_floats
 int vf_regnet_flow(vf_regnet *r, const float *d_current, const float *d_reference, int32_t n, float *d_flow,
                    void *stream);
 
+/* Inverse-model policy: the action-inference network on the device (reference
+ * visual_mpc/policy/inverse_models/inverse_model_base_controller.py:4,31-32: predictor_class(model_params_path, {}, n_gpus,
+ * first_gpu) and restore(); :76-80: one call per replanning step with the start image, the goal image, the context actions
+ * and the context frames of camera 0, which returns the next T actions).  The robonet.inverse_model package is not part of
+ * the reference snapshot; the network is this project's (visual_foresight_amd/video_prediction/inverse_model_arch.py: two
+ * towers of the frame scorer's four 3x3 / 2 convolutions with a mean over the positions - `pair` on concat[goal, start],
+ * `ctx` on every context frame - and an LSTM cell of 128 units, warmed up on the context, that decodes n_actions actions).
+ * height and width are multiples of 16, width at most 128, adim 1..8, n_context 1..4, n_actions 1..32, max_batch the most
+ * problems of one call.  Every device buffer is allocated in vf_invmodel_create; vf_invmodel_load_weights is the one
+ * blocking call.  The activations are scratch of the model: like a scorer, a model is driven from ONE stream at a time.  A
+ * problem's actions have the same bits whatever n, slot or call they are computed in. */
+typedef struct vf_invmodel_config {
+    int32_t height, width, adim, n_context, n_actions, max_batch, device;
+    float input_scale;          /* the images are multiplied by this (float32) before c1 */
+} vf_invmodel_config;
+
+typedef struct vf_invmodel vf_invmodel;
+
+/* float32 values of the weights, the canonical table of inverse_model_arch.py concatenated in table order; 0 +
+ * vf_last_error() for a bad config. */
+size_t vf_invmodel_weight_count(const vf_invmodel_config *cfg);
+int vf_invmodel_create(const vf_invmodel_config *cfg, vf_invmodel **out);
+int vf_invmodel_destroy(vf_invmodel *m);
+/* HOST blob; re-packs the convolution weights for the MFMA kernel into the buffers vf_invmodel_create allocated (replaces
+ * the restore() of the reference's predictor). */
+int vf_invmodel_load_weights(vf_invmodel *m, const float *host_blob, size_t n_floats);
+/* All DEVICE float32.  d_start, d_goal [n][H][W][3] and d_ctx_frames [n][n_context][H][W][3] in [0, 1], 16-byte aligned;
+ * d_ctx_actions [n][n_context][adim]; d_actions [n][n_actions][adim]; d_hidden (may be NULL)
+ * [n][n_context + n_actions][2][128] = h and c after every step of the recurrence (tests localise an error with it).
+ * Enqueues a fixed number of launches on `stream` whatever n_actions is, never synchronises, allocates nothing.
+ * VF_ERR_INVALID (nothing launched): a NULL pointer, a misaligned image pointer, n < 1 or n > max_batch, weights not
+ * loaded. */
+int vf_invmodel_infer(vf_invmodel *m, const float *d_start, const float *d_goal, const float *d_ctx_frames,
+                      const float *d_ctx_actions, int32_t n, float *d_actions, float *d_hidden, void *stream);
+
 /* Copy the predictions of the last vf_rollout out in the reference's layout (camera axis,
  * normalised distributions).  Any destination may be NULL.  first/count select a range of rolled
  * sequences.  Replaces the gen_images/gen_distrib/gen_states fetch of

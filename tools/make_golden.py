@@ -704,6 +704,84 @@ def golden_registration():
     return arrays, meta
 
 
+# ----------------------------------------------------------------------------- inverse-model policy
+INVERSE_MODEL_EPISODES = (   # name, seed, policy overrides, actions per plan of the fake, steps, steps after the second reset()
+    ('replan2', 7, {'T': 3}, 3, 9, 4),                          # num_context 2, replan_every 2 (the defaults)
+    ('replan2_short', 7, {'T': 3}, 1, 9, 4),                    # ... and a plan of one action: it runs out at its second step
+    ('replan1', 8, {'T': 2, 'replan_every': 1}, 2, 5, 3),
+    ('replan1_short', 8, {'T': 2, 'replan_every': 1}, 0, 5, 3),  # ... and an empty plan
+)
+
+
+def inverse_model_inputs(seed, steps, H=16, W=16, ncam=2):
+    """The image stream and the goal of an episode: uint8 frames ``[steps, ncam, H, W, 3]``, float64 goal ``[1, ncam, H, W, 3]``."""
+    rs = np.random.RandomState(seed)
+    return rs.randint(0, 256, (steps, ncam, H, W, 3)).astype(np.uint8), rs.uniform(0, 1, (1, ncam, H, W, 3))
+
+
+def run_inverse_model_episode(ctrl_class, fake, seed, overrides, steps, steps_again):
+    """Drive a controller class (the reference's while minting, this repo's in tests/test_inverse_model.py) through one
+    episode, ``reset()`` and a second one -> (arrays, meta)."""
+    ag = {'adim': 4, 'sdim': 5, 'image_height': 16, 'image_width': 16}
+    frames, goal = inverse_model_inputs(seed, max(steps, steps_again))
+    ctrl = ctrl_class(ag, dict(overrides), 0, 1)
+    pred = fake.instances[-1]
+    arrays, meta = {}, {'seed': seed, 'overrides': overrides, 'steps': steps, 'steps_again': steps_again,
+                        'constructed': {'model_params_path': pred.model_params_path, 'n_gpus': pred.n_gpus,
+                                        'first_gpu': pred.first_gpu, 'restored': pred.restored}}
+    try:
+        ctrl.act(t=0, i_tr=0, images=frames[:1], goal_image=goal)
+        meta['act_before_reset'] = 'ok'
+    except AttributeError as e:
+        meta['act_before_reset'] = 'AttributeError: ' + str(e).split("'")[-2]
+    for episode, n in enumerate((steps, steps_again)):
+        ctrl.reset()
+        np.random.seed(seed + 100 * episode)
+        actions, counters, error = [], [], None
+        for t in range(n):
+            try:
+                out = ctrl.act(t=t, i_tr=episode, images=frames[:t + 1], goal_image=goal)
+            except AssertionError as e:
+                error = {'t': t, 'text': str(e)}
+                break
+            assert out['plan_stat'] is ctrl.plan_stat and out['plan_stat'] == {}
+            actions.append(np.asarray(out['actions'], dtype=np.float64))
+            counters.append(ctrl.action_counter)
+        if actions:
+            arrays['ep%d/actions' % episode] = np.stack(actions)
+            arrays['ep%d/context_frames' % episode] = np.stack(ctrl.context_frames)
+            arrays['ep%d/context_actions' % episode] = np.stack([np.asarray(a, np.float64) for a in ctrl.context_actions])
+        meta['ep%d' % episode] = {'counters': counters, 'error': error, 'calls_so_far': len(pred.calls),
+                                  'action_dtypes': [str(np.asarray(a).dtype) for a in actions]}
+    meta['calls'] = pred.calls
+    return arrays, meta
+
+
+def golden_inverse_model():
+    """Run the reference's REAL ``InvModelBaseController`` (``visual_mpc/policy/inverse_models/
+    inverse_model_base_controller.py``) behind an import stub for ``robonet.inverse_model.testing.
+    action_inference_interface`` (absent from the snapshot) whose ``ActionInferenceInterface`` is the deterministic fake of
+    ``tests/helpers/fake_action_inference.py`` - the default ``predictor_class`` the reference then constructs."""
+    from tests.helpers.fake_action_inference import make_fake_action_inference
+    arrays, meta = {}, {'numpy': np.__version__, 'episodes': {}}
+    for name, seed, overrides, n_plan, steps, steps_again in INVERSE_MODEL_EPISODES:
+        fake = make_fake_action_inference(n_plan, 4)
+        base = 'robonet.inverse_model'
+        im, testing, aii = (types.ModuleType(base), types.ModuleType(base + '.testing'),
+                            types.ModuleType(base + '.testing.action_inference_interface'))
+        aii.ActionInferenceInterface = fake
+        im.testing, testing.action_inference_interface = testing, aii
+        sys.modules['robonet'].inverse_model = im
+        sys.modules.update({base: im, base + '.testing': testing, base + '.testing.action_inference_interface': aii})
+        sys.modules.pop('visual_mpc.policy.inverse_models.inverse_model_base_controller', None)   # (binds the class at import)
+        from visual_mpc.policy.inverse_models.inverse_model_base_controller import InvModelBaseController
+        with quiet():
+            a, m = run_inverse_model_episode(InvModelBaseController, fake, seed, overrides, steps, steps_again)
+        arrays.update({name + '/' + k: v for k, v in a.items()})
+        meta['episodes'][name] = m
+    return arrays, meta
+
+
 def main():
     install_stubs()
     from visual_mpc.policy.cem_controllers import PixelCostController, CEMBaseController
@@ -724,6 +802,7 @@ def main():
     dump('pred_util', *golden_pred_util(ref))
     dump('traj_layout', *golden_traj_layout())
     dump('registration', *golden_registration())
+    dump('inverse_model', *golden_inverse_model())
     dump('experiment_files', None, golden_experiment_files())
     print('wrote fixtures to', OUT, 'with numpy', np.__version__)
     for fn in sorted(os.listdir(OUT)):

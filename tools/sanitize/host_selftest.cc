@@ -279,6 +279,41 @@ int main() {
             if (vf_regnet_create(&bad_rn, &r) == 0 || vf_regnet_weight_count(&bad_rn) != 0) { std::fprintf(stderr, "regnet at 64x136 accepted\n"); rc = 1; }
             std::printf("  registration net: ch_mult 1 / 2 / 4 at 64x64 / 48x64 / 128x128, refusals: %s\n", rc ? "FAILED" : "ok");
         }
+        // the action-inference network of the inverse-model policy: table, buffers and packer (two towers in one buffer per
+        // layer) at the ends of every range; the refusals of vf_invmodel_infer
+        {
+            alignas(16) static float img[8];
+            float act[8];
+            const int shapes[4][5] = {{16, 16, 1, 1, 1}, {64, 64, 4, 2, 15}, {48, 64, 5, 3, 7}, {96, 128, 8, 4, 32}};
+            for (const auto &sh : shapes) {
+                vf_invmodel_config ic = {sh[0], sh[1], sh[2], sh[3], sh[4], 2, 0, 1.f};
+                vf_invmodel *m = nullptr;
+                if (vf_invmodel_create(&ic, &m)) { std::fprintf(stderr, "vf_invmodel_create: %s\n", vf_last_error()); rc = 1; continue; }
+                const size_t n = vf_invmodel_weight_count(&ic);
+                std::vector<float> w(n, 0.5f);
+                if (vf_invmodel_infer(m, img, img, img, act, 1, act, nullptr, nullptr) != VF_ERR_INVALID || std::string(vf_last_error()).find("not loaded") == std::string::npos) rc = 1;
+                if (n == 0 || vf_invmodel_load_weights(m, w.data(), n) || vf_invmodel_load_weights(m, w.data(), n)) {
+                    std::fprintf(stderr, "vf_invmodel_load_weights: %s\n", vf_last_error()); rc = 1;
+                }
+                if (vf_invmodel_load_weights(m, w.data(), n - 1) == 0) { std::fprintf(stderr, "short inverse-model blob accepted\n"); rc = 1; }
+                if (vf_invmodel_infer(m, img, img, img, act, 3, act, nullptr, nullptr) != VF_ERR_INVALID || std::string(vf_last_error()).find("max_batch") == std::string::npos) rc = 1;
+                if (vf_invmodel_infer(m, img, img, img, act, 0, act, nullptr, nullptr) != VF_ERR_INVALID) rc = 1;
+                if (vf_invmodel_infer(m, img + 1, img, img, act, 1, act, nullptr, nullptr) != VF_ERR_INVALID || std::string(vf_last_error()).find("aligned") == std::string::npos) rc = 1;
+                if (vf_invmodel_infer(m, img, img, img + 1, act, 1, act, nullptr, nullptr) != VF_ERR_INVALID || std::string(vf_last_error()).find("aligned") == std::string::npos) rc = 1;
+                if (vf_invmodel_infer(m, img, nullptr, img, act, 1, act, nullptr, nullptr) != VF_ERR_INVALID) rc = 1;
+                if (vf_invmodel_infer(m, img, img, img, nullptr, 1, act, nullptr, nullptr) != VF_ERR_INVALID) rc = 1;
+                if (vf_invmodel_infer(m, img, img, img, act, 1, nullptr, nullptr, nullptr) != VF_ERR_INVALID) rc = 1;
+                if (vf_invmodel_destroy(m)) rc = 1;
+            }
+            const vf_invmodel_config bad_im[7] = {{40, 64, 4, 2, 15, 1, 0, 1.f}, {64, 144, 4, 2, 15, 1, 0, 1.f}, {64, 64, 9, 2, 15, 1, 0, 1.f},
+                                                  {64, 64, 4, 5, 15, 1, 0, 1.f}, {64, 64, 4, 2, 33, 1, 0, 1.f}, {64, 64, 4, 2, 15, 0, 0, 1.f},
+                                                  {64, 64, 4, 2, 15, 1, 0, 0.f}};
+            for (const vf_invmodel_config &b : bad_im) {
+                vf_invmodel *m = nullptr;
+                if (vf_invmodel_create(&b, &m) == 0 || m != nullptr || vf_invmodel_weight_count(&b) != 0) { std::fprintf(stderr, "bad inverse-model config accepted\n"); rc = 1; }
+            }
+            std::printf("  inverse model: four shapes from 16x16 / adim 1 to 96x128 / adim 8, refusals: %s\n", rc ? "FAILED" : "ok");
+        }
         if (hh && vf_destroy(hh)) { std::fprintf(stderr, "vf_destroy after the injected failures failed\n"); rc = 1; }
         std::printf("  injected failures (bad_alloc, std::exception, foreign) in vf_create / vf_load_weights / build_schedule: %s\n",
                     rc ? "FAILED" : "status codes returned, handle reusable");

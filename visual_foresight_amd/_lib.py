@@ -15,7 +15,7 @@ REPO = os.path.dirname(_HERE)
 LIB_PATH = os.environ.get('VF_LIBRARY') or os.path.join(_HERE, 'libvf_hip.so')     # override: experiments only
 SOURCES = [os.path.join(_HERE, 'csrc', f) for f in
            ('vf_engine.hip', 'vf_conv_mfma.h', 'vf_conv_gsplit.h', 'vf_small_kernels.h', 'vf_goal_image.h', 'vf_plan_render.h', 'vf_net_conv.h',
-            'vf_frame_scorer.h', 'vf_engine_sidenet.inc', 'vf_engine_scorer.inc', 'vf_registration_net.h', 'vf_engine_regnet.inc', 'vf_persistent.h',
+            'vf_frame_scorer.h', 'vf_engine_sidenet.inc', 'vf_engine_scorer.inc', 'vf_registration_net.h', 'vf_engine_regnet.inc', 'vf_inverse_model.h', 'vf_engine_invmodel.inc', 'vf_persistent.h',
             'vf_conv_bf16x6.h', 'vf_fused_top.h', 'vf_fc_tile.h', 'vf_conv_first.h', 'vf_savp3.h', 'vf_engine_savp3.inc')] + \
           [os.path.join(REPO, 'include', 'vf_hip.h')]
 
@@ -29,7 +29,9 @@ EXPORTS = ('vf_abi_version', 'vf_last_error', 'vf_weight_count', 'vf_create', 'v
            'vf_ensemble_scores', 'vf_goal_image_scores', 'vf_render_plans',
            'vf_scorer_weight_count', 'vf_scorer_create', 'vf_scorer_destroy', 'vf_scorer_load_weights', 'vf_scorer_embed',
            'vf_scorer_scores',
-           'vf_regnet_weight_count', 'vf_regnet_create', 'vf_regnet_destroy', 'vf_regnet_load_weights', 'vf_regnet_flow')
+           'vf_regnet_weight_count', 'vf_regnet_create', 'vf_regnet_destroy', 'vf_regnet_load_weights', 'vf_regnet_flow',
+           'vf_invmodel_weight_count', 'vf_invmodel_create', 'vf_invmodel_destroy', 'vf_invmodel_load_weights',
+           'vf_invmodel_infer')
 ABI_VERSION = 7
 
 
@@ -50,6 +52,11 @@ class VfScorerConfig(ctypes.Structure):
 
 class VfRegnetConfig(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ('height', 'width', 'ncam', 'ch_mult', 'max_pairs', 'device')]
+
+
+class VfInvModelConfig(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ('height', 'width', 'adim', 'n_context', 'n_actions', 'max_batch', 'device')] + \
+               [('input_scale', ctypes.c_float)]
 
 
 def _hipcc():
@@ -131,6 +138,12 @@ def load_library():
     lib.vf_regnet_destroy.argtypes = [P]
     lib.vf_regnet_load_weights.argtypes = [P, P, ctypes.c_size_t]
     lib.vf_regnet_flow.argtypes = [P, P, P, ctypes.c_int32, P, P]
+    lib.vf_invmodel_weight_count.restype = ctypes.c_size_t
+    lib.vf_invmodel_weight_count.argtypes = [ctypes.POINTER(VfInvModelConfig)]
+    lib.vf_invmodel_create.argtypes = [ctypes.POINTER(VfInvModelConfig), ctypes.POINTER(P)]
+    lib.vf_invmodel_destroy.argtypes = [P]
+    lib.vf_invmodel_load_weights.argtypes = [P, P, ctypes.c_size_t]
+    lib.vf_invmodel_infer.argtypes = [P, P, P, P, P, ctypes.c_int32, P, P, P]
     lib.vf_register.argtypes = [P, P, P, P, P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, P, P, P, P, P]
     lib.vf_allgather_scores.argtypes = [P, P, P, ctypes.c_int32, P, P]
     lib.vf_comm_init_all.argtypes = [ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(P)]
@@ -161,6 +174,7 @@ def load_library():
                  'vf_goal_image_scores', 'vf_render_plans', 'vf_scorer_create', 'vf_scorer_destroy',
                  'vf_scorer_load_weights', 'vf_scorer_embed', 'vf_scorer_scores',
                  'vf_regnet_create', 'vf_regnet_destroy', 'vf_regnet_load_weights', 'vf_regnet_flow',
+                 'vf_invmodel_create', 'vf_invmodel_destroy', 'vf_invmodel_load_weights', 'vf_invmodel_infer',
                  'vf_export', 'vf_register', 'vf_allgather_scores', 'vf_comm_init_all', 'vf_comm_destroy',
                  'vf_allgather_scores_group', 'vf_set_phase_stats',
                  'vf_debug_phase_stats', 'vf_debug_poison_status'):

@@ -38,6 +38,7 @@
 #include "vf_goal_image.h"
 #include "vf_frame_scorer.h"
 #include "vf_registration_net.h"
+#include "vf_inverse_model.h"
 #include "vf_plan_render.h"
 #include "vf_conv_bf16x6.h"
 #include "vf_persistent.h"
@@ -3123,3 +3124,4 @@ int vf_get_profile(vf_handle *h, double *kernel_ms, int64_t *launches, double *f
 #include "vf_engine_sidenet.inc"
 #include "vf_engine_scorer.inc"
 #include "vf_engine_regnet.inc"
+#include "vf_engine_invmodel.inc"
