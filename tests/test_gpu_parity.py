@@ -36,8 +36,18 @@ def _predictor(H, W, T, nd, bs, seed=3, n_context=2, precision='fp32'):
     return pred, weights
 
 
+def _designated(H, W, shape, rs):
+    """Designated pixels ``shape + (2,)``: rows from [0, H), columns from [0, W).  They are drawn on a copy of the generator,
+    and ``rs`` itself moves on as the former ``randint(0, min(H, W))`` moved it: every later draw of a test - frames,
+    actions, goals - is what it was."""
+    fork = np.random.RandomState()
+    fork.set_state(rs.get_state())
+    rs.randint(0, min(H, W), tuple(shape) + (2,))
+    return np.stack([fork.randint(0, H, shape), fork.randint(0, W, shape)], axis=-1)
+
+
 def _context(H, W, nd, rs, hist=3):
-    desig = rs.randint(0, min(H, W), (1, nd, 2))
+    desig = _designated(H, W, (1, nd), rs)
     return {'context_frames': rs.randint(0, 256, (hist, 1, H, W, 3)).astype(np.uint8),
             'context_actions': rs.normal(0, 0.05, (hist - 1, 4)),
             'context_states': rs.normal(0, 0.1, (hist, 5)),
@@ -308,7 +318,7 @@ def test_two_view_predictor_matches_per_view_oracle():
     weights = [CdnaWeights.random(cfg, seed=10 + c, bias_scale=0.05, ln_jitter=0.1) for c in range(ncam)]
     pred.restore(weights)
     rs = np.random.RandomState(77)
-    desig = rs.randint(0, H, (ncam, nd, 2))
+    desig = _designated(H, W, (ncam, nd), rs)
     ctx = {'context_frames': rs.randint(0, 256, (3, ncam, H, W, 3)).astype(np.uint8),
            'context_actions': rs.normal(0, 0.05, (2, 4)), 'context_states': rs.normal(0, 0.1, (3, 5)),
            'context_pixel_distributions': pixel_cost.one_hot_distrib(desig, 2, ncam, H, W, nd)}

@@ -32,7 +32,12 @@ def _predictor(H, W, T, nd, bs, adim=6, seed=3, arch='savp', **extra):
 
 
 def _context(H, W, nd, adim, rs, hist=3):
-    desig = rs.randint(0, min(H, W), (1, nd, 2))
+    # rows from [0, H), columns from [0, W), on a copy of the generator: ``rs`` itself moves on as the former
+    # ``randint(0, min(H, W))`` moved it, so every later draw of a test - frames, actions, goals - is what it was
+    fork = np.random.RandomState()
+    fork.set_state(rs.get_state())
+    rs.randint(0, min(H, W), (1, nd, 2))
+    desig = np.stack([fork.randint(0, H, (1, nd)), fork.randint(0, W, (1, nd))], axis=-1)
     d = pixel_cost.one_hot_distrib(desig, 2, 1, H, W, nd)
     d[1] = 0.5 * d[1] + 0.5 / (H * W)        # the two context distributions differ: the first-frame term is visible
     return {'context_frames': rs.randint(0, 256, (hist, 1, H, W, 3)).astype(np.uint8),

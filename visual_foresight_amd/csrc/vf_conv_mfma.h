@@ -349,7 +349,21 @@ __device__ __forceinline__ long long wave_sum(long long v) {
 // fp32 rounding), and integer addition is associative.  The per-sample totals - and therefore every
 // result of the network - do not depend on how a layer is cut into tiles, waves and lanes, which is
 // what allows the tile plan to follow the batch size without giving up bit-identical scores across
-// chunkings, rank counts and launch strategies.  Range: |v| < 46340 (outputs here are O(1) .. O(100)).
+// chunkings, rank counts and launch strategies.
+// Range - two bounds, the second is the one a layer meets first:
+//   per element  |v| < 46340            (v^2 2^32 < 2^63)
+//   per sample   sum v^2 < 2^31         (the int64 total of trunc(v^2 2^32)), i.e. rms < sqrt(2^31 / n) for n elements:
+//       raw-statistic layer          n at 64x64   rms limit   n at 128x128   rms limit
+//       arch 0    enc0   (ln1)          2^15         256          2^17          128
+//       arch 0    convt3 (ln9)          2^17         128          2^19           64     ('public' decoder: 2^18 / 91, 2^20 / 45)
+//       arch 1/2  enc00  (lna)          2^14         362          2^16          181
+//       arch 1/2  enc0   (ln1)          2^13         512          2^15          256
+//       arch 1/2  convt3 (ln9)          2^15         256          2^17          128
+//       arch 1/2  convt4 (lnb)          2^17         128          2^19           64
+//   (the conv-LSTM outputs behind ln2 .. ln8 are bounded by 1.)  Beyond the second bound the total wraps silently: var
+//   clamps to 0 and rstd becomes 1e6 - nothing on the device detects it.  Tested up to sum v^2 / 2^31 = 0.25, with values
+//   up to 750 and waves of one sample on both sides of the 128 of the float64 fast path below
+//   (tests/test_weight_regimes.py, tests/test_gpu_magnitudes.py).
 constexpr double kStatScale = 4294967296.0;         // 2^32
 __device__ __forceinline__ long long stat_q(const float v) { return (long long)((double)v * kStatScale); }
 __device__ __forceinline__ long long stat_q2(const float v) { return (long long)((double)v * (double)v * kStatScale); }

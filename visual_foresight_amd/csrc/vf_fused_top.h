@@ -65,8 +65,8 @@ __device__ __forceinline__ void fused_top_body(const PT &p, const CT &c, f32x16 
     }
     // The exact statistics are the integers trunc(v 2^32), trunc(v^2 2^32).  While every |v| of the wave is below 128 the
     // lane's 64 terms can be added as float64 integers (each below 2^46, the sum below 2^53: exact) and converted once -
-    // 8 instead of ~24 instructions per value; a wave with a larger value (never seen) takes the per-value conversion.
-    // Either way the same integers.
+    // 8 instead of ~24 instructions per value; a wave with a larger value takes the per-value conversion.  Either way the
+    // same integers: tests/test_gpu_magnitudes.py runs layers whose waves split between the two branches.
     if (__all(vmax < 128.f)) {
         StatSumD st;
 #pragma unroll
