@@ -97,7 +97,11 @@ typedef struct vf_config {
     int32_t zdim;               /* arch 3: how many of the adim action channels are the per-step latent z_t (they go
                                  * through the rnn_z cell and do not reach the state predictor); 0 for arch 0 - 2 */
     int32_t layer_spec;         /* arch 3: 0 = encoder / decoder table by min(height, width) as the public code selects it;
-                                 * 32 / 64 / 128 force a table (64 = the paper's five-cell network); 0 for arch 0 - 2 */
+                                 * 32 / 64 / 128 force a table (64 = the paper's five-cell network).  arch 0: 0 = the survey
+                                 * table, 1 = the decoder widths of the public CDNA code, 2 = the survey table with
+                                 * appearance-flow compositing (a 1x1 flow head and nine bilinearly gathered warps in place of
+                                 * the CDNA FC and kernels; tensors flow/w, flow/b where cdna/w, cdna/b sit); 1 and 2 are
+                                 * exact fp32 only (precision 0).  0 for arch 1 - 2 */
 } vf_config;
 
 typedef struct vf_handle vf_handle;

@@ -84,6 +84,14 @@ int main() {
     // arch 0 on the decoder widths of the public CDNA code (layer_spec 1: convt2 96 -> 96, convt3 64 -> 64, unfused top)
     rc |= run_case(64, 64, 4, 5, 2, 2, 3, 37, 0, 1, 1, b_small, 4, 0, 0, 1);
     rc |= run_case(48, 64, 3, 3, 1, 2, 13, 200, 0, 2, 1, b_c2, 3, 0, 0, 1);
+    // arch 0 with appearance-flow compositing (layer_spec 2: no CDNA FC, no kernel-finish items; fused and two-phase top, the
+    // shape that cannot be fused, four designated pixels, two views) - and, first, the cdna table of the first flow shape:
+    // the two may differ by exactly the FC and finish items (tests/test_appflow.py)
+    rc |= run_case(64, 64, 7, 5, 2, 2, 3, 37, 0, 1, 1, b_small, 4, 0, 0, 0);
+    rc |= run_case(64, 64, 7, 5, 2, 2, 3, 37, 0, 1, 1, b_small, 4, 0, 0, 2);
+    rc |= run_case(32, 32, 7, 5, 1, 1, 2, 16, 0, 1, 1, b_small, 3, 0, 0, 2);
+    rc |= run_case(40, 56, 7, 5, 4, 2, 2, 16, 0, 2, 1, b_small, 3, 0, 0, 2);
+    rc |= run_case(64, 64, 7, 3, 1, 2, 13, 200, 0, 1, 1, b_c2, 3, 0, 0, 2);
     // arch 3: the published SAVP generator - every layer table (32 / 64 / 128 pixels, the paper's table forced on 128 x 128),
     // a config-5 shard, two views, an odd shape
     rc |= run_case(32, 32, 12, 5, 1, 2, 3, 37, 0, 1, 1, b_small, 4, 3, 8);
@@ -109,6 +117,10 @@ int main() {
     if (vf_create(&bad7, &h) == 0) { std::fprintf(stderr, "zdim with arch 0 accepted\n"); rc = 1; }
     vf_config bad8 = {72, 64, 12, 5, 1, 2, 15, 4, 8, 0, 0, 1, 1, 3, 8, 128};   // four scales need multiples of 16
     if (vf_create(&bad8, &h) == 0) { std::fprintf(stderr, "arch 3 / four scales at 72x64 accepted\n"); rc = 1; }
+    vf_config bad9 = {64, 64, 4, 5, 1, 2, 15, 10, 8, 0, 1, 1, 1, 0, 0, 2};     // appearance flow is fp32 only
+    if (vf_create(&bad9, &h) == 0) { std::fprintf(stderr, "appearance flow in the split-bf16 mode accepted\n"); rc = 1; }
+    vf_config bad10 = {128, 128, 12, 5, 1, 2, 15, 10, 8, 0, 0, 1, 1, 1, 0, 2};  // ... and belongs to arch 0
+    if (vf_create(&bad10, &h) == 0) { std::fprintf(stderr, "appearance flow with arch 1 accepted\n"); rc = 1; }
     // "No exception crosses this boundary" (include/vf_hip.h): a std::bad_alloc / std::exception / foreign throw inside the
     // schedule builder, the weight packer or vf_create comes back as a status code with vf_last_error() set, leaks nothing
     // (ASan's leak check runs at exit) and leaves the handle usable and destroyable

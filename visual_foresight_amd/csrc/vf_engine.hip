@@ -127,6 +127,8 @@ struct TensorDesc {
 };
 
 static int a_of(const vf_config &c) { return c.adim + c.sdim; }
+// arch 0, layer_spec 2: appearance-flow compositing (cdna_arch.py transformation='flow')
+static bool is_flow(const vf_config &c) { return c.arch == 0 && c.layer_spec == 2; }
 
 // arch 3 (the published SAVP generator): vf_engine_savp3.inc
 struct Savp3;
@@ -166,7 +168,9 @@ static std::vector<TensorDesc> tensor_table(const vf_config &c) {
     // arch 0 with layer_spec = 1: the decoder widths of the PUBLIC CDNA prediction_model (arXiv:1605.07157's code keeps the
     // concatenated width through its transposed convs: convt2 96 -> 96, convt3 64 -> 64, so lstm7 reads 96 + 32 channels and
     // the heads 64); layer_spec = 0: the widths of SURVEY row a14 (convt2 96 -> 64, convt3 64 -> 32)
-    const bool pub = c.arch == 0 && c.layer_spec == 1;
+    // arch 0 with layer_spec = 2: the survey widths with the appearance-flow head in place of the CDNA FC (cdna_arch.py
+    // transformation='flow'): flow/w [1][1][32][2 * kFlowWarps], flow/b where cdna/w, cdna/b sat
+    const bool pub = c.arch == 0 && c.layer_spec == 1, flow = is_flow(c);
     const int c_t2 = pub ? L[5] + L[1] : L[5], c_top = pub ? L[6] + 32 : 32;
     if (savp) { conv("enc00", 5, 5, 3, kEnc00Ch); ln("lna", kEnc00Ch); }
     conv("enc0", 5, 5, savp ? kEnc00Ch : 3, 32); ln("ln1", 32);
@@ -188,8 +192,11 @@ static std::vector<TensorDesc> tensor_table(const vf_config &c) {
     conv("masks", 1, 1, c_top, K + 1);
     // arch 2: the FOUR CDNA kernels of the published generator (the engine pads them to its num_masks = 6 slots at load)
     const int KF = c.arch == 2 ? K - 2 : K;
-    add("cdna/w", {fc_in, kTaps * KF});
-    add("cdna/b", {kTaps * KF});
+    if (flow) conv("flow", 1, 1, c_top, 2 * kFlowWarps);
+    else {
+        add("cdna/w", {fc_in, kTaps * KF});
+        add("cdna/b", {kTaps * KF});
+    }
     add("state/w", {a, c.sdim});
     add("state/b", {c.sdim});
     return t;
@@ -453,6 +460,7 @@ struct ViewData {
     float *ln_g[kNumLn] = {nullptr}, *ln_b[kNumLn] = {nullptr};    // ln1..ln9, lna (enc00), lnb (convt4)
     float *w_rgb = nullptr, *b_rgb = nullptr, *w_mask = nullptr, *b_mask = nullptr;
     float *w_state = nullptr, *b_state = nullptr, *w_sa = nullptr, *b_fc = nullptr;
+    float *w_flow = nullptr, *b_flow = nullptr;     // appearance-flow engines: the flow head (no CDNA FC, no b_fc)
     float *w_cond[7] = {nullptr};       // arch 2: conditioning rows of every conv-LSTM's weights, [25][adim + sdim][4C]
     float *ctx_frames = nullptr, *ctx_distrib = nullptr;
 };
@@ -466,6 +474,8 @@ struct vf_handle {
     bool savp = false;                  // vf_config.arch >= 1: four-scale SAVP-class generator (savp_arch.py)
     vf::Savp3 *s3 = nullptr;            // vf_config.arch == 3: the published SAVP generator (vf_engine_savp3.inc)
     bool cond = false;                  // vf_config.arch == 2: [action, latent, state] conditions every conv-LSTM
+    bool flow = false;                  // arch 0, layer_spec 2: appearance-flow compositing - no CDNA FC, no kernels; the flow
+                                        // kernels (composite_flow_kernel, rollout_flow_kernel) run in place of the CDNA ones
     float *cond_bias[7] = {nullptr};    // ... through per-sample border-class biases [2 step parities][ncam][max_batch][25][4C]
     int Hc, Wc;                         // input size of the three-scale conv-LSTM core (H, W; arch 1: H/2, W/2)
     int c_t2 = 64, c_top = 32;          // output channels of convt2 / convt3 (arch 0, layer_spec 1 - the public table: 96 / 64)
@@ -632,10 +642,13 @@ static int validate(const vf_config *c) {
         return s3_validate(c);
     }
     if (c->zdim != 0) return fail(VF_ERR_INVALID, "zdim belongs to arch 3 (must be 0 otherwise)");
-    if (c->layer_spec != 0 && !(c->arch == 0 && c->layer_spec == 1))
-        return fail(VF_ERR_INVALID, "layer_spec: arch 3's layer table, or 1 with arch 0 (the public CDNA decoder widths); 0 otherwise");
+    if (c->layer_spec != 0 && !(c->arch == 0 && (c->layer_spec == 1 || c->layer_spec == 2)))
+        return fail(VF_ERR_INVALID, "layer_spec: arch 3's layer table, or with arch 0 1 (the public CDNA decoder widths) or 2 "
+                                    "(appearance-flow compositing); 0 otherwise");
     if (c->arch == 0 && c->layer_spec == 1 && c->precision != 0)
         return fail(VF_ERR_INVALID, "the public decoder table (arch 0, layer_spec 1) is built for precision 0 (exact fp32) only");
+    if (is_flow(*c) && c->precision != 0)
+        return fail(VF_ERR_INVALID, "the appearance-flow table (arch 0, layer_spec 2) is built for precision 0 (exact fp32) only");
     if (c->arch == 2 ? c->num_masks != 6 : c->num_masks != 10)
         return fail(VF_ERR_INVALID, "num_masks must be 10 (arch 0 / 1), 6 (arch 2: four CDNA warps + previous + first + scratch) or 4 (arch 3)");
     if (c->max_batch < 1) return fail(VF_ERR_INVALID, "max_batch must be >= 1");
@@ -735,6 +748,10 @@ static int configure_kernels(vf_handle *h) {
     if ((rc = allow_lds(&rollout_persistent_kernel<2>, np))) return rc;
     if ((rc = allow_lds(&rollout_persistent_kernel<3>, np))) return rc;
     if ((rc = allow_lds(&rollout_persistent_kernel<4>, np))) return rc;
+    if ((rc = allow_lds(&rollout_flow_kernel<1>, np))) return rc;
+    if ((rc = allow_lds(&rollout_flow_kernel<2>, np))) return rc;
+    if ((rc = allow_lds(&rollout_flow_kernel<3>, np))) return rc;
+    if ((rc = allow_lds(&rollout_flow_kernel<4>, np))) return rc;
     return VF_OK;
 }
 
@@ -878,7 +895,14 @@ double vf_macs_per_sample_step(const vf_config *cfg) {
         macs += (double)r.h * r.w * d->shape[0] * d->shape[1] * d->shape[2] * d->shape[3];
     }
     const TensorDesc *fc = find_tensor(t, "cdna/w"), *sw = find_tensor(t, "state/w");
-    macs += (double)fc->shape[0] * fc->shape[1] + (double)sw->shape[0] * sw->shape[1];
+    macs += (double)sw->shape[0] * sw->shape[1];
+    if (is_flow(*cfg)) {        // the flow head, and four bilinear taps per warp and channel in place of the FC and the 5 x 5 warps
+        const TensorDesc *fw = find_tensor(t, "flow/w");
+        macs += (double)HF * WF * fw->shape[2] * fw->shape[3];
+        macs += (double)HF * WF * 4 * (3 + cfg->ndesig) * kFlowWarps;
+        return macs;
+    }
+    macs += (double)fc->shape[0] * fc->shape[1];
     macs += (double)HF * WF * kTaps * (3 + cfg->ndesig) * (cfg->arch == 2 ? cfg->num_masks - 2 : cfg->num_masks);
     return macs;
     VF_API_CATCH(double)
@@ -952,7 +976,8 @@ static int cdna_create(vf_handle *h) {
         h->fc_wide_ok = f.KC == 32 && f.ncg <= kFcGroups && f.nseg == 1 && f.segC[0] % 32 == 0;
     }
     h->layers = {&h->enc0, &h->lstm[0], &h->lstm[1], &h->enc1, &h->lstm[2], &h->lstm[3], &h->enc2, &h->enc3,
-                 &h->lstm[4], &h->convt1, &h->lstm[5], &h->convt2, &h->lstm[6], &h->convt3, &h->fc};
+                 &h->lstm[4], &h->convt1, &h->lstm[5], &h->convt2, &h->lstm[6], &h->convt3};
+    if (!h->flow) h->layers.push_back(&h->fc);      // (a flow engine has no CDNA FC: the plan above exists, nothing is packed or run)
     if (h->savp) { h->layers.push_back(&h->enc00); h->layers.push_back(&h->convt4); }
     h->small_plans = cfg->precision == 0;   // the split-bf16 tile has 128 rows only
     for (int k = 0; k < 7; ++k) {
@@ -1014,7 +1039,9 @@ static int cdna_create(vf_handle *h) {
         VF_ALLOC(vd.w_rgb, h->c_top * 3); VF_ALLOC(vd.b_rgb, 3);
         VF_ALLOC(vd.w_mask, h->c_top * (h->K + 1)); VF_ALLOC(vd.b_mask, h->K + 1);
         VF_ALLOC(vd.w_state, (size_t)nsa * cfg->sdim); VF_ALLOC(vd.b_state, cfg->sdim);
-        VF_ALLOC(vd.w_sa, (size_t)nsa * L[3]); VF_ALLOC(vd.b_fc, kTaps * h->K);
+        VF_ALLOC(vd.w_sa, (size_t)nsa * L[3]);
+        if (h->flow) { VF_ALLOC(vd.w_flow, (size_t)h->c_top * 2 * kFlowWarps); VF_ALLOC(vd.b_flow, 2 * kFlowWarps); }
+        else VF_ALLOC(vd.b_fc, kTaps * h->K);
         if (h->cond)
             for (int k = 0; k < 7; ++k) VF_ALLOC(vd.w_cond[k], (size_t)kTaps * nsa * 4 * L[k]);
     }
@@ -1053,8 +1080,8 @@ static int cdna_create(vf_handle *h) {
     VF_ALLOC(h->sbias, BV * L[3]);
     if (h->cond)
         for (int k = 0; k < 7; ++k) VF_ALLOC(h->cond_bias[k], 2 * BV * kCondClasses * 4 * L[k]);
-    VF_ALLOC(h->fc_part, BV * h->fc.nsplit * kTaps * h->K);
-    VF_ALLOC(h->kern, BV * kTaps * h->K);
+    VF_ALLOC(h->fc_part, h->flow ? 0 : BV * h->fc.nsplit * kTaps * h->K);
+    VF_ALLOC(h->kern, h->flow ? 0 : BV * kTaps * h->K);
     VF_ALLOC(h->frames_all, BV * h->T * H * W * 3);
     VF_ALLOC(h->distrib_all, BV * h->T * H * W * ND);
     VF_ALLOC(h->states_all, BV * h->T * cfg->sdim);
@@ -1132,6 +1159,7 @@ int vf_create(const vf_config *cfg, vf_handle **out) {
     h->blob_floats = h->table.back().offset + h->table.back().size();
     h->savp = cfg->arch == 1 || cfg->arch == 2;
     h->cond = cfg->arch == 2;
+    h->flow = is_flow(*cfg);
     h->Hc = h->savp ? h->H / 2 : h->H; h->Wc = h->savp ? h->W / 2 : h->W;
     const int H = h->H, W = h->W;
     h->ntiles = ((H + kCompTile - 1) / kCompTile) * ((W + kCompTile - 1) / kCompTile);
@@ -1301,7 +1329,11 @@ int vf_load_weights(vf_handle *h, const float *blob_all, size_t n_floats) {
         d = T("state/w"); if ((rc = dev_write(h, vd.w_state, blob + d->offset, d->size() * sizeof(float)))) return rc;
         d = T("state/b"); if ((rc = dev_write(h, vd.b_state, blob + d->offset, d->size() * sizeof(float)))) return rc;
         d = T("cdna/b");
-        if (h->cond) {
+        if (h->flow) {
+            const TensorDesc *fw = T("flow/w"), *fb = T("flow/b");
+            if ((rc = dev_write(h, vd.w_flow, blob + fw->offset, fw->size() * sizeof(float)))) return rc;
+            if ((rc = dev_write(h, vd.b_flow, blob + fb->offset, fb->size() * sizeof(float)))) return rc;
+        } else if (h->cond) {
             std::vector<float> bw((size_t)kTaps * h->K, 0.f);
             for (int tap = 0; tap < kTaps; ++tap)
                 for (int k = 0; k < h->K - 2; ++k) bw[(size_t)tap * h->K + k] = (blob + d->offset)[(size_t)tap * (h->K - 2) + k];
@@ -1492,7 +1524,14 @@ struct LaunchSink {
     }
     int composite(const CompositeParams &p, int ntiles, int /*view*/, std::initializer_list<int>) {
         dim3 grid(ntiles, p.B);
-        if (p.K == 6) {         // arch 2: four CDNA warps + previous + first frame + scratch
+        if (p.w_flow) {         // appearance flow
+            switch (p.ND) {
+                case 1: hipLaunchKernelGGL(composite_flow_kernel<1>, grid, dim3(256), 0, st, p); break;
+                case 2: hipLaunchKernelGGL(composite_flow_kernel<2>, grid, dim3(256), 0, st, p); break;
+                case 3: hipLaunchKernelGGL(composite_flow_kernel<3>, grid, dim3(256), 0, st, p); break;
+                default: hipLaunchKernelGGL(composite_flow_kernel<4>, grid, dim3(256), 0, st, p); break;
+            }
+        } else if (p.K == 6) {         // arch 2: four CDNA warps + previous + first frame + scratch
             switch (p.ND) {
                 case 1: hipLaunchKernelGGL((composite_kernel<1, 6>), grid, dim3(256), 0, st, p); break;
                 case 2: hipLaunchKernelGGL((composite_kernel<2, 6>), grid, dim3(256), 0, st, p); break;
@@ -1977,8 +2016,9 @@ static int emit_rollout(vf_handle *h, int view, const BatchView &v, const BatchV
         // and its only consumer is the compositing at the end of the step: it is emitted here, behind lstm6, where
         // its ready-to-run items fill the slots that would otherwise draw transposed-conv items still waiting for
         // the second round of lstm6 tiles.
+        // (An appearance-flow engine has no kernels: neither item is emitted, and the top depends on its two inputs alone.)
         int u_fin = -1, u_fc = -1;
-        if (produce) {
+        if (produce && !h->flow) {
             SegArg flat = h5n;      // same LayerNorm, viewed as [B][1][1][H8*W8*128]
             const ConvLayer &fc_l = Sink::fc_plan(h);
             p = params(fc_l, B, flat, nullptr);
@@ -1997,7 +2037,7 @@ static int emit_rollout(vf_handle *h, int view, const BatchView &v, const BatchV
             const int now[7] = {u_l1, u_l2, u_l3, u_l4, u_l5, u_l6, u_l7};
             for (int k = 0; k < 7; ++k) u_prev[k] = now[k];
         }
-        if (produce) {      // the (tiny) finalise step of the CDNA kernels: behind lstm7, by when the FC has long finished
+        if (produce && !h->flow) {      // the (tiny) finalise step of the CDNA kernels: behind lstm7, by when the FC has long finished
             FinParams fp;
             fp.partial = v.fc_part; fp.nsplit = h->fc.nsplit; fp.B = B; fp.K = h->K;
             fp.bias = vd.b_fc; fp.kern = v.kern;
@@ -2036,7 +2076,11 @@ static int emit_rollout(vf_handle *h, int view, const BatchView &v, const BatchV
             cp.ln_inv_n = (float)(1.0 / ((double)H * W * h->c_top));
             cp.CF = h->c_top;
             cp.w_rgb = vd.w_rgb; cp.b_rgb = vd.b_rgb; cp.w_mask = vd.w_mask; cp.b_mask = vd.b_mask;
-            cp.kern = v.kern;
+            // Appearance flow: the warps gather from the WHOLE previous frame / distributions of the sample.  Both routes of the
+            // top are released by this step's first conv (top_early), every tile of which waited for EVERY compositing tile of
+            // the previous step (`last`, dep_on: all tiles of the sample), so the gathers find the frame complete.
+            if (h->flow) { cp.w_flow = vd.w_flow; cp.b_flow = vd.b_flow; }
+            else cp.kern = v.kern;
             cp.prev_frame = frame_in; cp.prev_frame_bstride = frame_bs;
             if (s < nc) {
                 cp.prev_distrib = vd.ctx_distrib + (size_t)s * H * W * ND; cp.prev_distrib_bstride = 0;
@@ -2229,6 +2273,8 @@ extern "C" int vf_selftest_schedule(vf_handle *h, int32_t B, int32_t skip_shared
         if (P.first_ticket != ticket || P.n_items <= 0) return fail(VF_ERR_INVALID, "tickets are not contiguous");
         ticket += P.n_items;
         if (P.ndep < 0 || P.ndep > kMaxDeps) return fail(VF_ERR_INVALID, "bad dependency count");
+        if (h->flow && (P.type == PH_FC_PARTIAL || P.type == PH_CDNA_FIN))
+            return fail(VF_ERR_INVALID, "phase " + std::to_string(i) + ": a CDNA kernel item in an appearance-flow schedule");
         for (int d = 0; d < P.ndep; ++d) {
             // a dependency must point at the counters of a phase with smaller tickets
             bool found = false;
@@ -2355,6 +2401,10 @@ extern "C" int vf_selftest_schedule(vf_handle *h, int32_t B, int32_t skip_shared
             ok = ok && in_allocs(h, c.out_distrib, ((size_t)(P.B - 1) * c.out_distrib_bstride + hw * c.ND) * 4);
             ok = ok && in_allocs(h, c.out_sums, (size_t)P.B * c.ND * h->nblocks * 2 * 8);
             ok = ok && in_allocs(h, c.kern, (size_t)P.B * kTaps * c.K * 4);
+            // an appearance-flow engine: the flow head instead of kernels, on the survey table's compositing only
+            ok = ok && (h->flow ? (c.w_flow && c.b_flow && !c.kern && !c.first_frame && c.K == kFlowWarps + 1 && c.CF == 32)
+                                : (!c.w_flow && !c.b_flow && c.kern));
+            ok = ok && in_allocs(h, c.w_flow, (size_t)32 * 2 * kFlowWarps * 4) && in_allocs(h, c.b_flow, (size_t)2 * kFlowWarps * 4);
             ok = ok && in_allocs(h, c.first_frame, hw * 3 * 4) && in_allocs(h, c.first_distrib, hw * c.ND * 4);
         } else if (P.type == PH_SA) {
             ok = ok && in_allocs(h, P.sa.sbias, (size_t)P.B * P.sa.n_out * 4) && in_allocs(h, P.sa.action, 4) &&
@@ -2512,8 +2562,9 @@ static bool shared_cache_hit(vf_handle *h, int cfg) {
 }
 
 template <int ND>
-static int launch_persistent_t(const Schedule &sc, int grid, size_t lds, hipStream_t st) {
-    hipLaunchKernelGGL((rollout_persistent_kernel<ND>), dim3(grid), dim3(kConvThreads), lds, st, sc.phases, sc);
+static int launch_persistent_t(const Schedule &sc, bool flow, int grid, size_t lds, hipStream_t st) {
+    if (flow) hipLaunchKernelGGL((rollout_flow_kernel<ND>), dim3(grid), dim3(kConvThreads), lds, st, sc.phases, sc);
+    else hipLaunchKernelGGL((rollout_persistent_kernel<ND>), dim3(grid), dim3(kConvThreads), lds, st, sc.phases, sc);
     VF_HIP_CHECK(hipGetLastError());
     return VF_OK;
 }
@@ -2619,10 +2670,10 @@ static int run_persistent(vf_handle *h, const float *d_actions, int B, const int
         VF_HIP_CHECK(hipEventRecord(e0, st));
     }
     switch (h->ND) {
-        case 1: rc = launch_persistent_t<1>(sc, grid, lds, st); break;
-        case 2: rc = launch_persistent_t<2>(sc, grid, lds, st); break;
-        case 3: rc = launch_persistent_t<3>(sc, grid, lds, st); break;
-        default: rc = launch_persistent_t<4>(sc, grid, lds, st); break;
+        case 1: rc = launch_persistent_t<1>(sc, h->flow, grid, lds, st); break;
+        case 2: rc = launch_persistent_t<2>(sc, h->flow, grid, lds, st); break;
+        case 3: rc = launch_persistent_t<3>(sc, h->flow, grid, lds, st); break;
+        default: rc = launch_persistent_t<4>(sc, h->flow, grid, lds, st); break;
     }
     if (rc) return rc;
     if (h->profiling) {

@@ -32,7 +32,10 @@ __host__ __device__ inline size_t fused_top_lds_floats(int TH, int TW, int ND) {
     return (size_t)256 * kCompEncPad + halo * comp_px_stride(ND) + (size_t)kTaps * kCompKernPad + 16 + 64;
 }
 
-template <int ND, bool FIRST, int K, class PT, class CT>
+// FLOW (appearance-flow engines, vf_small_kernels.h): step 3 stages neither halo nor kernels - only the scale of the previous
+// distributions - and step 5 gathers the warps from the sample's whole previous frame in global memory.  The item was released
+// by the first conv of the step, every tile of which waited for every compose tile of the previous step: the frame is complete.
+template <int ND, bool FIRST, int K, class PT, class CT, bool FLOW = false>
 __device__ __forceinline__ void fused_top_body(const PT &p, const CT &c, f32x16 (&acc)[1][4], const int bx,
                                                long long *red, float *smem, const int *goal) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -162,13 +165,15 @@ __device__ __forceinline__ void fused_top_body(const PT &p, const CT &c, f32x16 
             for (int k = lane; k < nblocks; k += 64) dsum[j] += pp[2 * k];
         }
     }
-    float kv[(kTaps * K + 255) / 256];
+    [[maybe_unused]] float kv[(kTaps * K + 255) / 256];
+    if constexpr (!FLOW) {
 #pragma unroll
-    for (int j = 0; j < (kTaps * K + 255) / 256; ++j) {
-        const int i = tid + 256 * j;
-        kv[j] = i < kTaps * K ? c.kern[(long long)b * kTaps * K + i] : 0.f;
+        for (int j = 0; j < (kTaps * K + 255) / 256; ++j) {
+            const int i = tid + 256 * j;
+            kv[j] = i < kTaps * K ? c.kern[(long long)b * kTaps * K + i] : 0.f;
+        }
+        halo_request(tid);
     }
-    halo_request(tid);
 #pragma unroll
     for (int j = 0; j < (ND + 3) / 4; ++j) {
         const int d = ((wave + 3) & 3) + 4 * j;
@@ -178,14 +183,18 @@ __device__ __forceinline__ void fused_top_body(const PT &p, const CT &c, f32x16 
             if (lane == 0) s_dscale[d] = sc;
         }
     }
+    if constexpr (!FLOW) {
 #pragma unroll
-    for (int j = 0; j < (kTaps * K + 255) / 256; ++j) {
-        const int i = tid + 256 * j;
-        if (i < kTaps * K) s_kern[(i / K) * kCompKernPad + i % K] = kv[j];
+        for (int j = 0; j < (kTaps * K + 255) / 256; ++j) {
+            const int i = tid + 256 * j;
+            if (i < kTaps * K) s_kern[(i / K) * kCompKernPad + i % K] = kv[j];
+        }
     }
     __syncthreads();
-    halo_store(tid);
-    for (int i0 = tid + kHaloU * 256; i0 < HH_ * HW_; i0 += kHaloU * 256) { halo_request(i0); halo_store(i0); }
+    if constexpr (!FLOW) {
+        halo_store(tid);
+        for (int i0 = tid + kHaloU * 256; i0 < HH_ * HW_; i0 += kHaloU * 256) { halo_request(i0); halo_store(i0); }
+    }
 
     [[maybe_unused]] const unsigned long long tf2 = VF_TS_NOW();
     VF_TRACE_EVT(TR_TOP_HALO);
@@ -236,7 +245,7 @@ __device__ __forceinline__ void fused_top_body(const PT &p, const CT &c, f32x16 
         // registers across composite_pixel, which has none to spare for ND > 2 - laundering the row base keeps the
         // handful of index instructions inside the pass)
         int row0 = wave * 32 + 4 * kh;
-        if constexpr (ND > 2) asm volatile("" : "+v"(row0));
+        if constexpr (ND > 2 || (FLOW && ND > 1)) asm volatile("" : "+v"(row0));      // (the flow pass spills at ND 2 without it)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int row = row0 + (r & 3) + 8 * (r >> 2);
@@ -262,7 +271,11 @@ __device__ __forceinline__ void fused_top_body(const PT &p, const CT &c, f32x16 
         float of[3] = {0.f, 0.f, 0.f}, od[ND];
 #pragma unroll
         for (int d = 0; d < ND; ++d) od[d] = 0.f;
-        if (valid)
+        if constexpr (FLOW) {
+            if (valid)
+                composite_pixel_values_flow<ND>(c, y, x, &s_enc[tid * kCompEncPad], mean, rstd, pf, pd, s_dscale, goal, cost,
+                                                of, od);
+        } else if (valid)
             composite_pixel_values<ND, K, FIRST>(c, y, x, &s_enc[tid * kCompEncPad], mean, rstd, s_px, s_kern, HW_,
                                                  hy, hx, goal, cost, of, od);
         const int y_blk = oy0 + byl * kSumBlockH, x_blk = ox0 + bxl * kSumBlockW;
@@ -328,7 +341,7 @@ __device__ __forceinline__ void fused_top_body(const PT &p, const CT &c, f32x16 
 
 // epilogue hook of conv_tile<4, fused_epi(ND, FIRST), 1>: the compositing parameters (a device address inside the
 // schedule) are read through the constant address space, the goal pixels from the launch's LDS control block
-template <int ND, bool FIRST, int K, class PT>
+template <int ND, bool FIRST, int K, bool FLOW, class PT>
 __device__ __forceinline__ void convt_fused_epilogue(const PT &p, f32x16 (&acc)[1][4], int bx, long long *red, float *smem) {
     typedef const __attribute__((address_space(4))) CompositeParams CT;
     const unsigned long long a = reinterpret_cast<unsigned long long>(p.fuse_comp);
@@ -337,7 +350,7 @@ __device__ __forceinline__ void convt_fused_epilogue(const PT &p, f32x16 (&acc)[
     CT &c = *(CT *)(((unsigned long long)hi << 32) | lo);
     extern __shared__ __attribute__((aligned(16))) float smem_all[];
     const int *goal = reinterpret_cast<const int *>(smem_all) + kFusedCtlGoal + p.fuse_view * ND * 2;
-    fused_top_body<ND, FIRST, K>(p, c, acc, bx, red, smem, goal);
+    fused_top_body<ND, FIRST, K, PT, CT, FLOW>(p, c, acc, bx, red, smem, goal);
 }
 
 }  // namespace vf

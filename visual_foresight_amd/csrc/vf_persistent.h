@@ -213,6 +213,13 @@ static __device__ __noinline__ __attribute__((not_tail_called)) void composite_t
     const int *goal = reinterpret_cast<const int *>(smem_all) + kCtlGoal + view * ND * 2;
     composite_tile<ND, K, FIRST, const VF_CONST_AS CompositeParams, CF>(const_params(p), tile, b, goal, tile_lds());
 }
+// the appearance-flow compositing tile (vf_small_kernels.h; rollout_flow_kernel only)
+template <int ND>
+static __device__ __noinline__ __attribute__((not_tail_called)) void composite_flow_tile_call(const CompositeParams *p, int tile, int b, int view) {
+    extern __shared__ __attribute__((aligned(16))) float smem_all[];
+    const int *goal = reinterpret_cast<const int *>(smem_all) + kCtlGoal + view * ND * 2;
+    composite_tile<ND, kFlowWarps + 1, false, const VF_CONST_AS CompositeParams, 32, true>(const_params(p), tile, b, goal, tile_lds());
+}
 static __device__ __noinline__ __attribute__((not_tail_called)) void gates_raw_tile_call(const ConvParams *p, int bx, int by) {
     conv_lstm_gsplit2_tile<4, const VF_CONST_AS ConvParams, true>(const_params(p), bx, by, tile_lds());
 }
@@ -261,10 +268,10 @@ static __device__ __noinline__ __attribute__((not_tail_called)) void small_item_
     }
 }
 
-// Two resident workgroups per CU (one wave of each per SIMD): 256 VGPRs per lane for every tile body.
-template <int ND>
-VF_GLOBAL VF_LAUNCH_BOUNDS(kConvThreads, 2) void rollout_persistent_kernel(
-    const PhaseDesc *__restrict__ phases, const Schedule sched) {
+// The scheduler loop, shared by the two kernels below.  FLOW picks the compositing bodies at compile time: the production
+// kernel carries no appearance-flow code and no run-time branch for it.
+template <int ND, bool FLOW>
+__device__ __forceinline__ void rollout_body(const PhaseDesc *__restrict__ phases, const Schedule sched) {
     extern __shared__ __attribute__((aligned(16))) float smem_all[];
     // all LDS in one dynamic array: the control block first, the tile workspace after it
     int *s_ctl = reinterpret_cast<int *>(smem_all);
@@ -445,12 +452,14 @@ VF_GLOBAL VF_LAUNCH_BOUNDS(kConvThreads, 2) void rollout_persistent_kernel(
                 // (K = 6: the compositing of arch 2 - four CDNA warps + previous + first frame + scratch - always with
                 // the first-frame layer; K = 10 otherwise)
                 case PH_TOP_FUSED:
-                    if (P.comp.K == 6) conv_tile_call<4, fused_epi(ND, true, true), 1>(&P.conv, bx, 0, 0);
+                    if constexpr (FLOW) conv_tile_call<4, fused_epi_flow(ND), 1>(&P.conv, bx, 0, 0);
+                    else if (P.comp.K == 6) conv_tile_call<4, fused_epi(ND, true, true), 1>(&P.conv, bx, 0, 0);
                     else if (P.comp.first_frame) conv_tile_call<4, fused_epi(ND, true), 1>(&P.conv, bx, 0, 0);
                     else conv_tile_call<4, fused_epi(ND, false), 1>(&P.conv, bx, 0, 0);
                     break;
                 case PH_COMPOSITE:
-                    if (P.comp.K == 6) composite_tile_call<ND, true, 6>(&P.comp, local % P.gx, b0, P.view);
+                    if constexpr (FLOW) composite_flow_tile_call<ND>(&P.comp, local % P.gx, b0, P.view);
+                    else if (P.comp.K == 6) composite_tile_call<ND, true, 6>(&P.comp, local % P.gx, b0, P.view);
                     else if (P.comp.first_frame) composite_tile_call<ND, true, 10>(&P.comp, local % P.gx, b0, P.view);
                     else if (P.comp.CF > 32) composite_tile_call<ND, false, 10, 64>(&P.comp, local % P.gx, b0, P.view);  // (public decoder)
                     else composite_tile_call<ND, false, 10>(&P.comp, local % P.gx, b0, P.view);
@@ -525,6 +534,21 @@ VF_GLOBAL VF_LAUNCH_BOUNDS(kConvThreads, 2) void rollout_persistent_kernel(
 #ifdef VF_TRACE
     if (tid == 0 && blockIdx.x < kTraceWgs) g_trace_n[blockIdx.x] = (unsigned)s_ctl[5];
 #endif
+}
+
+// Two resident workgroups per CU (one wave of each per SIMD): 256 VGPRs per lane for every tile body.
+template <int ND>
+VF_GLOBAL VF_LAUNCH_BOUNDS(kConvThreads, 2) void rollout_persistent_kernel(
+    const PhaseDesc *__restrict__ phases, const Schedule sched) {
+    rollout_body<ND, false>(phases, sched);
+}
+
+// The rollout of an appearance-flow engine (cdna_arch.py transformation='flow', vf_config arch 0 / layer_spec 2): the same
+// schedule and tiles, the compositing of the fused top and of PH_COMPOSITE with gathered warps instead of CDNA kernels.
+template <int ND>
+VF_GLOBAL VF_LAUNCH_BOUNDS(kConvThreads, 2) void rollout_flow_kernel(
+    const PhaseDesc *__restrict__ phases, const Schedule sched) {
+    rollout_body<ND, true>(phases, sched);
 }
 
 }  // namespace vf

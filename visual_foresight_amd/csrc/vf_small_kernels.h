@@ -231,6 +231,8 @@ struct CompositeParams {
                                         // does not depend on them
     int CF;                             // feature channels of enc6: 0 / 32, or 64 (the public CDNA decoder table, cdna_arch.py
                                         // decoder='public': the stand-alone compositing tile only, two 32-channel rounds)
+    const float *w_flow, *b_flow;       // appearance-flow engines (cdna_arch.py transformation='flow'): the 1x1 flow head
+                                        // [32][2 * kFlowWarps], [2 * kFlowWarps]; null = CDNA kernels (`kern` is null there)
 };
 
 // LDS floats needed by composite_tile<ND, K>
@@ -425,10 +427,126 @@ __device__ __forceinline__ void composite_values(const PT &p, const int y, const
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// Appearance-flow compositing (cdna_arch.py, transformation='flow').  Instead of the sample's CDNA kernels
+// a third 1x1 head predicts a displacement (dx_k, dy_k) in pixels per warp k and pixel; warp k samples the previous frame
+// and distributions at (x + dx_k, y + dy_k) with the clamped bilinear taps of bilinear_clamped() below.  A tap may lie
+// anywhere in the image, so nothing is staged in LDS: the gathers read the sample's previous frame / distributions from
+// global memory (L2), which therefore must be COMPLETE before any tile of the step starts - the dependency on the first conv
+// of the step, which itself waited for every compositing tile of the previous step, gives that (emit_rollout).
+constexpr int kFlowWarps = 9;           // NF = num_masks - 1 warps: the cdna path uses nine of its ten kernels too
+
+// the flow head of one pixel: a SECOND pass over its LDS feature row (with the rgb / mask sums of the first pass that would
+// be 32 live accumulators, which the compose pass of the fused top cannot hold for ND > 2).  Every sum is its own fma chain
+// over the channels ascending from the bias, as in composite_heads: the split into two passes does not show in the bits.
+template <class PT>
+__device__ __forceinline__ void composite_flow_heads(const PT &p, const float *feat, const float mean, const float rstd,
+                                                     float (&o_fl)[2 * kFlowWarps]) {
+    constexpr int NF2 = 2 * kFlowWarps;
+    typedef const __attribute__((address_space(4))) float cfloat;
+    auto as_const = [](const float *q) { return (cfloat *)(unsigned long long)q; };
+    cfloat *gam_ = as_const(p.gamma), *bet_ = as_const(p.beta);
+    cfloat *wfl_ = as_const(p.w_flow), *bfl_ = as_const(p.b_flow);
+#pragma unroll
+    for (int j = 0; j < NF2; ++j) o_fl[j] = bfl_[j];
+    const f32x4 *src = reinterpret_cast<const f32x4 *>(feat);
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+        const f32x4 raw = src[q];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int c = q * 4 + e;
+            const float f = fmaxf(fmaf((raw[e] - mean) * rstd, gam_[c], bet_[c]), 0.f);
+#pragma unroll
+            for (int j = 0; j < NF2; ++j) o_fl[j] = fmaf(f, wfl_[c * NF2 + j], o_fl[j]);
+        }
+    }
+}
+
+// One output pixel (y, x) behind its rgb / mask head outputs: softmax, the flow head, nine gathered warps, next frame /
+// distributions, cost terms.  pf / pd: the sample's previous frame [H][W][3] / distributions [H][W][ND] in global memory,
+// dscale[d] = 1 / (mass of previous distribution d), applied to every tap before the interpolation (as the halo load of the
+// cdna path applies it).  Accumulation order: previous frame, scratch, warps k ascending.  Coordinates are clamped before
+// they become indices (a NaN flow clamps to 0), so every gather stays inside the image.
+template <int ND, class PT>
+__device__ __forceinline__ void composite_values_flow(const PT &p, const int y, const int x, const float *feat,
+                                                      const float mean, const float rstd, float (&o_rgb)[3],
+                                                      float (&o_m)[kFlowWarps + 2], const float *pf, const float *pd,
+                                                      const float *dscale, const int *goal, double (&cost)[2 * ND],
+                                                      float (&of)[3], float (&od)[ND]) {
+    constexpr int NM = kFlowWarps + 2;
+    float mx = o_m[0];
+#pragma unroll
+    for (int j = 1; j < NM; ++j) mx = fmaxf(mx, o_m[j]);
+    float den = 0.f;
+#pragma unroll
+    for (int j = 0; j < NM; ++j) { o_m[j] = __expf(o_m[j] - mx); den += o_m[j]; }
+    const float inv = 1.0f / den;
+#pragma unroll
+    for (int j = 0; j < NM; ++j) o_m[j] *= inv;
+
+    float sc[ND];
+#pragma unroll
+    for (int d = 0; d < ND; ++d) sc[d] = dscale[d];
+    {
+        const long long o = (long long)y * p.W + x;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) of[c] = fmaf(o_m[0], pf[o * 3 + c], o_m[1] * sigmoidf_(o_rgb[c]));
+#pragma unroll
+        for (int d = 0; d < ND; ++d) od[d] = o_m[0] * (pd[o * ND + d] * sc[d]);
+    }
+    float o_fl[2 * kFlowWarps];
+    composite_flow_heads(p, feat, mean, rstd, o_fl);
+    const float xmax = (float)(p.W - 1), ymax = (float)(p.H - 1);
+#pragma unroll
+    for (int k = 0; k < kFlowWarps; ++k) {
+        // the taps of bilinear_clamped(), shared by the frame's channels and the distributions
+        const float sx = fminf(fmaxf((float)x + o_fl[2 * k], 0.f), xmax);
+        const float sy = fminf(fmaxf((float)y + o_fl[2 * k + 1], 0.f), ymax);
+        const int x0 = (int)floorf(sx), y0 = (int)floorf(sy);
+        const int x1 = min(x0 + 1, p.W - 1), y1 = min(y0 + 1, p.H - 1);
+        const float fx = sx - (float)x0, fy = sy - (float)y0;
+        const int o00 = y0 * p.W + x0, o01 = y0 * p.W + x1, o10 = y1 * p.W + x0, o11 = y1 * p.W + x1;
+        const float m = o_m[k + 2];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float a = pf[o00 * 3 + c], b = pf[o01 * 3 + c], cc = pf[o10 * 3 + c], dd = pf[o11 * 3 + c];
+            const float top = fmaf(fx, b - a, a), bot = fmaf(fx, dd - cc, cc);
+            of[c] = fmaf(m, fmaf(fy, bot - top, top), of[c]);
+        }
+#pragma unroll
+        for (int d = 0; d < ND; ++d) {
+            const float a = pd[o00 * ND + d] * sc[d], b = pd[o01 * ND + d] * sc[d];
+            const float cc = pd[o10 * ND + d] * sc[d], dd = pd[o11 * ND + d] * sc[d];
+            const float top = fmaf(fx, b - a, a), bot = fmaf(fx, dd - cc, cc);
+            od[d] = fmaf(m, fmaf(fy, bot - top, top), od[d]);
+        }
+    }
+#pragma unroll
+    for (int d = 0; d < ND; ++d) {
+        const float ry = (float)(y - goal[2 * d]), rx = (float)(x - goal[2 * d + 1]);
+        const float dist = sqrtf(fmaf(ry, ry, rx * rx));
+        cost[2 * d] = (double)od[d];
+        cost[2 * d + 1] = (double)od[d] * (double)dist;
+    }
+}
+// ... from the pixel's LDS feature row (the stand-alone tile and the fused top call this: same expressions, same bits)
+template <int ND, class PT>
+__device__ __forceinline__ void composite_pixel_values_flow(const PT &p, const int y, const int x, const float *feat,
+                                                            const float mean, const float rstd, const float *pf,
+                                                            const float *pd, const float *dscale, const int *goal,
+                                                            double (&cost)[2 * ND], float (&of)[3], float (&od)[ND]) {
+    float o_rgb[3], o_m[kFlowWarps + 2];
+    composite_head_bias<kFlowWarps + 1>(p, o_rgb, o_m);
+    composite_heads<kFlowWarps + 1>(p, feat, mean, rstd, 0, o_rgb, o_m);
+    composite_values_flow<ND>(p, y, x, feat, mean, rstd, o_rgb, o_m, pf, pd, dscale, goal, cost, of, od);
+}
+
 // one 16x16 pixel tile of one sample.  FIRST (arch 1, savp_arch.py): the first context frame is one more compositing
 // layer - a template parameter, because a run-time branch around the mask bookkeeping costs the CDNA path 3.5 us per
 // tile (measured).
-template <int ND, int K, bool FIRST, class PT, int CFT = 32>
+// FLOW (appearance flow, above): no halo tile and no kernel table are staged - the warps gather from global memory.
+template <int ND, int K, bool FIRST, class PT, int CFT = 32, bool FLOW = false>
 __device__ __forceinline__ void composite_tile(const PT &p, const int tile, const int b, const int *goal,
                                                float *smem) {
     constexpr int TS = kCompTile, HS = TS + 4;
@@ -483,12 +601,13 @@ __device__ __forceinline__ void composite_tile(const PT &p, const int tile, cons
             if (lane_ == 0) s_dscale[d] = sc;
         }
     }
-    for (int i = tid; i < kTaps * K; i += 256) s_kern[(i / K) * kCompKernPad + i % K] = p.kern[(long long)b * kTaps * K + i];
+    if constexpr (!FLOW)
+        for (int i = tid; i < kTaps * K; i += 256) s_kern[(i / K) * kCompKernPad + i % K] = p.kern[(long long)b * kTaps * K + i];
     __syncthreads();
 
     const float *pf = p.prev_frame + (long long)b * p.prev_frame_bstride;
     const float *pd = p.prev_distrib + (long long)b * p.prev_distrib_bstride;
-    for (int i = tid; i < HS * HS; i += 256) {
+    for (int i = tid; i < (FLOW ? 0 : HS * HS); i += 256) {
         const int ly = i / HS, lx = i % HS;
         const int y = ty0 + ly - 2, x = tx0 + lx - 2;
         const bool in = y >= 0 && y < p.H && x >= 0 && x < p.W;
@@ -512,7 +631,21 @@ __device__ __forceinline__ void composite_tile(const PT &p, const int tile, cons
 #pragma unroll
     for (int i = 0; i < 2 * ND; ++i) cost[i] = 0.0;
 
-    if constexpr (CF == 32) {
+    if constexpr (FLOW) {
+        static_assert(!FLOW || (CF == 32 && K == kFlowWarps + 1 && !FIRST), "the flow table: survey decoder, ten masks");
+        if (valid) {
+            float of[3], od[ND];
+            composite_pixel_values_flow<ND>(p, y, x, &s_enc[tid * kCompEncPad], s_ln[0], s_ln[1], pf, pd, s_dscale, goal,
+                                            cost, of, od);
+            const long long o = (long long)y * p.W + x;
+            float *fo = p.out_frame + (long long)b * p.out_frame_bstride + o * 3;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) fo[c] = of[c];
+            float *dout = p.out_distrib + (long long)b * p.out_distrib_bstride + o * ND;
+#pragma unroll
+            for (int d = 0; d < ND; ++d) dout[d] = od[d];
+        }
+    } else if constexpr (CF == 32) {
         if (valid)
             composite_pixel<ND, K, FIRST>(p, b, y, x, &s_enc[tid * kCompEncPad], s_ln[0], s_ln[1], s_px, s_kern, HS,
                                           ly, lx, goal, cost);
@@ -562,6 +695,13 @@ VF_GLOBAL VF_LAUNCH_BOUNDS(256) void composite_kernel(const CompositeParams p) {
         if (p.CF > 32) composite_tile<ND, K, false, CompositeParams, 64>(p, blockIdx.x, blockIdx.y, &p.goal[0][0], smem);
         else composite_tile<ND, K, false>(p, blockIdx.x, blockIdx.y, &p.goal[0][0], smem);
     }
+}
+
+// the per-layer launch of the appearance-flow compositing
+template <int ND>
+VF_GLOBAL VF_LAUNCH_BOUNDS(256) void composite_flow_kernel(const CompositeParams p) {
+    __shared__ __attribute__((aligned(16))) float smem[composite_lds_floats<ND, kFlowWarps + 1>()];
+    composite_tile<ND, kFlowWarps + 1, false, CompositeParams, 32, true>(p, blockIdx.x, blockIdx.y, &p.goal[0][0], smem);
 }
 
 // ------------------------------------------------------------------------------------------

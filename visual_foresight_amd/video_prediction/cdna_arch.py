@@ -42,6 +42,27 @@ Canonical tensor layouts (what ``weights.bin`` stores, all float32, C-order):
 conv / transposed conv ``[kh, kw, cin, cout]``; FC ``[in, out]``; vectors ``[n]``.
 For a transposed conv, output pixel ``(2*iy + ky, 2*ix + kx)`` accumulates
 ``in[iy, ix, ci] * w[ky, kx, ci, co]`` (outputs beyond ``2*H_in`` are cropped).
+
+Appearance flow (``CdnaConfig(transformation='flow')``; ``vf_config`` arch 0, layer_spec 2).  The reference's legacy
+predictor configurations all name ``'model': 'appflow'``; like every network here that model is external to the reference,
+so the table below is THIS project's specification of it, parity unpinned.  Everything up to and including ``enc6`` is the
+table above with the ``'survey'`` decoder; ``K = num_masks = 10`` keeps the eleven mask channels, ``NF = K - 1 = 9`` warps
+(the cdna path uses nine of its ten kernels too)::
+
+    scratch = sigmoid(conv1x1(enc6, ->3))
+    masks   = softmax_c(conv1x1(enc6, ->K+1))
+    flow    = conv1x1(enc6, ->2*NF)                channel 2k = dx_k, 2k+1 = dy_k, in pixels
+    warp_k(img)[y, x] = bilinear(img, x + dx_k[y, x], y + dy_k[y, x])
+    frame'  = masks_0 * frame + masks_1 * scratch + sum_{k<NF} masks_{k+2} * warp_k(frame)
+    distr'  = normalise_hw(masks_0 * distr + sum_{k<NF} masks_{k+2} * warp_k(distr))
+
+``flow/w [1, 1, 32, 2*NF]`` and ``flow/b`` sit where ``cdna/w`` and ``cdna/b`` sit in the cdna table; there is no CDNA FC
+and there are no kernels.  ``bilinear`` is the clamped sampler of the registration warp (``bilinear_clamped`` of
+``csrc/vf_small_kernels.h``, ``oracle/registration.py``): coordinates are clamped to the image, ``x1 = min(x0 + 1, W - 1)``,
+and the arithmetic is ``top = fma(fx, b - a, a)``, ``bot = fma(fx, d - c, c)``, ``fma(fy, bot - top, top)``.  The
+``1 / sum`` scale of a fed-back distribution is applied to each tap before the interpolation.  Accumulation order: previous
+frame, scratch, then the warps with ``k`` ascending; head sums run over the channels ascending from the bias.  Exact fp32
+only, ``'survey'`` decoder only.
 """
 import json
 import os
@@ -59,10 +80,19 @@ class CdnaConfig(object):
     """Static shape of one predictor instance."""
 
     def __init__(self, height=64, width=64, adim=4, sdim=5, ndesig=1, n_context=2,
-                 sequence_length=15, num_masks=10, ncam=1, decoder='survey'):
+                 sequence_length=15, num_masks=10, ncam=1, decoder='survey', transformation='cdna'):
         if decoder not in ('survey', 'public'):
             raise ValueError("decoder must be 'survey' or 'public', got %r" % (decoder,))
         self.decoder = decoder
+        if transformation not in ('cdna', 'flow'):
+            raise ValueError("transformation must be 'cdna' or 'flow', got %r" % (transformation,))
+        if transformation == 'flow' and self.arch != 'cdna':
+            raise ValueError("transformation='flow' is built for arch 'cdna' only, not %r" % (self.arch,))
+        if transformation == 'flow' and decoder != 'survey':
+            raise ValueError("transformation='flow' is built for the 'survey' decoder only, not %r" % (decoder,))
+        if transformation == 'flow' and int(num_masks) != 10:
+            raise ValueError("transformation='flow' needs num_masks = 10 (nine warps), got %r" % (num_masks,))
+        self.transformation = transformation
         if height % 8 or width % 8:
             raise ValueError('image size must be a multiple of 8, got %dx%d' % (height, width))
         if ncam != 1:
@@ -83,7 +113,9 @@ class CdnaConfig(object):
 
     @property
     def layer_spec(self):
-        """``vf_config.layer_spec`` of this table: 1 = the public decoder widths (arch 'cdna' only)."""
+        """``vf_config.layer_spec`` of this table (arch 'cdna' only): 1 = the public decoder widths, 2 = appearance flow."""
+        if self.transformation == 'flow':
+            return 2
         return 1 if self.decoder == 'public' else 0
 
     def as_dict(self):
@@ -92,6 +124,8 @@ class CdnaConfig(object):
                  sequence_length=self.sequence_length, num_masks=self.num_masks)
         if self.decoder != 'survey':
             d['decoder'] = self.decoder
+        if self.transformation != 'cdna':       # (written only then: the manifests of cdna checkpoints stay as they are)
+            d['transformation'] = self.transformation
         return d
 
     def tensor_shapes(self):
@@ -140,8 +174,11 @@ def tensor_shapes(cfg):
     conv('convt3', 3, 3, L[6] + 32, c_top);  ln('ln9', c_top)
     conv('rgb', 1, 1, c_top, 3)
     conv('masks', 1, 1, c_top, K + 1)
-    t['cdna/w'] = (fc_in, DNA_KERN * DNA_KERN * K)
-    t['cdna/b'] = (DNA_KERN * DNA_KERN * K,)
+    if getattr(cfg, 'transformation', 'cdna') == 'flow':      # the flow head where the CDNA FC sits; no kernels
+        conv('flow', 1, 1, c_top, 2 * (K - 1))
+    else:
+        t['cdna/w'] = (fc_in, DNA_KERN * DNA_KERN * K)
+        t['cdna/b'] = (DNA_KERN * DNA_KERN * K,)
     t['state/w'] = (a, cfg.sdim)
     t['state/b'] = (cfg.sdim,)
     return t
@@ -165,9 +202,15 @@ def macs_per_sample_step(cfg):
     for name, (h, w) in res.items():
         kh, kw, cin, cout = shp[name + '/w']
         out[name] = h * w * kh * kw * cin * cout
-    out['cdna_fc'] = shp['cdna/w'][0] * shp['cdna/w'][1]
-    out['warp_frame'] = H * W * DNA_KERN * DNA_KERN * 3 * cfg.num_masks
-    out['warp_distrib'] = H * W * DNA_KERN * DNA_KERN * cfg.ndesig * cfg.num_masks
+    if getattr(cfg, 'transformation', 'cdna') == 'flow':      # flow head + four bilinear taps per warp and channel
+        NF = cfg.num_masks - 1
+        out['flow'] = H * W * 32 * 2 * NF
+        out['warp_frame'] = H * W * 4 * 3 * NF
+        out['warp_distrib'] = H * W * 4 * cfg.ndesig * NF
+    else:
+        out['cdna_fc'] = shp['cdna/w'][0] * shp['cdna/w'][1]
+        out['warp_frame'] = H * W * DNA_KERN * DNA_KERN * 3 * cfg.num_masks
+        out['warp_distrib'] = H * W * DNA_KERN * DNA_KERN * cfg.ndesig * cfg.num_masks
     out['state_fc'] = shp['state/w'][0] * shp['state/w'][1]
     return out
 
@@ -250,8 +293,10 @@ class CdnaWeights(object):
         if cfg is not None:
             mine, theirs = cfg.as_dict(), file_cfg.as_dict()
             for k in ('height', 'width', 'adim', 'sdim', 'num_masks') + (('zdim', 'layer_spec') if arch == 'savp3' else ()) + \
-                    (('decoder',) if 'decoder' in mine or 'decoder' in theirs else ()):
+                    (('decoder',) if 'decoder' in mine or 'decoder' in theirs else ()) + \
+                    (('transformation',) if 'transformation' in mine or 'transformation' in theirs else ()):
                 mine.setdefault('decoder', 'survey'); theirs.setdefault('decoder', 'survey')
+                mine.setdefault('transformation', 'cdna'); theirs.setdefault('transformation', 'cdna')
                 if mine[k] != theirs[k]:
                     raise ValueError('checkpoint %s=%r does not match requested %r' % (k, theirs[k], mine[k]))
             file_cfg = cfg      # ndesig / sequence_length are run-time choices, not weights

@@ -73,6 +73,9 @@ def import_named_arrays(arrays, cfg, log=None):
     if getattr(cfg, 'arch_id', 0) != 0:
         raise ValueError("only arch 'cdna' checkpoints can be imported (no TensorFlow name table for %s)"
                          % type(cfg).__name__)
+    if getattr(cfg, 'transformation', 'cdna') != 'cdna':
+        raise ValueError("only transformation 'cdna' checkpoints can be imported: no TensorFlow name table exists for the "
+                         "appearance-flow head (transformation %r, tensors flow/w, flow/b)" % (cfg.transformation,))
     log = log or print
     names = list(arrays.keys())
     tensors = OrderedDict()
@@ -98,6 +101,8 @@ def import_named_arrays(arrays, cfg, log=None):
 def export_named_arrays(weights, scope='model'):
     """Inverse of ``import_named_arrays``: the arrays under TensorFlow-style names (for round-trip tests and
     for handing weights to a TF-side tool)."""
+    if getattr(weights.cfg, 'transformation', 'cdna') != 'cdna':
+        raise ValueError("no TensorFlow name table exists for transformation %r" % (weights.cfg.transformation,))
     out = OrderedDict()
     for name, arr in weights.tensors.items():
         suffix, transposed = tf_name(name)
