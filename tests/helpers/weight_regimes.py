@@ -16,6 +16,7 @@ It also restates the device's exact LayerNorm statistics (``stat_q``, ``stat_q2`
 """
 import contextlib
 import math
+import re
 from collections import OrderedDict
 
 import numpy as np
@@ -42,18 +43,27 @@ def _clone(weights):
     return CdnaWeights(weights.cfg, OrderedDict((k, v.copy()) for k, v in weights.tensors.items()))
 
 
+def raw_layer_names(weights):
+    """The layers ``raw_scaled`` accepts: those a normalisation follows directly.  arch 'savp3' normalises every conv
+    (``h{i}c``), every conv-LSTM gate conv (``h{i}l``, no bias) and the heads' hidden layers (``hm``, ``hs``) per instance."""
+    if weights.cfg.arch == 'savp3':
+        return [k[:-2] for k in weights.tensors if re.match(r'(h\d+[cl]|hm|hs)/w$', k)]
+    return list(RAW_LAYERS[weights.cfg.arch])
+
+
 def raw_scaled(weights, factors):
     """``w`` and ``b`` of the named raw layers times a power of two (exact in float32, so the layer's output is the unscaled
-    one times the factor, bit for bit, and the LayerNorm behind it cancels it up to its epsilon)."""
+    one times the factor, bit for bit, and the normalisation behind it cancels it up to its epsilon)."""
     out = _clone(weights)
-    raw = RAW_LAYERS[weights.cfg.arch]
+    raw = raw_layer_names(weights)
     for name, f in factors.items():
         if name not in raw:
             raise ValueError('%s is not a raw-statistic layer of arch %s' % (name, weights.cfg.arch))
         m, _ = math.frexp(float(f))
         if f <= 0 or m != 0.5:
             raise ValueError('factor %r of %s is not a power of two' % (f, name))
-        for kind in ('/w', '/b'):
+        gate_conv = weights.cfg.arch == 'savp3' and re.match(r'h\d+l$', name)       # (the only raw layers without a bias)
+        for kind in ('/w',) if gate_conv else ('/w', '/b'):
             out.tensors[name + kind] *= np.float32(f)
     return out
 
