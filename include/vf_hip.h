@@ -69,8 +69,13 @@ typedef struct vf_config {
                                  * 0 = exact fp32 MFMA (default);
                                  * 1 = fp32 emulated with six bf16 MFMA products per multiply
                                  *     (3-way exact operand split, fp32 accumulate; fp32-class
-                                 *     accuracy, see csrc/vf_conv_bf16x6.h).  Everything else is
-                                 *     fp32 in both modes. */
+                                 *     accuracy, see csrc/vf_conv_bf16x6.h);
+                                 * 2 = plain bf16: activations and weights of the gate GEMMs rounded
+                                 *     once (to nearest even) to bf16, ONE bf16 MFMA product per
+                                 *     multiply, fp32 accumulate (half-precision accuracy class: the
+                                 *     speed / accuracy trade of the reference's float16 predictor, see
+                                 *     csrc/vf_conv_bf16.h).  1 and 2: arch 0 with layer_spec 0, arch 1.
+                                 *     Everything else is fp32 in every mode. */
     int32_t ncam;               /* camera views (1..4; 0 = 1): one network (own weights) per view,
                                  * all rolled by the same launch on the same action sequences
                                  * (reference: IndepMultiSAVP..., vpred_model_interface.py:60-88) */
@@ -445,6 +450,14 @@ int vf_set_phase_stats(vf_handle *h, int32_t enable);
 int vf_debug_phase_stats(vf_handle *h, int32_t max_phases, int32_t *types, int32_t *items,
                          uint64_t *wait_run);
 int vf_debug_poison_status(vf_handle *h);
+/* Debugging aid: conv-LSTM `layer` (0..6 = lstm1..lstm7; arch 0 / 1) as ONE per-layer launch on caller-owned NHWC
+ * device tensors, with the loaded weights of view 0 and the tile of the handle's own precision: d_x [B][h][w][Cx] is
+ * taken as it is (no producer LayerNorm, no relu), d_h / d_c [B][h][w][C] are the previous hidden and cell state,
+ * d_h_out / d_c_out receive the new ones.  B <= max_batch.  Uses the handle's statistics buffers: the rollout state
+ * is UNDEFINED afterwards until the next vf_set_context.  Allocates nothing and never synchronises. */
+int vf_debug_lstm_layer(vf_handle *h, int32_t layer /*0..6 = lstm1..lstm7*/, int32_t B,
+                        const float *d_x, const float *d_h, const float *d_c,
+                        float *d_h_out, float *d_c_out, void *stream);
 
 #ifdef __cplusplus
 }

@@ -13,7 +13,9 @@
  *
  *     gcc -O2 -std=c11 -D__HIP_PLATFORM_AMD__ -I include -I /opt/rocm/include tools/c_host/vf_c_host.c \
  *         visual_foresight_amd/libvf_hip.so -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,/opt/rocm/lib -o build/vf_c_host
- *     build/vf_c_host <input.bin> <output.bin>
+ *     build/vf_c_host <input.bin> <output.bin> [precision]
+ *
+ * precision: vf_config.precision, 0 (exact fp32, the default), 1 (split bf16) or 2 (plain bf16).
  *
  * input.bin : int32 header {H, W, adim, sdim, ndesig, n_context, sequence_length, B, n_export, n_weights}, then
  *             float32 weights[n_weights], uint8 frames[nc][1][H][W][3], float32 states[nc][sdim],
@@ -54,7 +56,9 @@ static int to_device(void **d, const void *h, size_t bytes) {
 }
 
 int main(int argc, char **argv) {
-    if (argc != 3) { fprintf(stderr, "usage: %s input.bin output.bin\n", argv[0]); return 1; }
+    if (argc != 3 && argc != 4) { fprintf(stderr, "usage: %s input.bin output.bin [precision 0|1|2]\n", argv[0]); return 1; }
+    const int precision = argc == 4 ? atoi(argv[3]) : 0;
+    if (precision < 0 || precision > 2) { fprintf(stderr, "precision must be 0, 1 or 2\n"); return 1; }
     if (vf_abi_version() != VF_ABI_VERSION) { fprintf(stderr, "ABI %d, header %d\n", vf_abi_version(), VF_ABI_VERSION); return 1; }
     FILE *f = fopen(argv[1], "rb");
     if (!f) { perror(argv[1]); return 1; }
@@ -66,7 +70,7 @@ int main(int argc, char **argv) {
 
     vf_config cfg = {0};
     cfg.height = H; cfg.width = W; cfg.adim = adim; cfg.sdim = sdim; cfg.ndesig = nd; cfg.n_context = nc;
-    cfg.sequence_length = seq; cfg.num_masks = 10; cfg.max_batch = B; cfg.device = 0; cfg.precision = 0;
+    cfg.sequence_length = seq; cfg.num_masks = 10; cfg.max_batch = B; cfg.device = 0; cfg.precision = precision;
     cfg.ncam = 1; cfg.n_draws = 1; cfg.arch = 0;
     if (vf_weight_count(&cfg) != nw) { fprintf(stderr, "weights: file has %zu, library wants %zu\n", nw, vf_weight_count(&cfg)); return 4; }
 

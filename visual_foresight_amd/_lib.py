@@ -16,7 +16,7 @@ LIB_PATH = os.environ.get('VF_LIBRARY') or os.path.join(_HERE, 'libvf_hip.so')  
 SOURCES = [os.path.join(_HERE, 'csrc', f) for f in
            ('vf_engine.hip', 'vf_conv_mfma.h', 'vf_conv_gsplit.h', 'vf_small_kernels.h', 'vf_goal_image.h', 'vf_plan_render.h', 'vf_net_conv.h',
             'vf_frame_scorer.h', 'vf_engine_sidenet.inc', 'vf_engine_scorer.inc', 'vf_registration_net.h', 'vf_engine_regnet.inc', 'vf_inverse_model.h', 'vf_engine_invmodel.inc', 'vf_persistent.h',
-            'vf_conv_bf16x6.h', 'vf_fused_top.h', 'vf_fc_tile.h', 'vf_conv_first.h', 'vf_savp3.h', 'vf_engine_savp3.inc')] + \
+            'vf_conv_bf16x6.h', 'vf_conv_bf16.h', 'vf_fused_top.h', 'vf_fc_tile.h', 'vf_conv_first.h', 'vf_savp3.h', 'vf_engine_savp3.inc')] + \
           [os.path.join(REPO, 'include', 'vf_hip.h')]
 
 # every symbol include/vf_hip.h declares
@@ -31,7 +31,7 @@ EXPORTS = ('vf_abi_version', 'vf_last_error', 'vf_weight_count', 'vf_create', 'v
            'vf_scorer_scores',
            'vf_regnet_weight_count', 'vf_regnet_create', 'vf_regnet_destroy', 'vf_regnet_load_weights', 'vf_regnet_flow',
            'vf_invmodel_weight_count', 'vf_invmodel_create', 'vf_invmodel_destroy', 'vf_invmodel_load_weights',
-           'vf_invmodel_infer')
+           'vf_invmodel_infer', 'vf_debug_lstm_layer')
 ABI_VERSION = 7
 
 
@@ -154,6 +154,7 @@ def load_library():
     lib.vf_debug_phase_stats.argtypes = [P, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32),
                                          ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_uint64)]
     lib.vf_debug_poison_status.argtypes = [P]
+    lib.vf_debug_lstm_layer.argtypes = [P, ctypes.c_int32, ctypes.c_int32, P, P, P, P, P, P]
     lib.vf_export.argtypes = [P, ctypes.c_int32, ctypes.c_int32, P, P, P, P]
     lib.vf_set_profiling.argtypes = [P, ctypes.c_int32]
     lib.vf_get_profile.argtypes = [P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64),
@@ -177,7 +178,7 @@ def load_library():
                  'vf_invmodel_create', 'vf_invmodel_destroy', 'vf_invmodel_load_weights', 'vf_invmodel_infer',
                  'vf_export', 'vf_register', 'vf_allgather_scores', 'vf_comm_init_all', 'vf_comm_destroy',
                  'vf_allgather_scores_group', 'vf_set_phase_stats',
-                 'vf_debug_phase_stats', 'vf_debug_poison_status'):
+                 'vf_debug_phase_stats', 'vf_debug_poison_status', 'vf_debug_lstm_layer'):
         getattr(lib, name).restype = ctypes.c_int
     if lib.vf_abi_version() != ABI_VERSION:
         raise VfError('libvf_hip.so ABI version %d, expected %d (stale build? run __graft_entry__.build())'

@@ -41,6 +41,7 @@
 #include "vf_inverse_model.h"
 #include "vf_plan_render.h"
 #include "vf_conv_bf16x6.h"
+#include "vf_conv_bf16.h"
 #include "vf_persistent.h"
 
 #ifndef VF_WT_DEFAULT
@@ -229,7 +230,7 @@ struct ConvLayer {          // geometry only: shared by every view; the packed w
     int KC, nchunk[2];
     TileKind tile = TILE_CONV;      // the tile body (plan_geometry / init_layer; vf_persistent.h)
     int mrep = 1;                   // TILE_CONV: MFMA row blocks per wave - the workgroup covers 128 * mrep rows
-    int prec = 0;                   // 1: split-bf16 tile (conv-LSTM only)
+    int prec = 0;                   // 1: split-bf16 tile, 2: plain-bf16 tile (conv-LSTM only)
     int NI, TH, TW, RPI, tilesY, tilesX;
     int ni_cap = 0;                 // > 0: at most this many whole images per workgroup (plans for narrow phases)
     int kc_cap = 0;                 // > 0: chunk size at most this (a narrow-phase plan that shares the regular plan's packed weights)
@@ -241,7 +242,9 @@ struct ConvLayer {          // geometry only: shared by every view; the packed w
         if (tile == TILE_FIRST_VALU) return (size_t)KH * KW * segC[0] * Cout;   // canonical [tap][channel][Cout]
         return (size_t)(nchunk[0] + nchunk[1]) * KH * KW * (KC / 8) * 2 * ((size_t)ncg * G * 32) * 4;
     }
-    size_t packed_w16() const {     // bf16 values of the 3-plane split weights (pack_weights_bf16x3)
+    size_t packed_w16() const {     // bf16 values of the 3-plane split weights (pack_weights_bf16x3) or of the one rounded
+                                    // plane (pack_weights_bf16: a stage per 16-channel k-step and kernel row)
+        if (prec == 2) return (size_t)(nchunk[0] + nchunk[1]) * kBf1KS * KH * ncg * kBf1StageUnits * 8;
         return prec == 1 ? (size_t)(nchunk[0] + nchunk[1]) * KH * KW * ncg * 4 * 3 * 64 * 8 : 0;
     }
     size_t packed_b() const { return (size_t)ncg * G * 32; }
@@ -278,6 +281,7 @@ static void plan_geometry(ConvLayer &l, int rows, bool needs_stats, bool one_pix
     if (l.mode == PACK_LSTM) {
         l.mrep = 1;
         if (l.prec == 1) { l.tile = TILE_LSTM_BF16X6; rows = 128; }
+        else if (l.prec == 2) { l.tile = TILE_LSTM_BF16; rows = 128; }
         else l.tile = rows == 64 ? TILE_LSTM_GS64 : (rows == 32 ? TILE_LSTM_ROW32 : TILE_LSTM_GS128);
     }
     const int wrows = std::max(32, rows / 4);
@@ -307,6 +311,7 @@ static void plan_geometry(ConvLayer &l, int rows, bool needs_stats, bool one_pix
                       l.segC[0] % KC || (l.nseg > 1 && l.segC[1] % KC)))
         KC >>= 1;
     if (l.tile == TILE_LSTM_BF16X6) KC = kBfKC;        // the split-bf16 tile stages 16-channel chunks
+    if (l.tile == TILE_LSTM_BF16) KC = kBf1KC;         // the plain-bf16 tile its own chunk (vf_conv_bf16.h)
     l.KC = KC;
     for (int s = 0; s < 2; ++s) l.nchunk[s] = s < l.nseg ? (l.segC[s] + KC - 1) / KC : 0;
     l.lds_bytes = conv_lds_bytes(l, KC);
@@ -324,6 +329,7 @@ static void plan_geometry(ConvLayer &l, int rows, bool needs_stats, bool one_pix
         l.lds_bytes = std::max(l.lds_bytes - b_lds, (size_t)vf::kGsXchFloats * 4 + 64);
     }
     if (l.tile == TILE_LSTM_BF16X6) l.lds_bytes = bf16x6_lds_bytes(l.NI, LH, LW);
+    if (l.tile == TILE_LSTM_BF16) l.lds_bytes = bf16_lds_bytes(l.NI, LH, LW);
     l.stats_nparts = (l.NI == 1 ? l.tilesY * l.tilesX : 1) * l.ncg;
 }
 
@@ -413,6 +419,38 @@ static std::vector<unsigned short> pack_weights_bf16x3(const ConvLayer &l, const
                                     out[unit * 8 + j] = pc[pl];
                                 }
                             }
+    }
+    return out;
+}
+
+// canonical LSTM weights [5][5][Cin][4C] -> ONE bf16 plane, every weight rounded to nearest even, packed for the row-wise K
+// loop of vf_conv_bf16.h:  [chunk16][ky][cg][kx][gate][k-half][32 columns][8 channels]
+// A (chunk16, ky, cg) block - five taps x four gates x 64 lanes of 16 B = 20 KiB - is what one barrier of that loop covers.
+// chunk16 counts 16-channel k-steps in the tile's K order: segment 0 (the recurrent input) first, and a segment's channels
+// padded with zeros to whole staged chunks of kBf1KC, so the layout does not depend on the staged chunk size beyond that.
+static std::vector<unsigned short> pack_weights_bf16(const ConvLayer &l, const float *w, int Cin, int Ctot) {
+    const int nchunks = l.nchunk[0] + l.nchunk[1];
+    std::vector<unsigned short> out((size_t)nchunks * kBf1KS * l.KH * l.ncg * kBf1StageUnits * 8, 0);
+    for (int ci = 0; ci < nchunks; ++ci) {
+        const int s = ci < l.nchunk[0] ? 0 : 1;
+        const int seg_off = l.seg_off[s];
+        for (int ks = 0; ks < kBf1KS; ++ks) {
+            const int c0 = (s == 0 ? ci : ci - l.nchunk[0]) * kBf1KC + ks * 16;
+            for (int ky = 0; ky < l.KH; ++ky)
+                for (int cgi = 0; cgi < l.ncg; ++cgi)
+                    for (int kx = 0; kx < l.KW; ++kx)
+                        for (int g = 0; g < 4; ++g)
+                            for (int kh = 0; kh < 2; ++kh)
+                                for (int nn = 0; nn < 32; ++nn)
+                                    for (int j = 0; j < 8; ++j) {
+                                        const int c = c0 + kh * 8 + j, co = cgi * 32 + nn;
+                                        if (c >= l.segC[s] || co >= l.Cout) continue;
+                                        const float x = w[((size_t)(ky * l.KW + kx) * Cin + seg_off + c) * Ctot + g * l.Cout + co];
+                                        const size_t stage = ((size_t)(ci * kBf1KS + ks) * l.KH + ky) * l.ncg + cgi;
+                                        const size_t unit = stage * kBf1StageUnits + (size_t)(kx * 4 + g) * 64 + kh * 32 + nn;
+                                        out[unit * 8 + j] = bf16_rne(x);
+                                    }
+        }
     }
     return out;
 }
@@ -652,7 +690,8 @@ static int validate(const vf_config *c) {
     if (c->arch == 2 ? c->num_masks != 6 : c->num_masks != 10)
         return fail(VF_ERR_INVALID, "num_masks must be 10 (arch 0 / 1), 6 (arch 2: four CDNA warps + previous + first + scratch) or 4 (arch 3)");
     if (c->max_batch < 1) return fail(VF_ERR_INVALID, "max_batch must be >= 1");
-    if (c->precision != 0 && c->precision != 1) return fail(VF_ERR_INVALID, "precision must be 0 (fp32) or 1 (split bf16)");
+    if (c->precision < 0 || c->precision > 2)
+        return fail(VF_ERR_INVALID, "precision must be 0 (fp32), 1 (split bf16) or 2 (plain bf16)");
     if (c->ncam < 0 || c->ncam > kMaxCam) return fail(VF_ERR_INVALID, "ncam must be 1..4 (0 = 1)");
     if (c->n_draws < 0) return fail(VF_ERR_INVALID, "n_draws must be >= 1 (0 = 1)");
     if (c->n_draws > 1 && c->max_batch % c->n_draws)
@@ -730,6 +769,7 @@ static int configure_kernels(vf_handle *h) {
     if ((rc = allow_lds(&conv_mfma_kernel<4, EPI_CONVT_RAW_STATS, 1>, n))) return rc;
     if ((rc = allow_lds(&conv_mfma_kernel<1, EPI_PARTIAL, 2>, n))) return rc;
     if ((rc = allow_lds(&conv_lstm_bf16x6_kernel<1>, n))) return rc;
+    if ((rc = allow_lds(&conv_lstm_bf16_kernel<1>, n))) return rc;
     if ((rc = allow_lds(&conv_lstm_gsplit64_kernel, n))) return rc;
     if ((rc = allow_lds(&conv_lstm_gsplit2_kernel<4>, n))) return rc;
     if ((rc = allow_lds(&conv_lstm_row32_kernel, n))) return rc;
@@ -774,6 +814,7 @@ static int launch_lstm(const ConvLayer &l, const ConvParams &p, hipStream_t st) 
         case TILE_LSTM_GS64: hipLaunchKernelGGL(conv_lstm_gsplit64_kernel, grid, dim3(kConvThreads), l.lds_bytes, st, p); break;
         case TILE_LSTM_ROW32: hipLaunchKernelGGL(conv_lstm_row32_kernel, grid, dim3(kConvThreads), l.lds_bytes, st, p); break;
         case TILE_LSTM_BF16X6: hipLaunchKernelGGL(conv_lstm_bf16x6_kernel<1>, grid, dim3(kConvThreads), l.lds_bytes, st, p); break;
+        case TILE_LSTM_BF16: hipLaunchKernelGGL(conv_lstm_bf16_kernel<1>, grid, dim3(kConvThreads), l.lds_bytes, st, p); break;
         default: return fail(VF_ERR_INVALID, "internal: " + l.name + " is planned without a conv-LSTM tile");
     }
     VF_HIP_CHECK(hipGetLastError());
@@ -815,7 +856,7 @@ static ConvParams make_params(const ConvLayer &l, const LayerW &w, int B, const 
     p.ncg = l.ncg; p.Cout = l.Cout; p.Wp = w.w; p.Wp16 = w.w16; p.bias = w.b;
     p.chunks_per_split = l.chunks_per_split; p.n_valid = l.n_valid;
     p.stats_nparts = l.stats_nparts;    // row stride of p.stats; the conv-LSTM plans overwrite it with st_rows[k]
-    p.tile_variant = l.prec == 1 ? 1 : 0;
+    p.tile_variant = l.mode == PACK_LSTM ? l.prec : 0;
     p.pad_skip = pad_skip ? 1 : 0;
     return p;
 }
@@ -979,7 +1020,7 @@ static int cdna_create(vf_handle *h) {
                  &h->lstm[4], &h->convt1, &h->lstm[5], &h->convt2, &h->lstm[6], &h->convt3};
     if (!h->flow) h->layers.push_back(&h->fc);      // (a flow engine has no CDNA FC: the plan above exists, nothing is packed or run)
     if (h->savp) { h->layers.push_back(&h->enc00); h->layers.push_back(&h->convt4); }
-    h->small_plans = cfg->precision == 0;   // the split-bf16 tile has 128 rows only
+    h->small_plans = cfg->precision == 0;   // the split-bf16 and plain-bf16 tiles have 128 rows only
     for (int k = 0; k < 7; ++k) {
         h->st_rows[k] = h->lstm[k].stats_nparts;
         if (!h->small_plans) continue;
@@ -1028,7 +1069,7 @@ static int cdna_create(vf_handle *h) {
         for (const ConvLayer *l : h->layers) {
             VF_ALLOC(vd.lw[l->id].w, l->packed_w());
             VF_ALLOC(vd.lw[l->id].b, l->packed_b());
-            if (l->prec == 1) VF_ALLOC(vd.lw[l->id].w16, l->packed_w16());
+            if (l->prec != 0) VF_ALLOC(vd.lw[l->id].w16, l->packed_w16());
         }
         for (int i = 0; i < kNumLn; ++i) {
             const TensorDesc *g = find_tensor(h->table, ln_name(i) + "/g");
@@ -1282,8 +1323,9 @@ int vf_load_weights(vf_handle *h, const float *blob_all, size_t n_floats) {
                 return fail(VF_ERR_INVALID, "internal: packed size of " + l.name + " differs from its plan");
             if ((rc = dev_write(h, vd.lw[l.id].w, wp.data(), wp.size() * sizeof(float)))) return rc;
             if ((rc = dev_write(h, vd.lw[l.id].b, bp.data(), bp.size() * sizeof(float)))) return rc;
-            if (l.prec == 1) {
-                std::vector<unsigned short> w16 = pack_weights_bf16x3(l, blob + w->offset, w->shape[2], w->shape[3]);
+            if (l.prec != 0) {
+                std::vector<unsigned short> w16 = l.prec == 2 ? pack_weights_bf16(l, blob + w->offset, w->shape[2], w->shape[3])
+                                                              : pack_weights_bf16x3(l, blob + w->offset, w->shape[2], w->shape[3]);
                 if (w16.size() != l.packed_w16())
                     return fail(VF_ERR_INVALID, "internal: split-bf16 size of " + l.name + " differs from its plan");
                 if ((rc = dev_write(h, vd.lw[l.id].w16, w16.data(), w16.size() * sizeof(unsigned short)))) return rc;
@@ -2903,6 +2945,37 @@ int vf_debug_poison_status(vf_handle *h) {
     return VF_OK;
     VF_API_CATCH(int)
 }
+
+#ifndef VF_HOST_SELFTEST
+// debugging aid: ONE conv-LSTM layer as a per-layer launch on caller-owned NHWC tensors - the only way to feed a gate tile
+// operands whose bits the caller controls.  x [B][h][w][Cx] is taken as it is (no producer LayerNorm, no relu), h / c
+// [B][h][w][C] are the previous hidden and cell state; the handle's own precision selects the tile, its loaded weights of
+// view 0 are used, and the layer's LayerNorm partials land in the handle's own statistics buffer: the rollout state is
+// undefined afterwards until the next vf_set_context.  Allocates nothing, never synchronises.
+int vf_debug_lstm_layer(vf_handle *h, int32_t layer, int32_t B, const float *d_x, const float *d_h, const float *d_c,
+                        float *d_h_out, float *d_c_out, void *stream) {
+    VF_API_TRY
+    if (!h || !d_x || !d_h || !d_c || !d_h_out || !d_c_out) return fail(VF_ERR_INVALID, "null argument");
+    if (h->cfg.arch >= 2) return fail(VF_ERR_INVALID, "vf_debug_lstm_layer: arch 0 / 1 only");
+    if (layer < 0 || layer > 6) return fail(VF_ERR_INVALID, "vf_debug_lstm_layer: layer must be 0..6 (lstm1..lstm7)");
+    if (B < 1 || B > h->cfg.max_batch) return fail(VF_ERR_INVALID, "vf_debug_lstm_layer: B must be 1..max_batch");
+    if (!h->have_weights) return fail(VF_ERR_NOWEIGHTS, "vf_load_weights has not been called");
+    VF_HIP_CHECK(hipSetDevice(h->cfg.device));
+    const ConvLayer &l = h->lstm[layer];
+    const long long px = (long long)l.Hin * l.Win;
+    SegArg sh, sx;
+    memset(&sh, 0, sizeof(sh)); memset(&sx, 0, sizeof(sx));
+    sh.ptr = d_h; sh.bstride = px * l.segC[0]; sh.gamma_mod = 1;       // (segment 0 is the recurrent input)
+    sx.ptr = d_x; sx.bstride = px * l.segC[1]; sx.gamma_mod = 1;
+    ConvParams q = make_params(l, h->views[0].lw[l.id], B, sh, &sx, h->pad_skip);
+    q.out = d_h_out; q.cstate = d_c_out; q.cstate_in = d_c; q.cin_bstride = px * l.Cout;
+    q.stats = h->st_h[layer]; q.stats_nparts = h->st_rows[layer];
+    h->have_context = false;
+    h->shared_valid = false;
+    return launch_lstm(l, q, reinterpret_cast<hipStream_t>(stream));
+    VF_API_CATCH(int)
+}
+#endif
 
 // debugging aid: per-phase (type, items, wait ticks, run ticks) of the last persistent rollout
 int vf_set_phase_stats(vf_handle *h, int32_t enable) {

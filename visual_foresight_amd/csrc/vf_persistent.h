@@ -20,6 +20,7 @@
 #include "vf_conv_mfma.h"
 #include "vf_small_kernels.h"
 #include "vf_conv_bf16x6.h"
+#include "vf_conv_bf16.h"
 #include "vf_conv_gsplit.h"
 #include "vf_fused_top.h"
 #include "vf_fc_tile.h"
@@ -59,7 +60,8 @@ enum TileKind : int {
     TILE_LSTM_ROW32,        // conv-LSTM, 32 rows, weights from a register ring (conv_tile<4, EPI_LSTM, 1, PT, 1>)
     TILE_LSTM_BF16X6,       // conv-LSTM, split-bf16, 128 rows (vf_conv_bf16x6.h)
     TILE_FC_WIDE,           // CDNA FC: all column groups in one item per (row tile, K split) (vf_fc_tile.h)
-    TILE_FIRST_VALU         // first conv of the encoder (3-channel frame, 5 x 5 / 2) on the vector ALUs (vf_conv_first.h)
+    TILE_FIRST_VALU,        // first conv of the encoder (3-channel frame, 5 x 5 / 2) on the vector ALUs (vf_conv_first.h)
+    TILE_LSTM_BF16          // conv-LSTM, plain bf16 (one product per multiply), 128 rows (vf_conv_bf16.h)
 };
 
 constexpr int kMaxDeps = 3;
@@ -93,7 +95,7 @@ struct PhaseDesc {
     int NI, tiles_per_img;  // conv phases: how an item maps to samples
     int whole;              // 1: completion is counted once per item on counter 0
     TileKind tile;          // conv phases: the tile body
-    int prec;               // conv-LSTM tile: 0 exact fp32, 1 split-bf16 (TILE_LSTM_BF16X6)
+    int prec;               // conv-LSTM tile: 0 exact fp32, 1 split-bf16 (TILE_LSTM_BF16X6), 2 plain bf16 (TILE_LSTM_BF16)
     int view;               // camera view this phase belongs to (selects the goal pixels of PH_COMPOSITE)
     int cnt_base;
     int aux_base;           // PH_TOP_FUSED: first of the per-sample "LayerNorm partial published" counters
@@ -199,6 +201,10 @@ static __device__ __noinline__ __attribute__((not_tail_called)) void lstm_gsplit
 template <int MREP>
 static __device__ __noinline__ __attribute__((not_tail_called)) void lstm_bf16x6_tile_call(const ConvParams *p, int bx, int by) {
     conv_lstm_bf16x6_tile<MREP>(const_params(p), bx, by, tile_lds());
+}
+template <int MREP>
+static __device__ __noinline__ __attribute__((not_tail_called)) void lstm_bf16_tile_call(const ConvParams *p, int bx, int by) {
+    conv_lstm_bf16_tile<MREP>(const_params(p), bx, by, tile_lds());
 }
 template <int CO>
 static __device__ __noinline__ __attribute__((not_tail_called)) void conv_first_tile_call(const ConvParams *p, int bx) {
@@ -430,6 +436,7 @@ __device__ __forceinline__ void rollout_body(const PhaseDesc *__restrict__ phase
                     // tiles, the 32-row tile, the split-bf16 tile and - only for a geometry the gate-split tile cannot
                     // stage - the 128-row tile with its weights through LDS)
                     if (P.tile == TILE_LSTM_BF16X6) lstm_bf16x6_tile_call<1>(&P.conv, bx, by);
+                    else if (P.tile == TILE_LSTM_BF16) lstm_bf16_tile_call<1>(&P.conv, bx, by);
                     else if (P.tile == TILE_LSTM_GS128) lstm_gsplit2_tile_call<4>(&P.conv, bx, by);
                     else if (P.tile == TILE_LSTM_GS64) lstm_gsplit64_tile_call(&P.conv, bx, by);
                     else if (P.tile == TILE_LSTM_ROW32) lstm_row32_tile_call(&P.conv, bx, by);

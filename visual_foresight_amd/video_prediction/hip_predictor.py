@@ -134,9 +134,13 @@ class HipVPredEvaluation(object):
         # The reference's reduced-precision switch is the bare key 'float16' in the predictor conf
         # (video_prediction/setup_predictor.py:92-95: placeholders and model in tf.float16).  Its counterpart here is
         # the split-bf16 mode: the same kind of opt-in for speed, but with fp32-class accuracy.
+        # 'bf16' (2): plain bf16 - operands of the gate GEMMs rounded once, one bf16 MFMA product per multiply, fp32
+        # accumulation.  THIS is the mode with the reference's speed / accuracy trade (half-precision arithmetic for
+        # speed); the bare 'float16' key keeps selecting 'bf16x6', so ask for it by name: precision='bf16' or
+        # VF_PRECISION=bf16.
         default_precision = 'bf16x6' if 'float16' in hp else os.environ.get('VF_PRECISION', 'fp32')
         precision = hp.get('precision', default_precision)
-        self.precision = {'fp32': 0, '0': 0, 0: 0, 'bf16x6': 1, '1': 1, 1: 1}[precision]
+        self.precision = {'fp32': 0, '0': 0, 0: 0, 'bf16x6': 1, '1': 1, 1: 1, 'bf16': 2, '2': 2, 2: 2}[precision]
         self._c_cfg = _lib.VfConfig(c.height, c.width, c.adim, c.sdim, c.ndesig, c.n_context,
                                     c.sequence_length, c.num_masks, self.run_batch_size,
                                     self.device_index, self.precision, self.n_cam, self.n_draws, c.arch_id,
