@@ -62,7 +62,8 @@ typedef struct vf_config {
     int32_t n_context;          /* context frames (>= 1) */
     int32_t sequence_length;    /* n_context + T */
     int32_t num_masks;          /* CDNA kernel slots K (masks = K + 1): 10 for arch 0 / 1; 6 for arch 2 (four kernels in
-                                 * the checkpoint, seven compositing layers); 4 for arch 3 (four kernels, seven layers) */
+                                 * the checkpoint, seven compositing layers); 4 for arch 3 (four kernels, seven layers); 1 for arch 0 with
+                                 * layer_spec 3 (DNA: one transform, two mask channels) */
     int32_t max_batch;          /* run_batch_size: most samples per vf_rollout call */
     int32_t device;             /* HIP device ordinal */
     int32_t precision;          /* arithmetic of the conv-LSTM gate GEMMs (96 % of the work):
@@ -105,8 +106,10 @@ typedef struct vf_config {
                                  * 32 / 64 / 128 force a table (64 = the paper's five-cell network).  arch 0: 0 = the survey
                                  * table, 1 = the decoder widths of the public CDNA code, 2 = the survey table with
                                  * appearance-flow compositing (a 1x1 flow head and nine bilinearly gathered warps in place of
-                                 * the CDNA FC and kernels; tensors flow/w, flow/b where cdna/w, cdna/b sit); 1 and 2 are
-                                 * exact fp32 only (precision 0).  0 for arch 1 - 2 */
+                                 * the CDNA FC and kernels; tensors flow/w, flow/b where cdna/w, cdna/b sit), 3 = the survey
+                                 * table with DNA compositing (selector: arch 0, layer_spec 3, num_masks 1 - a 1x1 head predicts
+                                 * a normalised 5x5 kernel per pixel; no rgb head, two mask channels, tensors dna/w [1][1][32][25],
+                                 * dna/b where cdna/w, cdna/b sit); 1, 2 and 3 are exact fp32 only (precision 0).  0 for arch 1 - 2 */
 } vf_config;
 
 typedef struct vf_handle vf_handle;

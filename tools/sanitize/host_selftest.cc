@@ -25,7 +25,8 @@ extern "C" int vf_selftest_schedule(vf_handle *h, int32_t B, int32_t skip_shared
 
 static int run_case(int H, int W, int adim, int sdim, int nd, int nctx, int T, int max_batch, int precision, int ncam,
                     int n_draws, const int *batches, int n_batches, int arch = 0, int zdim = 0, int layer_spec = 0) {
-    vf_config cfg = {H, W, adim, sdim, nd, nctx, nctx + T, arch == 3 ? 4 : (arch == 2 ? 6 : 10), max_batch, 0, precision, ncam, n_draws, arch,
+    const int num_masks = arch == 3 ? 4 : (arch == 2 ? 6 : (arch == 0 && layer_spec == 3 ? 1 : 10));     // (DNA: one transform)
+    vf_config cfg = {H, W, adim, sdim, nd, nctx, nctx + T, num_masks, max_batch, 0, precision, ncam, n_draws, arch,
                      zdim, layer_spec};
     const size_t n = vf_weight_count(&cfg);
     if (n == 0) { std::fprintf(stderr, "weight count failed: %s\n", vf_last_error()); return 1; }
@@ -99,6 +100,15 @@ int main() {
     rc |= run_case(48, 64, 6, 3, 4, 1, 2, 16, 0, 1, 1, b_small, 3, 3, 2);
     rc |= run_case(128, 128, 12, 5, 1, 2, 15, 125, 0, 1, 5, b_c2 + 1, 2, 3, 8);
     rc |= run_case(128, 128, 12, 5, 1, 2, 4, 10, 0, 1, 5, b_c5 + 1, 1, 3, 8, 64);
+    // arch 0 with DNA compositing (layer_spec 3, num_masks 1: a 5x5 kernel per pixel from a 1x1 head - no CDNA FC, no
+    // kernel-finish items, no kernel table): a fusable shape, the shape that cannot be fused (two views, four designated
+    // pixels), one context frame, a planning-size batch - each behind the cdna table of the same shape, from which it may
+    // differ by exactly the FC and finish items (tests/test_dna.py).  Appended behind every other shape, under shape lines of
+    // their own (adim 5), so that the rows the other tests count and index stay where they are.
+    for (int spec : {0, 3}) rc |= run_case(64, 64, 5, 5, 2, 2, 3, 37, 0, 1, 1, b_small, 4, 0, 0, spec);
+    for (int spec : {0, 3}) rc |= run_case(40, 56, 5, 5, 4, 2, 2, 16, 0, 2, 1, b_small, 3, 0, 0, spec);
+    for (int spec : {0, 3}) rc |= run_case(32, 32, 5, 5, 1, 1, 2, 16, 0, 1, 1, b_small, 3, 0, 0, spec);
+    for (int spec : {0, 3}) rc |= run_case(64, 64, 5, 3, 1, 2, 13, 200, 0, 1, 1, b_c2, 3, 0, 0, spec);
     // invalid configurations are refused, not crashed on
     vf_config bad = {60, 64, 4, 5, 1, 2, 15, 10, 8, 0, 0, 1, 1, 0};
     vf_handle *h = nullptr;
@@ -121,6 +131,12 @@ int main() {
     if (vf_create(&bad9, &h) == 0) { std::fprintf(stderr, "appearance flow in the split-bf16 mode accepted\n"); rc = 1; }
     vf_config bad10 = {128, 128, 12, 5, 1, 2, 15, 10, 8, 0, 0, 1, 1, 1, 0, 2};  // ... and belongs to arch 0
     if (vf_create(&bad10, &h) == 0) { std::fprintf(stderr, "appearance flow with arch 1 accepted\n"); rc = 1; }
+    vf_config bad11 = {64, 64, 4, 5, 1, 2, 15, 1, 8, 0, 2, 1, 1, 0, 0, 3};      // DNA is fp32 only
+    if (vf_create(&bad11, &h) == 0) { std::fprintf(stderr, "DNA in the plain-bf16 mode accepted\n"); rc = 1; }
+    vf_config bad12 = {64, 64, 4, 5, 1, 2, 15, 10, 8, 0, 0, 1, 1, 0, 0, 3};     // ... has one transform
+    if (vf_create(&bad12, &h) == 0) { std::fprintf(stderr, "DNA with num_masks 10 accepted\n"); rc = 1; }
+    vf_config bad13 = {128, 128, 12, 5, 1, 2, 15, 1, 8, 0, 0, 1, 1, 1, 0, 3};   // ... and belongs to arch 0
+    if (vf_create(&bad13, &h) == 0) { std::fprintf(stderr, "DNA with arch 1 accepted\n"); rc = 1; }
     // "No exception crosses this boundary" (include/vf_hip.h): a std::bad_alloc / std::exception / foreign throw inside the
     // schedule builder, the weight packer or vf_create comes back as a status code with vf_last_error() set, leaks nothing
     // (ASan's leak check runs at exit) and leaves the handle usable and destroyable

@@ -108,7 +108,8 @@ enum Epilogue {
     EPI_CONVT_FUSED = 6,      // top transposed conv whose tile is composed into the next frame right away
                               // (vf_fused_top.h); 6 + 2 * (designated pixels - 1) + (arch 1 / 2 first-frame layer)
                               // + 8 for the six-kernel compositing of arch 2 (four CDNA warps + previous + first + scratch);
-                              // + 16 for the appearance-flow compositing (fused_epi_flow: never with the other two flags)
+                              // + 16 for the appearance-flow compositing (fused_epi_flow: never with the other two flags);
+                              // + 16 + 1 for the DNA compositing (fused_epi_dna: the first-frame bit means DNA behind + 16)
     EPI_CONV_PAIR = 30,       // a conv whose whole-image tiles feed a 1x1 conv in the same item (conv_pair_epilogue: enc2 ->
                               // enc3, the 8 x 8 bottleneck; G = 2: both 32-channel groups of the first conv in one workgroup)
     EPI_RAW = 31              // acc + bias, nothing else (arch 3: instance norm needs the whole image's statistics first; the
@@ -119,7 +120,8 @@ __host__ __device__ constexpr int fused_epi(int nd, bool first, bool k6 = false)
     return EPI_CONVT_FUSED + 2 * (nd - 1) + (first ? 1 : 0) + (k6 ? 8 : 0);
 }
 __host__ __device__ constexpr int fused_epi_flow(int nd) { return EPI_CONVT_FUSED + 16 + 2 * (nd - 1); }
-static_assert(fused_epi_flow(4) < EPI_CONV_PAIR, "the fused epilogues end in front of EPI_CONV_PAIR");
+__host__ __device__ constexpr int fused_epi_dna(int nd) { return fused_epi_flow(nd) + 1; }
+static_assert(fused_epi_dna(4) < EPI_CONV_PAIR, "the fused epilogues end in front of EPI_CONV_PAIR");
 
 struct ConvSeg {
     const float *ptr;       // NHWC activations of this input segment
@@ -1110,7 +1112,7 @@ __device__ __forceinline__ void conv_pair_epilogue(const PT &p, f32x16 (&acc)[1]
 // rollout - RB 1: 32 rows (one row block, wave w = gate w), RB -2: the gate-split 64-row tile (two row blocks, wave w =
 // gate w of both); same chunking and K order, i.e. the same bits.
 // epilogue of EPI_CONVT_FUSED, defined in vf_fused_top.h (it needs the compositing code)
-template <int ND, bool FIRST, int K, bool FLOW, class PT>
+template <int ND, bool FIRST, int K, int MODE, class PT>
 __device__ __forceinline__ void convt_fused_epilogue(const PT &p, f32x16 (&acc)[1][4], int bx, long long *red, float *smem);
 
 template <int G, int EPI, int MREP, class PT, int RB = 4>
@@ -1864,8 +1866,10 @@ __device__ __forceinline__ void conv_tile(const PT &p, const int bx_, const int 
     // vectorised cell update: 16-byte loads and stores instead of 48 scalar ones per lane)
     if constexpr (GSPLIT || ROW32) lstm_gsplit_epilogue<MR>(p, acc, bx, by, smem);
     else if constexpr (is_top_fused(EPI))
-        convt_fused_epilogue<((EPI - EPI_CONVT_FUSED) & 7) / 2 + 1, ((EPI - EPI_CONVT_FUSED) & 1) != 0,
-                             ((EPI - EPI_CONVT_FUSED) & 8) != 0 ? 6 : 10, (EPI - EPI_CONVT_FUSED) >= 16>(p, acc, bx, red, smem);
+        // (behind + 16 the low bit selects DNA, not the first-frame layer; modes: CompMode of vf_small_kernels.h)
+        convt_fused_epilogue<((EPI - EPI_CONVT_FUSED) & 7) / 2 + 1, (EPI - EPI_CONVT_FUSED) < 16 && ((EPI - EPI_CONVT_FUSED) & 1) != 0,
+                             (EPI - EPI_CONVT_FUSED) >= 16 && ((EPI - EPI_CONVT_FUSED) & 1) != 0 ? 1 : (((EPI - EPI_CONVT_FUSED) & 8) != 0 ? 6 : 10),
+                             (EPI - EPI_CONVT_FUSED) < 16 ? 0 : 1 + ((EPI - EPI_CONVT_FUSED) & 1)>(p, acc, bx, red, smem);
     else if constexpr (EPI == EPI_CONV_PAIR) conv_pair_epilogue(p, acc, bx, smem);
     else conv_epilogue<G, EPI, MREP>(p, acc, bx, by, bz, red, smem);
 #ifdef VF_TILE_STATS

@@ -130,6 +130,8 @@ struct TensorDesc {
 static int a_of(const vf_config &c) { return c.adim + c.sdim; }
 // arch 0, layer_spec 2: appearance-flow compositing (cdna_arch.py transformation='flow')
 static bool is_flow(const vf_config &c) { return c.arch == 0 && c.layer_spec == 2; }
+// arch 0, layer_spec 3: DNA compositing - a 5x5 kernel per pixel from a 1x1 head (dna_arch.py)
+static bool is_dna(const vf_config &c) { return c.arch == 0 && c.layer_spec == 3; }
 
 // arch 3 (the published SAVP generator): vf_engine_savp3.inc
 struct Savp3;
@@ -171,7 +173,9 @@ static std::vector<TensorDesc> tensor_table(const vf_config &c) {
     // the heads 64); layer_spec = 0: the widths of SURVEY row a14 (convt2 96 -> 64, convt3 64 -> 32)
     // arch 0 with layer_spec = 2: the survey widths with the appearance-flow head in place of the CDNA FC (cdna_arch.py
     // transformation='flow'): flow/w [1][1][32][2 * kFlowWarps], flow/b where cdna/w, cdna/b sat
-    const bool pub = c.arch == 0 && c.layer_spec == 1, flow = is_flow(c);
+    // arch 0 with layer_spec = 3: the survey widths with the DNA head (dna_arch.py): no rgb head, two mask channels
+    // (num_masks = 1), dna/w [1][1][32][kTaps], dna/b where cdna/w, cdna/b sat
+    const bool pub = c.arch == 0 && c.layer_spec == 1, flow = is_flow(c), dna = is_dna(c);
     const int c_t2 = pub ? L[5] + L[1] : L[5], c_top = pub ? L[6] + 32 : 32;
     if (savp) { conv("enc00", 5, 5, 3, kEnc00Ch); ln("lna", kEnc00Ch); }
     conv("enc0", 5, 5, savp ? kEnc00Ch : 3, 32); ln("ln1", 32);
@@ -189,11 +193,12 @@ static std::vector<TensorDesc> tensor_table(const vf_config &c) {
     conv("lstm7", 5, 5, c_t2 + cc + L[6], 4 * L[6]); ln("ln8", L[6]);
     conv("convt3", 3, 3, L[6] + 32, c_top);     ln("ln9", c_top);
     if (savp) { conv("convt4", 3, 3, 32 + kEnc00Ch, 32); ln("lnb", 32); }
-    conv("rgb", 1, 1, c_top, 3);
+    if (!dna) conv("rgb", 1, 1, c_top, 3);
     conv("masks", 1, 1, c_top, K + 1);
     // arch 2: the FOUR CDNA kernels of the published generator (the engine pads them to its num_masks = 6 slots at load)
     const int KF = c.arch == 2 ? K - 2 : K;
     if (flow) conv("flow", 1, 1, c_top, 2 * kFlowWarps);
+    else if (dna) conv("dna", 1, 1, c_top, kTaps);
     else {
         add("cdna/w", {fc_in, kTaps * KF});
         add("cdna/b", {kTaps * KF});
@@ -514,6 +519,8 @@ struct vf_handle {
     bool cond = false;                  // vf_config.arch == 2: [action, latent, state] conditions every conv-LSTM
     bool flow = false;                  // arch 0, layer_spec 2: appearance-flow compositing - no CDNA FC, no kernels; the flow
                                         // kernels (composite_flow_kernel, rollout_flow_kernel) run in place of the CDNA ones
+    bool dna = false;                   // arch 0, layer_spec 3: DNA compositing - no CDNA FC, no kernel table, no rgb head; the
+                                        // head lives in ViewData::w_flow / b_flow; composite_dna_kernel, rollout_dna_kernel run
     float *cond_bias[7] = {nullptr};    // ... through per-sample border-class biases [2 step parities][ncam][max_batch][25][4C]
     int Hc, Wc;                         // input size of the three-scale conv-LSTM core (H, W; arch 1: H/2, W/2)
     int c_t2 = 64, c_top = 32;          // output channels of convt2 / convt3 (arch 0, layer_spec 1 - the public table: 96 / 64)
@@ -680,14 +687,19 @@ static int validate(const vf_config *c) {
         return s3_validate(c);
     }
     if (c->zdim != 0) return fail(VF_ERR_INVALID, "zdim belongs to arch 3 (must be 0 otherwise)");
-    if (c->layer_spec != 0 && !(c->arch == 0 && (c->layer_spec == 1 || c->layer_spec == 2)))
-        return fail(VF_ERR_INVALID, "layer_spec: arch 3's layer table, or with arch 0 1 (the public CDNA decoder widths) or 2 "
-                                    "(appearance-flow compositing); 0 otherwise");
+    if (c->layer_spec != 0 && !(c->arch == 0 && c->layer_spec >= 1 && c->layer_spec <= 3))
+        return fail(VF_ERR_INVALID, "layer_spec: arch 3's layer table, or with arch 0 1 (the public CDNA decoder widths), 2 "
+                                    "(appearance-flow compositing) or 3 (DNA compositing); 0 otherwise");
     if (c->arch == 0 && c->layer_spec == 1 && c->precision != 0)
         return fail(VF_ERR_INVALID, "the public decoder table (arch 0, layer_spec 1) is built for precision 0 (exact fp32) only");
     if (is_flow(*c) && c->precision != 0)
         return fail(VF_ERR_INVALID, "the appearance-flow table (arch 0, layer_spec 2) is built for precision 0 (exact fp32) only");
-    if (c->arch == 2 ? c->num_masks != 6 : c->num_masks != 10)
+    if (is_dna(*c)) {
+        if (c->precision != 0)
+            return fail(VF_ERR_INVALID, "the DNA table (arch 0, layer_spec 3) is built for precision 0 (exact fp32) only");
+        if (c->num_masks != 1)
+            return fail(VF_ERR_INVALID, "the DNA table (arch 0, layer_spec 3) has one transform: num_masks must be 1");
+    } else if (c->arch == 2 ? c->num_masks != 6 : c->num_masks != 10)
         return fail(VF_ERR_INVALID, "num_masks must be 10 (arch 0 / 1), 6 (arch 2: four CDNA warps + previous + first + scratch) or 4 (arch 3)");
     if (c->max_batch < 1) return fail(VF_ERR_INVALID, "max_batch must be >= 1");
     if (c->precision < 0 || c->precision > 2)
@@ -792,6 +804,10 @@ static int configure_kernels(vf_handle *h) {
     if ((rc = allow_lds(&rollout_flow_kernel<2>, np))) return rc;
     if ((rc = allow_lds(&rollout_flow_kernel<3>, np))) return rc;
     if ((rc = allow_lds(&rollout_flow_kernel<4>, np))) return rc;
+    if ((rc = allow_lds(&rollout_dna_kernel<1>, np))) return rc;
+    if ((rc = allow_lds(&rollout_dna_kernel<2>, np))) return rc;
+    if ((rc = allow_lds(&rollout_dna_kernel<3>, np))) return rc;
+    if ((rc = allow_lds(&rollout_dna_kernel<4>, np))) return rc;
     return VF_OK;
 }
 
@@ -943,6 +959,12 @@ double vf_macs_per_sample_step(const vf_config *cfg) {
         macs += (double)HF * WF * 4 * (3 + cfg->ndesig) * kFlowWarps;
         return macs;
     }
+    if (is_dna(*cfg)) {         // the DNA head, and one 5 x 5 kernel per pixel in place of the FC and the mixed CDNA kernels
+        const TensorDesc *dw = find_tensor(t, "dna/w");
+        macs += (double)HF * WF * dw->shape[2] * dw->shape[3];
+        macs += (double)HF * WF * kTaps * (3 + cfg->ndesig);
+        return macs;
+    }
     macs += (double)fc->shape[0] * fc->shape[1];
     macs += (double)HF * WF * kTaps * (3 + cfg->ndesig) * (cfg->arch == 2 ? cfg->num_masks - 2 : cfg->num_masks);
     return macs;
@@ -1003,14 +1025,15 @@ static int cdna_create(vf_handle *h) {
     init_layer(h->lstm[6], "lstm7", PACK_LSTM, H2, W2, H2, W2, 5, 5, 1, 2, h->c_t2, L[6], L[6], true, false, 128, cfg->precision, false, ccond);
     init_layer(h->convt3, "convt3", PACK_CONVT, H2, W2, H2, W2, 2, 2, 1, 1, L[6], 32, h->c_top, true, false, 128, 0, true);
     // CDNA FC as a K-split GEMM over 1x1 "images"
-    init_layer(h->fc, "cdna", PACK_PLAIN, 1, 1, 1, 1, 1, 1, 1, 0, H8 * W8 * L[4], 0, kTaps * h->K, false, true, 256);
+    const int fc_k = h->dna ? 10 : h->K;        // (a DNA engine never runs the FC: its unused plan is sized as the cdna table's)
+    init_layer(h->fc, "cdna", PACK_PLAIN, 1, 1, 1, 1, 1, 1, 1, 0, H8 * W8 * L[4], 0, kTaps * fc_k, false, true, 256);
     {
         ConvLayer &f = h->fc;
         const int total = f.nchunk[0];
         f.nsplit = std::min(32, total);
         f.chunks_per_split = (total + f.nsplit - 1) / f.nsplit;
         f.nsplit = (total + f.chunks_per_split - 1) / f.chunks_per_split;
-        f.n_valid = kTaps * h->K;
+        f.n_valid = kTaps * fc_k;
         // the persistent schedule's plan: same packed weights, same chunks and splits, 128 rows x all column groups
         h->fc_wide = f;
         h->fc_wide.tile = TILE_FC_WIDE; h->fc_wide.NI = kFcRows; h->fc_wide.lds_bytes = fc_wide_lds_bytes();
@@ -1018,7 +1041,7 @@ static int cdna_create(vf_handle *h) {
     }
     h->layers = {&h->enc0, &h->lstm[0], &h->lstm[1], &h->enc1, &h->lstm[2], &h->lstm[3], &h->enc2, &h->enc3,
                  &h->lstm[4], &h->convt1, &h->lstm[5], &h->convt2, &h->lstm[6], &h->convt3};
-    if (!h->flow) h->layers.push_back(&h->fc);      // (a flow engine has no CDNA FC: the plan above exists, nothing is packed or run)
+    if (!h->flow && !h->dna) h->layers.push_back(&h->fc);   // (a flow / DNA engine has no CDNA FC: the plan above exists, nothing is packed or run)
     if (h->savp) { h->layers.push_back(&h->enc00); h->layers.push_back(&h->convt4); }
     h->small_plans = cfg->precision == 0;   // the split-bf16 and plain-bf16 tiles have 128 rows only
     for (int k = 0; k < 7; ++k) {
@@ -1082,6 +1105,7 @@ static int cdna_create(vf_handle *h) {
         VF_ALLOC(vd.w_state, (size_t)nsa * cfg->sdim); VF_ALLOC(vd.b_state, cfg->sdim);
         VF_ALLOC(vd.w_sa, (size_t)nsa * L[3]);
         if (h->flow) { VF_ALLOC(vd.w_flow, (size_t)h->c_top * 2 * kFlowWarps); VF_ALLOC(vd.b_flow, 2 * kFlowWarps); }
+        else if (h->dna) { VF_ALLOC(vd.w_flow, (size_t)h->c_top * kTaps); VF_ALLOC(vd.b_flow, kTaps); }
         else VF_ALLOC(vd.b_fc, kTaps * h->K);
         if (h->cond)
             for (int k = 0; k < 7; ++k) VF_ALLOC(vd.w_cond[k], (size_t)kTaps * nsa * 4 * L[k]);
@@ -1121,8 +1145,8 @@ static int cdna_create(vf_handle *h) {
     VF_ALLOC(h->sbias, BV * L[3]);
     if (h->cond)
         for (int k = 0; k < 7; ++k) VF_ALLOC(h->cond_bias[k], 2 * BV * kCondClasses * 4 * L[k]);
-    VF_ALLOC(h->fc_part, h->flow ? 0 : BV * h->fc.nsplit * kTaps * h->K);
-    VF_ALLOC(h->kern, h->flow ? 0 : BV * kTaps * h->K);
+    VF_ALLOC(h->fc_part, h->flow || h->dna ? 0 : BV * h->fc.nsplit * kTaps * h->K);
+    VF_ALLOC(h->kern, h->flow || h->dna ? 0 : BV * kTaps * h->K);
     VF_ALLOC(h->frames_all, BV * h->T * H * W * 3);
     VF_ALLOC(h->distrib_all, BV * h->T * H * W * ND);
     VF_ALLOC(h->states_all, BV * h->T * cfg->sdim);
@@ -1201,6 +1225,7 @@ int vf_create(const vf_config *cfg, vf_handle **out) {
     h->savp = cfg->arch == 1 || cfg->arch == 2;
     h->cond = cfg->arch == 2;
     h->flow = is_flow(*cfg);
+    h->dna = is_dna(*cfg);
     h->Hc = h->savp ? h->H / 2 : h->H; h->Wc = h->savp ? h->W / 2 : h->W;
     const int H = h->H, W = h->W;
     h->ntiles = ((H + kCompTile - 1) / kCompTile) * ((W + kCompTile - 1) / kCompTile);
@@ -1339,8 +1364,10 @@ int vf_load_weights(vf_handle *h, const float *blob_all, size_t n_floats) {
             if ((rc = dev_write(h, vd.ln_b[i], blob + b->offset, b->size() * sizeof(float)))) return rc;
         }
         const TensorDesc *d;
-        d = T("rgb/w");   if ((rc = dev_write(h, vd.w_rgb, blob + d->offset, d->size() * sizeof(float)))) return rc;
-        d = T("rgb/b");   if ((rc = dev_write(h, vd.b_rgb, blob + d->offset, d->size() * sizeof(float)))) return rc;
+        if (!h->dna) {      // (the DNA table has no scratch image)
+            d = T("rgb/w");   if ((rc = dev_write(h, vd.w_rgb, blob + d->offset, d->size() * sizeof(float)))) return rc;
+            d = T("rgb/b");   if ((rc = dev_write(h, vd.b_rgb, blob + d->offset, d->size() * sizeof(float)))) return rc;
+        }
         {   // mask head.  arch 2 keeps the PUBLISHED order of the compositing layers in the checkpoint - [four CDNA warps,
             // previous frame, first frame, scratch] - and the kernels' order on the device: [previous, scratch, first, warps]
             const TensorDesc *mw = T("masks/w"), *mb = T("masks/b");
@@ -1375,6 +1402,10 @@ int vf_load_weights(vf_handle *h, const float *blob_all, size_t n_floats) {
             const TensorDesc *fw = T("flow/w"), *fb = T("flow/b");
             if ((rc = dev_write(h, vd.w_flow, blob + fw->offset, fw->size() * sizeof(float)))) return rc;
             if ((rc = dev_write(h, vd.b_flow, blob + fb->offset, fb->size() * sizeof(float)))) return rc;
+        } else if (h->dna) {
+            const TensorDesc *dw = T("dna/w"), *db = T("dna/b");
+            if ((rc = dev_write(h, vd.w_flow, blob + dw->offset, dw->size() * sizeof(float)))) return rc;
+            if ((rc = dev_write(h, vd.b_flow, blob + db->offset, db->size() * sizeof(float)))) return rc;
         } else if (h->cond) {
             std::vector<float> bw((size_t)kTaps * h->K, 0.f);
             for (int tap = 0; tap < kTaps; ++tap)
@@ -1566,7 +1597,14 @@ struct LaunchSink {
     }
     int composite(const CompositeParams &p, int ntiles, int /*view*/, std::initializer_list<int>) {
         dim3 grid(ntiles, p.B);
-        if (p.w_flow) {         // appearance flow
+        if (p.w_flow && p.K == 1) {     // DNA: the per-pixel kernel head travels in the flow head's fields
+            switch (p.ND) {
+                case 1: hipLaunchKernelGGL(composite_dna_kernel<1>, grid, dim3(256), 0, st, p); break;
+                case 2: hipLaunchKernelGGL(composite_dna_kernel<2>, grid, dim3(256), 0, st, p); break;
+                case 3: hipLaunchKernelGGL(composite_dna_kernel<3>, grid, dim3(256), 0, st, p); break;
+                default: hipLaunchKernelGGL(composite_dna_kernel<4>, grid, dim3(256), 0, st, p); break;
+            }
+        } else if (p.w_flow) {         // appearance flow
             switch (p.ND) {
                 case 1: hipLaunchKernelGGL(composite_flow_kernel<1>, grid, dim3(256), 0, st, p); break;
                 case 2: hipLaunchKernelGGL(composite_flow_kernel<2>, grid, dim3(256), 0, st, p); break;
@@ -2058,9 +2096,10 @@ static int emit_rollout(vf_handle *h, int view, const BatchView &v, const BatchV
         // and its only consumer is the compositing at the end of the step: it is emitted here, behind lstm6, where
         // its ready-to-run items fill the slots that would otherwise draw transposed-conv items still waiting for
         // the second round of lstm6 tiles.
-        // (An appearance-flow engine has no kernels: neither item is emitted, and the top depends on its two inputs alone.)
+        // (An appearance-flow engine has no kernels: neither item is emitted, and the top depends on its two inputs alone.
+        // A DNA engine likewise: its kernels come from a head of the top itself.)
         int u_fin = -1, u_fc = -1;
-        if (produce && !h->flow) {
+        if (produce && !h->flow && !h->dna) {
             SegArg flat = h5n;      // same LayerNorm, viewed as [B][1][1][H8*W8*128]
             const ConvLayer &fc_l = Sink::fc_plan(h);
             p = params(fc_l, B, flat, nullptr);
@@ -2079,7 +2118,7 @@ static int emit_rollout(vf_handle *h, int view, const BatchView &v, const BatchV
             const int now[7] = {u_l1, u_l2, u_l3, u_l4, u_l5, u_l6, u_l7};
             for (int k = 0; k < 7; ++k) u_prev[k] = now[k];
         }
-        if (produce && !h->flow) {      // the (tiny) finalise step of the CDNA kernels: behind lstm7, by when the FC has long finished
+        if (produce && !h->flow && !h->dna) {      // the (tiny) finalise step of the CDNA kernels: behind lstm7, by when the FC has long finished
             FinParams fp;
             fp.partial = v.fc_part; fp.nsplit = h->fc.nsplit; fp.B = B; fp.K = h->K;
             fp.bias = vd.b_fc; fp.kern = v.kern;
@@ -2117,11 +2156,13 @@ static int emit_rollout(vf_handle *h, int view, const BatchView &v, const BatchV
             }
             cp.ln_inv_n = (float)(1.0 / ((double)H * W * h->c_top));
             cp.CF = h->c_top;
-            cp.w_rgb = vd.w_rgb; cp.b_rgb = vd.b_rgb; cp.w_mask = vd.w_mask; cp.b_mask = vd.b_mask;
+            if (!h->dna) { cp.w_rgb = vd.w_rgb; cp.b_rgb = vd.b_rgb; }
+            cp.w_mask = vd.w_mask; cp.b_mask = vd.b_mask;
             // Appearance flow: the warps gather from the WHOLE previous frame / distributions of the sample.  Both routes of the
             // top are released by this step's first conv (top_early), every tile of which waited for EVERY compositing tile of
             // the previous step (`last`, dep_on: all tiles of the sample), so the gathers find the frame complete.
-            if (h->flow) { cp.w_flow = vd.w_flow; cp.b_flow = vd.b_flow; }
+            // DNA: every tap lies inside the tile's halo, as for CDNA, so the CDNA dependency rules hold as they are.
+            if (h->flow || h->dna) { cp.w_flow = vd.w_flow; cp.b_flow = vd.b_flow; }
             else cp.kern = v.kern;
             cp.prev_frame = frame_in; cp.prev_frame_bstride = frame_bs;
             if (s < nc) {
@@ -2315,8 +2356,9 @@ extern "C" int vf_selftest_schedule(vf_handle *h, int32_t B, int32_t skip_shared
         if (P.first_ticket != ticket || P.n_items <= 0) return fail(VF_ERR_INVALID, "tickets are not contiguous");
         ticket += P.n_items;
         if (P.ndep < 0 || P.ndep > kMaxDeps) return fail(VF_ERR_INVALID, "bad dependency count");
-        if (h->flow && (P.type == PH_FC_PARTIAL || P.type == PH_CDNA_FIN))
-            return fail(VF_ERR_INVALID, "phase " + std::to_string(i) + ": a CDNA kernel item in an appearance-flow schedule");
+        if ((h->flow || h->dna) && (P.type == PH_FC_PARTIAL || P.type == PH_CDNA_FIN))
+            return fail(VF_ERR_INVALID, "phase " + std::to_string(i) + ": a CDNA kernel item in " +
+                                        (h->dna ? "a DNA schedule" : "an appearance-flow schedule"));
         for (int d = 0; d < P.ndep; ++d) {
             // a dependency must point at the counters of a phase with smaller tickets
             bool found = false;
@@ -2444,9 +2486,13 @@ extern "C" int vf_selftest_schedule(vf_handle *h, int32_t B, int32_t skip_shared
             ok = ok && in_allocs(h, c.out_sums, (size_t)P.B * c.ND * h->nblocks * 2 * 8);
             ok = ok && in_allocs(h, c.kern, (size_t)P.B * kTaps * c.K * 4);
             // an appearance-flow engine: the flow head instead of kernels, on the survey table's compositing only
-            ok = ok && (h->flow ? (c.w_flow && c.b_flow && !c.kern && !c.first_frame && c.K == kFlowWarps + 1 && c.CF == 32)
-                                : (!c.w_flow && !c.b_flow && c.kern));
-            ok = ok && in_allocs(h, c.w_flow, (size_t)32 * 2 * kFlowWarps * 4) && in_allocs(h, c.b_flow, (size_t)2 * kFlowWarps * 4);
+            // a DNA engine: the per-pixel kernel head in the same two fields, no rgb head, one transform
+            const size_t head_n = h->dna ? kTaps : 2 * kFlowWarps;
+            if (h->dna && !(c.w_flow && c.b_flow && !c.kern && !c.first_frame && !c.w_rgb && !c.b_rgb && c.K == 1 && c.CF == 32))
+                return fail(VF_ERR_INVALID, "phase " + std::to_string(i) + ": a compositing phase without the dna head in a DNA schedule");
+            ok = ok && (h->dna || (h->flow ? (c.w_flow && c.b_flow && !c.kern && !c.first_frame && c.K == kFlowWarps + 1 && c.CF == 32)
+                                           : (!c.w_flow && !c.b_flow && c.kern)));
+            ok = ok && in_allocs(h, c.w_flow, (size_t)32 * head_n * 4) && in_allocs(h, c.b_flow, head_n * 4);
             ok = ok && in_allocs(h, c.first_frame, hw * 3 * 4) && in_allocs(h, c.first_distrib, hw * c.ND * 4);
         } else if (P.type == PH_SA) {
             ok = ok && in_allocs(h, P.sa.sbias, (size_t)P.B * P.sa.n_out * 4) && in_allocs(h, P.sa.action, 4) &&
@@ -2604,8 +2650,9 @@ static bool shared_cache_hit(vf_handle *h, int cfg) {
 }
 
 template <int ND>
-static int launch_persistent_t(const Schedule &sc, bool flow, int grid, size_t lds, hipStream_t st) {
-    if (flow) hipLaunchKernelGGL((rollout_flow_kernel<ND>), dim3(grid), dim3(kConvThreads), lds, st, sc.phases, sc);
+static int launch_persistent_t(const Schedule &sc, int mode, int grid, size_t lds, hipStream_t st) {
+    if (mode == COMP_DNA) hipLaunchKernelGGL((rollout_dna_kernel<ND>), dim3(grid), dim3(kConvThreads), lds, st, sc.phases, sc);
+    else if (mode == COMP_FLOW) hipLaunchKernelGGL((rollout_flow_kernel<ND>), dim3(grid), dim3(kConvThreads), lds, st, sc.phases, sc);
     else hipLaunchKernelGGL((rollout_persistent_kernel<ND>), dim3(grid), dim3(kConvThreads), lds, st, sc.phases, sc);
     VF_HIP_CHECK(hipGetLastError());
     return VF_OK;
@@ -2711,11 +2758,12 @@ static int run_persistent(vf_handle *h, const float *d_actions, int B, const int
         e0 = h->ev_pool[h->ev_used]; e1 = h->ev_pool[h->ev_used + 1];
         VF_HIP_CHECK(hipEventRecord(e0, st));
     }
+    const int mode = h->dna ? COMP_DNA : (h->flow ? COMP_FLOW : COMP_CDNA);
     switch (h->ND) {
-        case 1: rc = launch_persistent_t<1>(sc, h->flow, grid, lds, st); break;
-        case 2: rc = launch_persistent_t<2>(sc, h->flow, grid, lds, st); break;
-        case 3: rc = launch_persistent_t<3>(sc, h->flow, grid, lds, st); break;
-        default: rc = launch_persistent_t<4>(sc, h->flow, grid, lds, st); break;
+        case 1: rc = launch_persistent_t<1>(sc, mode, grid, lds, st); break;
+        case 2: rc = launch_persistent_t<2>(sc, mode, grid, lds, st); break;
+        case 3: rc = launch_persistent_t<3>(sc, mode, grid, lds, st); break;
+        default: rc = launch_persistent_t<4>(sc, mode, grid, lds, st); break;
     }
     if (rc) return rc;
     if (h->profiling) {

@@ -35,9 +35,11 @@ __host__ __device__ inline size_t fused_top_lds_floats(int TH, int TW, int ND) {
 // FLOW (appearance-flow engines, vf_small_kernels.h): step 3 stages neither halo nor kernels - only the scale of the previous
 // distributions - and step 5 gathers the warps from the sample's whole previous frame in global memory.  The item was released
 // by the first conv of the step, every tile of which waited for every compose tile of the previous step: the frame is complete.
-template <int ND, bool FIRST, int K, class PT, class CT, bool FLOW = false>
+// MODE COMP_DNA (DNA engines): step 3 stages the halo as for CDNA but no kernel table; step 5 runs the per-pixel 5x5 kernels.
+template <int ND, bool FIRST, int K, class PT, class CT, int MODE = COMP_CDNA>
 __device__ __forceinline__ void fused_top_body(const PT &p, const CT &c, f32x16 (&acc)[1][4], const int bx,
                                                long long *red, float *smem, const int *goal) {
+    constexpr bool FLOW = MODE == COMP_FLOW, DNA = MODE == COMP_DNA;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int n = lane & 31, kh = lane >> 5;
     const int tiles_per_img = p.tilesY * p.tilesX;
@@ -166,14 +168,14 @@ __device__ __forceinline__ void fused_top_body(const PT &p, const CT &c, f32x16 
         }
     }
     [[maybe_unused]] float kv[(kTaps * K + 255) / 256];
-    if constexpr (!FLOW) {
+    if constexpr (MODE == COMP_CDNA) {
 #pragma unroll
         for (int j = 0; j < (kTaps * K + 255) / 256; ++j) {
             const int i = tid + 256 * j;
             kv[j] = i < kTaps * K ? c.kern[(long long)b * kTaps * K + i] : 0.f;
         }
-        halo_request(tid);
     }
+    if constexpr (!FLOW) halo_request(tid);
 #pragma unroll
     for (int j = 0; j < (ND + 3) / 4; ++j) {
         const int d = ((wave + 3) & 3) + 4 * j;
@@ -183,7 +185,7 @@ __device__ __forceinline__ void fused_top_body(const PT &p, const CT &c, f32x16 
             if (lane == 0) s_dscale[d] = sc;
         }
     }
-    if constexpr (!FLOW) {
+    if constexpr (MODE == COMP_CDNA) {
 #pragma unroll
         for (int j = 0; j < (kTaps * K + 255) / 256; ++j) {
             const int i = tid + 256 * j;
@@ -275,6 +277,10 @@ __device__ __forceinline__ void fused_top_body(const PT &p, const CT &c, f32x16 
             if (valid)
                 composite_pixel_values_flow<ND>(c, y, x, &s_enc[tid * kCompEncPad], mean, rstd, pf, pd, s_dscale, goal, cost,
                                                 of, od);
+        } else if constexpr (DNA) {
+            if (valid)
+                composite_pixel_values_dna<ND>(c, y, x, &s_enc[tid * kCompEncPad], mean, rstd, s_px, HW_, hy, hx, goal, cost,
+                                               of, od);
         } else if (valid)
             composite_pixel_values<ND, K, FIRST>(c, y, x, &s_enc[tid * kCompEncPad], mean, rstd, s_px, s_kern, HW_,
                                                  hy, hx, goal, cost, of, od);
@@ -341,7 +347,7 @@ __device__ __forceinline__ void fused_top_body(const PT &p, const CT &c, f32x16 
 
 // epilogue hook of conv_tile<4, fused_epi(ND, FIRST), 1>: the compositing parameters (a device address inside the
 // schedule) are read through the constant address space, the goal pixels from the launch's LDS control block
-template <int ND, bool FIRST, int K, bool FLOW, class PT>
+template <int ND, bool FIRST, int K, int MODE, class PT>
 __device__ __forceinline__ void convt_fused_epilogue(const PT &p, f32x16 (&acc)[1][4], int bx, long long *red, float *smem) {
     typedef const __attribute__((address_space(4))) CompositeParams CT;
     const unsigned long long a = reinterpret_cast<unsigned long long>(p.fuse_comp);
@@ -350,7 +356,7 @@ __device__ __forceinline__ void convt_fused_epilogue(const PT &p, f32x16 (&acc)[
     CT &c = *(CT *)(((unsigned long long)hi << 32) | lo);
     extern __shared__ __attribute__((aligned(16))) float smem_all[];
     const int *goal = reinterpret_cast<const int *>(smem_all) + kFusedCtlGoal + p.fuse_view * ND * 2;
-    fused_top_body<ND, FIRST, K, PT, CT, FLOW>(p, c, acc, bx, red, smem, goal);
+    fused_top_body<ND, FIRST, K, PT, CT, MODE>(p, c, acc, bx, red, smem, goal);
 }
 
 }  // namespace vf

@@ -224,7 +224,14 @@ template <int ND>
 static __device__ __noinline__ __attribute__((not_tail_called)) void composite_flow_tile_call(const CompositeParams *p, int tile, int b, int view) {
     extern __shared__ __attribute__((aligned(16))) float smem_all[];
     const int *goal = reinterpret_cast<const int *>(smem_all) + kCtlGoal + view * ND * 2;
-    composite_tile<ND, kFlowWarps + 1, false, const VF_CONST_AS CompositeParams, 32, true>(const_params(p), tile, b, goal, tile_lds());
+    composite_tile<ND, kFlowWarps + 1, false, const VF_CONST_AS CompositeParams, 32, COMP_FLOW>(const_params(p), tile, b, goal, tile_lds());
+}
+// the DNA compositing tile (vf_small_kernels.h; rollout_dna_kernel only)
+template <int ND>
+static __device__ __noinline__ __attribute__((not_tail_called)) void composite_dna_tile_call(const CompositeParams *p, int tile, int b, int view) {
+    extern __shared__ __attribute__((aligned(16))) float smem_all[];
+    const int *goal = reinterpret_cast<const int *>(smem_all) + kCtlGoal + view * ND * 2;
+    composite_tile<ND, 1, false, const VF_CONST_AS CompositeParams, 32, COMP_DNA>(const_params(p), tile, b, goal, tile_lds());
 }
 static __device__ __noinline__ __attribute__((not_tail_called)) void gates_raw_tile_call(const ConvParams *p, int bx, int by) {
     conv_lstm_gsplit2_tile<4, const VF_CONST_AS ConvParams, true>(const_params(p), bx, by, tile_lds());
@@ -274,9 +281,9 @@ static __device__ __noinline__ __attribute__((not_tail_called)) void small_item_
     }
 }
 
-// The scheduler loop, shared by the two kernels below.  FLOW picks the compositing bodies at compile time: the production
-// kernel carries no appearance-flow code and no run-time branch for it.
-template <int ND, bool FLOW>
+// The scheduler loop, shared by the three kernels below.  MODE (CompMode) picks the compositing bodies at compile time: the
+// production kernel carries no appearance-flow or DNA code and no run-time branch for them.
+template <int ND, int MODE>
 __device__ __forceinline__ void rollout_body(const PhaseDesc *__restrict__ phases, const Schedule sched) {
     extern __shared__ __attribute__((aligned(16))) float smem_all[];
     // all LDS in one dynamic array: the control block first, the tile workspace after it
@@ -459,13 +466,15 @@ __device__ __forceinline__ void rollout_body(const PhaseDesc *__restrict__ phase
                 // (K = 6: the compositing of arch 2 - four CDNA warps + previous + first frame + scratch - always with
                 // the first-frame layer; K = 10 otherwise)
                 case PH_TOP_FUSED:
-                    if constexpr (FLOW) conv_tile_call<4, fused_epi_flow(ND), 1>(&P.conv, bx, 0, 0);
+                    if constexpr (MODE == COMP_FLOW) conv_tile_call<4, fused_epi_flow(ND), 1>(&P.conv, bx, 0, 0);
+                    else if constexpr (MODE == COMP_DNA) conv_tile_call<4, fused_epi_dna(ND), 1>(&P.conv, bx, 0, 0);
                     else if (P.comp.K == 6) conv_tile_call<4, fused_epi(ND, true, true), 1>(&P.conv, bx, 0, 0);
                     else if (P.comp.first_frame) conv_tile_call<4, fused_epi(ND, true), 1>(&P.conv, bx, 0, 0);
                     else conv_tile_call<4, fused_epi(ND, false), 1>(&P.conv, bx, 0, 0);
                     break;
                 case PH_COMPOSITE:
-                    if constexpr (FLOW) composite_flow_tile_call<ND>(&P.comp, local % P.gx, b0, P.view);
+                    if constexpr (MODE == COMP_FLOW) composite_flow_tile_call<ND>(&P.comp, local % P.gx, b0, P.view);
+                    else if constexpr (MODE == COMP_DNA) composite_dna_tile_call<ND>(&P.comp, local % P.gx, b0, P.view);
                     else if (P.comp.K == 6) composite_tile_call<ND, true, 6>(&P.comp, local % P.gx, b0, P.view);
                     else if (P.comp.first_frame) composite_tile_call<ND, true, 10>(&P.comp, local % P.gx, b0, P.view);
                     else if (P.comp.CF > 32) composite_tile_call<ND, false, 10, 64>(&P.comp, local % P.gx, b0, P.view);  // (public decoder)
@@ -547,7 +556,7 @@ __device__ __forceinline__ void rollout_body(const PhaseDesc *__restrict__ phase
 template <int ND>
 VF_GLOBAL VF_LAUNCH_BOUNDS(kConvThreads, 2) void rollout_persistent_kernel(
     const PhaseDesc *__restrict__ phases, const Schedule sched) {
-    rollout_body<ND, false>(phases, sched);
+    rollout_body<ND, COMP_CDNA>(phases, sched);
 }
 
 // The rollout of an appearance-flow engine (cdna_arch.py transformation='flow', vf_config arch 0 / layer_spec 2): the same
@@ -555,7 +564,15 @@ VF_GLOBAL VF_LAUNCH_BOUNDS(kConvThreads, 2) void rollout_persistent_kernel(
 template <int ND>
 VF_GLOBAL VF_LAUNCH_BOUNDS(kConvThreads, 2) void rollout_flow_kernel(
     const PhaseDesc *__restrict__ phases, const Schedule sched) {
-    rollout_body<ND, true>(phases, sched);
+    rollout_body<ND, COMP_FLOW>(phases, sched);
+}
+
+// The rollout of a DNA engine (dna_arch.py, vf_config arch 0 / layer_spec 3): the same schedule and tiles, the compositing
+// of the fused top and of PH_COMPOSITE with a 5x5 kernel per pixel from a 1x1 head instead of the sample's CDNA kernels.
+template <int ND>
+VF_GLOBAL VF_LAUNCH_BOUNDS(kConvThreads, 2) void rollout_dna_kernel(
+    const PhaseDesc *__restrict__ phases, const Schedule sched) {
+    rollout_body<ND, COMP_DNA>(phases, sched);
 }
 
 }  // namespace vf

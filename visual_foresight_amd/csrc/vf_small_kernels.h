@@ -232,7 +232,8 @@ struct CompositeParams {
     int CF;                             // feature channels of enc6: 0 / 32, or 64 (the public CDNA decoder table, cdna_arch.py
                                         // decoder='public': the stand-alone compositing tile only, two 32-channel rounds)
     const float *w_flow, *b_flow;       // appearance-flow engines (cdna_arch.py transformation='flow'): the 1x1 flow head
-                                        // [32][2 * kFlowWarps], [2 * kFlowWarps]; null = CDNA kernels (`kern` is null there)
+                                        // [32][2 * kFlowWarps], [2 * kFlowWarps]; null = CDNA kernels (`kern` is null there).
+                                        // DNA engines (dna_arch.py, K == 1) pass their 1x1 kernel head here: [32][kTaps], [kTaps]
 };
 
 // LDS floats needed by composite_tile<ND, K>
@@ -542,11 +543,125 @@ __device__ __forceinline__ void composite_pixel_values_flow(const PT &p, const i
     composite_values_flow<ND>(p, y, x, feat, mean, rstd, o_rgb, o_m, pf, pd, dscale, goal, cost, of, od);
 }
 
+// ------------------------------------------------------------------------------------------
+// DNA compositing (dna_arch.py; arXiv:1605.07157 section 3.1).  A 1x1 head predicts 25 values per PIXEL;
+// relu-shifted and normalised they are that pixel's own 5x5 kernel over the previous frame and distributions - where the
+// CDNA path mixes the sample's nine kernels by its masks.  One transform, two mask channels (previous frame | transformed),
+// no scratch image.  The halo tile in LDS is the CDNA path's; the kernel table is not staged.  The head reaches the device
+// through CompositeParams::w_flow / b_flow ([32][kTaps], [kTaps]) with K == 1.
+//
+// The two mask sums and the 25 tap sums of one pixel: each its own fma chain over the channels ascending from the bias, on
+// f_c = relu(LN9(enc6)_c), as composite_heads builds its sums (27 live accumulators, one pass over the LDS feature row).
+template <class PT>
+__device__ __forceinline__ void composite_dna_heads(const PT &p, const float *feat, const float mean, const float rstd,
+                                                    float (&o_m)[2], float (&o_a)[kTaps]) {
+    typedef const __attribute__((address_space(4))) float cfloat;
+    auto as_const = [](const float *q) { return (cfloat *)(unsigned long long)q; };
+    cfloat *gam_ = as_const(p.gamma), *bet_ = as_const(p.beta);
+    cfloat *wmask_ = as_const(p.w_mask), *bmask_ = as_const(p.b_mask);
+    cfloat *wdna_ = as_const(p.w_flow), *bdna_ = as_const(p.b_flow);
+#pragma unroll
+    for (int j = 0; j < 2; ++j) o_m[j] = bmask_[j];
+#pragma unroll
+    for (int t = 0; t < kTaps; ++t) o_a[t] = bdna_[t];
+    const f32x4 *src = reinterpret_cast<const f32x4 *>(feat);
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+        const f32x4 raw = src[q];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int c = q * 4 + e;
+            const float f = fmaxf(fmaf((raw[e] - mean) * rstd, gam_[c], bet_[c]), 0.f);
+#pragma unroll
+            for (int j = 0; j < 2; ++j) o_m[j] = fmaf(f, wmask_[c * 2 + j], o_m[j]);
+#pragma unroll
+            for (int t = 0; t < kTaps; ++t) o_a[t] = fmaf(f, wdna_[c * kTaps + t], o_a[t]);
+        }
+    }
+}
+
+// One output pixel (y, x) behind its head outputs: the two-way softmax (as composite_values: max, __expf, 1 / den), the
+// pixel's kernel v_t = relu(a_t - shift) + shift, s = sum_t v_t (t ascending), g = mask_1 / s, ke_t = g * v_t, then
+// of_c = mask_0 * prev_c and of_c = fma(ke_t, tap_t, of_c) with t ascending over the halo tile of composite_values
+// (zero outside the image, fed-back distributions scaled by 1 / mass at the halo load); the distributions likewise; the
+// cost terms of the CDNA path.
+template <int ND, class PT>
+__device__ __forceinline__ void composite_values_dna(const PT &p, const int y, const int x, float (&o_m)[2],
+                                                     float (&o_a)[kTaps], const float *s_px, const int halo_w, const int hy,
+                                                     const int hx, const int *goal, double (&cost)[2 * ND], float (&of)[3],
+                                                     float (&od)[ND]) {
+    constexpr int PS = comp_px_stride(ND);
+    auto load_px = [&](const int sp, float (&fr)[3], float (&di)[ND]) {
+        const f32x4 a = *reinterpret_cast<const f32x4 *>(s_px + sp * PS);
+        fr[0] = a[0]; fr[1] = a[1]; fr[2] = a[2]; di[0] = a[3];
+        if constexpr (ND > 1) {
+            const f32x4 c2 = *reinterpret_cast<const f32x4 *>(s_px + sp * PS + 4);
+#pragma unroll
+            for (int d = 1; d < ND; ++d) di[d] = c2[d - 1];
+        }
+    };
+    const float mx = fmaxf(o_m[0], o_m[1]);
+    float den = 0.f;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) { o_m[j] = __expf(o_m[j] - mx); den += o_m[j]; }
+    const float inv = 1.0f / den;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) o_m[j] *= inv;
+
+    float s = 0.f;
+#pragma unroll
+    for (int t = 0; t < kTaps; ++t) { o_a[t] = fmaxf(o_a[t] - kReluShift, 0.f) + kReluShift; s += o_a[t]; }
+    const float g = o_m[1] / s;
+    {
+        float fr[3], di[ND];
+        load_px((hy + 2) * halo_w + (hx + 2), fr, di);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) of[c] = o_m[0] * fr[c];
+#pragma unroll
+        for (int d = 0; d < ND; ++d) od[d] = o_m[0] * di[d];
+    }
+#pragma unroll
+    for (int dy = 0; dy < kDnaKern; ++dy) {
+#pragma unroll
+        for (int dx = 0; dx < kDnaKern; ++dx) {
+            const float ke = g * o_a[dy * kDnaKern + dx];
+            float fr[3], di[ND];
+            load_px((hy + dy) * halo_w + (hx + dx), fr, di);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) of[c] = fmaf(ke, fr[c], of[c]);
+#pragma unroll
+            for (int d = 0; d < ND; ++d) od[d] = fmaf(ke, di[d], od[d]);
+        }
+    }
+#pragma unroll
+    for (int d = 0; d < ND; ++d) {
+        const float ry = (float)(y - goal[2 * d]), rx = (float)(x - goal[2 * d + 1]);
+        const float dist = sqrtf(fmaf(ry, ry, rx * rx));
+        cost[2 * d] = (double)od[d];
+        cost[2 * d + 1] = (double)od[d] * (double)dist;
+    }
+}
+// ... from the pixel's LDS feature row (the stand-alone tile and the fused top call this: same expressions, same bits)
+template <int ND, class PT>
+__device__ __forceinline__ void composite_pixel_values_dna(const PT &p, const int y, const int x, const float *feat,
+                                                           const float mean, const float rstd, const float *s_px,
+                                                           const int halo_w, const int hy, const int hx, const int *goal,
+                                                           double (&cost)[2 * ND], float (&of)[3], float (&od)[ND]) {
+    float o_m[2], o_a[kTaps];
+    composite_dna_heads(p, feat, mean, rstd, o_m, o_a);
+    composite_values_dna<ND>(p, y, x, o_m, o_a, s_px, halo_w, hy, hx, goal, cost, of, od);
+}
+
+// compositing variants of composite_tile / fused_top_body / rollout_body (compile-time: the production kernel carries
+// neither appearance-flow nor DNA code and no run-time branch for them)
+enum CompMode { COMP_CDNA = 0, COMP_FLOW = 1, COMP_DNA = 2 };
+
 // one 16x16 pixel tile of one sample.  FIRST (arch 1, savp_arch.py): the first context frame is one more compositing
 // layer - a template parameter, because a run-time branch around the mask bookkeeping costs the CDNA path 3.5 us per
 // tile (measured).
-// FLOW (appearance flow, above): no halo tile and no kernel table are staged - the warps gather from global memory.
-template <int ND, int K, bool FIRST, class PT, int CFT = 32, bool FLOW = false>
+// MODE COMP_FLOW (appearance flow, above): no halo tile and no kernel table are staged - the warps gather from global memory.
+// MODE COMP_DNA (above): the halo tile is staged, the kernel table is not.
+template <int ND, int K, bool FIRST, class PT, int CFT = 32, int MODE = COMP_CDNA>
 __device__ __forceinline__ void composite_tile(const PT &p, const int tile, const int b, const int *goal,
                                                float *smem) {
     constexpr int TS = kCompTile, HS = TS + 4;
@@ -601,7 +716,8 @@ __device__ __forceinline__ void composite_tile(const PT &p, const int tile, cons
             if (lane_ == 0) s_dscale[d] = sc;
         }
     }
-    if constexpr (!FLOW)
+    constexpr bool FLOW = MODE == COMP_FLOW, DNA = MODE == COMP_DNA;
+    if constexpr (MODE == COMP_CDNA)
         for (int i = tid; i < kTaps * K; i += 256) s_kern[(i / K) * kCompKernPad + i % K] = p.kern[(long long)b * kTaps * K + i];
     __syncthreads();
 
@@ -637,6 +753,20 @@ __device__ __forceinline__ void composite_tile(const PT &p, const int tile, cons
             float of[3], od[ND];
             composite_pixel_values_flow<ND>(p, y, x, &s_enc[tid * kCompEncPad], s_ln[0], s_ln[1], pf, pd, s_dscale, goal,
                                             cost, of, od);
+            const long long o = (long long)y * p.W + x;
+            float *fo = p.out_frame + (long long)b * p.out_frame_bstride + o * 3;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) fo[c] = of[c];
+            float *dout = p.out_distrib + (long long)b * p.out_distrib_bstride + o * ND;
+#pragma unroll
+            for (int d = 0; d < ND; ++d) dout[d] = od[d];
+        }
+    } else if constexpr (DNA) {
+        static_assert(!DNA || (CF == 32 && K == 1 && !FIRST), "the dna table: survey decoder, one transform");
+        if (valid) {
+            float of[3], od[ND];
+            composite_pixel_values_dna<ND>(p, y, x, &s_enc[tid * kCompEncPad], s_ln[0], s_ln[1], s_px, HS, ly, lx, goal,
+                                           cost, of, od);
             const long long o = (long long)y * p.W + x;
             float *fo = p.out_frame + (long long)b * p.out_frame_bstride + o * 3;
 #pragma unroll
@@ -701,7 +831,14 @@ VF_GLOBAL VF_LAUNCH_BOUNDS(256) void composite_kernel(const CompositeParams p) {
 template <int ND>
 VF_GLOBAL VF_LAUNCH_BOUNDS(256) void composite_flow_kernel(const CompositeParams p) {
     __shared__ __attribute__((aligned(16))) float smem[composite_lds_floats<ND, kFlowWarps + 1>()];
-    composite_tile<ND, kFlowWarps + 1, false, CompositeParams, 32, true>(p, blockIdx.x, blockIdx.y, &p.goal[0][0], smem);
+    composite_tile<ND, kFlowWarps + 1, false, CompositeParams, 32, COMP_FLOW>(p, blockIdx.x, blockIdx.y, &p.goal[0][0], smem);
+}
+
+// the per-layer launch of the DNA compositing
+template <int ND>
+VF_GLOBAL VF_LAUNCH_BOUNDS(256) void composite_dna_kernel(const CompositeParams p) {
+    __shared__ __attribute__((aligned(16))) float smem[composite_lds_floats<ND, 1>()];
+    composite_tile<ND, 1, false, CompositeParams, 32, COMP_DNA>(p, blockIdx.x, blockIdx.y, &p.goal[0][0], smem);
 }
 
 // ------------------------------------------------------------------------------------------

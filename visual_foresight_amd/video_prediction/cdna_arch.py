@@ -63,6 +63,9 @@ and the arithmetic is ``top = fma(fx, b - a, a)``, ``bot = fma(fx, d - c, c)``, 
 ``1 / sum`` scale of a fed-back distribution is applied to each tap before the interpolation.  Accumulation order: previous
 frame, scratch, then the warps with ``k`` ascending; head sums run over the channels ascending from the bias.  Exact fp32
 only, ``'survey'`` decoder only.
+
+DNA (a 5x5 kernel per pixel from a 1x1 head; ``vf_config`` arch 0, layer_spec 3) has its own configuration class and
+manifest tag: ``dna_arch.py`` (``DnaConfig``).  ``CdnaConfig(transformation='dna')`` stays refused.
 """
 import json
 import os
@@ -286,6 +289,9 @@ class CdnaWeights(object):
         elif arch == 'savp3':
             from visual_foresight_amd.video_prediction.savp3_arch import Savp3Config
             file_cfg = Savp3Config(**manifest['config'])
+        elif arch == 'dna':
+            from visual_foresight_amd.video_prediction.dna_arch import DnaConfig
+            file_cfg = DnaConfig(**manifest['config'])
         else:
             raise ValueError('unknown architecture %r in %s' % (arch, model_dir))
         if cfg is not None and cfg.arch != arch:

@@ -73,6 +73,9 @@ def import_named_arrays(arrays, cfg, log=None):
     if getattr(cfg, 'arch_id', 0) != 0:
         raise ValueError("only arch 'cdna' checkpoints can be imported (no TensorFlow name table for %s)"
                          % type(cfg).__name__)
+    if getattr(cfg, 'transformation', 'cdna') == 'dna':
+        raise ValueError("only transformation 'cdna' checkpoints can be imported: no TensorFlow name table exists for the "
+                         "DNA head (transformation 'dna', tensors dna/w, dna/b)")
     if getattr(cfg, 'transformation', 'cdna') != 'cdna':
         raise ValueError("only transformation 'cdna' checkpoints can be imported: no TensorFlow name table exists for the "
                          "appearance-flow head (transformation %r, tensors flow/w, flow/b)" % (cfg.transformation,))

@@ -47,11 +47,12 @@ from visual_foresight_amd.video_prediction.sharding import dist_info as _dist_in
 
 
 def transformation_of(hparams):
-    """The compositing table a predictor hyper-parameter dictionary selects: ``'transformation'``: ``'cdna'`` (default) or
-    ``'flow'``, the appearance-flow compositing of ``cdna_arch.py``.  The reference's legacy predictor configurations name it
-    as ``'model': 'appflow'`` (``experiments/sawyer/*/conf.py``: "CDNA, DNA, or STP"); that key selects flow when
+    """The compositing table a predictor hyper-parameter dictionary selects: ``'transformation'``: ``'cdna'`` (default),
+    ``'flow'``, the appearance-flow compositing of ``cdna_arch.py``, or ``'dna'``, the per-pixel kernels of ``dna_arch.py``.
+    The reference's legacy predictor configurations name it as ``'model': 'appflow'`` (``experiments/sawyer/*/conf.py``:
+    "CDNA, DNA, or STP"); that key selects flow - and ``'model': 'DNA'``, in any letter case, dna - when
     ``'transformation'`` itself is absent, and every other value of ``'model'`` is left to its other readers."""
-    legacy = 'flow' if str(hparams.get('model', '')).lower() == 'appflow' else 'cdna'
+    legacy = {'appflow': 'flow', 'dna': 'dna'}.get(str(hparams.get('model', '')).lower(), 'cdna')
     return str(hparams.get('transformation', legacy))
 
 
@@ -89,7 +90,11 @@ class HipVPredEvaluation(object):
         if transformation != 'cdna':
             if self.arch != 'cdna':
                 raise ValueError("transformation %r needs arch 'cdna', got %r" % (transformation, self.arch))
-            extra = dict(extra, transformation=transformation)
+            if transformation == 'dna':         # its own configuration class and manifest tag (dna_arch.py)
+                from visual_foresight_amd.video_prediction.dna_arch import DnaConfig
+                cfg_cls = DnaConfig
+            else:
+                extra = dict(extra, transformation=transformation)
         self.cfg = cfg_cls(height=hp.get('image_height', 64), width=hp.get('image_width', 64),
                            adim=hp.get('adim', 4), sdim=hp.get('sdim', 5),
                            ndesig=hp.get('designated_pixel_count', 1), n_context=self.n_context,
