@@ -58,7 +58,11 @@ typedef enum vf_status {
 typedef struct vf_config {
     int32_t height, width;      /* multiples of 8 */
     int32_t adim, sdim;
-    int32_t ndesig;             /* designated pixels per view (1..4) */
+    int32_t ndesig;             /* designated pixels per view (0..4).  0 = a FRAMES-ONLY engine (arch 0 - 2; arch 3 refuses
+                                 * it): the same frames and states, bit for bit, and no pixel distribution anywhere - none
+                                 * allocated, staged, warped, summed, scored or exported (the reference's predictor conf key
+                                 * no_pix_distrib, video_prediction/setup_predictor.py:110-114).  The weights do not depend
+                                 * on ndesig.  See "Frames-only handles" below for what the entry points then expect. */
     int32_t n_context;          /* context frames (>= 1) */
     int32_t sequence_length;    /* n_context + T */
     int32_t num_masks;          /* CDNA kernel slots K (masks = K + 1): 10 for arch 0 / 1; 6 for arch 2 (four kernels in
@@ -117,6 +121,22 @@ typedef struct vf_handle vf_handle;
 int vf_abi_version(void);
 const char *vf_last_error(void);
 
+/* Frames-only handles (vf_config.ndesig == 0).  Every argument that carries or receives a designated-pixel quantity
+ * must be NULL; a violation returns VF_ERR_INVALID with a vf_last_error() message that says "frames-only" and launches
+ * nothing, and the handle stays usable:
+ *   vf_set_context      d_ctx_distrib must be NULL
+ *   vf_rollout          goal_pix, task_weights, d_scores, d_scores_per_task must be NULL; nothing is written for them
+ *                       and no score reduction is launched
+ *   vf_export           d_distrib must be NULL (frames and states as usual)
+ *   vf_render_plans     d_distrib_u8 must be NULL (frames as usual; d_lut may be NULL)
+ *   vf_ensemble_scores  refuses such members
+ * vf_goal_image_scores, vf_scorer_scores, vf_debug_lstm_layer, vf_device_status, vf_register and the setters work
+ * unchanged; an abandoned launch still turns the goal-image and scorer outputs into NaN.  Call sequence:
+ *   vf_create(cfg with ndesig 0) - vf_load_weights - vf_set_context(h, frames, states, actions, NULL, st) -
+ *   vf_rollout(h, d_actions, B, NULL, 0.f, NULL, NULL, NULL, st) - vf_goal_image_scores / vf_scorer_scores /
+ *   vf_export(h, first, count, d_frames, NULL, d_states, st) / vf_render_plans(h, d_seq, K, NULL, d_frames_u8, NULL, st).
+ * vf_create of such a config allocates no distribution tensor, no context-distribution buffer and no block-sum buffer. */
+
 /* Number of float32 values of ONE view's weights for `cfg` (the canonical tensor table of
  * visual_foresight_amd/video_prediction/cdna_arch.py, concatenated in table order);
  * vf_load_weights expects ncam such blobs back to back. */
@@ -138,7 +158,8 @@ int vf_load_weights(vf_handle *h, const float *host_blob, size_t n_floats);
 /* Install the planning context (device pointers).  Replaces get_context(),
  * visual_mpc/video_prediction/pred_util.py:4-13 (last n_context frames, uint8 -> float/255) and
  * the batch-1 placeholders tiled per tower, setup_predictor.py:40-44: the context is kept once
- * and broadcast to every sample by the kernels, never materialised per sample. */
+ * and broadcast to every sample by the kernels, never materialised per sample.  A frames-only handle (ndesig 0) wants
+ * d_ctx_distrib == NULL and refuses anything else. */
 int vf_set_context(vf_handle *h, const uint8_t *d_frames, const float *d_states,
                    const float *d_ctx_actions, const float *d_ctx_distrib, void *stream);
 
@@ -155,7 +176,9 @@ int vf_set_context(vf_handle *h, const uint8_t *d_frames, const float *d_states,
  * the handle until the next vf_rollout (see vf_export).  If a tile of the launch gave up
  * waiting for its producers (see vf_device_status) every score of this and of later rollouts
  * is NaN until the status has been read, and the predictions vf_export would copy out are
- * undefined (the launch was abandoned): check the scores or vf_device_status first. */
+ * undefined (the launch was abandoned): check the scores or vf_device_status first.
+ * Frames-only handles (ndesig 0): goal_pix, task_weights, d_scores and d_scores_per_task must all be NULL, nothing is
+ * reduced or written for them; read vf_device_status, or the NaN of vf_goal_image_scores / vf_scorer_scores. */
 int vf_rollout(vf_handle *h, const float *d_actions, int32_t B, const int32_t *goal_pix,
                float finalweight, const float *task_weights, double *d_scores,
                double *d_scores_per_task, void *stream);
@@ -174,7 +197,7 @@ int vf_rollout(vf_handle *h, const float *d_actions, int32_t B, const int32_t *g
  * Drive every member from ONE stream, one rollout after the other, and score on that stream: two persistent rollouts
  * running at the same time can starve each other, their tiles give up waiting and every score becomes NaN.
  * Returns VF_ERR_INVALID (nothing launched) for a NULL / empty / too long member list, differing configs, a member
- * that has not rolled, differing B or differing goal pixels. */
+ * that has not rolled, differing B or differing goal pixels, or a frames-only member (ndesig 0: it keeps no sums). */
 int vf_ensemble_scores(vf_handle *const *members, int32_t n_members, float lambda_variance, float finalweight,
                        const float *task_weights, double *d_scores, double *d_scores_per_task,
                        double *d_cost_per_step, void *stream);
@@ -207,8 +230,8 @@ int vf_goal_image_scores(vf_handle *h, const float *d_goal, int32_t steps_mode, 
  *       mx = max over the plane of p;  q = p / (mx + 1e-6f)  (float32 add, IEEE float32 division);
  *       pixel = d_lut[min((int)(q * 256.0f), 255)]                                                       (:114-115)
  * Enqueues at most two kernels on `stream`, allocates nothing, never synchronises.  Returns VF_ERR_INVALID (nothing
- * launched) for a NULL handle / d_seq, both outputs NULL, d_distrib_u8 without d_lut, K < 1 or K > max_batch, or a
- * handle that has not rolled. */
+ * launched) for a NULL handle / d_seq, both outputs NULL, d_distrib_u8 without d_lut, K < 1 or K > max_batch, a
+ * handle that has not rolled, or d_distrib_u8 on a frames-only handle (ndesig 0). */
 int vf_render_plans(vf_handle *h, const int32_t *d_seq, int32_t K, const uint8_t *d_lut, uint8_t *d_frames_u8,
                     uint8_t *d_distrib_u8, void *stream);
 
@@ -337,7 +360,7 @@ int vf_invmodel_infer(vf_invmodel *m, const float *d_start, const float *d_goal,
 /* Copy the predictions of the last vf_rollout out in the reference's layout (camera axis,
  * normalised distributions).  Any destination may be NULL.  first/count select a range of rolled
  * sequences.  Replaces the gen_images/gen_distrib/gen_states fetch of
- * setup_predictor.py:155-200. */
+ * setup_predictor.py:155-200.  A frames-only handle (ndesig 0) wants d_distrib == NULL and refuses anything else. */
 int vf_export(vf_handle *h, int32_t first, int32_t count, float *d_frames, float *d_distrib,
               float *d_states, void *stream);
 

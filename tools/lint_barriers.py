@@ -93,7 +93,9 @@ def scheduler_barrier_is_guarded(lines):
     if func:
         spans.append((func, start, len(lines)))
     for name, a, b in spans:
-        if not name.startswith('_ZN2vf25rollout_persistent_kernel'):
+        # (the frames-only rollouts run the same scheduler loop under names of their own)
+        if not name.startswith(('_ZN2vf25rollout_persistent_kernel', '_ZN2vf21rollout_frames_kernel',
+                                '_ZN2vf26rollout_flow_frames_kernel', '_ZN2vf25rollout_dna_frames_kernel')):
             continue
         marks = [k for k in range(a, b) if SCHED_MARKER in lines[k]]
         ok = len(marks) == 1 and 's_waitcnt' in lines[marks[0]] and 'lgkmcnt(0)' in lines[marks[0]]

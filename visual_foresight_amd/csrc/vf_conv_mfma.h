@@ -112,10 +112,20 @@ enum Epilogue {
                               // + 16 + 1 for the DNA compositing (fused_epi_dna: the first-frame bit means DNA behind + 16)
     EPI_CONV_PAIR = 30,       // a conv whose whole-image tiles feed a 1x1 conv in the same item (conv_pair_epilogue: enc2 ->
                               // enc3, the 8 x 8 bottleneck; G = 2: both 32-channel groups of the first conv in one workgroup)
-    EPI_RAW = 31              // acc + bias, nothing else (arch 3: instance norm needs the whole image's statistics first; the
+    EPI_RAW = 31,             // acc + bias, nothing else (arch 3: instance norm needs the whole image's statistics first; the
                               // element-wise items of vf_savp3.h normalise)
+    EPI_CONVT_FUSED_FRAMES = 32   // the fused top of a frames-only engine (no designated pixel): + 0 CDNA,
+                              // + 1 with the first-frame layer (arch 1), + 2 the six-kernel compositing of arch 2,
+                              // + 3 appearance flow, + 4 DNA (fused_epi_frames)
 };
-__host__ __device__ constexpr bool is_top_fused(int epi) { return epi >= EPI_CONVT_FUSED && epi < EPI_CONV_PAIR; }
+__host__ __device__ constexpr bool is_top_fused_frames(int epi) { return epi >= EPI_CONVT_FUSED_FRAMES && epi < EPI_CONVT_FUSED_FRAMES + 5; }
+__host__ __device__ constexpr bool is_top_fused(int epi) {
+    return (epi >= EPI_CONVT_FUSED && epi < EPI_CONV_PAIR) || is_top_fused_frames(epi);
+}
+// frames-only fused epilogue of compositing mode `mode` (CompMode of vf_small_kernels.h: 0 CDNA, 1 flow, 2 DNA)
+__host__ __device__ constexpr int fused_epi_frames(int mode, bool first = false, bool k6 = false) {
+    return EPI_CONVT_FUSED_FRAMES + (mode == 1 ? 3 : (mode == 2 ? 4 : (k6 ? 2 : (first ? 1 : 0))));
+}
 __host__ __device__ constexpr int fused_epi(int nd, bool first, bool k6 = false) {
     return EPI_CONVT_FUSED + 2 * (nd - 1) + (first ? 1 : 0) + (k6 ? 8 : 0);
 }
@@ -1865,6 +1875,11 @@ __device__ __forceinline__ void conv_tile(const PT &p, const int bx_, const int 
     // (the 32-row tile: wave w = gate w of its one row block - the gate-split exchange with one row block, and with it the
     // vectorised cell update: 16-byte loads and stores instead of 48 scalar ones per lane)
     if constexpr (GSPLIT || ROW32) lstm_gsplit_epilogue<MR>(p, acc, bx, by, smem);
+    else if constexpr (is_top_fused_frames(EPI))
+        // <ND = 0, first-frame layer, kernels K, CompMode>
+        convt_fused_epilogue<0, EPI - EPI_CONVT_FUSED_FRAMES == 1 || EPI - EPI_CONVT_FUSED_FRAMES == 2,
+                             EPI - EPI_CONVT_FUSED_FRAMES == 2 ? 6 : (EPI - EPI_CONVT_FUSED_FRAMES == 4 ? 1 : 10),
+                             EPI - EPI_CONVT_FUSED_FRAMES >= 3 ? EPI - EPI_CONVT_FUSED_FRAMES - 2 : 0>(p, acc, bx, red, smem);
     else if constexpr (is_top_fused(EPI))
         // (behind + 16 the low bit selects DNA, not the first-frame layer; modes: CompMode of vf_small_kernels.h)
         convt_fused_epilogue<((EPI - EPI_CONVT_FUSED) & 7) / 2 + 1, (EPI - EPI_CONVT_FUSED) < 16 && ((EPI - EPI_CONVT_FUSED) & 1) != 0,

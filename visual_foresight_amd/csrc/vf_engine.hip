@@ -674,7 +674,9 @@ static int validate(const vf_config *c) {
     if (!c) return fail(VF_ERR_INVALID, "null config");
     if (c->height <= 0 || c->width <= 0 || c->height % 8 || c->width % 8)
         return fail(VF_ERR_INVALID, "height/width must be positive multiples of 8");
-    if (c->ndesig < 1 || c->ndesig > kMaxDesig) return fail(VF_ERR_INVALID, "ndesig must be 1..4");
+    if (c->ndesig < 0 || c->ndesig > kMaxDesig) return fail(VF_ERR_INVALID, "ndesig must be 0..4 (0: a frames-only engine)");
+    if (c->ndesig == 0 && c->arch == 3)
+        return fail(VF_ERR_INVALID, "arch 3 has no frames-only mode: ndesig must be 1..4 (frames-only engines are arch 0 - 2)");
     if (c->n_context < 1 || c->sequence_length <= c->n_context)
         return fail(VF_ERR_INVALID, "need n_context >= 1 and sequence_length > n_context");
     if (c->adim < 1 || c->sdim < 1 || c->adim + c->sdim > 32)
@@ -808,6 +810,9 @@ static int configure_kernels(vf_handle *h) {
     if ((rc = allow_lds(&rollout_dna_kernel<2>, np))) return rc;
     if ((rc = allow_lds(&rollout_dna_kernel<3>, np))) return rc;
     if ((rc = allow_lds(&rollout_dna_kernel<4>, np))) return rc;
+    if ((rc = allow_lds(&rollout_frames_kernel, np))) return rc;
+    if ((rc = allow_lds(&rollout_flow_frames_kernel, np))) return rc;
+    if ((rc = allow_lds(&rollout_dna_frames_kernel, np))) return rc;
     return VF_OK;
 }
 
@@ -1111,10 +1116,12 @@ static int cdna_create(vf_handle *h) {
             for (int k = 0; k < 7; ++k) VF_ALLOC(vd.w_cond[k], (size_t)kTaps * nsa * 4 * L[k]);
     }
     VF_ALLOC(h->ctx_frames_all, (size_t)NV * nc * H * W * 3);
-    VF_ALLOC(h->ctx_distrib_all, (size_t)NV * nc * H * W * ND);
+    // (a frames-only engine, ndesig 0: no context distributions, no predicted distributions, no block sums - the pointers stay
+    // null and nothing on the device reads them)
+    if (ND > 0) VF_ALLOC(h->ctx_distrib_all, (size_t)NV * nc * H * W * ND);
     for (int v = 0; v < NV; ++v) {
         h->views[v].ctx_frames = h->ctx_frames_all + (size_t)v * nc * H * W * 3;
-        h->views[v].ctx_distrib = h->ctx_distrib_all + (size_t)v * nc * H * W * ND;
+        h->views[v].ctx_distrib = ND > 0 ? h->ctx_distrib_all + (size_t)v * nc * H * W * ND : nullptr;
     }
     VF_ALLOC(h->ctx_states, (size_t)nc * cfg->sdim);
     VF_ALLOC(h->ctx_actions, (size_t)std::max(nc - 1, 1) * cfg->adim);
@@ -1148,11 +1155,11 @@ static int cdna_create(vf_handle *h) {
     VF_ALLOC(h->fc_part, h->flow || h->dna ? 0 : BV * h->fc.nsplit * kTaps * h->K);
     VF_ALLOC(h->kern, h->flow || h->dna ? 0 : BV * kTaps * h->K);
     VF_ALLOC(h->frames_all, BV * h->T * H * W * 3);
-    VF_ALLOC(h->distrib_all, BV * h->T * H * W * ND);
+    if (ND > 0) VF_ALLOC(h->distrib_all, BV * h->T * H * W * ND);
     VF_ALLOC(h->states_all, BV * h->T * cfg->sdim);
     h->sums_view_stride = (long long)Bc * ND * h->nblocks * 2;
     h->sums_step_stride = h->sums_view_stride * NV;
-    VF_ALLOC(h->sums, (size_t)h->T * h->sums_step_stride);
+    if (ND > 0) VF_ALLOC(h->sums, (size_t)h->T * h->sums_step_stride);
     VF_ALLOC(h->goal_mse, BV * h->T);
     VF_ALLOC(h->actions_buf, (size_t)Bc * h->T * cfg->adim);
     h->sched_capacity = ((size_t)h->S * 32 + 8) * NV;       // (arch 2: up to 29 phases per step)
@@ -1432,7 +1439,10 @@ int vf_load_weights(vf_handle *h, const float *blob_all, size_t n_floats) {
 int vf_set_context(vf_handle *h, const uint8_t *d_frames, const float *d_states, const float *d_ctx_actions,
                    const float *d_ctx_distrib, void *stream) {
     VF_API_TRY
-    if (!h || !d_frames || !d_states || !d_ctx_distrib) return fail(VF_ERR_INVALID, "null argument");
+    if (!h || !d_frames || !d_states) return fail(VF_ERR_INVALID, "null argument");
+    if (h->ND == 0 && d_ctx_distrib)
+        return fail(VF_ERR_INVALID, "vf_set_context: a frames-only handle (ndesig 0) takes no context distributions: d_ctx_distrib must be NULL");
+    if (h->ND > 0 && !d_ctx_distrib) return fail(VF_ERR_INVALID, "null argument");
     const int nc = h->cfg.n_context;
     if (nc > 1 && !d_ctx_actions) return fail(VF_ERR_INVALID, "context actions required when n_context > 1");
     VF_HIP_CHECK(hipSetDevice(h->cfg.device));
@@ -1493,9 +1503,9 @@ static BatchView make_view(vf_handle *h, int view, const float *d_actions, int b
     v.fc_part = h->fc_part + b * h->fc.nsplit * kTaps * h->K;
     v.kern = h->kern + b * kTaps * h->K;
     v.frames_all = h->frames_all + b * T * H * W * 3;
-    v.distrib_all = h->distrib_all + b * T * H * W * ND;
+    v.distrib_all = ND > 0 ? h->distrib_all + b * T * H * W * ND : nullptr;
     v.states_all = h->states_all + b * T * c.sdim;
-    v.sums = h->sums + (long long)view * h->sums_view_stride + (size_t)b0 * ND * h->nblocks * 2;
+    v.sums = ND > 0 ? h->sums + (long long)view * h->sums_view_stride + (size_t)b0 * ND * h->nblocks * 2 : nullptr;
     v.actions = d_actions + (size_t)b0 * T * c.adim;       // the views share the action sequences
     return v;
 }
@@ -1597,7 +1607,12 @@ struct LaunchSink {
     }
     int composite(const CompositeParams &p, int ntiles, int /*view*/, std::initializer_list<int>) {
         dim3 grid(ntiles, p.B);
-        if (p.w_flow && p.K == 1) {     // DNA: the per-pixel kernel head travels in the flow head's fields
+        if (p.ND == 0) {                // frames-only engines: one kernel per compositing mode (vf_small_kernels.h)
+            if (p.w_flow && p.K == 1) hipLaunchKernelGGL(composite_dna_frames_kernel, grid, dim3(256), 0, st, p);
+            else if (p.w_flow) hipLaunchKernelGGL(composite_flow_frames_kernel, grid, dim3(256), 0, st, p);
+            else if (p.K == 6) hipLaunchKernelGGL(composite_frames_kernel<6>, grid, dim3(256), 0, st, p);
+            else hipLaunchKernelGGL(composite_frames_kernel<10>, grid, dim3(256), 0, st, p);
+        } else if (p.w_flow && p.K == 1) {     // DNA: the per-pixel kernel head travels in the flow head's fields
             switch (p.ND) {
                 case 1: hipLaunchKernelGGL(composite_dna_kernel<1>, grid, dim3(256), 0, st, p); break;
                 case 2: hipLaunchKernelGGL(composite_dna_kernel<2>, grid, dim3(256), 0, st, p); break;
@@ -2149,7 +2164,7 @@ static int emit_rollout(vf_handle *h, int view, const BatchView &v, const BatchV
             if (h->savp) {
                 cp.enc6 = v.enc7_o; cp.ln_part = v.st_enc7; cp.ln_nparts = h->convt4.stats_nparts;
                 cp.gamma = vd.ln_g[10]; cp.beta = vd.ln_b[10];
-                cp.first_frame = vd.ctx_frames; cp.first_distrib = vd.ctx_distrib;     // context frame 0
+                cp.first_frame = vd.ctx_frames; cp.first_distrib = vd.ctx_distrib;     // context frame 0 (frames-only: null)
             } else {
                 cp.enc6 = v.enc6_o; cp.ln_part = v.st_enc6; cp.ln_nparts = h->convt3.stats_nparts;
                 cp.gamma = vd.ln_g[8]; cp.beta = vd.ln_b[8];
@@ -2165,7 +2180,9 @@ static int emit_rollout(vf_handle *h, int view, const BatchView &v, const BatchV
             if (h->flow || h->dna) { cp.w_flow = vd.w_flow; cp.b_flow = vd.b_flow; }
             else cp.kern = v.kern;
             cp.prev_frame = frame_in; cp.prev_frame_bstride = frame_bs;
-            if (s < nc) {
+            if (ND == 0) {      // frames-only: the tile neither reads nor writes a distribution or a block sum
+                cp.prev_distrib = nullptr; cp.prev_distrib_bstride = 0; cp.prev_sums = nullptr;
+            } else if (s < nc) {
                 cp.prev_distrib = vd.ctx_distrib + (size_t)s * H * W * ND; cp.prev_distrib_bstride = 0;
                 cp.prev_sums = nullptr;
             } else {
@@ -2174,9 +2191,11 @@ static int emit_rollout(vf_handle *h, int view, const BatchView &v, const BatchV
                 cp.prev_sums = v.sums + (long long)(s - nc) * h->sums_step_stride;
             }
             cp.out_frame = v.frames_all + (size_t)t_out * H * W * 3; cp.out_frame_bstride = (long long)T * H * W * 3;
-            cp.out_distrib = v.distrib_all + (size_t)t_out * H * W * ND;
-            cp.out_distrib_bstride = (long long)T * H * W * ND;
-            cp.out_sums = v.sums + (long long)t_out * h->sums_step_stride;
+            if (ND > 0) {
+                cp.out_distrib = v.distrib_all + (size_t)t_out * H * W * ND;
+                cp.out_distrib_bstride = (long long)T * H * W * ND;
+                cp.out_sums = v.sums + (long long)t_out * h->sums_step_stride;
+            }
             if (goal_pix)
                 for (int d = 0; d < ND; ++d) { cp.goal[d][0] = goal_pix[2 * d]; cp.goal[d][1] = goal_pix[2 * d + 1]; }
             VF_EMIT(u_comp, sink.top(*top_l, p, cp, h->ntiles, view, top_early, top_late, u_fin, h->fuse_top))
@@ -2300,7 +2319,7 @@ static int build_schedule(vf_handle *h, int B, bool skip_shared, BuiltSchedule &
     out.counters = counters;
     const size_t comp_lds[kMaxDesig] = {(size_t)composite_lds_floats<1, 10>() * 4, (size_t)composite_lds_floats<2, 10>() * 4,
                                         (size_t)composite_lds_floats<3, 10>() * 4, (size_t)composite_lds_floats<4, 10>() * 4};
-    out.lds = std::max(max_lds, comp_lds[h->ND - 1]) + 16;
+    out.lds = std::max(max_lds, h->ND > 0 ? comp_lds[h->ND - 1] : (size_t)composite_lds_floats<0, 10>() * 4) + 16;
     if (out.phases.size() > h->sched_capacity || (size_t)counters > h->counter_capacity)
         return fail(VF_ERR_INVALID, "persistent schedule exceeds its preallocated capacity");
     return VF_OK;
@@ -2326,6 +2345,9 @@ static int render_plans_check(const vf_handle *h, const int32_t *d_seq, int32_t 
     if (K > h->cfg.max_batch)
         return fail(VF_ERR_INVALID, "K = " + std::to_string(K) + " plans exceed max_batch = " +
                                         std::to_string(h->cfg.max_batch));
+    // (behind the argument refusals, which come before the handle is read)
+    if (h->ND == 0 && d_distrib_u8)
+        return fail(VF_ERR_INVALID, "vf_render_plans: a frames-only handle (ndesig 0) has no distributions to render: d_distrib_u8 must be NULL");
     if (h->last_B < 1) return fail(VF_ERR_INVALID, "the handle has not rolled");
     return VF_OK;
 }
@@ -2737,7 +2759,7 @@ static int run_persistent(vf_handle *h, const float *d_actions, int B, const int
     sc.cu_tab = yield_for(h, B) > 0 ? h->d_sync + kTicketInts : nullptr;
     sc.stats = nullptr;
     sc.nd = h->ND;
-    for (int i = 0; i < h->ncam * h->ND * 2; ++i) sc.goal[i] = goal_pix[i];
+    for (int i = 0; i < h->ncam * h->ND * 2; ++i) sc.goal[i] = goal_pix[i];     // (frames-only: no goal pixel, goal_pix is null)
     if (h->phase_stats) {
         VF_HIP_CHECK(hipMemsetAsync(h->d_stats, 0, h->sched_capacity * 2 * sizeof(unsigned long long), st));
         sc.stats = h->d_stats;
@@ -2760,6 +2782,12 @@ static int run_persistent(vf_handle *h, const float *d_actions, int B, const int
     }
     const int mode = h->dna ? COMP_DNA : (h->flow ? COMP_FLOW : COMP_CDNA);
     switch (h->ND) {
+        case 0:     // frames-only engines: kernels of their own names (vf_persistent.h)
+            if (mode == COMP_DNA) hipLaunchKernelGGL(rollout_dna_frames_kernel, dim3(grid), dim3(kConvThreads), lds, st, sc.phases, sc);
+            else if (mode == COMP_FLOW) hipLaunchKernelGGL(rollout_flow_frames_kernel, dim3(grid), dim3(kConvThreads), lds, st, sc.phases, sc);
+            else hipLaunchKernelGGL(rollout_frames_kernel, dim3(grid), dim3(kConvThreads), lds, st, sc.phases, sc);
+            rc = hipGetLastError() == hipSuccess ? VF_OK : fail(VF_ERR_HIP, "launch of the frames-only rollout kernel failed");
+            break;
         case 1: rc = launch_persistent_t<1>(sc, mode, grid, lds, st); break;
         case 2: rc = launch_persistent_t<2>(sc, mode, grid, lds, st); break;
         case 3: rc = launch_persistent_t<3>(sc, mode, grid, lds, st); break;
@@ -2781,7 +2809,12 @@ extern "C" {
 int vf_rollout(vf_handle *h, const float *d_actions, int32_t B, const int32_t *goal_pix, float finalweight,
                const float *task_weights, double *d_scores, double *d_scores_per_task, void *stream) {
     VF_API_TRY
-    if (!h || !d_actions || !goal_pix || !d_scores) return fail(VF_ERR_INVALID, "null argument");
+    if (!h || !d_actions) return fail(VF_ERR_INVALID, "null argument");
+    const bool frames_only = h->ND == 0;
+    if (frames_only && (goal_pix || task_weights || d_scores || d_scores_per_task))
+        return fail(VF_ERR_INVALID, "vf_rollout: a frames-only handle (ndesig 0) has no pixel cost: goal_pix, task_weights, d_scores "
+                                    "and d_scores_per_task must be NULL");
+    if (!frames_only && (!goal_pix || !d_scores)) return fail(VF_ERR_INVALID, "null argument");
     if (!h->have_weights) return fail(VF_ERR_NOWEIGHTS, "vf_load_weights has not been called");
     if (!h->have_context) return fail(VF_ERR_NOCONTEXT, "vf_set_context has not been called");
     if (B < 1 || B > h->cfg.max_batch)
@@ -2804,6 +2837,11 @@ int vf_rollout(vf_handle *h, const float *d_actions, int32_t B, const int32_t *g
             if ((rc = run_steps(h, v, bv, h->shared_views[(size_t)v], B, goal_pix, st, skip))) return rc;
         }
         h->shared_valid = h->dedup; h->shared_cfg = 1;
+    }
+    if (frames_only) {      // no block sums to reduce: the costs of such a handle come from vf_goal_image_scores / vf_scorer_scores
+        h->last_B = B;
+        h->last_goal.clear();
+        return VF_OK;
     }
     TaskWeights tw;
     memset(&tw, 0, sizeof(tw));
@@ -2835,6 +2873,7 @@ int vf_ensemble_scores(vf_handle *const *members, int32_t n_members, float lambd
         const vf_handle *h = members[m];
         const std::string who = "member " + std::to_string(m);
         if (!h) return fail(VF_ERR_INVALID, who + " is NULL");
+        if (h->ND == 0) return fail(VF_ERR_INVALID, who + " is a frames-only handle (ndesig 0): it keeps no pixel-cost sums to combine");
         if (memcmp(&h->cfg, &h0->cfg, sizeof(vf_config)) != 0)
             return fail(VF_ERR_INVALID, who + ": vf_config differs from member 0's (device included)");
         if (h->last_B < 1) return fail(VF_ERR_INVALID, who + " has not rolled");
@@ -3086,6 +3125,8 @@ int vf_export(vf_handle *h, int32_t first, int32_t count, float *d_frames, float
               void *stream) {
     VF_API_TRY
     if (!h) return fail(VF_ERR_INVALID, "null handle");
+    if (h->ND == 0 && d_distrib)
+        return fail(VF_ERR_INVALID, "vf_export: a frames-only handle (ndesig 0) predicts no distributions: d_distrib must be NULL");
     if (first < 0 || count < 1 || first + count > h->last_B)
         return fail(VF_ERR_INVALID, "sample range outside the last rollout");
     VF_HIP_CHECK(hipSetDevice(h->cfg.device));

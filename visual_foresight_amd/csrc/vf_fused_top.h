@@ -118,13 +118,15 @@ __device__ __forceinline__ void fused_top_body(const PT &p, const CT &c, f32x16 
     float *s_ln = s_kern + kTaps * kCompKernPad;         // [2]
     float *s_dscale = s_ln + 2;                          // [ND]
     int *s_flag = reinterpret_cast<int *>(s_dscale + ND + 1);
-    const int nblocks = sum_blocks(c.H, c.W);
+    [[maybe_unused]] const int nblocks = sum_blocks(c.H, c.W);
 
     // ---- 3. scale of the previous distributions, CDNA kernels, halo.  Three independent groups of loads: all of them are
     // requested before the first is used (the halo of up to 1024 pixels sits in registers across the reduction of the
     // block sums and the barrier), so the item waits for ONE memory latency here instead of three or more
     const float *pf = c.prev_frame + (long long)b * c.prev_frame_bstride;
-    const float *pd = c.prev_distrib + (long long)b * c.prev_distrib_bstride;
+    // (a frames-only item, ND = 0 - DESIGN.md 4.14: no distribution is requested, scaled, staged, stored or summed below;
+    // every such statement is a loop over d < ND or sits behind `if constexpr (ND > 0)`.  The frame's statements are untouched.)
+    const float *pd = ND > 0 ? c.prev_distrib + (long long)b * c.prev_distrib_bstride : nullptr;
     const TileDiv div_hw(HW_);
     constexpr int kHaloU = 4;
     float hv[kHaloU][3 + ND];
@@ -157,7 +159,7 @@ __device__ __forceinline__ void fused_top_body(const PT &p, const CT &c, f32x16 
             }
         }
     };
-    double dsum[(ND + 3) / 4];
+    double dsum[nd_slots((ND + 3) / 4)];
 #pragma unroll
     for (int j = 0; j < (ND + 3) / 4; ++j) {
         dsum[j] = 0.0;
@@ -267,10 +269,10 @@ __device__ __forceinline__ void fused_top_body(const PT &p, const CT &c, f32x16 
         const int hy = byl * kSumBlockH + (lane >> 4), hx = bxl * kSumBlockW + (lane & 15);   // inside the region
         const int y = oy0 + hy, x = ox0 + hx;
         const bool valid = blk < nblk && y < c.H && x < c.W;
-        double cost[2 * ND];
+        double cost[2 * nd_slots(ND)];
 #pragma unroll
         for (int i = 0; i < 2 * ND; ++i) cost[i] = 0.0;
-        float of[3] = {0.f, 0.f, 0.f}, od[ND];
+        float of[3] = {0.f, 0.f, 0.f}, od[nd_slots(ND)];
 #pragma unroll
         for (int d = 0; d < ND; ++d) od[d] = 0.f;
         if constexpr (FLOW) {
@@ -307,7 +309,7 @@ __device__ __forceinline__ void fused_top_body(const PT &p, const CT &c, f32x16 
             const unsigned fr_bytes = (unsigned)(c.H * c.W * 3) * 4u, di_bytes = (unsigned)(c.H * c.W * ND) * 4u;
             const __amdgpu_buffer_rsrc_t r_fr = __builtin_amdgcn_make_buffer_rsrc(
                 c.out_frame + (long long)b * c.out_frame_bstride, 0, blk_ok ? (int)fr_bytes : 0, 0x00020000);
-            const __amdgpu_buffer_rsrc_t r_di = __builtin_amdgcn_make_buffer_rsrc(
+            [[maybe_unused]] const __amdgpu_buffer_rsrc_t r_di = __builtin_amdgcn_make_buffer_rsrc(
                 c.out_distrib + (long long)b * c.out_distrib_bstride, 0, blk_ok ? (int)di_bytes : 0, 0x00020000);
             if (lane < 48) {
                 const int row = lane / 12, q = lane - row * 12;
@@ -316,17 +318,19 @@ __device__ __forceinline__ void fused_top_body(const PT &p, const CT &c, f32x16 
                 if (wt) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_, v), r_fr, off, 0, 16);
                 else __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_, v), r_fr, off, 0, 0);
             }
-            for (int j = lane; j < 16 * ND; j += 64) {
-                const int row = j / (4 * ND), q = j - row * (4 * ND);
-                const f32x4 v = *reinterpret_cast<const f32x4 *>(slab + 192 + row * 16 * ND + 4 * q);
-                const unsigned off = (unsigned)(((y_blk + row) * c.W + x_blk) * ND + 4 * q) * 4u;
-                if (wt) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_, v), r_di, off, 0, 16);
-                else __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_, v), r_di, off, 0, 0);
+            if constexpr (ND > 0) {      // (frames-only: r_di is never used and the compiler drops it)
+                for (int j = lane; j < 16 * ND; j += 64) {
+                    const int row = j / (4 * ND), q = j - row * (4 * ND);
+                    const f32x4 v = *reinterpret_cast<const f32x4 *>(slab + 192 + row * 16 * ND + 4 * q);
+                    const unsigned off = (unsigned)(((y_blk + row) * c.W + x_blk) * ND + 4 * q) * 4u;
+                    if (wt) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_, v), r_di, off, 0, 16);
+                    else __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_, v), r_di, off, 0, 0);
+                }
             }
         }
 #pragma unroll
         for (int i = 0; i < 2 * ND; ++i) cost[i] = wave_sum(cost[i]);
-        if (lane == 0 && blk_ok) {
+        if (ND > 0 && lane == 0 && blk_ok) {
             const int gblk = (y_blk / kSumBlockH) * sum_blocks_x(c.W) + x_blk / kSumBlockW;
 #pragma unroll
             for (int d = 0; d < ND; ++d) {

@@ -233,6 +233,18 @@ static __device__ __noinline__ __attribute__((not_tail_called)) void composite_d
     const int *goal = reinterpret_cast<const int *>(smem_all) + kCtlGoal + view * ND * 2;
     composite_tile<ND, 1, false, const VF_CONST_AS CompositeParams, 32, COMP_DNA>(const_params(p), tile, b, goal, tile_lds());
 }
+// the compositing tiles of a frames-only engine (ND = 0): bodies of their own names - the tiles above are
+// counted per designated-pixel count - around the same composite_tile; no goal pixels
+template <bool FIRST, int K, int CF = 32>
+static __device__ __noinline__ __attribute__((not_tail_called)) void composite_frames_tile_call(const CompositeParams *p, int tile, int b) {
+    composite_tile<0, K, FIRST, const VF_CONST_AS CompositeParams, CF>(const_params(p), tile, b, nullptr, tile_lds());
+}
+static __device__ __noinline__ __attribute__((not_tail_called)) void composite_flow_frames_tile_call(const CompositeParams *p, int tile, int b) {
+    composite_tile<0, kFlowWarps + 1, false, const VF_CONST_AS CompositeParams, 32, COMP_FLOW>(const_params(p), tile, b, nullptr, tile_lds());
+}
+static __device__ __noinline__ __attribute__((not_tail_called)) void composite_dna_frames_tile_call(const CompositeParams *p, int tile, int b) {
+    composite_tile<0, 1, false, const VF_CONST_AS CompositeParams, 32, COMP_DNA>(const_params(p), tile, b, nullptr, tile_lds());
+}
 static __device__ __noinline__ __attribute__((not_tail_called)) void gates_raw_tile_call(const ConvParams *p, int bx, int by) {
     conv_lstm_gsplit2_tile<4, const VF_CONST_AS ConvParams, true>(const_params(p), bx, by, tile_lds());
 }
@@ -466,14 +478,28 @@ __device__ __forceinline__ void rollout_body(const PhaseDesc *__restrict__ phase
                 // (K = 6: the compositing of arch 2 - four CDNA warps + previous + first frame + scratch - always with
                 // the first-frame layer; K = 10 otherwise)
                 case PH_TOP_FUSED:
-                    if constexpr (MODE == COMP_FLOW) conv_tile_call<4, fused_epi_flow(ND), 1>(&P.conv, bx, 0, 0);
+                    if constexpr (ND == 0) {        // frames-only engines: the same dispatch over the frames-only epilogues
+                        if constexpr (MODE != COMP_CDNA) conv_tile_call<4, fused_epi_frames(MODE), 1>(&P.conv, bx, 0, 0);
+                        else if (P.comp.K == 6) conv_tile_call<4, fused_epi_frames(MODE, true, true), 1>(&P.conv, bx, 0, 0);
+                        else if (P.comp.first_frame) conv_tile_call<4, fused_epi_frames(MODE, true), 1>(&P.conv, bx, 0, 0);
+                        else conv_tile_call<4, fused_epi_frames(MODE), 1>(&P.conv, bx, 0, 0);
+                    }
+                    else if constexpr (MODE == COMP_FLOW) conv_tile_call<4, fused_epi_flow(ND), 1>(&P.conv, bx, 0, 0);
                     else if constexpr (MODE == COMP_DNA) conv_tile_call<4, fused_epi_dna(ND), 1>(&P.conv, bx, 0, 0);
                     else if (P.comp.K == 6) conv_tile_call<4, fused_epi(ND, true, true), 1>(&P.conv, bx, 0, 0);
                     else if (P.comp.first_frame) conv_tile_call<4, fused_epi(ND, true), 1>(&P.conv, bx, 0, 0);
                     else conv_tile_call<4, fused_epi(ND, false), 1>(&P.conv, bx, 0, 0);
                     break;
                 case PH_COMPOSITE:
-                    if constexpr (MODE == COMP_FLOW) composite_flow_tile_call<ND>(&P.comp, local % P.gx, b0, P.view);
+                    if constexpr (ND == 0) {
+                        if constexpr (MODE == COMP_FLOW) composite_flow_frames_tile_call(&P.comp, local % P.gx, b0);
+                        else if constexpr (MODE == COMP_DNA) composite_dna_frames_tile_call(&P.comp, local % P.gx, b0);
+                        else if (P.comp.K == 6) composite_frames_tile_call<true, 6>(&P.comp, local % P.gx, b0);
+                        else if (P.comp.first_frame) composite_frames_tile_call<true, 10>(&P.comp, local % P.gx, b0);
+                        else if (P.comp.CF > 32) composite_frames_tile_call<false, 10, 64>(&P.comp, local % P.gx, b0);
+                        else composite_frames_tile_call<false, 10>(&P.comp, local % P.gx, b0);
+                    }
+                    else if constexpr (MODE == COMP_FLOW) composite_flow_tile_call<ND>(&P.comp, local % P.gx, b0, P.view);
                     else if constexpr (MODE == COMP_DNA) composite_dna_tile_call<ND>(&P.comp, local % P.gx, b0, P.view);
                     else if (P.comp.K == 6) composite_tile_call<ND, true, 6>(&P.comp, local % P.gx, b0, P.view);
                     else if (P.comp.first_frame) composite_tile_call<ND, true, 10>(&P.comp, local % P.gx, b0, P.view);
@@ -499,9 +525,11 @@ __device__ __forceinline__ void rollout_body(const PhaseDesc *__restrict__ phase
                         case EW_INORM: ew_inorm_call(&P.ew, idx, b0, b1); break;
                         case EW_INCELL: ew_incell_call(&P.ew, idx, b0, b1); break;
                         case EW_UPSAMPLE: ew_upsample_call(&P.ew, idx, b0, b1); break;
-                        case EW_TRANSFORM: ew_transform_call<ND>(&P.ew, idx, b0); break;
-                        case EW_TOP3: ew_top3_call<ND>(&P.ew, idx, b0, P.view); break;
-                        default: ew_compose_call<ND>(&P.ew, idx, b0, P.view); break;
+                        // (arch 3 has no frames-only heads: vf_create refuses ndesig 0 there, a frames-only schedule
+                        // holds no such item)
+                        case EW_TRANSFORM: if constexpr (ND > 0) ew_transform_call<ND>(&P.ew, idx, b0); break;
+                        case EW_TOP3: if constexpr (ND > 0) ew_top3_call<ND>(&P.ew, idx, b0, P.view); break;
+                        default: if constexpr (ND > 0) ew_compose_call<ND>(&P.ew, idx, b0, P.view); break;
                     }
                     break;
                 }
@@ -573,6 +601,21 @@ template <int ND>
 VF_GLOBAL VF_LAUNCH_BOUNDS(kConvThreads, 2) void rollout_dna_kernel(
     const PhaseDesc *__restrict__ phases, const Schedule sched) {
     rollout_body<ND, COMP_DNA>(phases, sched);
+}
+
+// The rollouts of frames-only engines (vf_config.ndesig = 0): the same scheduler loop and tiles with ND = 0,
+// one kernel per compositing mode.  Names of their own: the three templates above are counted per designated-pixel count.
+VF_GLOBAL VF_LAUNCH_BOUNDS(kConvThreads, 2) void rollout_frames_kernel(
+    const PhaseDesc *__restrict__ phases, const Schedule sched) {
+    rollout_body<0, COMP_CDNA>(phases, sched);
+}
+VF_GLOBAL VF_LAUNCH_BOUNDS(kConvThreads, 2) void rollout_flow_frames_kernel(
+    const PhaseDesc *__restrict__ phases, const Schedule sched) {
+    rollout_body<0, COMP_FLOW>(phases, sched);
+}
+VF_GLOBAL VF_LAUNCH_BOUNDS(kConvThreads, 2) void rollout_dna_frames_kernel(
+    const PhaseDesc *__restrict__ phases, const Schedule sched) {
+    rollout_body<0, COMP_DNA>(phases, sched);
 }
 
 }  // namespace vf

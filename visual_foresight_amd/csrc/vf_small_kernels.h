@@ -16,6 +16,10 @@
 namespace vf {
 
 constexpr int kMaxDesig = 4;
+// Extent of an array with one entry per designated pixel.  A frames-only item (ND = 0) has no such values:
+// every loop over them runs zero times and every access sits behind `if constexpr (ND > 0)`, so the one slot that keeps the
+// array type well-formed is never read or written and costs no register.  For ND >= 1 the extent is ND itself.
+__host__ __device__ constexpr int nd_slots(int nd) { return nd > 0 ? nd : 1; }
 constexpr int kDnaKern = 5;
 constexpr int kTaps = kDnaKern * kDnaKern;
 constexpr int kCompTile = 16;           // composite: 16x16 pixels per workgroup
@@ -291,12 +295,12 @@ __device__ __forceinline__ void composite_heads(const PT &p, const float *feat, 
 template <int ND, int K, bool FIRST, class PT>
 __device__ __forceinline__ void composite_finish(const PT &p, const int b, const int y, const int x, float (&o_rgb)[3],
                                                  float (&o_m)[K + 1], const float *s_px, const float *s_kern, const int halo_w,
-                                                 const int hy, const int hx, const int *goal, double (&cost)[2 * ND]);
+                                                 const int hy, const int hx, const int *goal, double (&cost)[2 * nd_slots(ND)]);
 template <int ND, int K, bool FIRST, class PT>
 __device__ __forceinline__ void composite_values(const PT &p, const int y, const int x, float (&o_rgb)[3],
                                                  float (&o_m)[K + 1], const float *s_px, const float *s_kern, const int halo_w,
-                                                 const int hy, const int hx, const int *goal, double (&cost)[2 * ND],
-                                                 float (&of)[3], float (&od)[ND]);
+                                                 const int hy, const int hx, const int *goal, double (&cost)[2 * nd_slots(ND)],
+                                                 float (&of)[3], float (&od)[nd_slots(ND)]);
 
 // One output pixel (y, x) of sample b: LN + relu of its 32 features (a row of the LDS feature tile), the two 1x1
 // heads, softmax, the effective 5x5 flow kernel over the haloed previous frame / distributions in LDS
@@ -307,7 +311,7 @@ template <int ND, int K, bool FIRST, class PT>
 __device__ __forceinline__ void composite_pixel(const PT &p, const int b, const int y, const int x, const float *feat,
                                                 const float mean, const float rstd, const float *s_px,
                                                 const float *s_kern, const int halo_w,
-                                                const int hy, const int hx, const int *goal, double (&cost)[2 * ND]) {
+                                                const int hy, const int hx, const int *goal, double (&cost)[2 * nd_slots(ND)]) {
     constexpr int NM = K + 1;
     static_assert(K <= 10 && ND <= 4, "LDS record layouts");
     float o_rgb[3], o_m[NM];
@@ -321,7 +325,7 @@ template <int ND, int K, bool FIRST, class PT>
 __device__ __forceinline__ void composite_pixel_values(const PT &p, const int y, const int x, const float *feat,
                                                        const float mean, const float rstd, const float *s_px,
                                                        const float *s_kern, const int halo_w, const int hy, const int hx,
-                                                       const int *goal, double (&cost)[2 * ND], float (&of)[3], float (&od)[ND]) {
+                                                       const int *goal, double (&cost)[2 * nd_slots(ND)], float (&of)[3], float (&od)[nd_slots(ND)]) {
     constexpr int NM = K + 1;
     float o_rgb[3], o_m[NM];
     composite_head_bias<K>(p, o_rgb, o_m);
@@ -333,27 +337,30 @@ __device__ __forceinline__ void composite_pixel_values(const PT &p, const int y,
 template <int ND, int K, bool FIRST, class PT>
 __device__ __forceinline__ void composite_finish(const PT &p, const int b, const int y, const int x, float (&o_rgb)[3],
                                                  float (&o_m)[K + 1], const float *s_px, const float *s_kern, const int halo_w,
-                                                 const int hy, const int hx, const int *goal, double (&cost)[2 * ND]) {
-    float of[3], od[ND];
+                                                 const int hy, const int hx, const int *goal, double (&cost)[2 * nd_slots(ND)]) {
+    float of[3], od[nd_slots(ND)];
     composite_values<ND, K, FIRST>(p, y, x, o_rgb, o_m, s_px, s_kern, halo_w, hy, hx, goal, cost, of, od);
     const long long o = (long long)y * p.W + x;
     float *fo = p.out_frame + (long long)b * p.out_frame_bstride + o * 3;
 #pragma unroll
     for (int c = 0; c < 3; ++c) fo[c] = of[c];
-    float *dout = p.out_distrib + (long long)b * p.out_distrib_bstride + o * ND;
+    if constexpr (ND > 0) {
+        float *dout = p.out_distrib + (long long)b * p.out_distrib_bstride + o * ND;
 #pragma unroll
-    for (int d = 0; d < ND; ++d) dout[d] = od[d];
+        for (int d = 0; d < ND; ++d) dout[d] = od[d];
+    }
 }
 template <int ND, int K, bool FIRST, class PT>
 __device__ __forceinline__ void composite_values(const PT &p, const int y, const int x, float (&o_rgb)[3],
                                                  float (&o_m)[K + 1], const float *s_px, const float *s_kern, const int halo_w,
-                                                 const int hy, const int hx, const int *goal, double (&cost)[2 * ND],
-                                                 float (&of)[3], float (&od)[ND]) {
+                                                 const int hy, const int hx, const int *goal, double (&cost)[2 * nd_slots(ND)],
+                                                 float (&of)[3], float (&od)[nd_slots(ND)]) {
     constexpr int NM = K + 1;
     constexpr int PS = comp_px_stride(ND);
-    auto load_px = [&](const int sp, float (&fr)[3], float (&di)[ND]) {
+    auto load_px = [&](const int sp, float (&fr)[3], float (&di)[nd_slots(ND)]) {
         const f32x4 a = *reinterpret_cast<const f32x4 *>(s_px + sp * PS);
-        fr[0] = a[0]; fr[1] = a[1]; fr[2] = a[2]; di[0] = a[3];
+        fr[0] = a[0]; fr[1] = a[1]; fr[2] = a[2];
+        if constexpr (ND > 0) di[0] = a[3];
         if constexpr (ND > 1) {
             const f32x4 c2 = *reinterpret_cast<const f32x4 *>(s_px + sp * PS + 4);
 #pragma unroll
@@ -374,7 +381,7 @@ __device__ __forceinline__ void composite_values(const PT &p, const int y, const
     // (arch 1: mask 2 weighs the first context frame, the warps use masks 3.. and kernels 0..K-3)
     const int ctr = (hy + 2) * halo_w + (hx + 2);
     {
-        float fr[3], di[ND];
+        float fr[3], di[nd_slots(ND)];
         load_px(ctr, fr, di);
 #pragma unroll
         for (int c = 0; c < 3; ++c) of[c] = fmaf(o_m[0], fr[c], o_m[1] * sigmoidf_(o_rgb[c]));
@@ -411,7 +418,7 @@ __device__ __forceinline__ void composite_values(const PT &p, const int y, const
 #pragma unroll
             for (int k = 0; k < K - 1; ++k) ke = fmaf(o_m[k + 2], kr[k], ke);
             const int sp = (hy + dy) * halo_w + (hx + dx);
-            float fr[3], di[ND];
+            float fr[3], di[nd_slots(ND)];
             load_px(sp, fr, di);
 #pragma unroll
             for (int c = 0; c < 3; ++c) of[c] = fmaf(ke, fr[c], of[c]);
@@ -473,8 +480,8 @@ template <int ND, class PT>
 __device__ __forceinline__ void composite_values_flow(const PT &p, const int y, const int x, const float *feat,
                                                       const float mean, const float rstd, float (&o_rgb)[3],
                                                       float (&o_m)[kFlowWarps + 2], const float *pf, const float *pd,
-                                                      const float *dscale, const int *goal, double (&cost)[2 * ND],
-                                                      float (&of)[3], float (&od)[ND]) {
+                                                      const float *dscale, const int *goal, double (&cost)[2 * nd_slots(ND)],
+                                                      float (&of)[3], float (&od)[nd_slots(ND)]) {
     constexpr int NM = kFlowWarps + 2;
     float mx = o_m[0];
 #pragma unroll
@@ -486,7 +493,7 @@ __device__ __forceinline__ void composite_values_flow(const PT &p, const int y, 
 #pragma unroll
     for (int j = 0; j < NM; ++j) o_m[j] *= inv;
 
-    float sc[ND];
+    float sc[nd_slots(ND)];
 #pragma unroll
     for (int d = 0; d < ND; ++d) sc[d] = dscale[d];
     {
@@ -536,7 +543,7 @@ template <int ND, class PT>
 __device__ __forceinline__ void composite_pixel_values_flow(const PT &p, const int y, const int x, const float *feat,
                                                             const float mean, const float rstd, const float *pf,
                                                             const float *pd, const float *dscale, const int *goal,
-                                                            double (&cost)[2 * ND], float (&of)[3], float (&od)[ND]) {
+                                                            double (&cost)[2 * nd_slots(ND)], float (&of)[3], float (&od)[nd_slots(ND)]) {
     float o_rgb[3], o_m[kFlowWarps + 2];
     composite_head_bias<kFlowWarps + 1>(p, o_rgb, o_m);
     composite_heads<kFlowWarps + 1>(p, feat, mean, rstd, 0, o_rgb, o_m);
@@ -588,12 +595,13 @@ __device__ __forceinline__ void composite_dna_heads(const PT &p, const float *fe
 template <int ND, class PT>
 __device__ __forceinline__ void composite_values_dna(const PT &p, const int y, const int x, float (&o_m)[2],
                                                      float (&o_a)[kTaps], const float *s_px, const int halo_w, const int hy,
-                                                     const int hx, const int *goal, double (&cost)[2 * ND], float (&of)[3],
-                                                     float (&od)[ND]) {
+                                                     const int hx, const int *goal, double (&cost)[2 * nd_slots(ND)], float (&of)[3],
+                                                     float (&od)[nd_slots(ND)]) {
     constexpr int PS = comp_px_stride(ND);
-    auto load_px = [&](const int sp, float (&fr)[3], float (&di)[ND]) {
+    auto load_px = [&](const int sp, float (&fr)[3], float (&di)[nd_slots(ND)]) {
         const f32x4 a = *reinterpret_cast<const f32x4 *>(s_px + sp * PS);
-        fr[0] = a[0]; fr[1] = a[1]; fr[2] = a[2]; di[0] = a[3];
+        fr[0] = a[0]; fr[1] = a[1]; fr[2] = a[2];
+        if constexpr (ND > 0) di[0] = a[3];
         if constexpr (ND > 1) {
             const f32x4 c2 = *reinterpret_cast<const f32x4 *>(s_px + sp * PS + 4);
 #pragma unroll
@@ -613,7 +621,7 @@ __device__ __forceinline__ void composite_values_dna(const PT &p, const int y, c
     for (int t = 0; t < kTaps; ++t) { o_a[t] = fmaxf(o_a[t] - kReluShift, 0.f) + kReluShift; s += o_a[t]; }
     const float g = o_m[1] / s;
     {
-        float fr[3], di[ND];
+        float fr[3], di[nd_slots(ND)];
         load_px((hy + 2) * halo_w + (hx + 2), fr, di);
 #pragma unroll
         for (int c = 0; c < 3; ++c) of[c] = o_m[0] * fr[c];
@@ -625,7 +633,7 @@ __device__ __forceinline__ void composite_values_dna(const PT &p, const int y, c
 #pragma unroll
         for (int dx = 0; dx < kDnaKern; ++dx) {
             const float ke = g * o_a[dy * kDnaKern + dx];
-            float fr[3], di[ND];
+            float fr[3], di[nd_slots(ND)];
             load_px((hy + dy) * halo_w + (hx + dx), fr, di);
 #pragma unroll
             for (int c = 0; c < 3; ++c) of[c] = fmaf(ke, fr[c], of[c]);
@@ -646,7 +654,7 @@ template <int ND, class PT>
 __device__ __forceinline__ void composite_pixel_values_dna(const PT &p, const int y, const int x, const float *feat,
                                                            const float mean, const float rstd, const float *s_px,
                                                            const int halo_w, const int hy, const int hx, const int *goal,
-                                                           double (&cost)[2 * ND], float (&of)[3], float (&od)[ND]) {
+                                                           double (&cost)[2 * nd_slots(ND)], float (&of)[3], float (&od)[nd_slots(ND)]) {
     float o_m[2], o_a[kTaps];
     composite_dna_heads(p, feat, mean, rstd, o_m, o_a);
     composite_values_dna<ND>(p, y, x, o_m, o_a, s_px, halo_w, hy, hx, goal, cost, of, od);
@@ -675,7 +683,7 @@ __device__ __forceinline__ void composite_tile(const PT &p, const int tile, cons
 
     const int tid = threadIdx.x;
     const int tilesX = (p.W + TS - 1) / TS;
-    const int nblocks = sum_blocks(p.H, p.W);
+    [[maybe_unused]] const int nblocks = sum_blocks(p.H, p.W);
     const int ty0 = (tile / tilesX) * TS, tx0 = (tile % tilesX) * TS;
     constexpr int CF = CFT;                     // feature channels per pixel (64: the public decoder table, two rounds below)
 
@@ -722,7 +730,8 @@ __device__ __forceinline__ void composite_tile(const PT &p, const int tile, cons
     __syncthreads();
 
     const float *pf = p.prev_frame + (long long)b * p.prev_frame_bstride;
-    const float *pd = p.prev_distrib + (long long)b * p.prev_distrib_bstride;
+    // (a frames-only tile, ND = 0: no distribution is staged, scaled or gathered; prev_distrib is null)
+    const float *pd = ND > 0 ? p.prev_distrib + (long long)b * p.prev_distrib_bstride : nullptr;
     for (int i = tid; i < (FLOW ? 0 : HS * HS); i += 256) {
         const int ly = i / HS, lx = i % HS;
         const int y = ty0 + ly - 2, x = tx0 + lx - 2;
@@ -743,37 +752,41 @@ __device__ __forceinline__ void composite_tile(const PT &p, const int tile, cons
     const int ly = tid / TS, lx = tid % TS;
     const int y = ty0 + ly, x = tx0 + lx;
     const bool valid = y < p.H && x < p.W;
-    double cost[2 * ND];
+    double cost[2 * nd_slots(ND)];
 #pragma unroll
     for (int i = 0; i < 2 * ND; ++i) cost[i] = 0.0;
 
     if constexpr (FLOW) {
         static_assert(!FLOW || (CF == 32 && K == kFlowWarps + 1 && !FIRST), "the flow table: survey decoder, ten masks");
         if (valid) {
-            float of[3], od[ND];
+            float of[3], od[nd_slots(ND)];
             composite_pixel_values_flow<ND>(p, y, x, &s_enc[tid * kCompEncPad], s_ln[0], s_ln[1], pf, pd, s_dscale, goal,
                                             cost, of, od);
             const long long o = (long long)y * p.W + x;
             float *fo = p.out_frame + (long long)b * p.out_frame_bstride + o * 3;
 #pragma unroll
             for (int c = 0; c < 3; ++c) fo[c] = of[c];
-            float *dout = p.out_distrib + (long long)b * p.out_distrib_bstride + o * ND;
+            if constexpr (ND > 0) {
+                float *dout = p.out_distrib + (long long)b * p.out_distrib_bstride + o * ND;
 #pragma unroll
-            for (int d = 0; d < ND; ++d) dout[d] = od[d];
+                for (int d = 0; d < ND; ++d) dout[d] = od[d];
+            }
         }
     } else if constexpr (DNA) {
         static_assert(!DNA || (CF == 32 && K == 1 && !FIRST), "the dna table: survey decoder, one transform");
         if (valid) {
-            float of[3], od[ND];
+            float of[3], od[nd_slots(ND)];
             composite_pixel_values_dna<ND>(p, y, x, &s_enc[tid * kCompEncPad], s_ln[0], s_ln[1], s_px, HS, ly, lx, goal,
                                            cost, of, od);
             const long long o = (long long)y * p.W + x;
             float *fo = p.out_frame + (long long)b * p.out_frame_bstride + o * 3;
 #pragma unroll
             for (int c = 0; c < 3; ++c) fo[c] = of[c];
-            float *dout = p.out_distrib + (long long)b * p.out_distrib_bstride + o * ND;
+            if constexpr (ND > 0) {
+                float *dout = p.out_distrib + (long long)b * p.out_distrib_bstride + o * ND;
 #pragma unroll
-            for (int d = 0; d < ND; ++d) dout[d] = od[d];
+                for (int d = 0; d < ND; ++d) dout[d] = od[d];
+            }
         }
     } else if constexpr (CF == 32) {
         if (valid)
@@ -803,16 +816,19 @@ __device__ __forceinline__ void composite_tile(const PT &p, const int tile, cons
         if (valid) composite_finish<ND, K, FIRST>(p, b, y, x, o_rgb, o_m, s_px, s_kern, HS, ly, lx, goal, cost);
     }
     // ---- cost sums of this wave's block (4 rows x 16 columns): lanes in a fixed butterfly, one entry per block
+    // (a frames-only tile has no cost terms and no out_sums)
+    if constexpr (ND > 0) {
 #pragma unroll
-    for (int i = 0; i < 2 * ND; ++i) cost[i] = wave_sum(cost[i]);
-    const int lane = tid & 63, wave = tid >> 6;
-    const int by = ty0 / kSumBlockH + wave, bxk = tx0 / kSumBlockW;
-    if (lane == 0 && by * kSumBlockH < p.H && tx0 < p.W) {
-        const int blk = by * sum_blocks_x(p.W) + bxk;
+        for (int i = 0; i < 2 * ND; ++i) cost[i] = wave_sum(cost[i]);
+        const int lane = tid & 63, wave = tid >> 6;
+        const int by = ty0 / kSumBlockH + wave, bxk = tx0 / kSumBlockW;
+        if (lane == 0 && by * kSumBlockH < p.H && tx0 < p.W) {
+            const int blk = by * sum_blocks_x(p.W) + bxk;
 #pragma unroll
-        for (int d = 0; d < ND; ++d) {
-            double *dst = p.out_sums + (((long long)b * ND + d) * nblocks + blk) * 2;
-            dst[0] = cost[2 * d]; dst[1] = cost[2 * d + 1];
+            for (int d = 0; d < ND; ++d) {
+                double *dst = p.out_sums + (((long long)b * ND + d) * nblocks + blk) * 2;
+                dst[0] = cost[2 * d]; dst[1] = cost[2 * d + 1];
+            }
         }
     }
 }
@@ -839,6 +855,28 @@ template <int ND>
 VF_GLOBAL VF_LAUNCH_BOUNDS(256) void composite_dna_kernel(const CompositeParams p) {
     __shared__ __attribute__((aligned(16))) float smem[composite_lds_floats<ND, 1>()];
     composite_tile<ND, 1, false, CompositeParams, 32, COMP_DNA>(p, blockIdx.x, blockIdx.y, &p.goal[0][0], smem);
+}
+
+// Frames-only engines (vf_config.ndesig = 0): the same tile with ND = 0 - no distribution halo, no scale of
+// the previous distributions, no cost terms, no out_distrib / out_sums; a frame pixel runs the very fma chain of the ND = 1
+// instance.  Kernels of their own NAME, not a fifth instance of the templates above: those are counted per designated-pixel
+// count (tests/test_kernel_lint*.py).
+template <int K>
+VF_GLOBAL VF_LAUNCH_BOUNDS(256) void composite_frames_kernel(const CompositeParams p) {
+    __shared__ __attribute__((aligned(16))) float smem[composite_lds_floats<0, K>()];
+    if (K == 6 || p.first_frame) composite_tile<0, K, true>(p, blockIdx.x, blockIdx.y, nullptr, smem);
+    else if constexpr (K != 6) {
+        if (p.CF > 32) composite_tile<0, K, false, CompositeParams, 64>(p, blockIdx.x, blockIdx.y, nullptr, smem);
+        else composite_tile<0, K, false>(p, blockIdx.x, blockIdx.y, nullptr, smem);
+    }
+}
+VF_GLOBAL VF_LAUNCH_BOUNDS(256) void composite_flow_frames_kernel(const CompositeParams p) {
+    __shared__ __attribute__((aligned(16))) float smem[composite_lds_floats<0, kFlowWarps + 1>()];
+    composite_tile<0, kFlowWarps + 1, false, CompositeParams, 32, COMP_FLOW>(p, blockIdx.x, blockIdx.y, nullptr, smem);
+}
+VF_GLOBAL VF_LAUNCH_BOUNDS(256) void composite_dna_frames_kernel(const CompositeParams p) {
+    __shared__ __attribute__((aligned(16))) float smem[composite_lds_floats<0, 1>()];
+    composite_tile<0, 1, false, CompositeParams, 32, COMP_DNA>(p, blockIdx.x, blockIdx.y, nullptr, smem);
 }
 
 // ------------------------------------------------------------------------------------------

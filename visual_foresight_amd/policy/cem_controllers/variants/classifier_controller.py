@@ -103,7 +103,10 @@ class LearnedCostController(CEMBaseController):
         return None
 
     def _with_centre_distribution(self, context):
-        """``context`` plus the one distribution channel the network carries, switched on at the image centre."""
+        """``context`` plus the one distribution channel the network carries, switched on at the image centre - or, for a
+        frames-only predictor (``predictor.frames_only``: no such channel, ``FramesOnlyHipVPredEvaluation``), as it is."""
+        if getattr(self.predictor, 'frames_only', False):
+            return context
         one_hot = np.zeros((self._net_context, self._n_cam, self._img_height, self._img_width, 1), np.float32)
         one_hot[:, :, self._img_height // 2, self._img_width // 2, :] = 1.
         return dict(context, context_pixel_distributions=one_hot)

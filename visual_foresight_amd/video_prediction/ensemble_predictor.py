@@ -49,6 +49,10 @@ class EnsembleHipPredictor(object):
         if _dist_info()[1] == 1 and int(n_gpus) > 1:
             raise ValueError('EnsembleHipPredictor has no in-process multi-GPU lanes (n_gpus=%d): run one rank per GPU '
                              'under torch.distributed instead' % int(n_gpus))
+        from visual_foresight_amd.video_prediction.hip_predictor import designated_pixel_count_of
+        if designated_pixel_count_of(hp) == 0:      # (before a member engine is built)
+            raise ValueError('EnsembleHipPredictor combines the members\' pixel-cost sums: its members cannot be frames-only '
+                             '(designated_pixel_count 0 / no_pix_distrib)')
         stochastic = hp.pop('stochastic', None)
         if stochastic is None:
             stochastic = 'n_latent' in hp or hp.get('arch', 'cdna') != 'cdna'

@@ -56,10 +56,31 @@ def transformation_of(hparams):
     return str(hparams.get('transformation', legacy))
 
 
+def designated_pixel_count_of(hparams):
+    """Designated pixels per view a predictor hyper-parameter dictionary asks for: ``'designated_pixel_count'`` (default 1).
+    0 builds a FRAMES-ONLY engine - the same frames and states, no pixel distribution anywhere.  The
+    reference names that mode by the bare predictor conf key ``no_pix_distrib`` (``video_prediction/setup_predictor.py:
+    110-114``: ``pix_distrib = None``, ``gen_distrib`` is never built; its learned-cost experiments set it to ``''``): the
+    key's presence, whatever its value, selects 0 here too."""
+    if 'no_pix_distrib' in hparams:
+        return 0
+    n = int(hparams.get('designated_pixel_count', 1))
+    if not 0 <= n <= 4:
+        raise ValueError('designated_pixel_count must be 0 (frames-only) .. 4, got %r' % (n,))
+    return n
+
+
 class HipVPredEvaluation(object):
     wants_agent_params = True       # PixelCostController passes adim/sdim/size/sequence_length
     supports_task_weights = True    # score(..., task_weights=) applies trade-off weights on the device
+    supports_frames_only = True     # designated_pixel_count 0 / no_pix_distrib: an engine without distributions
+    force_frames_only = False       # FramesOnlyHipVPredEvaluation: 0 whatever the hyper-parameters say
     n_context_default = 2
+
+    @classmethod
+    def ndesig_of(cls, hparams):
+        """The engine's designated-pixel count for ``hparams`` (no device needed)."""
+        return 0 if cls.force_frames_only else designated_pixel_count_of(hparams)
 
     def __init__(self, model_path, hparams, n_gpus=1, first_gpu=0):
         import torch
@@ -97,8 +118,12 @@ class HipVPredEvaluation(object):
                 extra = dict(extra, transformation=transformation)
         self.cfg = cfg_cls(height=hp.get('image_height', 64), width=hp.get('image_width', 64),
                            adim=hp.get('adim', 4), sdim=hp.get('sdim', 5),
-                           ndesig=hp.get('designated_pixel_count', 1), n_context=self.n_context,
+                           ndesig=self.ndesig_of(hp), n_context=self.n_context,
                            sequence_length=self.sequence_length, **extra)
+        self.frames_only = self.cfg.ndesig == 0
+        if self.frames_only and self.arch == 'savp3':
+            raise ValueError("arch 'savp3' has no frames-only mode (designated_pixel_count 0 / no_pix_distrib): "
+                             "use 1..4 designated pixels")
         if not torch.cuda.is_available():
             raise _lib.VfError('HipVPredEvaluation needs a ROCm GPU (no CPU fallback)')
         world = _dist_info()[1]
@@ -170,6 +195,8 @@ class HipVPredEvaluation(object):
             raise ValueError("gather must be 'auto', 'rccl' or 'host'")
         if world == 1 and self.n_gpus > 1 and not hp.get('_lane'):
             lane_hp = dict(hp, _lane=True, oversubscribe_gpus=1)
+            lane_hp['designated_pixel_count'] = self.cfg.ndesig     # (a frames-only predictor's lanes are frames-only)
+            lane_hp.pop('no_pix_distrib', None)
             self._lanes = [self] + [HipVPredEvaluation(model_path, lane_hp, n_gpus=1, first_gpu=int(first_gpu) + i)
                                     for i in range(1, self.n_gpus)]
             distinct = len({l.device_index for l in self._lanes}) == self.n_gpus
@@ -250,6 +277,15 @@ class HipVPredEvaluation(object):
             raise _lib.VfError('the persistent rollout kernel reported a failure (device status %d): a tile gave '
                                'up waiting for its producers; scores are invalid' % self.device_status())
 
+    def _check_status(self):
+        """The same refusal for a frames-only rollout, which has no pixel scores to poison: read the failure word."""
+        st = self.device_status()
+        if st != 0:
+            for lane in self._all_lanes():
+                lane._ctx_key = None
+            raise _lib.VfError('the persistent rollout kernel reported a failure (device status %d): a tile gave '
+                               'up waiting for its producers; predictions are invalid' % st)
+
     def set_dedup(self, enable):
         """Switch context de-duplication (bit-identical results either way; for A/B timing)."""
         for lane in self._all_lanes():
@@ -296,8 +332,14 @@ class HipVPredEvaluation(object):
         if frames.dtype != np.uint8 or frames.shape != (nc, ncam, c.height, c.width, 3):
             raise ValueError('context_frames must be uint8 [>=%d, %d, %d, %d, 3], got %s %s'
                              % (nc, ncam, c.height, c.width, frames.dtype, frames.shape))
-        distrib = np.ascontiguousarray(
-            np.asarray(context['context_pixel_distributions'], dtype=np.float32)[-nc:, :ncam])
+        if self.frames_only:
+            if context.get('context_pixel_distributions') is not None:
+                raise ValueError('this predictor is frames-only (designated_pixel_count 0 / no_pix_distrib): the context '
+                                 'must not carry context_pixel_distributions')
+            distrib = np.zeros((nc, ncam, c.height, c.width, 0), np.float32)
+        else:
+            distrib = np.ascontiguousarray(
+                np.asarray(context['context_pixel_distributions'], dtype=np.float32)[-nc:, :ncam])
         states = np.ascontiguousarray(np.asarray(context['context_states'], dtype=np.float32)[-nc:])
         if states.shape != (nc, c.sdim) or distrib.shape != (nc, ncam, c.height, c.width, c.ndesig):
             raise ValueError('bad context shapes: states %s distrib %s' % (states.shape, distrib.shape))
@@ -318,11 +360,15 @@ class HipVPredEvaluation(object):
         self._ctx = [torch.from_numpy(a).to(dev) for a in (frames, states, acts, distrib)]
         f, s, a, d = self._ctx
         _lib.check(self._libh.vf_set_context(self._handle, f.data_ptr(), s.data_ptr(), a.data_ptr(),
-                                             d.data_ptr(), self._stream()))
+                                             None if self.frames_only else d.data_ptr(), self._stream()))
 
     # ------------------------------------------------------------------ rollouts
     def _rollout_chunk(self, actions_dev, goal_pix, finalweight, scores_dev, per_task_dev, task_weights=None):
         B = actions_dev.shape[0]
+        if self.frames_only:        # no goal pixel, no pixel cost: the library wants NULL for all of them
+            _lib.check(self._libh.vf_rollout(self._handle, actions_dev.data_ptr(), B, None, ctypes.c_float(finalweight),
+                                             None, None, None, self._stream()))
+            return
         ntask = self.n_cam * self.cfg.ndesig
         goal = np.asarray(goal_pix).reshape(-1)
         if goal.size != 2 * ntask:
@@ -386,6 +432,7 @@ class HipVPredEvaluation(object):
         ``fetch_pixel_distributions``; with ``M <= run_batch_size`` (the reference default,
         ``pixel_cost_controller.py:31``) that is the whole local shard.
         """
+        self._refuse_frames_only('score')
         actions = self._check_actions(inputs['actions'])
         M = actions.shape[0]
         rank, world = _dist_info()
@@ -414,6 +461,21 @@ class HipVPredEvaluation(object):
             per_task_np = per_task_np[:, :1]
             scores_np = per_task_np[:, 0].copy()
         return scores_np, per_task_np
+
+    def _refuse_frames_only(self, what):
+        if self.frames_only:
+            raise ValueError('%s needs pixel distributions; this predictor is frames-only (designated_pixel_count 0 / '
+                             'no_pix_distrib)' % what)
+
+    def _centre_context(self, context):
+        """``context`` as the frame costs roll it: with the image centre switched on in the distribution channels the
+        network carries - or, frames-only, as it is (there is no such channel)."""
+        if self.frames_only:
+            return context
+        c = self.cfg
+        centre = np.zeros((self.n_context, self.n_cam, c.height, c.width, c.ndesig), np.float32)
+        centre[:, :, c.height // 2, c.width // 2, :] = 1.0
+        return dict(context, context_pixel_distributions=centre)
 
     # ------------------------------------------------------------------ goal-image cost
     def _check_goal_image(self, goal_image):
@@ -469,7 +531,7 @@ class HipVPredEvaluation(object):
         Sharding, chunking, lanes and latent draws are those of ``score``.  The rollout entry still wants goal pixels
         and a distribution context: the image centre is passed for both (``context_pixel_distributions`` of
         ``context`` is not read) and its pixel scores are dropped - the price is the ``ndesig`` distribution
-        channels the network carries anyway."""
+        channels the network carries anyway.  A frames-only predictor carries none and passes neither."""
         goal = self._check_goal_image(goal_image)
         if steps not in ('last', 'weighted'):
             raise ValueError("steps must be 'last' or 'weighted', got %r" % (steps,))
@@ -478,9 +540,7 @@ class HipVPredEvaluation(object):
         M = actions.shape[0]
         ncam, c, nd = self.n_cam, self.cfg, self.n_draws
         T = self.sequence_length - self.n_context
-        centre = np.zeros((self.n_context, ncam, c.height, c.width, c.ndesig), np.float32)
-        centre[:, :, c.height // 2, c.width // 2, :] = 1.0
-        ctx_p, seqs = self._prepare(dict(context, context_pixel_distributions=centre), actions)
+        ctx_p, seqs = self._prepare(self._centre_context(context), actions)
         self._last_prepared = (ctx_p, seqs, M)
         rank, world = _dist_info()
         torch = self._torch
@@ -590,9 +650,7 @@ class HipVPredEvaluation(object):
             goal_enc = None
         actions = self._check_actions(inputs['actions'])
         M = actions.shape[0]
-        centre = np.zeros((self.n_context, ncam, c.height, c.width, c.ndesig), np.float32)
-        centre[:, :, c.height // 2, c.width // 2, :] = 1.0
-        ctx_p, seqs = self._prepare(dict(context, context_pixel_distributions=centre), actions)
+        ctx_p, seqs = self._prepare(self._centre_context(context), actions)
         self._last_prepared = (ctx_p, seqs, M)
         rank, world = _dist_info()
         torch = self._torch
@@ -729,6 +787,7 @@ class HipVPredEvaluation(object):
         more - ``num_samples > vpred_batch_size``, e.g. the reference's 600-sample RoboNet configs - is simply rolled
         again, alone: a sample's arithmetic does not depend on the batch it is rolled in, so the result is
         bit-identical to the first pass, and every rank can do it locally without a collective."""
+        self._refuse_frames_only('fetch_pixel_distributions')
         torch, c = self._torch, self.cfg
         T = self.sequence_length - self.n_context
         rank, world = _dist_info()
@@ -776,7 +835,8 @@ class HipVPredEvaluation(object):
         rows = (np.asarray(indices, dtype=np.int64)[:, None] * nd + np.arange(nd)[None]).reshape(-1)
         self._set_context(ctx_p)
         seq = torch.from_numpy(np.ascontiguousarray(np.asarray(seqs)[rows], dtype=np.float32)).to(self.device)
-        scores = torch.empty(n, dtype=torch.float64, device=self.device)
+        # (a frames-only rollout writes no pixel scores: zeros stand in, the failure word is read instead)
+        scores = (torch.zeros if self.frames_only else torch.empty)(n, dtype=torch.float64, device=self.device)
         per_task = torch.empty((n, ntask), dtype=torch.float64, device=self.device)
         self._rollout_chunk(seq, np.zeros((self.n_cam, self.cfg.ndesig, 2), np.int32), 1.0, scores, per_task)
         # what is resident now is not a range of the scoring call, unless it is one action.  Under torch.distributed
@@ -831,6 +891,8 @@ class HipVPredEvaluation(object):
             raise ValueError('indices must be a non-empty 1-d integer sequence, got %r' % (indices,))
         if not (frames or distributions):
             raise ValueError('nothing to render: frames and distributions are both off')
+        if distributions:
+            self._refuse_frames_only('render_plans(distributions=True)')
         if idx.min() < 0 or idx.max() >= prepared[2]:
             raise IndexError('indices %s outside the last scoring call (%d actions)' % (idx.tolist(), prepared[2]))
         if len(np.unique(idx)) != idx.size:
@@ -849,6 +911,8 @@ class HipVPredEvaluation(object):
                     rolled.append(self._reroll(group))
                     parts.append(self._render_resident(np.arange(group.size) * nd, lut_dev, frames, distributions))
                 self._check_scores(torch.cat(rolled).cpu().numpy())
+                if self.frames_only:
+                    self._check_status()
             out = {}
             if frames:
                 out['frames'] = torch.cat([p[0] for p in parts]).cpu().numpy()
@@ -928,7 +992,12 @@ class HipVPredEvaluation(object):
             frames = np.asarray(input_images)[0]
             if frames.dtype != np.uint8:        # get_context hands over float frames in [0, 1]
                 frames = np.rint(frames * 255.).astype(np.uint8)
-            if input_one_hot_images is None:
+            if self.frames_only:
+                if input_one_hot_images is not None:
+                    raise ValueError('this predictor is frames-only (designated_pixel_count 0 / no_pix_distrib): '
+                                     'input_one_hot_images must be None')
+                distrib = None
+            elif input_one_hot_images is None:
                 distrib = np.zeros((nc, 1, c.height, c.width, c.ndesig), np.float32)
                 distrib[:, :, 0, 0, :] = 1.0
             else:
@@ -936,6 +1005,8 @@ class HipVPredEvaluation(object):
             context = {'context_frames': frames, 'context_states': np.asarray(input_state)[0],
                        'context_actions': ctx_actions[0] if nc > 1 else np.zeros((1, c.adim)),
                        'context_pixel_distributions': distrib}
+            if distrib is None:
+                del context['context_pixel_distributions']
             out = self(context, {'actions': future})
             return (out['predicted_frames'],
                     None if input_one_hot_images is None else out['predicted_pixel_distributions'],
@@ -960,7 +1031,7 @@ class HipVPredEvaluation(object):
                     lane._last_lo, lane._last_M = lo, 0
             if not parts:       # M == 0: empty arrays of the right shapes
                 return self._materialise(context, seqs, 0, 0)
-            return {k: np.concatenate([p[k] for p in parts], axis=0) for k in parts[0]}
+            return {k: None if parts[0][k] is None else np.concatenate([p[k] for p in parts], axis=0) for k in parts[0]}
         return self._materialise(context, seqs, actions.shape[0], 0)
 
     def _materialise(self, context, seqs, M, index_base):
@@ -968,7 +1039,9 @@ class HipVPredEvaluation(object):
         T = self.sequence_length - self.n_context
         ncam, nd = self.n_cam, self.n_draws
         frames = np.empty((M, T, ncam, c.height, c.width, 3), np.float32)
-        distrib = np.empty((M, T, ncam, c.height, c.width, c.ndesig), np.float32)
+        # (frames-only: 'predicted_pixel_distributions' is None - what the reference's predictor_func returns for gen_distrib
+        # under no_pix_distrib)
+        distrib = None if self.frames_only else np.empty((M, T, ncam, c.height, c.width, c.ndesig), np.float32)
         states = np.empty((M, T, c.sdim), np.float32)
         zero_goal = np.zeros((ncam, c.ndesig, 2), np.int32)
         bs = self.run_batch_size // nd
@@ -983,20 +1056,32 @@ class HipVPredEvaluation(object):
                 self._rollout_chunk(acts[c0 * nd:c1 * nd], zero_goal, 1.0, scores[:n], per_task[:n])
                 self._last_lo, self._last_M = index_base + c0, n
                 f = torch.empty((n * nd, T, ncam, c.height, c.width, 3), dtype=torch.float32, device=self.device)
-                d = torch.empty((n * nd, T, ncam, c.height, c.width, c.ndesig), dtype=torch.float32,
-                                device=self.device)
+                d = None if self.frames_only else torch.empty((n * nd, T, ncam, c.height, c.width, c.ndesig),
+                                                              dtype=torch.float32, device=self.device)
                 s = torch.empty((n * nd, T, c.sdim), dtype=torch.float32, device=self.device)
-                _lib.check(self._libh.vf_export(self._handle, 0, n * nd, f.data_ptr(), d.data_ptr(), s.data_ptr(),
-                                                self._stream()))
+                _lib.check(self._libh.vf_export(self._handle, 0, n * nd, f.data_ptr(), None if d is None else d.data_ptr(),
+                                                s.data_ptr(), self._stream()))
                 frames[c0:c1] = f[::nd].cpu().numpy()
-                distrib[c0:c1] = d[::nd].cpu().numpy()
+                if d is not None:
+                    distrib[c0:c1] = d[::nd].cpu().numpy()
                 states[c0:c1] = s[::nd].cpu().numpy()
-            if M > 0:
+            if M > 0 and not self.frames_only:
                 self._check_scores(scores[:n].cpu().numpy())
+            elif M > 0:
+                self._check_status()
             else:
                 self._last_lo, self._last_M = index_base, 0
         return {'predicted_frames': frames, 'predicted_pixel_distributions': distrib,
                 'predicted_states': states}
+
+
+class FramesOnlyHipVPredEvaluation(HipVPredEvaluation):
+    """``HipVPredEvaluation`` with zero designated pixels whatever ``designated_pixel_count`` its hyper-parameters carry:
+    the controllers that score predicted FRAMES (``ClassifierController``, ``NCECostController``, ``GoalImController``) pass
+    1, because the network used to need a distribution channel.  ``policy['predictor_class'] =
+    FramesOnlyHipVPredEvaluation`` selects the frames-only engine without a new policy hyper-parameter - the reference's
+    ``no_pix_distrib`` predictor conf."""
+    force_frames_only = True
 
 
 class MultiViewHipPredictor(HipVPredEvaluation):
