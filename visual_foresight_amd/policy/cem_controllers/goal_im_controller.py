@@ -31,7 +31,7 @@ With one view and the default hyper-parameters the score is the reference's: the
 import numpy as np
 
 from .cem_base_controller import CEMBaseController
-from .pixel_cost_controller import _default_predictor_class, build_predictor
+from .pixel_cost_controller import _default_predictor_class, build_predictor, context_states
 
 
 def prepare_goal_image(goal_image, ncam, height, width, raw=False):
@@ -112,7 +112,7 @@ class GoalImController(CEMBaseController):
         context = {
             "context_frames": self._images,
             "context_actions": self._sampler.chosen_actions,
-            "context_states": self._state,
+            "context_states": context_states(self),
         }
         if hasattr(self.predictor, 'score_goal_image'):
             scores, per_view = self.predictor.score_goal_image(

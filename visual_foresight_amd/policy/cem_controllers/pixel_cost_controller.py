@@ -25,10 +25,25 @@ def _default_predictor_class(ncam=1):
     return HipVPredEvaluation
 
 
+def context_states(ctrl):
+    """The state history a controller hands to its predictor: ``ctrl._state [t+1, sdim]`` as it is, or - with the
+    ``state_append`` hyper-parameter, a list of k constants - ``[t+1, sdim + k]`` with the constants appended to every
+    row, as ``pred_util.get_context`` appends them at the legacy boundary (reference ``pred_util.py:9-11``).  Experiments
+    use it for state dimensions the network was trained with and the robot does not report.  The sampler keeps
+    receiving the agent's own state."""
+    extra = ctrl._hp.get('state_append')
+    if not extra:
+        return ctrl._state
+    state = np.asarray(ctrl._state)
+    tail = np.broadcast_to(np.asarray(extra), state.shape[:-1] + (len(extra),))
+    return np.concatenate((state, tail), axis=-1)
+
+
 def build_predictor(ctrl, predictor_class, ag_params, gpu_id, ngpu, designated_pixel_count, horizon):
     """Construct and restore the video predictor of a CEM controller (reference ``pixel_cost_controller.py:29-36``) and
     raise the controller's ``start_planning`` to the network's context.  Shared by the controllers that plan on
-    predicted videos (``PixelCostController`` and its variants, ``GoalImController``)."""
+    predicted videos (``PixelCostController`` and its variants, ``GoalImController``).  The predictor's ``sdim`` is the
+    agent's plus the number of ``state_append`` constants: the width of ``context_states(ctrl)``."""
     hp = ctrl._hp
     predictor_hparams = {
         'designated_pixel_count': designated_pixel_count,
@@ -38,7 +53,7 @@ def build_predictor(ctrl, predictor_class, ag_params, gpu_id, ngpu, designated_p
         # the HIP predictor is shape-specialised at construction (no checkpoint json to read
         # adim/sdim/size/T from), so it is told what the controller will ask of it
         predictor_hparams.update(
-            adim=ctrl._adim, sdim=ctrl._sdim,
+            adim=ctrl._adim, sdim=ctrl._sdim + len(hp.get('state_append') or ()),
             image_height=ag_params['image_height'], image_width=ag_params['image_width'],
             ncam=ag_params.get('ncam', 1),
             sequence_length=horizon + predictor_class.n_context_default)
@@ -113,7 +128,7 @@ class PixelCostController(CEMBaseController):
             "context_frames": self._images,
             "context_actions": self._sampler.chosen_actions,
             "context_pixel_distributions": self._make_input_distrib(cem_itr),
-            "context_states": self._state,
+            "context_states": context_states(self),
         }
         if hasattr(self.predictor, 'score'):
             weights = self._task_weights()

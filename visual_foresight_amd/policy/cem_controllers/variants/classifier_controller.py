@@ -34,7 +34,7 @@ import json
 import numpy as np
 
 from ..cem_base_controller import CEMBaseController
-from ..pixel_cost_controller import _default_predictor_class, build_predictor
+from ..pixel_cost_controller import _default_predictor_class, build_predictor, context_states
 from visual_foresight_amd.video_prediction import frame_scorer_arch
 
 
@@ -115,7 +115,7 @@ class LearnedCostController(CEMBaseController):
         context = {
             "context_frames": self._images,
             "context_actions": self._sampler.chosen_actions,
-            "context_states": self._state,
+            "context_states": context_states(self),
         }
         goal_enc = self._goal_enc()
         if hasattr(self.predictor, 'score_frames'):

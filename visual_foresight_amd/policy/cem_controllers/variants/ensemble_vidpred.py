@@ -13,7 +13,7 @@ axis here and any M works.
 """
 import numpy as np
 
-from ..pixel_cost_controller import PixelCostController
+from ..pixel_cost_controller import PixelCostController, context_states
 
 
 def ensemble_expected_distance(gen_distrib, distance_grid, lambda_variance, finalweight, normalize=True):
@@ -65,7 +65,7 @@ class CEM_Controller_Ensemble_Vidpred(PixelCostController):
             "context_frames": self._images,
             "context_actions": self._sampler.chosen_actions,
             "context_pixel_distributions": self._make_input_distrib(cem_itr),
-            "context_states": self._state,
+            "context_states": context_states(self),
         }
         prediction = self.predictor(context, {'actions': actions})
         scores = self._eval_pixel_cost(cem_itr, prediction['ensemble_pixel_distributions'],
