@@ -25,6 +25,7 @@
 #include <cstring>
 #include <cstdlib>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include <dlfcn.h>
@@ -479,7 +480,8 @@ static std::vector<float> pack_bias(const ConvLayer &l, const float *b) {
 using namespace vf;
 
 // Views of the engine's working buffers: one per camera view and one "shared" set of batch-1
-// buffers per view for tensors that are identical for every sample (see emit_rollout).
+// buffers per view for tensors that are identical for every sample (see emit_rollout).  This is the one list of the
+// buffers' names: every member is a pointer, and the engine's layout table (vf_handle::spec) has one entry per member.
 struct BatchView {
     float *enc0_o, *enc1_o, *enc2_o, *enc3_o, *enc4_o, *enc5_o, *enc6_o;
     float *enc00_o, *enc7_o;            // arch 1: extra encoder / decoder scale
@@ -493,6 +495,16 @@ struct BatchView {
     float *frames_all, *distrib_all, *states_all;
     double *sums;
     const float *actions;
+};
+static const int kViewSlots = (int)(sizeof(BatchView) / sizeof(void *));
+static_assert(sizeof(BatchView) == kViewSlots * sizeof(void *) && std::is_standard_layout<BatchView>::value,
+              "BatchView is an array of pointers");
+
+// Layout of one BatchView member: rows of `per` elements, one row per sample, [ncam][max_batch] rows in the full buffer
+struct BufSpec {
+    size_t per = 0;                     // elements per sample
+    int esize = 0;                      // bytes per element; 0: this engine has no such buffer
+    bool shared = false;                // the shared views hold a batch-1 copy
 };
 
 // Device-resident parameters and context of one camera view (the reference's multi-view models
@@ -517,11 +529,11 @@ struct vf_handle {
     bool savp = false;                  // vf_config.arch >= 1: four-scale SAVP-class generator (savp_arch.py)
     vf::Savp3 *s3 = nullptr;            // vf_config.arch == 3: the published SAVP generator (vf_engine_savp3.inc)
     bool cond = false;                  // vf_config.arch == 2: [action, latent, state] conditions every conv-LSTM
+                                        // ... through per-sample border-class biases (BatchView::cond_bias)
     bool flow = false;                  // arch 0, layer_spec 2: appearance-flow compositing - no CDNA FC, no kernels; the flow
                                         // kernels (composite_flow_kernel, rollout_flow_kernel) run in place of the CDNA ones
     bool dna = false;                   // arch 0, layer_spec 3: DNA compositing - no CDNA FC, no kernel table, no rgb head; the
                                         // head lives in ViewData::w_flow / b_flow; composite_dna_kernel, rollout_dna_kernel run
-    float *cond_bias[7] = {nullptr};    // ... through per-sample border-class biases [2 step parities][ncam][max_batch][25][4C]
     int Hc, Wc;                         // input size of the three-scale conv-LSTM core (H, W; arch 1: H/2, W/2)
     int c_t2 = 64, c_top = 32;          // output channels of convt2 / convt3 (arch 0, layer_spec 1 - the public table: 96 / 64)
     int ncam = 1, n_draws = 1;
@@ -558,14 +570,18 @@ struct vf_handle {
     float *ctx_frames_all = nullptr, *ctx_distrib_all = nullptr;
     float *ctx_states = nullptr, *ctx_actions = nullptr;
 
-    // activations, [ncam][max_batch] samples each
-    float *enc0_o = nullptr, *enc1_o = nullptr, *enc2_o = nullptr, *enc3_o = nullptr;
-    float *enc4_o = nullptr, *enc5_o = nullptr, *enc6_o = nullptr, *enc00_o = nullptr, *enc7_o = nullptr;
-    float *c_state[7] = {nullptr}, *h_state[7][2] = {{nullptr}};
-    long long *st_enc0 = nullptr, *st_h[7] = {nullptr}, *st_enc6 = nullptr, *st_enc00 = nullptr, *st_enc7 = nullptr;
-    float *sbias = nullptr, *fc_part = nullptr, *kern = nullptr;
+    // Activations, states, statistics and predictions, [ncam][max_batch] samples each: `base` holds the first row of every
+    // buffer, `spec` its layout, slot by slot (row_spec / alloc_view / make_view).  The engine's
+    // create function fills `spec` once, from its layer plans; nothing else writes a per-sample size.
+    BatchView base = {};
+    BufSpec spec[kViewSlots];
+    // the slot of `field`, a member of `base`, and its elements per sample
+    template <class T> int slot(T *const &field) const {
+        return (int)((reinterpret_cast<const char *>(&field) - reinterpret_cast<const char *>(&base)) / sizeof(void *));
+    }
+    template <class T> long long per(T *const &field) const { return (long long)spec[slot(field)].per; }
 
-    // predictions of the last rollout
+    // predictions of the last rollout (= base.frames_all, ...: the calls that read them whole take them from here)
     float *frames_all = nullptr, *distrib_all = nullptr, *states_all = nullptr;
     double *sums = nullptr;
     long long sums_step_stride = 0, sums_view_stride = 0;
@@ -636,9 +652,8 @@ struct vf_handle {
 
 namespace vf {
 
-template <typename T>
-static int dev_alloc(vf_handle *h, T **p, size_t n) {
-    const size_t bytes = std::max<size_t>(n, 1) * sizeof(T);
+static int dev_alloc_bytes(vf_handle *h, void **p, size_t n, size_t esize) {
+    const size_t bytes = std::max<size_t>(n, 1) * esize;
     void *q = nullptr;
 #ifdef VF_HOST_SELFTEST
     // address reservation only: the self-test never dereferences a "device" pointer
@@ -651,8 +666,16 @@ static int dev_alloc(vf_handle *h, T **p, size_t n) {
         return fail(VF_ERR_NOMEM, "hipMalloc of " + std::to_string(bytes) + " bytes failed");
 #endif
     h->allocs.push_back({q, bytes});
-    *p = reinterpret_cast<T *>(q);
+    *p = q;
     return VF_OK;
+}
+
+template <typename T>
+static int dev_alloc(vf_handle *h, T **p, size_t n) {
+    void *q = nullptr;
+    const int rc = dev_alloc_bytes(h, &q, n, sizeof(T));
+    if (rc == VF_OK) *p = static_cast<T *>(q);
+    return rc;
 }
 
 // host -> device copy of freshly packed parameters (blocking; vf_load_weights only)
@@ -919,6 +942,126 @@ static double gs_pad_skipped_pairs(const ConvLayer &l, int B) {
 
 }  // namespace vf
 
+// (in a create function: allocate, or return the error)
+#define VF_ALLOC(ptr, n)                           \
+    do {                                           \
+        rc = dev_alloc(h, &(ptr), (size_t)(n));    \
+        if (rc) return rc;      \
+    } while (0)
+
+// ------------------------------------------------------------------ per-sample buffers
+// A create function describes every per-sample buffer of its engine ONCE, with row_spec(); the loops below - alloc_view for the
+// full buffers and the shared views, make_view - are all that sizes or strides one.  The exceptions, hand-written here and nowhere
+// else, are the BatchView members that are not [ncam][max_batch] rows:
+//   cond_bias  (arch 2) [parity][ncam][max_batch] rows in the full buffer; the two parities of a shared view are contiguous
+//   rec_part   shared views only
+//   sums       [step][view][max_batch] (sums_step_stride, sums_view_stride)
+//   actions    the caller's sequences, shared by the views
+static void *view_get(const BatchView &v, int slot) {
+    void *p;
+    memcpy(&p, reinterpret_cast<const char *>(&v) + slot * sizeof(void *), sizeof(p));
+    return p;
+}
+static void view_set(BatchView &v, int slot, void *p) { memcpy(reinterpret_cast<char *>(&v) + slot * sizeof(void *), &p, sizeof(p)); }
+
+// `field`, a member of h->base, is rows of `per` elements; `shared`: the shared views hold a batch-1 copy
+template <class T>
+static void row_spec(vf_handle *h, T *&field, size_t per, bool shared) {
+    BufSpec &b = h->spec[h->slot(field)];
+    b.per = per; b.esize = (int)sizeof(T); b.shared = shared;
+}
+static size_t cond_bias_elems(const vf_handle *h, int k) { return (size_t)kCondClasses * 4 * h->lstm[k].Cout; }
+
+// The buffers of `rows` samples: the full ones (h->base, ncam x max_batch rows), or - shared_only - the batch-1 copies of
+// one view for the tensors that context de-duplication shares between the samples
+static int alloc_view(vf_handle *h, BatchView &dst, size_t rows, bool shared_only) {
+    int rc;
+    for (int i = 0; i < kViewSlots; ++i) {
+        const BufSpec &b = h->spec[i];
+        if (!b.esize || (shared_only && !b.shared)) continue;
+        void *p = nullptr;
+        if ((rc = dev_alloc_bytes(h, &p, rows * b.per, b.esize))) return rc;
+        view_set(dst, i, p);
+    }
+    for (int k = 0; k < 7; ++k) {
+        // (the shared recurrent partial's image, raw gate sums [pixel][4C]: only where a unit can be emitted - emit_rollout)
+        if (shared_only && h->share_recurrent && h->lstm[k].tile == TILE_LSTM_GS128)
+            VF_ALLOC(dst.rec_part[k], 4 * h->per(h->base.c_state[k]));
+        if (!h->cond) continue;
+        VF_ALLOC(dst.cond_bias[k][0], 2 * rows * cond_bias_elems(h, k));
+        dst.cond_bias[k][1] = dst.cond_bias[k][0] + rows * cond_bias_elems(h, k);
+    }
+    return VF_OK;
+}
+
+// the rows of camera view `view` in every buffer
+static BatchView make_view(vf_handle *h, int view, const float *d_actions) {
+    const size_t row = (size_t)view * h->cfg.max_batch;
+    BatchView v;
+    memset(&v, 0, sizeof(v));
+    for (int i = 0; i < kViewSlots; ++i)
+        if (h->spec[i].esize)
+            view_set(v, i, static_cast<char *>(view_get(h->base, i)) + row * h->spec[i].per * h->spec[i].esize);
+    for (int k = 0; k < 7 && h->cond; ++k)
+        for (int par = 0; par < 2; ++par) v.cond_bias[k][par] = h->base.cond_bias[k][par] + row * cond_bias_elems(h, k);
+    v.sums = h->ND > 0 ? h->sums + (long long)view * h->sums_view_stride : nullptr;
+    v.actions = d_actions;
+    return v;
+}
+
+// The CDNA FC as a K-split GEMM over 1x1 "images": k_in inputs, the taps of n_kern kernels out
+static void plan_fc(vf_handle *h, int k_in, int n_kern) {
+    ConvLayer &f = h->fc;
+    init_layer(f, "cdna", PACK_PLAIN, 1, 1, 1, 1, 1, 1, 1, 0, k_in, 0, kTaps * n_kern, false, true, 256);
+    const int total = f.nchunk[0];
+    f.nsplit = std::min(32, total);
+    f.chunks_per_split = (total + f.nsplit - 1) / f.nsplit;
+    f.nsplit = (total + f.chunks_per_split - 1) / f.chunks_per_split;
+    f.n_valid = kTaps * n_kern;
+    // the persistent schedule's plan: same packed weights, same chunks and splits, 128 rows x all column groups
+    h->fc_wide = f;
+    h->fc_wide.tile = TILE_FC_WIDE; h->fc_wide.NI = kFcRows; h->fc_wide.lds_bytes = fc_wide_lds_bytes();
+    h->fc_wide_ok = f.KC == 32 && f.ncg <= kFcGroups && f.nseg == 1 && f.segC[0] % 32 == 0;
+}
+
+// What every engine has next to its layers' parameters and buffers: the context, the rows its create function described
+// (above) and those of the predictions, the cost sums, and the schedule and synchronisation words of the persistent launch,
+// sized for `phases_per_step` phases a step
+static int alloc_common(vf_handle *h, int phases_per_step) {
+    const vf_config &c = h->cfg;
+    const int H = h->H, W = h->W, ND = h->ND, NV = h->ncam, T = h->T, nc = c.n_context, Bc = c.max_batch;
+    int rc;
+    VF_ALLOC(h->ctx_frames_all, (size_t)NV * nc * H * W * 3);
+    // (a frames-only engine, ndesig 0: no context distributions, no predicted distributions, no block sums - the pointers stay
+    // null and nothing on the device reads them)
+    if (ND > 0) VF_ALLOC(h->ctx_distrib_all, (size_t)NV * nc * H * W * ND);
+    for (int v = 0; v < NV; ++v) {
+        h->views[v].ctx_frames = h->ctx_frames_all + (size_t)v * nc * H * W * 3;
+        h->views[v].ctx_distrib = ND > 0 ? h->ctx_distrib_all + (size_t)v * nc * H * W * ND : nullptr;
+    }
+    VF_ALLOC(h->ctx_states, (size_t)nc * c.sdim);
+    VF_ALLOC(h->ctx_actions, (size_t)std::max(nc - 1, 1) * c.adim);
+
+    row_spec(h, h->base.frames_all, (size_t)T * H * W * 3, false);
+    if (ND > 0) row_spec(h, h->base.distrib_all, (size_t)T * H * W * ND, false);
+    row_spec(h, h->base.states_all, (size_t)T * c.sdim, false);
+    if ((rc = alloc_view(h, h->base, (size_t)Bc * NV, false))) return rc;
+    h->frames_all = h->base.frames_all; h->distrib_all = h->base.distrib_all; h->states_all = h->base.states_all;
+    h->sums_view_stride = (long long)Bc * ND * h->nblocks * 2;
+    h->sums_step_stride = h->sums_view_stride * NV;
+    if (ND > 0) VF_ALLOC(h->sums, (size_t)T * h->sums_step_stride);
+    VF_ALLOC(h->goal_mse, (size_t)Bc * NV * T);
+    VF_ALLOC(h->actions_buf, (size_t)Bc * T * c.adim);
+    h->sched_capacity = ((size_t)h->S * phases_per_step + 8) * NV;
+    h->counter_capacity = h->sched_capacity * ((size_t)Bc + 1);
+    VF_ALLOC(h->sched[0].d_phases, h->sched_capacity);
+    VF_ALLOC(h->sched[1].d_phases, h->sched_capacity);
+    VF_ALLOC(h->d_sync, kSyncHead + h->counter_capacity);
+    VF_ALLOC(h->d_status, 1);
+    VF_ALLOC(h->d_stats, h->sched_capacity * 2);
+    return VF_OK;
+}
+
 #include "vf_engine_savp3.inc"
 
 // ================================================================== C ABI
@@ -982,8 +1125,7 @@ double vf_macs_per_sample_step(const vf_config *cfg) {
 static int cdna_create(vf_handle *h) {
     const vf_config *cfg = &h->cfg;
     int rc;
-    const int H = h->H, W = h->W, Bc = cfg->max_batch, ND = h->ND, NV = h->ncam;
-    const size_t BV = (size_t)Bc * NV;          // samples x views: rows of every per-sample buffer
+    const int H = h->H, W = h->W, NV = h->ncam;
     const int Hc = h->Hc, Wc = h->Wc;           // the three-scale core works on Hc x Wc
     const int H2 = Hc / 2, W2 = Wc / 2, H4 = Hc / 4, W4 = Wc / 4, H8 = Hc / 8, W8 = Wc / 8;
     const int *L = kLstmSizes;
@@ -1030,20 +1172,7 @@ static int cdna_create(vf_handle *h) {
     init_layer(h->lstm[6], "lstm7", PACK_LSTM, H2, W2, H2, W2, 5, 5, 1, 2, h->c_t2, L[6], L[6], true, false, 128, cfg->precision, false, ccond);
     init_layer(h->convt3, "convt3", PACK_CONVT, H2, W2, H2, W2, 2, 2, 1, 1, L[6], 32, h->c_top, true, false, 128, 0, true);
     // CDNA FC as a K-split GEMM over 1x1 "images"
-    const int fc_k = h->dna ? 10 : h->K;        // (a DNA engine never runs the FC: its unused plan is sized as the cdna table's)
-    init_layer(h->fc, "cdna", PACK_PLAIN, 1, 1, 1, 1, 1, 1, 1, 0, H8 * W8 * L[4], 0, kTaps * fc_k, false, true, 256);
-    {
-        ConvLayer &f = h->fc;
-        const int total = f.nchunk[0];
-        f.nsplit = std::min(32, total);
-        f.chunks_per_split = (total + f.nsplit - 1) / f.nsplit;
-        f.nsplit = (total + f.chunks_per_split - 1) / f.chunks_per_split;
-        f.n_valid = kTaps * fc_k;
-        // the persistent schedule's plan: same packed weights, same chunks and splits, 128 rows x all column groups
-        h->fc_wide = f;
-        h->fc_wide.tile = TILE_FC_WIDE; h->fc_wide.NI = kFcRows; h->fc_wide.lds_bytes = fc_wide_lds_bytes();
-        h->fc_wide_ok = f.KC == 32 && f.ncg <= kFcGroups && f.nseg == 1 && f.segC[0] % 32 == 0;
-    }
+    plan_fc(h, H8 * W8 * L[4], h->dna ? 10 : h->K);     // (a DNA engine never runs the FC: its unused plan is sized as the cdna table's)
     h->layers = {&h->enc0, &h->lstm[0], &h->lstm[1], &h->enc1, &h->lstm[2], &h->lstm[3], &h->enc2, &h->enc3,
                  &h->lstm[4], &h->convt1, &h->lstm[5], &h->convt2, &h->lstm[6], &h->convt3};
     if (!h->flow && !h->dna) h->layers.push_back(&h->fc);   // (a flow / DNA engine has no CDNA FC: the plan above exists, nothing is packed or run)
@@ -1083,14 +1212,7 @@ static int cdna_create(vf_handle *h) {
     }
     h->max_lds += 16;
 
-#define VF_ALLOC(ptr, n)                           \
-    do {                                           \
-        rc = dev_alloc(h, &(ptr), (size_t)(n));    \
-        if (rc) return rc;      \
-    } while (0)
-
-    // ---- per-view parameters and context: sized from the layer plans, filled by vf_load_weights
-    const int nc = cfg->n_context;
+    // ---- per-view parameters: sized from the layer plans, filled by vf_load_weights
     const int nsa = cfg->adim + cfg->sdim;
     h->views.resize(NV);
     for (ViewData &vd : h->views) {
@@ -1115,92 +1237,40 @@ static int cdna_create(vf_handle *h) {
         if (h->cond)
             for (int k = 0; k < 7; ++k) VF_ALLOC(vd.w_cond[k], (size_t)kTaps * nsa * 4 * L[k]);
     }
-    VF_ALLOC(h->ctx_frames_all, (size_t)NV * nc * H * W * 3);
-    // (a frames-only engine, ndesig 0: no context distributions, no predicted distributions, no block sums - the pointers stay
-    // null and nothing on the device reads them)
-    if (ND > 0) VF_ALLOC(h->ctx_distrib_all, (size_t)NV * nc * H * W * ND);
-    for (int v = 0; v < NV; ++v) {
-        h->views[v].ctx_frames = h->ctx_frames_all + (size_t)v * nc * H * W * 3;
-        h->views[v].ctx_distrib = ND > 0 ? h->ctx_distrib_all + (size_t)v * nc * H * W * ND : nullptr;
-    }
-    VF_ALLOC(h->ctx_states, (size_t)nc * cfg->sdim);
-    VF_ALLOC(h->ctx_actions, (size_t)std::max(nc - 1, 1) * cfg->adim);
 
-    VF_ALLOC(h->enc0_o, BV * H2 * W2 * 32);
-    VF_ALLOC(h->enc1_o, BV * H4 * W4 * L[1]);
-    VF_ALLOC(h->enc2_o, BV * H8 * W8 * L[3]);
-    VF_ALLOC(h->enc3_o, BV * H8 * W8 * L[3]);
-    VF_ALLOC(h->enc4_o, BV * H4 * W4 * L[4]);
-    VF_ALLOC(h->enc5_o, BV * H2 * W2 * h->c_t2);
-    VF_ALLOC(h->enc6_o, BV * Hc * Wc * h->c_top);
+    // ---- per-sample buffers: every size once, from the layer plans (a transposed conv's Hout x Wout is its GEMM row grid: the
+    // image it writes is twice that each way)
+    auto out_elems = [](const ConvLayer &l) { return (size_t)(l.mode == PACK_CONVT ? 4 : 1) * l.Hout * l.Wout * l.Cout; };
+    BatchView &b = h->base;
+    row_spec(h, b.enc0_o, out_elems(h->enc0), true);
+    row_spec(h, b.enc1_o, out_elems(h->enc1), true);
+    row_spec(h, b.enc2_o, out_elems(h->enc2), true);
+    row_spec(h, b.enc3_o, out_elems(h->enc3), true);
+    row_spec(h, b.enc4_o, out_elems(h->convt1), true);
+    row_spec(h, b.enc5_o, out_elems(h->convt2), true);
+    row_spec(h, b.enc6_o, out_elems(h->convt3), false);
     if (h->savp) {
-        VF_ALLOC(h->enc00_o, BV * Hc * Wc * kEnc00Ch);
-        VF_ALLOC(h->enc7_o, BV * H * W * 32);
-        VF_ALLOC(h->st_enc00, BV * h->enc00.stats_nparts * 2);
-        VF_ALLOC(h->st_enc7, BV * h->convt4.stats_nparts * 2);
+        row_spec(h, b.enc00_o, out_elems(h->enc00), true);
+        row_spec(h, b.enc7_o, out_elems(h->convt4), false);
+        row_spec(h, b.st_enc00, (size_t)h->enc00.stats_nparts * 2, true);
+        row_spec(h, b.st_enc7, (size_t)h->convt4.stats_nparts * 2, false);
     }
-    const int lh[7] = {H2, H2, H4, H4, H8, H4, H2}, lw[7] = {W2, W2, W4, W4, W8, W4, W2};
     for (int k = 0; k < 7; ++k) {
-        const size_t elems = BV * lh[k] * lw[k] * L[k];
-        VF_ALLOC(h->c_state[k], elems);
-        VF_ALLOC(h->h_state[k][0], elems);
-        VF_ALLOC(h->h_state[k][1], elems);
-        VF_ALLOC(h->st_h[k], BV * h->st_rows[k] * 2);
+        row_spec(h, b.c_state[k], out_elems(h->lstm[k]), true);
+        row_spec(h, b.h_state[k][0], out_elems(h->lstm[k]), true);
+        row_spec(h, b.h_state[k][1], out_elems(h->lstm[k]), true);
+        row_spec(h, b.st_h[k], (size_t)h->st_rows[k] * 2, true);
     }
-    VF_ALLOC(h->st_enc0, BV * h->enc0.stats_nparts * 2);
-    VF_ALLOC(h->st_enc6, BV * h->convt3.stats_nparts * 2);
-    VF_ALLOC(h->sbias, BV * L[3]);
-    if (h->cond)
-        for (int k = 0; k < 7; ++k) VF_ALLOC(h->cond_bias[k], 2 * BV * kCondClasses * 4 * L[k]);
-    VF_ALLOC(h->fc_part, h->flow || h->dna ? 0 : BV * h->fc.nsplit * kTaps * h->K);
-    VF_ALLOC(h->kern, h->flow || h->dna ? 0 : BV * kTaps * h->K);
-    VF_ALLOC(h->frames_all, BV * h->T * H * W * 3);
-    if (ND > 0) VF_ALLOC(h->distrib_all, BV * h->T * H * W * ND);
-    VF_ALLOC(h->states_all, BV * h->T * cfg->sdim);
-    h->sums_view_stride = (long long)Bc * ND * h->nblocks * 2;
-    h->sums_step_stride = h->sums_view_stride * NV;
-    if (ND > 0) VF_ALLOC(h->sums, (size_t)h->T * h->sums_step_stride);
-    VF_ALLOC(h->goal_mse, BV * h->T);
-    VF_ALLOC(h->actions_buf, (size_t)Bc * h->T * cfg->adim);
-    h->sched_capacity = ((size_t)h->S * 32 + 8) * NV;       // (arch 2: up to 29 phases per step)
-    h->counter_capacity = ((size_t)h->S * 32 + 8) * ((size_t)Bc + 1) * NV;
-    VF_ALLOC(h->sched[0].d_phases, h->sched_capacity);
-    VF_ALLOC(h->sched[1].d_phases, h->sched_capacity);
-    VF_ALLOC(h->d_sync, kSyncHead + h->counter_capacity);
-    VF_ALLOC(h->d_status, 1);
-    VF_ALLOC(h->d_stats, h->sched_capacity * 2);
-    for (int i = 0; i < NV; ++i) {
-        BatchView sv;
-        memset(&sv, 0, sizeof(sv));
-        VF_ALLOC(sv.enc0_o, (size_t)H2 * W2 * 32);
-        VF_ALLOC(sv.enc1_o, (size_t)H4 * W4 * L[1]);
-        VF_ALLOC(sv.enc2_o, (size_t)H8 * W8 * L[3]);
-        VF_ALLOC(sv.enc3_o, (size_t)H8 * W8 * L[3]);
-        VF_ALLOC(sv.enc4_o, (size_t)H4 * W4 * L[4]);
-        VF_ALLOC(sv.enc5_o, (size_t)H2 * W2 * h->c_t2);
-        for (int k = 0; k < 7; ++k) {
-            const size_t per = (size_t)lh[k] * lw[k] * L[k];
-            VF_ALLOC(sv.c_state[k], per);
-            VF_ALLOC(sv.h_state[k][0], per);
-            VF_ALLOC(sv.h_state[k][1], per);
-            VF_ALLOC(sv.st_h[k], (size_t)h->st_rows[k] * 2);
-            // (the shared recurrent partial's image: only where a unit can be emitted - emit_rollout)
-            if (h->share_recurrent && h->lstm[k].tile == TILE_LSTM_GS128) VF_ALLOC(sv.rec_part[k], 4 * per);
-        }
-        VF_ALLOC(sv.st_enc0, (size_t)h->enc0.stats_nparts * 2);
-        if (h->savp) {
-            VF_ALLOC(sv.enc00_o, (size_t)Hc * Wc * kEnc00Ch);
-            VF_ALLOC(sv.st_enc00, (size_t)h->enc00.stats_nparts * 2);
-        }
-        VF_ALLOC(sv.sbias, (size_t)L[3]);
-        if (h->cond)
-            for (int k = 0; k < 7; ++k) {
-                VF_ALLOC(sv.cond_bias[k][0], (size_t)2 * kCondClasses * 4 * L[k]);
-                sv.cond_bias[k][1] = sv.cond_bias[k][0] + (size_t)kCondClasses * 4 * L[k];
-            }
-        h->shared_views.push_back(sv);
-    }
-#undef VF_ALLOC
+    row_spec(h, b.st_enc0, (size_t)h->enc0.stats_nparts * 2, true);
+    row_spec(h, b.st_enc6, (size_t)h->convt3.stats_nparts * 2, false);
+    row_spec(h, b.sbias, (size_t)h->enc3.Cout, true);
+    // (a flow / DNA engine computes no CDNA kernels: rows of no elements, one unused element in all)
+    row_spec(h, b.fc_part, h->flow || h->dna ? 0 : (size_t)h->fc.nsplit * kTaps * h->K, false);
+    row_spec(h, b.kern, h->flow || h->dna ? 0 : (size_t)kTaps * h->K, false);
+    if ((rc = alloc_common(h, 32))) return rc;          // (arch 2: up to 29 phases per step)
+    h->shared_views.resize(NV);
+    for (BatchView &sv : h->shared_views)
+        if ((rc = alloc_view(h, sv, 1, true))) return rc;
     return VF_OK;
 }
 
@@ -1240,7 +1310,7 @@ int vf_create(const vf_config *cfg, vf_handle **out) {
 #ifdef VF_HOST_SELFTEST
     h->fake_size = (size_t)1 << 40;
     void *base = mmap(nullptr, h->fake_size, PROT_NONE, MAP_PRIVATE | MAP_ANONYMOUS | MAP_NORESERVE, -1, 0);
-    if (base == MAP_FAILED) { delete h; return fail(VF_ERR_NOMEM, "self-test address reservation failed"); }
+    if (base == MAP_FAILED) { made = nullptr; delete h; return fail(VF_ERR_NOMEM, "self-test address reservation failed"); }
     h->fake_base = static_cast<char *>(base);
 #endif
 
@@ -1249,6 +1319,7 @@ int vf_create(const vf_config *cfg, vf_handle **out) {
     VF_INJECT(3);
 #ifndef VF_HOST_SELFTEST
     if (hipMemset(h->d_sync, 0, kSyncHead * sizeof(int)) != hipSuccess || hipMemset(h->d_status, 0, sizeof(int)) != hipSuccess) {
+        made = nullptr;     // (fail() may throw: the handle must not be released twice)
         vf_destroy(h);
         return fail(VF_ERR_HIP, "hipMemset of the scheduler words failed");
     }
@@ -1256,6 +1327,7 @@ int vf_create(const vf_config *cfg, vf_handle **out) {
         void *q = nullptr;
         if (hipHostMalloc(&q, h->sched_capacity * sizeof(PhaseDesc), hipHostMallocDefault) != hipSuccess ||
             hipEventCreateWithFlags(&h->stage_done[i], hipEventDisableTiming) != hipSuccess) {
+            made = nullptr;
             vf_destroy(h);
             return fail(VF_ERR_NOMEM, "pinned staging buffer for the schedule failed");
         }
@@ -1463,52 +1535,6 @@ int vf_set_context(vf_handle *h, const uint8_t *d_frames, const float *d_states,
 #endif
 
 }  // extern "C"
-
-static BatchView make_view(vf_handle *h, int view, const float *d_actions, int b0) {
-    const vf_config &c = h->cfg;
-    const int H = h->H, W = h->W, T = h->T, ND = h->ND, Hc = h->Hc, Wc = h->Wc;
-    const int H2 = Hc / 2, W2 = Wc / 2, H4 = Hc / 4, W4 = Wc / 4, H8 = Hc / 8, W8 = Wc / 8;
-    const int *L = kLstmSizes;
-    const int lh[7] = {H2, H2, H4, H4, H8, H4, H2}, lw[7] = {W2, W2, W4, W4, W8, W4, W2};
-    const size_t b = (size_t)view * c.max_batch + (size_t)b0;      // row of every [ncam][max_batch] buffer
-    BatchView v;
-    memset(&v, 0, sizeof(v));
-    if (h->savp) {
-        v.enc00_o = h->enc00_o + b * Hc * Wc * kEnc00Ch;
-        v.enc7_o = h->enc7_o + b * H * W * 32;
-        v.st_enc00 = h->st_enc00 + b * h->enc00.stats_nparts * 2;
-        v.st_enc7 = h->st_enc7 + b * h->convt4.stats_nparts * 2;
-    }
-    v.enc0_o = h->enc0_o + b * H2 * W2 * 32;
-    v.enc1_o = h->enc1_o + b * H4 * W4 * L[1];
-    v.enc2_o = h->enc2_o + b * H8 * W8 * L[3];
-    v.enc3_o = h->enc3_o + b * H8 * W8 * L[3];
-    v.enc4_o = h->enc4_o + b * H4 * W4 * L[4];
-    v.enc5_o = h->enc5_o + b * H2 * W2 * h->c_t2;
-    v.enc6_o = h->enc6_o + b * Hc * Wc * h->c_top;
-    for (int k = 0; k < 7; ++k) {
-        const size_t per = (size_t)lh[k] * lw[k] * L[k];
-        v.c_state[k] = h->c_state[k] + b * per;
-        v.h_state[k][0] = h->h_state[k][0] + b * per;
-        v.h_state[k][1] = h->h_state[k][1] + b * per;
-        v.st_h[k] = h->st_h[k] + b * h->st_rows[k] * 2;
-    }
-    v.st_enc0 = h->st_enc0 + b * h->enc0.stats_nparts * 2;
-    v.st_enc6 = h->st_enc6 + b * h->convt3.stats_nparts * 2;
-    v.sbias = h->sbias + b * L[3];
-    if (h->cond)
-        for (int k = 0; k < 7; ++k)
-            for (int par = 0; par < 2; ++par)
-                v.cond_bias[k][par] = h->cond_bias[k] + ((size_t)par * c.max_batch * h->ncam + b) * kCondClasses * 4 * L[k];
-    v.fc_part = h->fc_part + b * h->fc.nsplit * kTaps * h->K;
-    v.kern = h->kern + b * kTaps * h->K;
-    v.frames_all = h->frames_all + b * T * H * W * 3;
-    v.distrib_all = ND > 0 ? h->distrib_all + b * T * H * W * ND : nullptr;
-    v.states_all = h->states_all + b * T * c.sdim;
-    v.sums = ND > 0 ? h->sums + (long long)view * h->sums_view_stride + (size_t)b0 * ND * h->nblocks * 2 : nullptr;
-    v.actions = d_actions + (size_t)b0 * T * c.adim;       // the views share the action sequences
-    return v;
-}
 
 // ------------------------------------------------------------------ rollout emission
 // emit_rollout() walks the S steps of the predictor once for one view and hands every unit of
@@ -1844,10 +1870,8 @@ static int emit_rollout(vf_handle *h, int view, const BatchView &v, const BatchV
                         const int32_t *goal_pix, Sink &sink, bool skip_shared) {
     const vf_config &c = h->cfg;
     const ViewData &vd = h->views[view];
-    const int H = h->H, W = h->W, T = h->T, ND = h->ND, nc = c.n_context, Hc = h->Hc, Wc = h->Wc;
-    const int H2 = Hc / 2, W2 = Wc / 2, H4 = Hc / 4, W4 = Wc / 4, H8 = Hc / 8, W8 = Wc / 8;
-    const int *L = kLstmSizes;
-    const int lh[7] = {H2, H2, H4, H4, H8, H4, H2}, lw[7] = {W2, W2, W4, W4, W8, W4, W2};
+    const int H = h->H, W = h->W, T = h->T, ND = h->ND, nc = c.n_context;
+    const BatchView &base = h->base;        // (names the buffer whose elements per sample h->per() returns)
     auto params = [&](const ConvLayer &l, int Bp, const SegArg &s0, const SegArg *s1) {
         return make_params(l, vd.lw[l.id], Bp, s0, s1, h->pad_skip);
     };
@@ -1936,7 +1960,7 @@ static int emit_rollout(vf_handle *h, int view, const BatchView &v, const BatchV
         if (s < nc) { sp.state = h->ctx_states + (size_t)s * c.sdim; sp.state_bstride = 0; }
         else { sp.state = v.states_all + (size_t)(s - nc) * c.sdim; sp.state_bstride = (long long)T * c.sdim; }
         sp.adim = c.adim; sp.sdim = c.sdim; sp.B = BD;
-        sp.w_state = vd.w_state; sp.b_state = vd.b_state; sp.w_sa = vd.w_sa; sp.n_out = L[3];
+        sp.w_state = vd.w_state; sp.b_state = vd.b_state; sp.w_sa = vd.w_sa; sp.n_out = h->enc3.Cout;
         sp.state_out = produce ? v.states_all + (size_t)t_out * c.sdim : nullptr;
         sp.state_out_bstride = (long long)T * c.sdim;
         sp.sbias = D.sbias;
@@ -1984,7 +2008,7 @@ static int emit_rollout(vf_handle *h, int view, const BatchView &v, const BatchV
                 cq.action = act; cq.action_bstride = act_bs;
                 cq.state = sta; cq.state_bstride = sta_bs;
                 cq.adim = c.adim; cq.sdim = c.sdim; cq.B = shd ? 1 : B;
-                cq.w = vd.w_cond[k]; cq.C4 = 4 * L[k];
+                cq.w = vd.w_cond[k]; cq.C4 = 4 * h->lstm[k].Cout;
                 cq.out = (shd ? sh : v).cond_bias[k][sc & 1];
                 VF_EMIT_SH(u_ck, shd, sink.cond(cq, {u_state}))
                 out[k] = u_ck;
@@ -2009,28 +2033,27 @@ static int emit_rollout(vf_handle *h, int view, const BatchView &v, const BatchV
             p.out = E0.enc00_o; p.stats = E0.st_enc00;
             VF_EMIT_SH(u_e00, enc0_sh, sink.conv(PH_CONV_RAW, h->enc00, p, {last}))
             u_enc00 = u_e00;
-            enc00_n = normed(E0.enc00_o, bs(enc0_sh, (long long)Hc * Wc * kEnc00Ch), E0.st_enc00, h->enc00.stats_nparts,
-                             h->enc00.stats_nparts, enc0_sh, (long long)Hc * Wc * kEnc00Ch, vd.ln_g[9], vd.ln_b[9],
-                             kEnc00Ch, 1);
+            enc00_n = normed(E0.enc00_o, bs(enc0_sh, h->per(base.enc00_o)), E0.st_enc00, h->enc00.stats_nparts,
+                             h->enc00.stats_nparts, enc0_sh, h->per(base.enc00_o), vd.ln_g[9], vd.ln_b[9], kEnc00Ch, 1);
         }
         p = params(h->enc0, BE0, h->savp ? enc00_n : plain(frame_in, frame_bs), nullptr);
         p.out = E0.enc0_o; p.stats = E0.st_enc0;
         VF_EMIT_SH(u_enc0, enc0_sh, sink.conv(PH_CONV_RAW, h->enc0, p, {u_enc00}))
 
-        SegArg enc0_n = normed(E0.enc0_o, bs(enc0_sh, (long long)H2 * W2 * 32), E0.st_enc0, h->enc0.stats_nparts,
-                               h->enc0.stats_nparts, enc0_sh, (long long)H2 * W2 * 32, vd.ln_g[0], vd.ln_b[0], 32, 1);
+        SegArg enc0_n = normed(E0.enc0_o, bs(enc0_sh, h->per(base.enc0_o)), E0.st_enc0, h->enc0.stats_nparts,
+                               h->enc0.stats_nparts, enc0_sh, h->per(base.enc0_o), vd.ln_g[0], vd.ln_b[0], h->enc0.Cout, 1);
         // LayerNorm index: ln1 = enc0, ln2..ln8 = lstm1..7, ln9 = convt3
         auto h_normed = [&](int k) {        // normalised new hidden state of lstm k at this step
             const bool shd = lstm_shared(k, s);
             const BatchView &O = shd ? sh : v;
-            const long long per = (long long)lh[k] * lw[k] * L[k];
+            const long long per = h->per(base.c_state[k]);
             return normed(O.h_state[k][nxt], bs(shd, per), O.st_h[k], lstm_plan(k, shd ? 1 : B).stats_nparts,
-                          h->st_rows[k], shd, per, vd.ln_g[k + 1], vd.ln_b[k + 1], L[k], 0);
+                          h->st_rows[k], shd, per, vd.ln_g[k + 1], vd.ln_b[k + 1], h->lstm[k].Cout, 0);
         };
         auto lstm_params = [&](int k, const SegArg &x) {
             const bool out_sh = lstm_shared(k, s), in_sh = lstm_shared(k, s - 1);
             const BatchView &O = out_sh ? sh : v, &I = in_sh ? sh : v;
-            const long long per = (long long)lh[k] * lw[k] * L[k];
+            const long long per = h->per(base.c_state[k]);
             SegArg hs = plain(I.h_state[k][cur], bs(in_sh, per));
             ConvParams q = params(lstm_plan(k, out_sh ? 1 : B), out_sh ? 1 : B, hs, &x);     // recurrent input first
             q.out = O.h_state[k][nxt]; q.cstate = O.c_state[k]; q.stats = O.st_h[k];
@@ -2064,15 +2087,15 @@ static int emit_rollout(vf_handle *h, int view, const BatchView &v, const BatchV
         p.out = E.enc1_o;
         VF_EMIT_SH(u_enc1, enc_sh, sink.conv(PH_CONV_RELU, h->enc1, p, {u_l2}))
 
-        VF_EMIT(u_l3, emit_lstm(2, plain(E.enc1_o, bs(enc_sh, (long long)H4 * W4 * L[1])), u_enc1))
+        VF_EMIT(u_l3, emit_lstm(2, plain(E.enc1_o, bs(enc_sh, h->per(base.enc1_o))), u_enc1))
         VF_EMIT(u_l4, emit_lstm(3, h_normed(2), u_l3))
 
         const ConvLayer &enc2_l = light_plan(h->enc2, h->enc2_one, BE);
         const ConvLayer &enc3_l = light_plan(h->enc3, h->enc3_one, BD);
         p = params(enc2_l, BE, h_normed(3), nullptr);
         p.out = E.enc2_o;
-        ConvParams p3 = params(enc3_l, BD, plain(E.enc2_o, bs(enc_sh, (long long)H8 * W8 * L[3])), nullptr);
-        p3.out = D.enc3_o; p3.sbias = D.sbias; p3.sbias_ld = L[3];
+        ConvParams p3 = params(enc3_l, BD, plain(E.enc2_o, bs(enc_sh, h->per(base.enc2_o))), nullptr);
+        p3.out = D.enc3_o; p3.sbias = D.sbias; p3.sbias_ld = (int)h->per(base.sbias);
         int u_enc3 = -1;
         // enc2 + enc3 as ONE item per row tile where both run on the same samples (the persistent schedule, from the first
         // step without shared encoder units on): one dependency hop and one memory round trip less on every sample's chain
@@ -2080,8 +2103,8 @@ static int emit_rollout(vf_handle *h, int view, const BatchView &v, const BatchV
         //  its weights are packed for that plan's 16-channel chunks - so the pair takes enc3's regular plan)
         const bool pair_ok = Sink::pair_capable() && h->fuse_pair && enc_sh == all_sh && BE == BD;
         if (pair_ok && !ScheduleSink::pairable(enc2_l, enc3_l) && ScheduleSink::pairable(enc2_l, h->enc3)) {
-            p3 = params(h->enc3, BD, plain(E.enc2_o, bs(enc_sh, (long long)H8 * W8 * L[3])), nullptr);
-            p3.out = D.enc3_o; p3.sbias = D.sbias; p3.sbias_ld = L[3];
+            p3 = params(h->enc3, BD, plain(E.enc2_o, bs(enc_sh, h->per(base.enc2_o))), nullptr);
+            p3.out = D.enc3_o; p3.sbias = D.sbias; p3.sbias_ld = (int)h->per(base.sbias);
             VF_EMIT_SH(u_pair, enc_sh, sink.conv_pair(enc2_l, p, h->enc3, p3, {u_l4, u_sa}))
             u_enc3 = u_pair;
         } else if (pair_ok && ScheduleSink::pairable(enc2_l, enc3_l)) {
@@ -2093,7 +2116,7 @@ static int emit_rollout(vf_handle *h, int view, const BatchView &v, const BatchV
             u_enc3 = u_enc3_;
         }
 
-        VF_EMIT(u_l5, emit_lstm(4, plain(D.enc3_o, bs(all_sh, (long long)H8 * W8 * L[3])), u_enc3))
+        VF_EMIT(u_l5, emit_lstm(4, plain(D.enc3_o, bs(all_sh, h->per(base.enc3_o))), u_enc3))
         SegArg h5n = h_normed(4);
 
         // ---- decoder
@@ -2105,7 +2128,7 @@ static int emit_rollout(vf_handle *h, int view, const BatchView &v, const BatchV
             if (Sink::failed(rcn)) return rcn;
         }
         VF_EMIT_SH(u_t1, all_sh, sink.conv(PH_CONVT_RELU, convt1_l, p, {u_l5}))
-        VF_EMIT(u_l6, emit_lstm(5, plain(D.enc4_o, bs(all_sh, (long long)H4 * W4 * L[4])), u_t1))
+        VF_EMIT(u_l6, emit_lstm(5, plain(D.enc4_o, bs(all_sh, h->per(base.enc4_o))), u_t1))
 
         // ---- CDNA kernels (only needed when this step's prediction is used).  The FC needs lstm5 of EVERY sample
         // and its only consumer is the compositing at the end of the step: it is emitted here, behind lstm6, where
@@ -2123,11 +2146,11 @@ static int emit_rollout(vf_handle *h, int view, const BatchView &v, const BatchV
             u_fc = u_fc_;
         }
 
-        SegArg enc1_s = plain(E.enc1_o, bs(enc_sh, (long long)H4 * W4 * L[1])), h6n = h_normed(5);
+        SegArg enc1_s = plain(E.enc1_o, bs(enc_sh, h->per(base.enc1_o))), h6n = h_normed(5);
         p = params(h->convt2, BD, enc1_s, &h6n);        // the skip tensor first: it exists since the encoder (early start)
         p.out = D.enc5_o;
         VF_EMIT_SH(u_t2, all_sh, sink.conv_late(PH_CONVT_RELU, h->convt2, p, u_enc1, u_l6))
-        VF_EMIT(u_l7, emit_lstm(6, plain(D.enc5_o, bs(all_sh, (long long)H2 * W2 * h->c_t2)), u_t2))
+        VF_EMIT(u_l7, emit_lstm(6, plain(D.enc5_o, bs(all_sh, h->per(base.enc5_o))), u_t2))
         last = u_l7;
         {
             const int now[7] = {u_l1, u_l2, u_l3, u_l4, u_l5, u_l6, u_l7};
@@ -2151,8 +2174,8 @@ static int emit_rollout(vf_handle *h, int view, const BatchView &v, const BatchV
             int top_early = u_enc0, top_late = u_l7;
             if (h->savp) {  // extra decoder scale: enc7 = convT(concat[relu(LN9(enc6)), relu(LNa(enc00))]), LNb on use
                 // (an encoder-shared enc00 of a context step is read with batch stride 0)
-                SegArg enc6_n = normed(v.enc6_o, (long long)Hc * Wc * 32, v.st_enc6, h->convt3.stats_nparts,
-                                       h->convt3.stats_nparts, false, (long long)Hc * Wc * 32, vd.ln_g[8], vd.ln_b[8], 32, 1);   // (arch 1 / 2: c_top = 32)
+                SegArg enc6_n = normed(v.enc6_o, h->per(base.enc6_o), v.st_enc6, h->convt3.stats_nparts,
+                                       h->convt3.stats_nparts, false, h->per(base.enc6_o), vd.ln_g[8], vd.ln_b[8], 32, 1);   // (arch 1 / 2: c_top = 32)
                 VF_EMIT(u_t3, sink.conv_late(PH_CONVT_RAW, h->convt3, p, u_enc0, u_l7))
                 p = params(h->convt4, B, enc00_n, &enc6_n);
                 p.out = v.enc7_o; p.stats = v.st_enc7;
@@ -2261,7 +2284,7 @@ static int build_schedule(vf_handle *h, int B, bool skip_shared, BuiltSchedule &
         if (h->cfg.arch == 3)
             rc = emit_rollout_s3(h, v, B, h->actions_buf, nullptr, sinks[v]);
         else
-            rc = emit_rollout(h, v, make_view(h, v, h->actions_buf, 0), h->shared_views[(size_t)v], B, nullptr, sinks[v],
+            rc = emit_rollout(h, v, make_view(h, v, h->actions_buf), h->shared_views[(size_t)v], B, nullptr, sinks[v],
                               skip_shared);
         if (rc < 0) return rc;
         counters = sinks[v].next_counter;
@@ -2607,12 +2630,8 @@ extern "C" int vf_render_plans(vf_handle *h, const int32_t *d_seq, int32_t K, co
 
 // the zero initial LSTM state is one shared image per layer
 static int zero_shared_state(vf_handle *h, const BatchView &sh, hipStream_t st) {
-    const int H = h->Hc, W = h->Wc;
-    const int *L = kLstmSizes;
-    const int lh[7] = {H / 2, H / 2, H / 4, H / 4, H / 8, H / 4, H / 2};
-    const int lw[7] = {W / 2, W / 2, W / 4, W / 4, W / 8, W / 4, W / 2};
     for (int k = 0; k < 7; ++k) {
-        const size_t bytes = (size_t)lh[k] * lw[k] * L[k] * sizeof(float);
+        const size_t bytes = (size_t)h->per(h->base.c_state[k]) * sizeof(float);
         VF_HIP_CHECK(hipMemsetAsync(sh.c_state[k], 0, bytes, st));
         VF_HIP_CHECK(hipMemsetAsync(sh.h_state[k][0], 0, bytes, st));
     }
@@ -2831,10 +2850,7 @@ int vf_rollout(vf_handle *h, const float *d_actions, int32_t B, const int32_t *g
     } else {
         const bool skip = shared_cache_hit(h, 1);
         for (int v = 0; v < h->ncam; ++v) {
-            BatchView bv;
-            if (h->cfg.arch == 3) { memset(&bv, 0, sizeof(bv)); bv.actions = d_actions; }      // (arch 3 keeps its buffers in Savp3)
-            else bv = make_view(h, v, d_actions, 0);
-            if ((rc = run_steps(h, v, bv, h->shared_views[(size_t)v], B, goal_pix, st, skip))) return rc;
+            if ((rc = run_steps(h, v, make_view(h, v, d_actions), h->shared_views[(size_t)v], B, goal_pix, st, skip))) return rc;
         }
         h->shared_valid = h->dedup; h->shared_cfg = 1;
     }
@@ -3056,7 +3072,7 @@ int vf_debug_lstm_layer(vf_handle *h, int32_t layer, int32_t B, const float *d_x
     sx.ptr = d_x; sx.bstride = px * l.segC[1]; sx.gamma_mod = 1;
     ConvParams q = make_params(l, h->views[0].lw[l.id], B, sh, &sx, h->pad_skip);
     q.out = d_h_out; q.cstate = d_c_out; q.cstate_in = d_c; q.cin_bstride = px * l.Cout;
-    q.stats = h->st_h[layer]; q.stats_nparts = h->st_rows[layer];
+    q.stats = h->base.st_h[layer]; q.stats_nparts = h->st_rows[layer];
     h->have_context = false;
     h->shared_valid = false;
     return launch_lstm(l, q, reinterpret_cast<hipStream_t>(stream));

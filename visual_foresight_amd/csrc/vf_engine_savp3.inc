@@ -196,8 +196,8 @@ static int s3_create(vf_handle *h) {
     h->s3 = s;
     s->nl = s3_layer_table(c, s->L, s->n_enc, s->n_dec);
     s->a_env = c.adim - c.zdim; s->zdim = c.zdim; s->ncond = s->a_env + c.sdim + c.zdim;
-    const int H = h->H, W = h->W, ND = h->ND, NV = h->ncam, Bc = c.max_batch;
-    const size_t BV = (size_t)Bc * NV;
+    const int H = h->H, W = h->W, ND = h->ND, NV = h->ncam;
+    const size_t BV = (size_t)c.max_batch * NV;
     int rc;
     h->layers.clear();
     for (int i = 0; i < s->nl; ++i) {
@@ -273,18 +273,7 @@ static int s3_create(vf_handle *h) {
     init_layer(s->masks, "masks", PACK_PLAIN, H, W, H, W, 3, 3, 1, 1, kS3Ngf, kTransCh, kMaskCh, false, false, rows_top);
     for (ConvLayer *l : {&s->hmhs, &s->scratch, &s->masks}) h->layers.push_back(l);
     const S3Layer &bot = s->L[s->n_enc - 1];
-    init_layer(h->fc, "cdna", PACK_PLAIN, 1, 1, 1, 1, 1, 1, 1, 0, bot.ho * bot.wo * bot.C, 0, kTaps * h->K, false, true, 256);
-    {
-        ConvLayer &f = h->fc;
-        const int total = f.nchunk[0];
-        f.nsplit = std::min(32, total);
-        f.chunks_per_split = (total + f.nsplit - 1) / f.nsplit;
-        f.nsplit = (total + f.chunks_per_split - 1) / f.chunks_per_split;
-        f.n_valid = kTaps * h->K;
-        h->fc_wide = f;
-        h->fc_wide.tile = TILE_FC_WIDE; h->fc_wide.NI = kFcRows; h->fc_wide.lds_bytes = fc_wide_lds_bytes();
-        h->fc_wide_ok = f.KC == 32 && f.ncg <= kFcGroups && f.nseg == 1 && f.segC[0] % 32 == 0;
-    }
+    plan_fc(h, bot.ho * bot.wo * bot.C, h->K);
     h->layers.push_back(&h->fc);
     if ((int)h->layers.size() > kNumConvLayers) return fail(VF_ERR_INVALID, "arch 3: too many GEMM layers");
     h->max_lds = ew_lds_bytes(EW_TOP3, h->ND);
@@ -305,7 +294,7 @@ static int s3_create(vf_handle *h) {
         rc = dev_alloc(h, &(ptr), (size_t)(n));    \
         if (rc) return rc;                         \
     } while (0)
-    const int nc = c.n_context, ncond = s->ncond;
+    const int ncond = s->ncond;
     h->views.resize(NV);
     s->vw.resize(NV);
     for (int v = 0; v < NV; ++v) {
@@ -332,14 +321,6 @@ static int s3_create(vf_handle *h) {
         S3_ALLOC(vd.w_state, (size_t)(s->a_env + c.sdim) * c.sdim); S3_ALLOC(vd.b_state, c.sdim);
         S3_ALLOC(vd.b_fc, kTaps * h->K);
     }
-    S3_ALLOC(h->ctx_frames_all, (size_t)NV * nc * H * W * 3);
-    S3_ALLOC(h->ctx_distrib_all, (size_t)NV * nc * H * W * ND);
-    for (int v = 0; v < NV; ++v) {
-        h->views[v].ctx_frames = h->ctx_frames_all + (size_t)v * nc * H * W * 3;
-        h->views[v].ctx_distrib = h->ctx_distrib_all + (size_t)v * nc * H * W * ND;
-    }
-    S3_ALLOC(h->ctx_states, (size_t)nc * c.sdim);
-    S3_ALLOC(h->ctx_actions, (size_t)std::max(nc - 1, 1) * c.adim);
     for (int i = 0; i < s->nl; ++i) {
         S3Layer &l = s->L[i];
         const size_t px = (size_t)l.ho * l.wo;
@@ -365,30 +346,12 @@ static int s3_create(vf_handle *h) {
     S3_ALLOC(s->norm_tab, BV * 128);
     S3_ALLOC(s->condvec, (size_t)h->S * BV * ncond);
     S3_ALLOC(s->rnn_state, BV * 2 * c.zdim);
-    S3_ALLOC(h->fc_part, BV * h->fc.nsplit * kTaps * h->K);
-    S3_ALLOC(h->kern, BV * kTaps * h->K);
-    S3_ALLOC(h->frames_all, BV * h->T * H * W * 3);
-    S3_ALLOC(h->distrib_all, BV * h->T * H * W * ND);
-    S3_ALLOC(h->states_all, BV * h->T * c.sdim);
-    h->sums_view_stride = (long long)Bc * ND * h->nblocks * 2;
-    h->sums_step_stride = h->sums_view_stride * NV;
-    S3_ALLOC(h->sums, (size_t)h->T * h->sums_step_stride);
-    S3_ALLOC(h->goal_mse, BV * h->T);
-    S3_ALLOC(h->actions_buf, (size_t)Bc * h->T * c.adim);
-    h->sched_capacity = ((size_t)h->S * 80 + 8) * NV;
-    h->counter_capacity = ((size_t)h->S * 80 + 8) * ((size_t)Bc + 1) * NV;
-    S3_ALLOC(h->sched[0].d_phases, h->sched_capacity);
-    S3_ALLOC(h->sched[1].d_phases, h->sched_capacity);
-    S3_ALLOC(h->d_sync, kSyncHead + h->counter_capacity);
-    S3_ALLOC(h->d_status, 1);
-    S3_ALLOC(h->d_stats, h->sched_capacity * 2);
-    for (int i = 0; i < NV; ++i) {
-        BatchView sv;
-        memset(&sv, 0, sizeof(sv));
-        h->shared_views.push_back(sv);
-    }
 #undef S3_ALLOC
-    return VF_OK;
+    // (of the rows of a BatchView an arch 3 engine has the CDNA kernels' and the predictions': its layers' buffers are above)
+    row_spec(h, h->base.fc_part, (size_t)h->fc.nsplit * kTaps * h->K, false);
+    row_spec(h, h->base.kern, (size_t)kTaps * h->K, false);
+    h->shared_views.resize(NV);         // (all null: no context de-duplication)
+    return alloc_common(h, 80);
 }
 
 static void s3_free(vf_handle *h) {
@@ -555,10 +518,9 @@ static int emit_rollout_s3(vf_handle *h, int view, int B, const float *d_actions
     const size_t BV = (size_t)c.max_batch * h->ncam;
     const size_t row = (size_t)view * c.max_batch;         // first row of this view in every [ncam][max_batch] buffer
     const long long HW = (long long)H * W;
-    float *frames_all = h->frames_all + row * T * HW * 3;
-    float *distrib_all = h->distrib_all + row * T * HW * ND;
-    float *states_all = h->states_all + row * T * c.sdim;
-    double *sums = h->sums + (long long)view * h->sums_view_stride;
+    const BatchView bv = make_view(h, view, d_actions);
+    float *frames_all = bv.frames_all, *distrib_all = bv.distrib_all, *states_all = bv.states_all;
+    double *sums = bv.sums;
     const float *actions = d_actions;
 
     auto plain = [](const float *ptr, long long bs) {
@@ -707,11 +669,11 @@ static int emit_rollout_s3(vf_handle *h, int view, int B, const float *d_actions
         const int ib = s->n_enc - 1;
         const ConvLayer &fc_l = Sink::fc_plan(h);
         ConvParams pf = params(fc_l, plain(out_ptr[ib], out_bs[ib]), nullptr);
-        pf.out = h->fc_part + row * h->fc.nsplit * kTaps * h->K;
+        pf.out = bv.fc_part;
         S3_EMIT(u_fc, sink.conv(PH_FC_PARTIAL, fc_l, pf, {u_out[ib]}))
         FinParams fp;
         fp.partial = pf.out; fp.nsplit = h->fc.nsplit; fp.B = B; fp.K = h->K;
-        fp.bias = vd.b_fc; fp.kern = h->kern + row * kTaps * h->K;
+        fp.bias = vd.b_fc; fp.kern = bv.kern;
         S3_EMIT(u_fin, sink.fin(fp, {u_fc}))
 
         // ---- heads
