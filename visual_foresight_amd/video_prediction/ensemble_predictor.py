@@ -21,8 +21,8 @@ import os
 import numpy as np
 
 from visual_foresight_amd import _lib
-from visual_foresight_amd.video_prediction.hip_predictor import HipVPredEvaluation
-from visual_foresight_amd.video_prediction.sharding import dist_info as _dist_info, shard_bounds, all_gather_rows
+from visual_foresight_amd.video_prediction.hip_predictor import HipVPredEvaluation, pixel_cost_columns, score_rows
+from visual_foresight_amd.video_prediction.sharding import dist_info as _dist_info
 from visual_foresight_amd.video_prediction.stochastic_predictor import StochasticHipPredictor
 
 
@@ -102,17 +102,8 @@ class EnsembleHipPredictor(object):
     def _prepare(self, context, actions):
         """The sequences every member rolls, prepared once (a stochastic member 0 draws the call's latents)."""
         m0 = self.members[0]
-        if isinstance(m0, StochasticHipPredictor):
-            m0._z = m0.draw_latents(np.asarray(actions).shape[1])
-            m0._calls += 1
-            try:
-                return m0._prepare(context, actions)
-            finally:
-                m0._z = None
-        return m0._prepare(context, actions)
-
-    def _stream(self):
-        return ctypes.c_void_p(self._torch.cuda.current_stream(self.device).cuda_stream)
+        with m0._scoring_call(actions):
+            return m0._prepare(context, actions)
 
     def score(self, context, inputs, goal_pix, finalweight=10., only_take_first_view=False, task_weights=None):
         """Ensemble cost of every action: (scores[M], scores_per_task[M, ncam*nd]) float64, as
@@ -125,24 +116,16 @@ class EnsembleHipPredictor(object):
         T = self.sequence_length - self.n_context
         ntask = self.n_cam * self.cfg.ndesig
         nd = self.n_draws
-        rank, world = _dist_info()
         ctx_p, seqs = self._prepare(context, actions)
         self._last_prepared = (ctx_p, seqs, M)
-        tw = None
-        if task_weights is not None:
-            w = np.asarray(task_weights, dtype=np.float64).reshape(-1)
-            if w.size != ntask:
-                raise ValueError('task_weights must hold ncam*ndesig = %d values' % ntask)
-            tw = (ctypes.c_float * ntask)(*[float(v) for v in w])
+        tw = m0._task_weights_c(task_weights)
         handles = (ctypes.c_void_p * self.num_ensembles)(*[m._handle.value for m in self.members])
-        libh = m0._libh
-        lo, hi = shard_bounds(M, rank, world)
-        n = hi - lo
-        with torch.cuda.device(self.device):
+
+        def rows_of(_, share, n, lo):       # [score | per task | per task x step]; the engines are the members
             for member in self.members:
                 member._last_prepared = (ctx_p, seqs, M)
                 member._set_context(ctx_p)
-            local = torch.from_numpy(np.ascontiguousarray(seqs[lo * nd:hi * nd], dtype=np.float32)).to(self.device)
+            local = torch.from_numpy(np.ascontiguousarray(share, dtype=np.float32)).to(self.device)
             rows = torch.empty((n, 1 + ntask + ntask * T), dtype=torch.float64, device=self.device)
             scores, per_task, cps = rows[:, 0], rows[:, 1:1 + ntask], rows[:, 1 + ntask:]
             bs = self.run_batch_size // nd
@@ -157,21 +140,15 @@ class EnsembleHipPredictor(object):
                     member._rollout_chunk(local[c0 * nd:c1 * nd], goal_pix, finalweight, own_s[:c1 - c0],
                                           own_pt[:c1 - c0], task_weights)
                     member._last_lo, member._last_M = lo + c0, c1 - c0
-                _lib.check(libh.vf_ensemble_scores(handles, self.num_ensembles, ctypes.c_float(self.lambda_variance),
-                                                   ctypes.c_float(finalweight), tw, c_s.data_ptr(), c_pt.data_ptr(),
-                                                   c_cps.data_ptr(), self._stream()))
+                _lib.check(m0._libh.vf_ensemble_scores(handles, self.num_ensembles, ctypes.c_float(self.lambda_variance),
+                                                       ctypes.c_float(finalweight), tw, c_s.data_ptr(), c_pt.data_ptr(),
+                                                       c_cps.data_ptr(), m0._stream()))
                 scores[c0:c1], per_task[c0:c1], cps[c0:c1] = c_s[:c1 - c0], c_pt[:c1 - c0], c_cps[:c1 - c0]
-            if world > 1:
-                rows = all_gather_rows(rows.contiguous(), M)
-            rows_np = rows.cpu().numpy()
-        scores_np = np.ascontiguousarray(rows_np[:, 0])
-        per_task_np = np.ascontiguousarray(rows_np[:, 1:1 + ntask])
+            return rows
+
+        rows_np = score_rows(self, seqs, M, 1 + ntask + ntask * T, rows_of)
         self.last_cost_per_step = np.ascontiguousarray(rows_np[:, 1 + ntask:]).reshape(M, ntask, T)
-        self._check_scores(scores_np)
-        if only_take_first_view:
-            per_task_np = per_task_np[:, :1]
-            scores_np = per_task_np[:, 0].copy()
-        return scores_np, per_task_np
+        return pixel_cost_columns(rows_np[:, :1 + ntask], only_take_first_view)
 
     def _check_scores(self, scores_np):
         if np.isnan(scores_np).any():

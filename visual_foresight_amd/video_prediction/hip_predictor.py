@@ -34,7 +34,9 @@ drives one GPU and ``n_gpus`` must be 1 or the world size.
 PyTorch is the buffer carrier only: tensors own the device memory whose pointers cross the
 C ABI of ``include/vf_hip.h``; all arithmetic runs in ``libvf_hip.so``.
 """
+import contextlib
 import ctypes
+import functools
 import os
 
 import numpy as np
@@ -68,6 +70,63 @@ def designated_pixel_count_of(hparams):
     if not 0 <= n <= 4:
         raise ValueError('designated_pixel_count must be 0 (frames-only) .. 4, got %r' % (n,))
     return n
+
+
+def score_rows(owner, seqs, M, width, rows_of):
+    """The sharded scoring driver of every cost: ``owner``'s engines roll their shares of the ``M`` actions
+    whose prepared sequences are ``seqs [M * n_draws, ...]``, and the score rows are gathered -> host float64 ``[M, width]``,
+    column 0 checked for the NaN of a failed rollout (``owner._check_scores``).
+
+    ``rows_of(engine, seqs_share, n, lo)`` rolls actions ``[lo, lo + n)`` on ``engine`` and returns its device float64
+    ``[n, width]`` rows; it is called under the engine's device and only enqueues work.  In-process lanes (``owner._lanes``):
+    every lane's share is enqueued before anything is waited for, then one gather of the lanes' rows.  Otherwise ``owner``
+    rolls its ``torch.distributed`` rank's share and the ranks all-gather (bracketed by the collective-timing events)."""
+    torch, nd = owner._torch, owner.n_draws
+    if getattr(owner, '_lanes', None):
+        packed = []
+        for lane, lo, hi in owner._lane_shares(M):
+            with torch.cuda.device(lane.device):
+                packed.append(rows_of(lane, seqs[lo * nd:hi * nd], hi - lo, lo) if hi > lo else
+                              torch.empty((0, width), dtype=torch.float64, device=lane.device))
+        rows_np = owner._gather_lane_rows(packed, M)
+    else:
+        rank, world = _dist_info()
+        lo, hi = shard_bounds(M, rank, world)
+        with torch.cuda.device(owner.device):
+            rows = rows_of(owner, seqs[lo * nd:hi * nd], hi - lo, lo)
+            if world > 1:
+                timing = getattr(owner, '_coll_events', None)       # set_collective_timing(True): a list of events
+                timed = timing is not None and len(timing) < 4096
+                if timed:
+                    start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    start.record(torch.cuda.current_stream(owner.device))
+                sent = rows.numel() * rows.element_size()
+                rows = all_gather_rows(rows, M)
+                if timed:
+                    stop.record(torch.cuda.current_stream(owner.device))
+                    timing.append((start, stop, sent))
+            rows_np = rows.cpu().numpy()
+    owner._check_scores(rows_np[:, 0])
+    return rows_np
+
+
+def pixel_cost_columns(rows_np, only_take_first_view):
+    """Host rows ``[score | per task]`` -> (scores[M], scores_per_task[M, tasks]); ``only_take_first_view`` keeps task 0 alone
+    and makes it the score (reference ``pixel_cost_controller.py:150-153``)."""
+    scores_np, per_task_np = np.ascontiguousarray(rows_np[:, 0]), np.ascontiguousarray(rows_np[:, 1:])
+    if only_take_first_view:
+        per_task_np = per_task_np[:, :1]
+        scores_np = per_task_np[:, 0].copy()
+    return scores_np, per_task_np
+
+
+def _scoring_entry(entry):
+    """A scoring entry ``entry(self, context, inputs, ...)``: one ``_scoring_call`` around the whole call, refusals included."""
+    @functools.wraps(entry)
+    def scored(self, context, inputs, *args, **kwargs):
+        with self._scoring_call(inputs['actions']):
+            return entry(self, context, inputs, *args, **kwargs)
+    return scored
 
 
 class HipVPredEvaluation(object):
@@ -121,6 +180,9 @@ class HipVPredEvaluation(object):
                            ndesig=self.ndesig_of(hp), n_context=self.n_context,
                            sequence_length=self.sequence_length, **extra)
         self.frames_only = self.cfg.ndesig == 0
+        # the image centre as goal pixels [ncam, ndesig, 2]: what the frame costs hand the rollout entry, which wants some
+        self._centre_pix = np.tile(np.array([self.cfg.height // 2, self.cfg.width // 2], np.int32),
+                                   (self.n_cam, self.cfg.ndesig, 1))
         if self.frames_only and self.arch == 'savp3':
             raise ValueError("arch 'savp3' has no frames-only mode (designated_pixel_count 0 / no_pix_distrib): "
                              "use 1..4 designated pixels")
@@ -229,34 +291,30 @@ class HipVPredEvaluation(object):
                                              ctypes.byref(fl), ctypes.byref(busy)))
         return ms.value, n.value, fl.value, busy.value
 
-    def set_persistent(self, enable):
-        """Run each rollout as one persistent launch (bit-identical results; see vf_persistent.h)."""
+    def _set_on_lanes(self, entry, *args, **attributes):
+        """``entry(handle, *args)`` of the library on every lane, under its device; ``attributes`` record the setting on it."""
         for lane in self._all_lanes():
             with self._torch.cuda.device(lane.device):
-                _lib.check(lane._libh.vf_set_persistent(lane._handle, int(bool(enable))))
-            lane.persistent = bool(enable)
+                _lib.check(getattr(lane._libh, entry)(lane._handle, *args))
+            for name, value in attributes.items():
+                setattr(lane, name, value)
+
+    def set_persistent(self, enable):
+        """Run each rollout as one persistent launch (bit-identical results; see vf_persistent.h)."""
+        self._set_on_lanes('vf_set_persistent', int(bool(enable)), persistent=bool(enable))
 
     def set_xcd_queues(self, enable):
         """One ticket queue per XCD (default) or plain phase order; placement only, bit-identical results."""
-        for lane in self._all_lanes():
-            with self._torch.cuda.device(lane.device):
-                _lib.check(lane._libh.vf_set_xcd_queues(lane._handle, int(bool(enable))))
-            lane.xcd_queues = bool(enable)
+        self._set_on_lanes('vf_set_xcd_queues', int(bool(enable)), xcd_queues=bool(enable))
 
     def set_fuse_top(self, enable):
         """Top transposed conv + compositing as one item per tile (vf_set_fuse_top); bit-identical results."""
-        for lane in self._all_lanes():
-            with self._torch.cuda.device(lane.device):
-                _lib.check(lane._libh.vf_set_fuse_top(lane._handle, int(bool(enable))))
-            lane.fuse_top = bool(enable)
+        self._set_on_lanes('vf_set_fuse_top', int(bool(enable)), fuse_top=bool(enable))
 
     def set_sched_option(self, option, value):
         """Timing-only options of the persistent launch (``vf_set_sched_option``): ``'yield_budget'`` (0 = off, -1 = automatic)
         and ``'write_through'`` (0 / 1).  Results are bit-identical for every setting."""
-        code = {'yield_budget': 0, 'write_through': 1}[option]
-        for lane in self._all_lanes():
-            with self._torch.cuda.device(lane.device):
-                _lib.check(lane._libh.vf_set_sched_option(lane._handle, code, int(value)))
+        self._set_on_lanes('vf_set_sched_option', {'yield_budget': 0, 'write_through': 1}[option], int(value))
 
     def device_status(self):
         """Synchronise, return the sticky failure word of the persistent kernel (0 = healthy), re-arm it."""
@@ -288,9 +346,7 @@ class HipVPredEvaluation(object):
 
     def set_dedup(self, enable):
         """Switch context de-duplication (bit-identical results either way; for A/B timing)."""
-        for lane in self._all_lanes():
-            with self._torch.cuda.device(lane.device):
-                _lib.check(lane._libh.vf_set_dedup(lane._handle, int(bool(enable))))
+        self._set_on_lanes('vf_set_dedup', int(bool(enable)))
 
     # ------------------------------------------------------------------ weights
     def restore(self, weights=None):
@@ -375,15 +431,19 @@ class HipVPredEvaluation(object):
             raise ValueError('goal_pix must hold [ncam=%d][ndesig=%d][2] values, got %d'
                              % (self.n_cam, self.cfg.ndesig, goal.size))
         goal_c = (ctypes.c_int32 * (2 * ntask))(*[int(v) for v in goal])
-        tw = None
-        if task_weights is not None:
-            w = np.asarray(task_weights, dtype=np.float64).reshape(-1)
-            if w.size != ntask:
-                raise ValueError('task_weights must hold ncam*ndesig = %d values' % ntask)
-            tw = (ctypes.c_float * ntask)(*[float(v) for v in w])
         _lib.check(self._libh.vf_rollout(self._handle, actions_dev.data_ptr(), B, goal_c,
-                                         ctypes.c_float(finalweight), tw, scores_dev.data_ptr(),
-                                         per_task_dev.data_ptr(), self._stream()))
+                                         ctypes.c_float(finalweight), self._task_weights_c(task_weights),
+                                         scores_dev.data_ptr(), per_task_dev.data_ptr(), self._stream()))
+
+    def _task_weights_c(self, task_weights):
+        """``task_weights`` ([ncam, ndesig], or None for the plain mean over tasks) as the library takes them."""
+        if task_weights is None:
+            return None
+        ntask = self.n_cam * self.cfg.ndesig
+        w = np.asarray(task_weights, dtype=np.float64).reshape(-1)
+        if w.size != ntask:
+            raise ValueError('task_weights must hold ncam*ndesig = %d values' % ntask)
+        return (ctypes.c_float * ntask)(*[float(v) for v in w])
 
     def _check_actions(self, actions):
         actions = np.asarray(actions)
@@ -399,6 +459,20 @@ class HipVPredEvaluation(object):
     def _prepare(self, context, actions):
         """(context, actions[n]) -> (engine context, sequences[n * n_draws])."""
         return context, actions
+
+    def _scoring_call(self, actions):
+        """Context manager around one scoring call on ``actions`` (``score*``; the ensemble enters member 0's): nothing here,
+        the stochastic predictor holds the call's latent draws in it."""
+        return contextlib.nullcontext()
+
+    def _lane_shares(self, M):
+        """(lane, lo, hi): every lane's contiguous share ``[lo, hi)`` of ``M`` actions, in lane order.  A lane whose share is
+        empty holds nothing of this call: its resident range is emptied, so that a stale one cannot match a fetch."""
+        for i, lane in enumerate(self._lanes):
+            lo, hi = shard_bounds(M, i, len(self._lanes))
+            if hi == lo:
+                lane._last_lo, lane._last_M = lo, 0
+            yield lane, lo, hi
 
     def _score_prepared(self, context, seqs, n, goal_pix, finalweight, index_base=0, task_weights=None,
                         after_chunk=None):
@@ -424,6 +498,26 @@ class HipVPredEvaluation(object):
                 after_chunk(c0, c1)
         return scores, per_task
 
+    def _roll_and_reduce(self, context, seqs, n, index_base, widths, reduce):
+        """Roll ``n`` actions on this engine (the image centre as goal pixels, their pixel scores dropped) and reduce every
+        chunk while its frames are resident: ``reduce(*scratch)`` makes the one library call that fills the scratch tensors
+        ``[chunk, w]``, one per column group ``w`` of ``widths`` -> device rows ``[n, sum(widths)]``."""
+        torch = self._torch
+        bs = self.run_batch_size // self.n_draws
+        rows = torch.empty((n, sum(widths)), dtype=torch.float64, device=self.device)
+        scratch = [torch.empty((bs, w), dtype=torch.float64, device=self.device) for w in widths]
+
+        def reduce_chunk(c0, c1):
+            reduce(*scratch)
+            col = 0
+            for s, w in zip(scratch, widths):
+                rows[c0:c1, col:col + w] = s[:c1 - c0]
+                col += w
+
+        self._score_prepared(context, seqs, n, self._centre_pix, 1.0, index_base=index_base, after_chunk=reduce_chunk)
+        return rows
+
+    @_scoring_entry
     def score(self, context, inputs, goal_pix, finalweight=10., only_take_first_view=False, task_weights=None):
         """Fused rollout + expected-pixel-distance cost.  Returns (scores[M], scores_per_task[M, ncam*nd]) float64.
 
@@ -435,32 +529,17 @@ class HipVPredEvaluation(object):
         self._refuse_frames_only('score')
         actions = self._check_actions(inputs['actions'])
         M = actions.shape[0]
-        rank, world = _dist_info()
         # every rank / lane slices the SAME prepared sequences (latent draws included); they are also what a
         # propagation fetch of a sample that is no longer resident is re-rolled from
         ctx_p, seqs = self._prepare(context, actions)
         self._last_prepared = (ctx_p, seqs, M)
-        nd = self.n_draws
-        if self._lanes:
-            scores_np, per_task_np = self._score_lanes(ctx_p, seqs, M, goal_pix, finalweight, task_weights)
-            self._check_scores(scores_np)
-            if only_take_first_view:
-                per_task_np = per_task_np[:, :1]
-                scores_np = per_task_np[:, 0].copy()
-            return scores_np, per_task_np
-        lo, hi = shard_bounds(M, rank, world)
-        with self._torch.cuda.device(self.device):
-            scores, per_task = self._score_prepared(ctx_p, seqs[lo * nd:hi * nd], hi - lo, goal_pix, finalweight,
-                                                    index_base=lo, task_weights=task_weights)
-            if world > 1:
-                scores, per_task = self._all_gather(scores, per_task, M, world)
-            scores_np = scores.cpu().numpy()
-            per_task_np = per_task.cpu().numpy()
-        self._check_scores(scores_np)
-        if only_take_first_view:
-            per_task_np = per_task_np[:, :1]
-            scores_np = per_task_np[:, 0].copy()
-        return scores_np, per_task_np
+
+        def rows_of(lane, share, n, lo):        # [score | per task]
+            s, pt = lane._score_prepared(ctx_p, share, n, goal_pix, finalweight, index_base=lo, task_weights=task_weights)
+            return self._torch.cat([s[:, None], pt], dim=1)
+
+        rows_np = score_rows(self, seqs, M, 1 + self.n_cam * self.cfg.ndesig, rows_of)
+        return pixel_cost_columns(rows_np, only_take_first_view)
 
     def _refuse_frames_only(self, what):
         if self.frames_only:
@@ -494,29 +573,7 @@ class HipVPredEvaluation(object):
             raise ValueError('goal_image must be uint8 or floating point, got %s' % g.dtype)
         return np.ascontiguousarray(g, dtype=np.float32)
 
-    def _goal_rows(self, context, seqs, n, index_base, goal, mode, finalweight, first_view_only):
-        """Roll ``n`` actions on this engine and reduce every chunk's resident frames against ``goal`` ->
-        device rows ``[n, 1 + ncam + ncam * T]`` = [score | per view | cost per step]."""
-        torch, ncam, c = self._torch, self.n_cam, self.cfg
-        T = self.sequence_length - self.n_context
-        goal_dev = torch.from_numpy(goal).to(self.device)
-        rows = torch.empty((n, 1 + ncam + ncam * T), dtype=torch.float64, device=self.device)
-        bs = self.run_batch_size // self.n_draws
-        c_s = torch.empty(bs, dtype=torch.float64, device=self.device)
-        c_pv = torch.empty((bs, ncam), dtype=torch.float64, device=self.device)
-        c_cps = torch.empty((bs, ncam * T), dtype=torch.float64, device=self.device)
-
-        def reduce_chunk(c0, c1):
-            _lib.check(self._libh.vf_goal_image_scores(
-                self._handle, goal_dev.data_ptr(), mode, ctypes.c_float(finalweight), int(bool(first_view_only)),
-                c_s.data_ptr(), c_pv.data_ptr(), c_cps.data_ptr(), self._stream()))
-            k = c1 - c0
-            rows[c0:c1, 0], rows[c0:c1, 1:1 + ncam], rows[c0:c1, 1 + ncam:] = c_s[:k], c_pv[:k], c_cps[:k]
-
-        centre = np.tile(np.array([c.height // 2, c.width // 2], np.int32), (ncam, c.ndesig, 1))
-        self._score_prepared(context, seqs, n, centre, 1.0, index_base=index_base, after_chunk=reduce_chunk)
-        return rows
-
+    @_scoring_entry
     def score_goal_image(self, context, inputs, goal_image, steps='last', finalweight=10., first_view_only=False):
         """Fused rollout + goal-image cost (reference ``policy/cem_controllers/goal_im_controller.py:93``): the mean
         squared error between predicted frames and ``goal_image``, reduced on the GPU from the frames resident in the
@@ -538,36 +595,23 @@ class HipVPredEvaluation(object):
         mode = 1 if steps == 'weighted' else 0
         actions = self._check_actions(inputs['actions'])
         M = actions.shape[0]
-        ncam, c, nd = self.n_cam, self.cfg, self.n_draws
-        T = self.sequence_length - self.n_context
+        ncam, T = self.n_cam, self.sequence_length - self.n_context
         ctx_p, seqs = self._prepare(self._centre_context(context), actions)
         self._last_prepared = (ctx_p, seqs, M)
-        rank, world = _dist_info()
-        torch = self._torch
-        if self._lanes:
-            packed = []
-            for i, lane in enumerate(self._lanes):
-                lo, hi = shard_bounds(M, i, len(self._lanes))
-                with torch.cuda.device(lane.device):
-                    if hi > lo:
-                        packed.append(lane._goal_rows(ctx_p, seqs[lo * nd:hi * nd], hi - lo, lo, goal, mode, finalweight,
-                                                      first_view_only))
-                    else:
-                        lane._last_lo, lane._last_M = lo, 0
-                        packed.append(torch.empty((0, 1 + ncam + ncam * T), dtype=torch.float64, device=lane.device))
-            rows_np = self._gather_lane_rows(packed, M)
-        else:
-            lo, hi = shard_bounds(M, rank, world)
-            with torch.cuda.device(self.device):
-                rows = self._goal_rows(ctx_p, seqs[lo * nd:hi * nd], hi - lo, lo, goal, mode, finalweight,
-                                       first_view_only)
-                if world > 1:
-                    rows = all_gather_rows(rows, M)
-                rows_np = rows.cpu().numpy()
-        scores_np = np.ascontiguousarray(rows_np[:, 0])
-        self._check_scores(scores_np)
+
+        def rows_of(lane, share, n, lo):        # [score | per view | cost per step]
+            goal_dev = self._torch.from_numpy(goal).to(lane.device)
+
+            def reduce(c_s, c_pv, c_cps):
+                _lib.check(lane._libh.vf_goal_image_scores(
+                    lane._handle, goal_dev.data_ptr(), mode, ctypes.c_float(finalweight), int(bool(first_view_only)),
+                    c_s.data_ptr(), c_pv.data_ptr(), c_cps.data_ptr(), lane._stream()))
+
+            return lane._roll_and_reduce(ctx_p, share, n, lo, (1, ncam, ncam * T), reduce)
+
+        rows_np = score_rows(self, seqs, M, 1 + ncam + ncam * T, rows_of)
         self.last_goal_cost_per_step = np.ascontiguousarray(rows_np[:, 1 + ncam:]).reshape(M, ncam, T)
-        return scores_np, np.ascontiguousarray(rows_np[:, 1:1 + ncam])
+        return np.ascontiguousarray(rows_np[:, 0]), np.ascontiguousarray(rows_np[:, 1:1 + ncam])
 
     # ------------------------------------------------------------------ learned cost (frame scorer)
     def _scorer_here(self, scorer):
@@ -581,29 +625,6 @@ class HipVPredEvaluation(object):
             while len(self._lane_scorers) > 4:          # a handful of scorers (two heads, a swap); older copies are freed
                 self._lane_scorers.pop(next(iter(self._lane_scorers)))
         return hit[1]
-
-    def _frame_rows(self, context, seqs, n, index_base, scorer, goal_enc, finalweight):
-        """Roll ``n`` actions on this engine and score every chunk's resident frames -> device rows ``[n, 1 + T]`` =
-        [score | cost per step]."""
-        torch, ncam, c = self._torch, self.n_cam, self.cfg
-        T = self.sequence_length - self.n_context
-        scorer = self._scorer_here(scorer)
-        goal_dev = None if goal_enc is None else torch.from_numpy(goal_enc).to(self.device)
-        rows = torch.empty((n, 1 + T), dtype=torch.float64, device=self.device)
-        bs = self.run_batch_size // self.n_draws
-        c_s = torch.empty(bs, dtype=torch.float64, device=self.device)
-        c_cps = torch.empty((bs, T), dtype=torch.float64, device=self.device)
-
-        def reduce_chunk(c0, c1):
-            _lib.check(self._libh.vf_scorer_scores(
-                scorer._handle, self._handle, None if goal_dev is None else goal_dev.data_ptr(),
-                ctypes.c_float(finalweight), c_s.data_ptr(), c_cps.data_ptr(), None, self._stream()))
-            k = c1 - c0
-            rows[c0:c1, 0], rows[c0:c1, 1:] = c_s[:k], c_cps[:k]
-
-        centre = np.tile(np.array([c.height // 2, c.width // 2], np.int32), (ncam, c.ndesig, 1))
-        self._score_prepared(context, seqs, n, centre, 1.0, index_base=index_base, after_chunk=reduce_chunk)
-        return rows
 
     def score_resident_frames(self, scorer, goal_enc=None, finalweight=100.):
         """Score the frames of this engine's LAST rollout chunk again, head outputs included -> (scores [A], cost per
@@ -622,6 +643,7 @@ class HipVPredEvaluation(object):
                 ctypes.c_float(finalweight), s.data_ptr(), cps.data_ptr(), out.data_ptr(), self._stream()))
             return s.cpu().numpy(), cps.cpu().numpy(), out.cpu().numpy()
 
+    @_scoring_entry
     def score_frames(self, context, inputs, scorer, goal_enc=None, finalweight=100.):
         """Fused rollout + learned cost (reference ``policy/cem_controllers/variants/classifier_controller.py:94-105``,
         ``nce_cost_controller.py:90-103``): every predicted frame goes through ``scorer`` (a ``HipFrameScorer``) where
@@ -635,7 +657,7 @@ class HipVPredEvaluation(object):
         Sharding, chunking, lanes and latent draws are those of ``score`` (with ``n_gpus > 1`` the scorer is copied to
         every lane's device once).  As in ``score_goal_image`` the image centre stands in for the goal pixels and
         the distribution context the rollout entry wants."""
-        c, ncam, nd = self.cfg, self.n_cam, self.n_draws
+        c, ncam = self.cfg, self.n_cam
         T = self.sequence_length - self.n_context
         if (scorer.cfg.height, scorer.cfg.width, scorer.n_cam) != (c.height, c.width, ncam):
             raise ValueError('the scorer is built for %dx%d, %d view(s); the predictor rolls %dx%d, %d view(s)'
@@ -652,54 +674,23 @@ class HipVPredEvaluation(object):
         M = actions.shape[0]
         ctx_p, seqs = self._prepare(self._centre_context(context), actions)
         self._last_prepared = (ctx_p, seqs, M)
-        rank, world = _dist_info()
-        torch = self._torch
-        if self._lanes:
-            packed = []
-            for i, lane in enumerate(self._lanes):
-                lo, hi = shard_bounds(M, i, len(self._lanes))
-                with torch.cuda.device(lane.device):
-                    if hi > lo:
-                        packed.append(lane._frame_rows(ctx_p, seqs[lo * nd:hi * nd], hi - lo, lo, scorer, goal_enc,
-                                                       finalweight))
-                    else:
-                        lane._last_lo, lane._last_M = lo, 0
-                        packed.append(torch.empty((0, 1 + T), dtype=torch.float64, device=lane.device))
-            rows_np = self._gather_lane_rows(packed, M)
-        else:
-            lo, hi = shard_bounds(M, rank, world)
-            with torch.cuda.device(self.device):
-                rows = self._frame_rows(ctx_p, seqs[lo * nd:hi * nd], hi - lo, lo, scorer, goal_enc, finalweight)
-                if world > 1:
-                    rows = all_gather_rows(rows, M)
-                rows_np = rows.cpu().numpy()
-        scores_np = np.ascontiguousarray(rows_np[:, 0])
-        self._check_scores(scores_np)
+
+        def rows_of(lane, share, n, lo):        # [score | cost per step]
+            here = lane._scorer_here(scorer)
+            goal_dev = None if goal_enc is None else self._torch.from_numpy(goal_enc).to(lane.device)
+
+            def reduce(c_s, c_cps):
+                _lib.check(lane._libh.vf_scorer_scores(
+                    here._handle, lane._handle, None if goal_dev is None else goal_dev.data_ptr(),
+                    ctypes.c_float(finalweight), c_s.data_ptr(), c_cps.data_ptr(), None, lane._stream()))
+
+            return lane._roll_and_reduce(ctx_p, share, n, lo, (1, T), reduce)
+
+        rows_np = score_rows(self, seqs, M, 1 + T, rows_of)
         self.last_frame_cost_per_step = np.ascontiguousarray(rows_np[:, 1:])
-        return scores_np
+        return np.ascontiguousarray(rows_np[:, 0])
 
     # ------------------------------------------------------------------ in-process multi-GPU (n_gpus > 1)
-    def _score_lanes(self, context, seqs, M, goal_pix, finalweight, task_weights):
-        """Lane i rolls the contiguous shard ``shard_bounds(M, i, n_gpus)`` of the prepared sequences on its own
-        device; every lane's work is enqueued before anything is waited for, then one gather of the
-        ``[M, 1 + tasks]`` score rows."""
-        torch = self._torch
-        lanes, nd = self._lanes, self.n_draws
-        packed = []
-        for i, lane in enumerate(lanes):
-            lo, hi = shard_bounds(M, i, len(lanes))
-            with torch.cuda.device(lane.device):
-                if hi > lo:
-                    s, pt = lane._score_prepared(context, seqs[lo * nd:hi * nd], hi - lo, goal_pix, finalweight,
-                                                 index_base=lo, task_weights=task_weights)
-                    packed.append(torch.cat([s[:, None], pt], dim=1).contiguous())
-                else:
-                    lane._last_lo, lane._last_M = lo, 0
-                    packed.append(torch.empty((0, 1 + self.n_cam * self.cfg.ndesig), dtype=torch.float64,
-                                              device=lane.device))
-        rows = self._gather_lane_rows(packed, M)
-        return np.ascontiguousarray(rows[:, 0]), np.ascontiguousarray(rows[:, 1:])
-
     def _gather_lane_rows(self, packed, M):
         """The lanes' device rows (lane order, any width) -> all ``M`` rows on the host."""
         rows = None
@@ -761,21 +752,6 @@ class HipVPredEvaluation(object):
         ms = [a.elapsed_time(b) for a, b, _ in ev]
         return {'calls': len(ms), 'mean_ms': float(np.mean(ms)), 'max_ms': float(np.max(ms)),
                 'bytes_per_rank': int(ev[-1][2])}
-
-    def _all_gather(self, scores, per_task, M, world):
-        """One collective: every rank's [score | per-task scores] rows -> all M rows on every rank."""
-        torch = self._torch
-        packed = torch.cat([scores[:, None], per_task], dim=1).contiguous()
-        timing = getattr(self, '_coll_events', None)
-        if timing is not None and len(timing) < 4096:
-            start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            start.record(torch.cuda.current_stream(self.device))
-            out = all_gather_rows(packed, M)
-            stop.record(torch.cuda.current_stream(self.device))
-            timing.append((start, stop, packed.numel() * packed.element_size()))
-        else:
-            out = all_gather_rows(packed, M)
-        return out[:, 0].contiguous(), out[:, 1:].contiguous()
 
     def fetch_pixel_distributions(self, sample_index):
         """Normalised distributions ``[T, ncam, H, W, ndesig]`` of one action of the last ``score()`` call (its first
@@ -1021,14 +997,9 @@ class HipVPredEvaluation(object):
         context, seqs = self._prepare(context, actions)
         self._last_prepared = (context, seqs, actions.shape[0])
         if self._lanes:     # lane i materialises its contiguous shard (one lane after the other: the D2H dominates)
-            M, n, nd = actions.shape[0], len(self._lanes), self.n_draws
-            parts = []
-            for i, lane in enumerate(self._lanes):
-                lo, hi = shard_bounds(M, i, n)
-                if hi > lo:
-                    parts.append(lane._materialise(context, seqs[lo * nd:hi * nd], hi - lo, lo))
-                else:           # nothing of THIS call is resident on the lane (a stale range must not match a fetch)
-                    lane._last_lo, lane._last_M = lo, 0
+            nd = self.n_draws
+            parts = [lane._materialise(context, seqs[lo * nd:hi * nd], hi - lo, lo)
+                     for lane, lo, hi in self._lane_shares(actions.shape[0]) if hi > lo]
             if not parts:       # M == 0: empty arrays of the right shapes
                 return self._materialise(context, seqs, 0, 0)
             return {k: None if parts[0][k] is None else np.concatenate([p[k] for p in parts], axis=0) for k in parts[0]}

@@ -19,6 +19,8 @@ action are consecutive rows of the rolled batch, the engine averages their costs
 propagation fetch work exactly as for the deterministic predictor (sharded by action, owner rank
 exports, all-reduce).
 """
+import contextlib
+
 import numpy as np
 
 from visual_foresight_amd.video_prediction.hip_predictor import HipVPredEvaluation
@@ -64,33 +66,13 @@ class StochasticHipPredictor(HipVPredEvaluation):
             [ctx_actions, np.zeros((ctx_actions.shape[0], self.zdim))], axis=1))
         return ctx, np.concatenate([tiled, zz], axis=2)
 
-    def score(self, context, inputs, goal_pix, finalweight=10., only_take_first_view=False, task_weights=None):
-        T = np.asarray(inputs['actions']).shape[1]
-        self._z = self.draw_latents(T)          # one set of draws per scoring call, shared by every rank
+    @contextlib.contextmanager
+    def _scoring_call(self, actions):
+        """One set of draws per scoring call (``score``, ``score_goal_image``, ``score_frames``), shared by every rank and
+        lane; the call counts whether or not it is refused afterwards.  ``__call__`` draws for itself and does not count."""
+        self._z = self.draw_latents(np.asarray(actions).shape[1])
         self._calls += 1
         try:
-            return super(StochasticHipPredictor, self).score(
-                context, inputs, goal_pix, finalweight=finalweight, only_take_first_view=only_take_first_view,
-                task_weights=task_weights)
-        finally:
-            self._z = None
-
-    def score_goal_image(self, context, inputs, goal_image, steps='last', finalweight=10., first_view_only=False):
-        T = np.asarray(inputs['actions']).shape[1]
-        self._z = self.draw_latents(T)          # as score(): one set of draws per scoring call
-        self._calls += 1
-        try:
-            return super(StochasticHipPredictor, self).score_goal_image(
-                context, inputs, goal_image, steps=steps, finalweight=finalweight, first_view_only=first_view_only)
-        finally:
-            self._z = None
-
-    def score_frames(self, context, inputs, scorer, goal_enc=None, finalweight=100.):
-        T = np.asarray(inputs['actions']).shape[1]
-        self._z = self.draw_latents(T)          # as score(): one set of draws per scoring call
-        self._calls += 1
-        try:
-            return super(StochasticHipPredictor, self).score_frames(context, inputs, scorer, goal_enc=goal_enc,
-                                                                    finalweight=finalweight)
+            yield
         finally:
             self._z = None
