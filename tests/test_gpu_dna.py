@@ -188,12 +188,12 @@ def test_closed_form_all_taps_at_the_relu_shift_is_the_box_filter():
     assert pred.device_status() == 0
 
 
-@pytest.mark.parametrize('H,W,nd,M', [(32, 32, 2, 9), (64, 64, 4, 6)])
-def test_launch_routes_are_invisible_in_the_results(H, W, nd, M):
+@pytest.mark.parametrize('H,W,nd,M,T', [pytest.param(32, 32, 2, 9, 3, id='32-32-2-9'), pytest.param(64, 64, 4, 6, 3, id='64-64-4-6'),
+                                        pytest.param(32, 32, 1, 3, 2, id='32-32-1-3-T2'), pytest.param(32, 32, 3, 3, 2, id='32-32-3-3-T2')])
+def test_launch_routes_are_invisible_in_the_results(H, W, nd, M, T):
     """Fused top, two-phase persistent schedule and per-layer launches run the same per-pixel code on the same floats: the
     same bits for scores, frames, distributions and states - in a second call (cached context) and with every sequence
-    moved to another slot of the batch."""
-    T = 3
+    moved to another slot of the batch.  The four cases are the four designated-pixel counts the kernels are instantiated for."""
     pred, _ = _predictor(H, W, T, nd, bs=M, seed=5)
     rs = np.random.RandomState(H + M)
     ctx = _context(H, W, nd, rs)

@@ -552,13 +552,15 @@ def test_float16_conf_key_selects_the_reduced_precision_mode():
     assert HipVPredEvaluation('', hp).precision == (1 if __import__('os').environ.get('VF_PRECISION') == 'bf16x6' else 0)
 
 
-@pytest.mark.parametrize('H,W,nd,M', [(64, 64, 1, 21), (64, 64, 4, 6), (32, 32, 2, 9), (48, 64, 1, 7), (40, 56, 2, 5)])
-def test_fused_decoder_top_is_invisible_in_the_results(H, W, nd, M):
+@pytest.mark.parametrize('H,W,nd,M,T', [pytest.param(64, 64, 1, 21, 3, id='64-64-1-21'), pytest.param(64, 64, 4, 6, 3, id='64-64-4-6'),
+                                        pytest.param(32, 32, 2, 9, 3, id='32-32-2-9'), pytest.param(48, 64, 1, 7, 3, id='48-64-1-7'),
+                                        pytest.param(40, 56, 2, 5, 3, id='40-56-2-5'), pytest.param(32, 32, 3, 3, 2, id='32-32-3-3-T2')])
+def test_fused_decoder_top_is_invisible_in_the_results(H, W, nd, M, T):
     """vf_set_fuse_top: the last transposed conv and the compositing as one item per tile (the decoder's top tensor
     never reaches memory) - same bits as the two-phase schedule and as the per-layer launches, several tile
-    geometries (40x56 cannot be fused and falls back)."""
+    geometries (40x56 cannot be fused and falls back), every designated-pixel count the per-layer compositing kernel
+    is instantiated for (three: the 32x32, T 2 case)."""
     from visual_foresight_amd.video_prediction.hip_predictor import HipVPredEvaluation
-    T = 3
     rs = np.random.RandomState(H + W + nd)
     ctx = _context(H, W, nd, rs)
     actions = rs.normal(0, 0.1, (M, T, 4))

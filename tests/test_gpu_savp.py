@@ -76,23 +76,24 @@ def test_savp_rollout_matches_oracle(arch, H, W, T, M, nd):
     assert pred.device_status() == 0
 
 
-@both_archs
-def test_savp_launch_strategies_and_chunking_are_bit_identical(arch):
+@pytest.mark.parametrize('arch,T,M,nd', [pytest.param('savp', 3, 23, 1, id='savp'), pytest.param('savp2', 3, 23, 1, id='savp2'),
+                                        pytest.param('savp2', 2, 3, 3, id='savp2-nd3-T2'), pytest.param('savp2', 2, 3, 4, id='savp2-nd4-T2')])
+def test_savp_launch_strategies_and_chunking_are_bit_identical(arch, T, M, nd):
     """Persistent launch == per-layer launches == ragged chunks == one XCD queue, bit for bit; context
-    de-duplication off gives the same bits too."""
+    de-duplication off gives the same bits too.  (Three and four designated pixels: the per-layer compositing kernels of
+    the seven-layer compositing that no other test launches - at 64 x 64, the smallest image that arch takes.)"""
     H = W = 64
-    T, M = 3, 23
     rs = np.random.RandomState(5)
-    ctx = _context(H, W, 1, 6, rs)
+    ctx = _context(H, W, nd, 6, rs)
     actions = rs.normal(0, 0.1, (M, T, 6))
-    goal = np.array([[[10, 50]]])
-    pred, weights = _predictor(H, W, T, 1, bs=M, arch=arch)
+    goal = np.array([[[10, 50], [40, 3], [0, 63], [33, 33]][:nd]])
+    pred, weights = _predictor(H, W, T, nd, bs=M, arch=arch)
     base, _ = pred.score(ctx, {'actions': actions}, goal)
     base_out = pred(ctx, {'actions': actions})
     for kw in (dict(persistent=0), dict(xcd_queues=0), dict(dedup=0), dict(run_batch_size=9), dict(fuse_top=0)):
         hp = dict(kw)
         bs = hp.pop('run_batch_size', M)
-        other, _ = _predictor(H, W, T, 1, bs=bs, arch=arch, **hp)
+        other, _ = _predictor(H, W, T, nd, bs=bs, arch=arch, **hp)
         got, _ = other.score(ctx, {'actions': actions}, goal)
         np.testing.assert_array_equal(got, base, err_msg=str(kw))
         out = other(ctx, {'actions': actions})

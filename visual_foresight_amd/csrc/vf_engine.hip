@@ -268,6 +268,11 @@ static bool top_fusable(const ConvLayer &l, int ND) {
 
 static int round_up(int x, int m) { return (x + m - 1) / m * m; }
 
+// items (workgroups) in x of a phase of B samples on plan `l`: the tiles of every image, or whole images in groups of NI
+static int conv_items_x(const ConvLayer &l, int B) { return l.NI == 1 ? B * l.tilesY * l.tilesX : (B + l.NI - 1) / l.NI; }
+// items of an element-wise phase of arch 3 (vf_savp3.h): gx items per sample, or one item per spi samples
+static int ew_items(const EwParams &p) { return p.spi > 0 ? (p.B + p.spi - 1) / p.spi : p.B * p.gx; }
+
 static size_t conv_lds_bytes(const ConvLayer &l, int KC) {
     const int LH = (l.TH - 1) * l.stride + l.KH, LW = (l.TW - 1) * l.stride + l.KW;
     // A tile + LayerNorm table + reduction scratch (+ for 4-gate layers the double-buffered
@@ -841,8 +846,7 @@ static int configure_kernels(vf_handle *h) {
 
 template <int G, int EPI, int MREP>
 static int launch_conv_m(const ConvLayer &l, const ConvParams &p, hipStream_t st) {
-    const int tiles = l.NI == 1 ? p.B * l.tilesY * l.tilesX : (p.B + l.NI - 1) / l.NI;
-    dim3 grid(tiles, l.ncg, l.nsplit);
+    dim3 grid(conv_items_x(l, p.B), l.ncg, l.nsplit);
     hipLaunchKernelGGL((conv_mfma_kernel<G, EPI, MREP>), grid, dim3(kConvThreads), l.lds_bytes, st, p);
     VF_HIP_CHECK(hipGetLastError());
     return VF_OK;
@@ -850,8 +854,7 @@ static int launch_conv_m(const ConvLayer &l, const ConvParams &p, hipStream_t st
 
 // the conv-LSTM tile bodies
 static int launch_lstm(const ConvLayer &l, const ConvParams &p, hipStream_t st) {
-    const int tiles = l.NI == 1 ? p.B * l.tilesY * l.tilesX : (p.B + l.NI - 1) / l.NI;
-    const dim3 grid(tiles, l.ncg);
+    const dim3 grid(conv_items_x(l, p.B), l.ncg);
     switch (l.tile) {
         case TILE_LSTM_LDS: return launch_conv_m<4, EPI_LSTM, 1>(l, p, st);
         case TILE_LSTM_GS128: hipLaunchKernelGGL(conv_lstm_gsplit2_kernel<4>, grid, dim3(kConvThreads), l.lds_bytes, st, p); break;
@@ -872,12 +875,29 @@ static int launch_conv_t(const ConvLayer &l, const ConvParams &p, hipStream_t st
     return launch_conv_m<G, EPI, EPI == EPI_PARTIAL ? 2 : 1>(l, p, st);
 }
 
+// The kernels that read designated pixels are instances per count: calls f with ND, 1..4 at run time, as a compile-time
+// constant (decltype(nd)::value).  The frames-only kernels (ND 0) have names of their own and are launched by name.
+// (One call per kernel template: a call instantiates its four instances together, and the code object lists them so.)
+template <class F>
+static auto with_nd(int ND, F &&f) {
+    switch (ND) {
+        case 1: return f(std::integral_constant<int, 1>());
+        case 2: return f(std::integral_constant<int, 2>());
+        case 3: return f(std::integral_constant<int, 3>());
+        default: return f(std::integral_constant<int, 4>());
+    }
+}
+
 #endif  // VF_HOST_SELFTEST
 
 struct SegArg {
     const float *ptr; long long bstride; const long long *ln_part; long long ln_bstride; int ln_nparts; float ln_inv_n;
     const float *gamma, *beta; int gamma_mod; int relu;
 };
+// a segment read as it is: no LayerNorm, no relu
+static SegArg plain(const float *ptr, long long bs) {
+    SegArg s; memset(&s, 0, sizeof(s)); s.ptr = ptr; s.bstride = bs; s.gamma_mod = 1; return s;
+}
 
 static ConvParams make_params(const ConvLayer &l, const LayerW &w, int B, const SegArg &s0, const SegArg *s1, bool pad_skip) {
     ConvParams p;
@@ -938,6 +958,18 @@ static double gs_pad_skipped_pairs(const ConvLayer &l, int B) {
         if (B % l.NI) pairs += per_wg(B % l.NI, 0, 0);
     }
     return pairs;
+}
+
+// Executed FLOPs of conv phase `type` on plan `l` with parameters `p` - what the persistent schedule sums up and what a profiled
+// per-layer launch counts (vf_get_profile reports the same number on both paths)
+static double conv_flops(int type, const ConvLayer &l, const ConvParams &p) {
+    if (l.tile == TILE_FIRST_VALU) return 0.0;      // (the first conv runs on the vector ALUs: not matrix work, not counted)
+    const double rows = (double)p.B * l.Hout * l.Wout;
+    const double taps = l.mode == PACK_CONVT ? 9.0 / 4.0 * 4.0 : (double)l.KH * l.KW;   // real taps
+    // (executed products: less the kernel rows the gate-split tile skips, ConvParams::pad_skip)
+    const double skipped = p.pad_skip && (type == PH_LSTM || type == PH_GATES_RAW) ? 5.0 * gs_pad_skipped_pairs(l, p.B) : 0.0;
+    return 2.0 * (rows * taps - skipped) * (l.segC[0] + (l.nseg > 1 ? l.segC[1] : 0) - p.chunk_begin * l.KC) *
+           (l.mode == PACK_LSTM ? 4.0 : (l.mode == PACK_PLAIN ? (double)l.G : 1.0)) * l.Cout;
 }
 
 }  // namespace vf
@@ -1009,6 +1041,55 @@ static BatchView make_view(vf_handle *h, int view, const float *d_actions) {
     return v;
 }
 
+// Where step s of a rollout reads its inputs and writes its prediction, in the rows `v` of one view.  Up to n_context an input
+// is the context, the same for every sample (batch stride 0); behind it, what the sample itself rolled (stride: its T steps).
+// The action of step s is the one executed BETWEEN frames s and s + 1, so the context holds n_context - 1 of them and the
+// caller's sequences take over one step before the rolled states and frames do.  Step s writes prediction s - (n_context - 1);
+// the steps before that write none (null outputs).  A frames-only engine (ND 0) reads and writes no distribution or block sum.
+struct StepIo {
+    const float *action, *state, *frame, *prev_distrib;
+    long long action_bs, state_bs, frame_bs, prev_distrib_bs;
+    const double *prev_sums;            // block sums of a rolled prev_distrib; null: the context's is normalised already
+    float *state_out, *out_frame, *out_distrib;
+    long long state_out_bs, out_frame_bs, out_distrib_bs;
+    double *out_sums;
+};
+static StepIo step_io(const vf_handle *h, const ViewData &vd, const BatchView &v, int s) {
+    const vf_config &c = h->cfg;
+    const int T = h->T, ND = h->ND, nc = c.n_context;
+    const size_t HW = (size_t)h->H * h->W;
+    StepIo io;
+    memset(&io, 0, sizeof(io));
+    if (s < nc - 1) io.action = h->ctx_actions + (size_t)s * c.adim;
+    else { io.action = v.actions + (size_t)(s - (nc - 1)) * c.adim; io.action_bs = (long long)T * c.adim; }
+    if (s < nc) {
+        io.state = h->ctx_states + (size_t)s * c.sdim;
+        io.frame = vd.ctx_frames + (size_t)s * HW * 3;
+        if (ND > 0) io.prev_distrib = vd.ctx_distrib + (size_t)s * HW * ND;
+    } else {
+        io.state = v.states_all + (size_t)(s - nc) * c.sdim; io.state_bs = (long long)T * c.sdim;
+        io.frame = v.frames_all + (size_t)(s - nc) * HW * 3; io.frame_bs = (long long)T * HW * 3;
+        if (ND > 0) {
+            io.prev_distrib = v.distrib_all + (size_t)(s - nc) * HW * ND; io.prev_distrib_bs = (long long)T * HW * ND;
+            io.prev_sums = v.sums + (long long)(s - nc) * h->sums_step_stride;
+        }
+    }
+    io.state_out_bs = (long long)T * c.sdim;
+    if (s < nc - 1) return io;
+    const size_t t_out = (size_t)(s - (nc - 1));
+    io.state_out = v.states_all + t_out * c.sdim;
+    io.out_frame = v.frames_all + t_out * HW * 3; io.out_frame_bs = (long long)T * HW * 3;
+    if (ND > 0) {
+        io.out_distrib = v.distrib_all + t_out * HW * ND; io.out_distrib_bs = (long long)T * HW * ND;
+        io.out_sums = v.sums + (long long)t_out * h->sums_step_stride;
+    }
+    return io;
+}
+// the goal pixels [ND][2] of one view, for the per-layer kernels that read them from their parameters
+static void set_goal(int (&goal)[kMaxDesig][2], const int32_t *goal_pix, int ND) {
+    for (int d = 0; d < ND && goal_pix; ++d) { goal[d][0] = goal_pix[2 * d]; goal[d][1] = goal_pix[2 * d + 1]; }
+}
+
 // The CDNA FC as a K-split GEMM over 1x1 "images": k_in inputs, the taps of n_kern kernels out
 static void plan_fc(vf_handle *h, int k_in, int n_kern) {
     ConvLayer &f = h->fc;
@@ -1061,6 +1142,11 @@ static int alloc_common(vf_handle *h, int phases_per_step) {
     VF_ALLOC(h->d_stats, h->sched_capacity * 2);
     return VF_OK;
 }
+
+// (in an emitter: hand a unit to the sink, keep its id, or return the sink's error)
+#define VF_EMIT(var, expr)                 \
+    const int var = (expr);                \
+    if (Sink::failed(var)) return var;
 
 #include "vf_engine_savp3.inc"
 
@@ -1544,6 +1630,24 @@ int vf_set_context(vf_handle *h, const uint8_t *d_frames, const float *d_states,
 static const int kSkipped = 1 << 30;      // id of a unit whose cached result is reused
 
 #ifndef VF_HOST_SELFTEST
+// Profiling (vf_set_profiling): a bracketed launch takes two events of the pool, grown on demand - the first is recorded in
+// front of it, the second behind it, together with the FLOPs the launch executes
+static int profile_begin(vf_handle *h, hipStream_t st) {
+    while (h->ev_pool.size() < h->ev_used + 2) {
+        hipEvent_t e;
+        VF_HIP_CHECK(hipEventCreate(&e));
+        h->ev_pool.push_back(e);
+    }
+    VF_HIP_CHECK(hipEventRecord(h->ev_pool[h->ev_used], st));
+    return VF_OK;
+}
+static int profile_end(vf_handle *h, hipStream_t st, double flops) {
+    VF_HIP_CHECK(hipEventRecord(h->ev_pool[h->ev_used + 1], st));
+    h->ev_used += 2;
+    h->prof_flops += flops;
+    return VF_OK;
+}
+
 struct LaunchSink {
     vf_handle *h;
     hipStream_t st;
@@ -1552,28 +1656,21 @@ struct LaunchSink {
     // a conv-LSTM gate GEMM of arch 0-2 (the cell's item, or the shared recurrent partial): with profiling on, bracketed by
     // two events and counted with the products it executes
     template <class F>
-    int profiled_lstm(const ConvLayer &l, const ConvParams &p, F launch) {
+    int profiled_lstm(int type, const ConvLayer &l, const ConvParams &p, F launch) {
         if (!h->profiling) return launch();
-        while (h->ev_pool.size() < h->ev_used + 2) {
-            hipEvent_t e;
-            VF_HIP_CHECK(hipEventCreate(&e));
-            h->ev_pool.push_back(e);
-        }
-        VF_HIP_CHECK(hipEventRecord(h->ev_pool[h->ev_used], st));
-        int r = launch();
-        VF_HIP_CHECK(hipEventRecord(h->ev_pool[h->ev_used + 1], st));
-        h->ev_used += 2;
-        h->prof_flops += 2.0 * (p.B * l.Hout * l.Wout * 25.0 - (p.pad_skip ? 5.0 * gs_pad_skipped_pairs(l, p.B) : 0.0)) *
-                         (l.segC[0] + (l.nseg > 1 ? l.segC[1] : 0) - p.chunk_begin * l.KC) * 4.0 * l.Cout;
-        return r;
+        int rc = profile_begin(h, st);
+        if (rc) return rc;
+        const int r = launch();
+        rc = profile_end(h, st, conv_flops(type, l, p));
+        return rc ? rc : r;
     }
     int conv(int type, const ConvLayer &l, const ConvParams &p, std::initializer_list<int>) {
         switch (type) {
-            case PH_LSTM: return profiled_lstm(l, p, [&] { return launch_lstm(l, p, st); });
+            case PH_LSTM: return profiled_lstm(type, l, p, [&] { return launch_lstm(l, p, st); });
             case PH_CONV_RELU: return launch_conv_t<1, EPI_BIAS_RELU>(l, p, st);
             case PH_CONV_RAW:
                 if (l.tile == TILE_FIRST_VALU) {
-                    const dim3 grid(p.B * l.tilesY * l.tilesX);
+                    const dim3 grid(conv_items_x(l, p.B));
                     if (l.Cout == 16) hipLaunchKernelGGL(conv_first_kernel<16>, grid, dim3(kConvThreads), l.lds_bytes, st, p);
                     else hipLaunchKernelGGL(conv_first_kernel<32>, grid, dim3(kConvThreads), l.lds_bytes, st, p);
                     VF_HIP_CHECK(hipGetLastError());
@@ -1587,27 +1684,21 @@ struct LaunchSink {
             case PH_CONV_RAW3G4: return launch_conv_m<4, EPI_RAW, 1>(l, p, st);
             case PH_GATES_RAW: {
                 auto launch = [&]() -> int {
-                    const int tiles = l.NI == 1 ? p.B * l.tilesY * l.tilesX : (p.B + l.NI - 1) / l.NI;
-                    hipLaunchKernelGGL(conv_gates_raw_kernel, dim3(tiles, l.ncg), dim3(kConvThreads), l.lds_bytes, st, p);
+                    hipLaunchKernelGGL(conv_gates_raw_kernel, dim3(conv_items_x(l, p.B), l.ncg), dim3(kConvThreads), l.lds_bytes, st, p);
                     VF_HIP_CHECK(hipGetLastError());
                     return VF_OK;
                 };
                 // (arch 3's gate GEMMs are not part of the conv-LSTM profile; the shared recurrent partial of arch 0-2 is)
-                return h->cfg.arch == 3 ? launch() : profiled_lstm(l, p, launch);
+                return h->cfg.arch == 3 ? launch() : profiled_lstm(type, l, p, launch);
             }
             default: return launch_conv_t<1, EPI_PARTIAL>(l, p, st);
         }
     }
     // element-wise items of arch 3 (vf_savp3.h): one workgroup per item
     int ew(const EwParams &p, int /*view*/, std::initializer_list<int>) {
-        const int items = p.spi > 0 ? (p.B + p.spi - 1) / p.spi : p.B * p.gx;
-        const size_t lds = ew_lds_bytes(p.op, h->ND);
-        switch (h->ND) {
-            case 1: hipLaunchKernelGGL(ew_kernel<1>, dim3(items), dim3(kConvThreads), lds, st, p); break;
-            case 2: hipLaunchKernelGGL(ew_kernel<2>, dim3(items), dim3(kConvThreads), lds, st, p); break;
-            case 3: hipLaunchKernelGGL(ew_kernel<3>, dim3(items), dim3(kConvThreads), lds, st, p); break;
-            default: hipLaunchKernelGGL(ew_kernel<4>, dim3(items), dim3(kConvThreads), lds, st, p); break;
-        }
+        with_nd(h->ND, [&](auto nd) {
+            hipLaunchKernelGGL(ew_kernel<decltype(nd)::value>, dim3(ew_items(p)), dim3(kConvThreads), ew_lds_bytes(p.op, h->ND), st, p);
+        });
         VF_HIP_CHECK(hipGetLastError());
         return VF_OK;
     }
@@ -1639,33 +1730,13 @@ struct LaunchSink {
             else if (p.K == 6) hipLaunchKernelGGL(composite_frames_kernel<6>, grid, dim3(256), 0, st, p);
             else hipLaunchKernelGGL(composite_frames_kernel<10>, grid, dim3(256), 0, st, p);
         } else if (p.w_flow && p.K == 1) {     // DNA: the per-pixel kernel head travels in the flow head's fields
-            switch (p.ND) {
-                case 1: hipLaunchKernelGGL(composite_dna_kernel<1>, grid, dim3(256), 0, st, p); break;
-                case 2: hipLaunchKernelGGL(composite_dna_kernel<2>, grid, dim3(256), 0, st, p); break;
-                case 3: hipLaunchKernelGGL(composite_dna_kernel<3>, grid, dim3(256), 0, st, p); break;
-                default: hipLaunchKernelGGL(composite_dna_kernel<4>, grid, dim3(256), 0, st, p); break;
-            }
+            with_nd(p.ND, [&](auto nd) { hipLaunchKernelGGL(composite_dna_kernel<decltype(nd)::value>, grid, dim3(256), 0, st, p); });
         } else if (p.w_flow) {         // appearance flow
-            switch (p.ND) {
-                case 1: hipLaunchKernelGGL(composite_flow_kernel<1>, grid, dim3(256), 0, st, p); break;
-                case 2: hipLaunchKernelGGL(composite_flow_kernel<2>, grid, dim3(256), 0, st, p); break;
-                case 3: hipLaunchKernelGGL(composite_flow_kernel<3>, grid, dim3(256), 0, st, p); break;
-                default: hipLaunchKernelGGL(composite_flow_kernel<4>, grid, dim3(256), 0, st, p); break;
-            }
+            with_nd(p.ND, [&](auto nd) { hipLaunchKernelGGL(composite_flow_kernel<decltype(nd)::value>, grid, dim3(256), 0, st, p); });
         } else if (p.K == 6) {         // arch 2: four CDNA warps + previous + first frame + scratch
-            switch (p.ND) {
-                case 1: hipLaunchKernelGGL((composite_kernel<1, 6>), grid, dim3(256), 0, st, p); break;
-                case 2: hipLaunchKernelGGL((composite_kernel<2, 6>), grid, dim3(256), 0, st, p); break;
-                case 3: hipLaunchKernelGGL((composite_kernel<3, 6>), grid, dim3(256), 0, st, p); break;
-                default: hipLaunchKernelGGL((composite_kernel<4, 6>), grid, dim3(256), 0, st, p); break;
-            }
+            with_nd(p.ND, [&](auto nd) { hipLaunchKernelGGL((composite_kernel<decltype(nd)::value, 6>), grid, dim3(256), 0, st, p); });
         } else {
-            switch (p.ND) {
-                case 1: hipLaunchKernelGGL((composite_kernel<1, 10>), grid, dim3(256), 0, st, p); break;
-                case 2: hipLaunchKernelGGL((composite_kernel<2, 10>), grid, dim3(256), 0, st, p); break;
-                case 3: hipLaunchKernelGGL((composite_kernel<3, 10>), grid, dim3(256), 0, st, p); break;
-                default: hipLaunchKernelGGL((composite_kernel<4, 10>), grid, dim3(256), 0, st, p); break;
-            }
+            with_nd(p.ND, [&](auto nd) { hipLaunchKernelGGL((composite_kernel<decltype(nd)::value, 10>), grid, dim3(256), 0, st, p); });
         }
         VF_HIP_CHECK(hipGetLastError());
         return VF_OK;
@@ -1702,6 +1773,13 @@ struct ScheduleSink {
         }
         return dp;
     }
+    // a descriptor of `type` for B samples, every other field zero
+    static PhaseDesc phase(int type, int B) {
+        PhaseDesc P;
+        memset(&P, 0, sizeof(P));
+        P.type = type; P.B = B;
+        return P;
+    }
     int add(PhaseDesc &P, int n_items, int counters, std::initializer_list<int> deps) {
         P.first_ticket = next_ticket; P.n_items = n_items;
         P.cnt_base = next_counter;
@@ -1715,6 +1793,13 @@ struct ScheduleSink {
         return (int)phases.size() - 1;
     }
     bool early_start = true;
+    // Is input u awaited LATE - mid-item, behind the chunks of the input that exists early (ConvParams::late_cnt) - instead of
+    // releasing the item?  Only with early start on and a producer that is emitted; `ld` is then how to recognise it done.
+    bool late_dep(int u, PhaseDep &ld) const {
+        if (!early_start || u < 0 || u == kSkipped) return false;
+        ld = dep_on(phases[u]);
+        return true;
+    }
     // conv-LSTM of one step: u_prev = the same cell at the previous step (producer of the recurrent input and of the
     // cell state), u_x = the producer of the layer input.  Early start: the item is released by u_prev alone and
     // waits for u_x after its recurrent chunks (ConvParams::late_cnt; the counters' address is patched in at upload).
@@ -1724,56 +1809,44 @@ struct ScheduleSink {
     // arch 2: the border-class biases of the tiled conditioning vector for one conv-LSTM, kCondPerItem samples per item
     // (the layer's conditioning weights are read once per item)
     int cond(const CondParams &p, std::initializer_list<int> deps) {
-        PhaseDesc P;
-        memset(&P, 0, sizeof(P));
-        P.type = PH_COND; P.cond = p; P.B = p.B;
+        PhaseDesc P = phase(PH_COND, p.B);
+        P.cond = p;
         return add(P, (p.B + kCondPerItem - 1) / kCondPerItem, p.B, deps);
     }
     // element-wise items of arch 3 (vf_savp3.h): gx items per sample, or one item per spi samples
     int ew(const EwParams &p, int view, std::initializer_list<int> deps) {
-        PhaseDesc P;
-        memset(&P, 0, sizeof(P));
-        P.type = PH_EW; P.ew = p; P.B = p.B; P.view = view;
+        PhaseDesc P = phase(PH_EW, p.B);
+        P.ew = p; P.view = view;
         P.gx = p.spi > 0 ? 1 : p.gx; P.gy = 1;
-        const int items = p.spi > 0 ? (p.B + p.spi - 1) / p.spi : p.B * p.gx;
         max_lds = std::max(max_lds, ew_lds_bytes(p.op, p.op == EW_TOP3 ? p.top.ND : 1));
-        return add(P, items, p.B, deps);
+        return add(P, ew_items(p), p.B, deps);
     }
     // a two-input tile whose segment 0 comes from u_early and whose segment 1 from u_late (decoder convs: the encoder
     // skip tensor first, the previous layer's output late)
     int conv_late(int type, const ConvLayer &l, const ConvParams &p, int u_early, int u_late, int u_extra = -1) {
-        const bool late = early_start && u_late >= 0 && u_late != kSkipped;
-        if (!late) return conv(type, l, p, {u_early, u_late, u_extra});
-        const PhaseDep ld = dep_on(phases[u_late]);
+        PhaseDep ld;
+        if (!late_dep(u_late, ld)) return conv(type, l, p, {u_early, u_late, u_extra});
         const int u = conv(type, l, p, {u_early, u_extra});
         if (u >= 0) { phases[u].has_late = 1; phases[u].late = ld; }
         return u;
     }
     int conv(int type, const ConvLayer &l, const ConvParams &p, std::initializer_list<int> deps) {
-        PhaseDesc P;
-        memset(&P, 0, sizeof(P));
-        P.type = type; P.conv = p; P.B = p.B;
+        PhaseDesc P = phase(type, p.B);
+        P.conv = p;
         P.NI = l.NI; P.tiles_per_img = l.tilesY * l.tilesX;
-        P.gx = l.NI == 1 ? p.B * P.tiles_per_img : (p.B + l.NI - 1) / l.NI;
+        P.gx = conv_items_x(l, p.B);
         P.gy = l.ncg;
         if (l.tile == TILE_FC_WIDE) P.gy = 1;     // all column groups in one item (vf_fc_tile.h)
         P.whole = type == PH_FC_PARTIAL;
         P.tile = l.tile; P.mrep = l.mrep;
         P.prec = p.tile_variant;
         max_lds = std::max(max_lds, l.lds_bytes);
-        const double rows = (double)p.B * l.Hout * l.Wout;
-        const double taps = l.mode == PACK_CONVT ? 9.0 / 4.0 * 4.0 : (double)l.KH * l.KW;   // real taps
-        // (executed products: less the kernel rows the gate-split tile skips, ConvParams::pad_skip)
-        const double skipped = p.pad_skip && (type == PH_LSTM || type == PH_GATES_RAW) ? 5.0 * gs_pad_skipped_pairs(l, p.B) : 0.0;
-        if (l.tile != TILE_FIRST_VALU)      // (the first conv runs on the vector ALUs: not matrix work, not counted)
-            flops += 2.0 * (rows * taps - skipped) * (l.segC[0] + (l.nseg > 1 ? l.segC[1] : 0) - p.chunk_begin * l.KC) *
-                     (l.mode == PACK_LSTM ? 4.0 : (l.mode == PACK_PLAIN ? (double)l.G : 1.0)) * l.Cout;
+        flops += conv_flops(type, l, p);
         return add(P, P.gx * P.gy * l.nsplit, P.whole ? 1 : p.B, deps);
     }
     int sa(const SaParams &p, std::initializer_list<int> deps) {
-        PhaseDesc P;
-        memset(&P, 0, sizeof(P));
-        P.type = PH_SA; P.sa = p; P.B = p.B;
+        PhaseDesc P = phase(PH_SA, p.B);
+        P.sa = p;
         return add(P, (p.B + kSaPerItem - 1) / kSaPerItem, p.B, deps);
     }
     // a conv whose tiles hold whole images + the 1x1 conv that consumes it, as one item per row tile (conv_pair_epilogue):
@@ -1790,9 +1863,8 @@ struct ScheduleSink {
     }
     int conv_pair(const ConvLayer &a, const ConvParams &pa, const ConvLayer &b, const ConvParams &pb,
                   std::initializer_list<int> deps) {
-        PhaseDesc P;
-        memset(&P, 0, sizeof(P));
-        P.type = PH_CONV_PAIR; P.conv = pa; P.conv2 = pb; P.B = pa.B;
+        PhaseDesc P = phase(PH_CONV_PAIR, pa.B);
+        P.conv = pa; P.conv2 = pb;
         P.conv.ncg = 1;         // both channel groups in this item
         P.NI = a.NI; P.tiles_per_img = 1;
         P.gx = (pa.B + a.NI - 1) / a.NI; P.gy = 1;
@@ -1803,15 +1875,13 @@ struct ScheduleSink {
         return add(P, P.gx, pa.B, deps);
     }
     int fin(const FinParams &p, std::initializer_list<int> deps) {
-        PhaseDesc P;
-        memset(&P, 0, sizeof(P));
-        P.type = PH_CDNA_FIN; P.fin = p; P.B = p.B;
+        PhaseDesc P = phase(PH_CDNA_FIN, p.B);
+        P.fin = p;
         return add(P, p.B, p.B, deps);
     }
     int composite(const CompositeParams &p, int ntiles, int view, std::initializer_list<int> deps) {
-        PhaseDesc P;
-        memset(&P, 0, sizeof(P));
-        P.type = PH_COMPOSITE; P.comp = p; P.B = p.B; P.gx = ntiles; P.view = view;
+        PhaseDesc P = phase(PH_COMPOSITE, p.B);
+        P.comp = p; P.gx = ntiles; P.view = view;
         return add(P, ntiles * p.B, p.B, deps);
     }
     // top transposed conv + compositing: one fused item per conv tile where the tile geometry allows it (a region
@@ -1824,18 +1894,16 @@ struct ScheduleSink {
             if (u < 0) return u;
             return composite(cp, ntiles, view, {u, dfin});
         }
-        const bool late = early_start && d_late >= 0 && d_late != kSkipped;
-        PhaseDesc P;
-        memset(&P, 0, sizeof(P));
-        P.type = PH_TOP_FUSED; P.conv = p; P.comp = cp; P.B = p.B; P.view = view;
+        PhaseDesc P = phase(PH_TOP_FUSED, p.B);
+        P.conv = p; P.comp = cp; P.view = view;
         P.NI = 1; P.tiles_per_img = l.tilesY * l.tilesX;
         P.gx = p.B * P.tiles_per_img; P.gy = 1;
         P.mrep = 1;
         P.aux_base = next_counter + p.B;        // behind the completion counters of this phase
         max_lds = std::max(max_lds, std::max(l.lds_bytes, fused_top_lds_floats(l.TH, l.TW, cp.ND) * 4));
         flops += 2.0 * (double)p.B * l.Hout * l.Wout * 9.0 * (l.segC[0] + (l.nseg > 1 ? l.segC[1] : 0)) * l.Cout;
-        if (!late) return add(P, P.gx, 2 * p.B, {d_early, d_late, dfin});
-        P.has_late = 1; P.late = dep_on(phases[d_late]);
+        if (!late_dep(d_late, P.late)) return add(P, P.gx, 2 * p.B, {d_early, d_late, dfin});
+        P.has_late = 1;
         return add(P, P.gx, 2 * p.B, {d_early, dfin});
     }
     static bool failed(int rc) { return rc < 0; }
@@ -1870,7 +1938,7 @@ static int emit_rollout(vf_handle *h, int view, const BatchView &v, const BatchV
                         const int32_t *goal_pix, Sink &sink, bool skip_shared) {
     const vf_config &c = h->cfg;
     const ViewData &vd = h->views[view];
-    const int H = h->H, W = h->W, T = h->T, ND = h->ND, nc = c.n_context;
+    const int H = h->H, W = h->W, ND = h->ND, nc = c.n_context;
     const BatchView &base = h->base;        // (names the buffer whose elements per sample h->per() returns)
     auto params = [&](const ConvLayer &l, int Bp, const SegArg &s0, const SegArg *s1) {
         return make_params(l, vd.lw[l.id], Bp, s0, s1, h->pad_skip);
@@ -1899,7 +1967,7 @@ static int emit_rollout(vf_handle *h, int view, const BatchView &v, const BatchV
         for (const Cand &c : cands) {           // largest tile first
             if (!c.l) continue;
             const ConvLayer &l = *c.l;
-            const double n = (double)(l.NI == 1 ? (long long)Bp * l.tilesY * l.tilesX : (Bp + l.NI - 1) / l.NI) * l.ncg;
+            const double n = (double)conv_items_x(l, Bp) * l.ncg;
             const double d = c.fixed + c.slope * K;
             const double t = std::max(d, n * d / S);
             if (best == 0.0 || t < 0.85 * best) { best = t; want = c.want; }
@@ -1912,7 +1980,7 @@ static int emit_rollout(vf_handle *h, int view, const BatchView &v, const BatchV
     // light layers of the bottleneck: one image per workgroup for small batches (measured: -2.1 % at 25 samples, 0 at 50, +0.3 % at 100, +1.1 % at 200)
     auto light_plan = [&](const ConvLayer &reg, const ConvLayer &one, int Bp) -> const ConvLayer & {
         if (reg.NI <= 1 || one.NI != 1 || one.KC != reg.KC) return reg;
-        const long long items = (long long)((Bp + reg.NI - 1) / reg.NI) * reg.ncg;
+        const long long items = (long long)conv_items_x(reg, Bp) * reg.ncg;
         return items <= h->n_cu / 8 ? one : reg;
     };
     auto all_shared = [&](int s) { return h->dedup && s < nc - 1; };
@@ -1923,9 +1991,6 @@ static int emit_rollout(vf_handle *h, int view, const BatchView &v, const BatchV
     // is the output of lstm k at step s one shared image?  (s < 0: the shared zero state)
     auto lstm_shared = [&](int k, int s) { return s < 0 || all_shared(s) || (k < 4 && core_shared(s)); };
 
-    auto plain = [](const float *ptr, long long bs) {
-        SegArg s; memset(&s, 0, sizeof(s)); s.ptr = ptr; s.bstride = bs; s.gamma_mod = 1; return s;
-    };
     auto normed = [](const float *ptr, long long bs, const long long *part, int nparts, int row_slots, bool shared,
                      long long count, const float *g, const float *b, int gmod, int relu) {
         SegArg s; s.ptr = ptr; s.bstride = bs; s.ln_part = part; s.ln_nparts = nparts;
@@ -1933,9 +1998,6 @@ static int emit_rollout(vf_handle *h, int view, const BatchView &v, const BatchV
         s.ln_inv_n = (float)(1.0 / (double)count); s.gamma = g; s.beta = b; s.gamma_mod = gmod; s.relu = relu;
         return s;
     };
-#define VF_EMIT(var, expr)                 \
-    const int var = (expr);                \
-    if (Sink::failed(var)) return var;
 // a shared unit whose result is still valid from an earlier rollout is not emitted again
 #define VF_EMIT_SH(var, shared, expr) VF_EMIT(var, ((shared) && skip_shared) ? Sink::skipped() : (expr))
 
@@ -1945,7 +2007,6 @@ static int emit_rollout(vf_handle *h, int view, const BatchView &v, const BatchV
     for (int s = 0; s < h->S; ++s) {
         const int cur = s & 1, nxt = cur ^ 1;
         const bool produce = s >= nc - 1;
-        const int t_out = s - (nc - 1);
         const bool enc0_sh = enc_shared(s), enc_sh = core_shared(s), all_sh = all_shared(s);
         const BatchView &E0 = enc0_sh ? sh : v;     // enc00 / enc0: the convs in front of lstm1
         const BatchView &E = enc_sh ? sh : v;       // the other encoder tensors of this step
@@ -1954,15 +2015,12 @@ static int emit_rollout(vf_handle *h, int view, const BatchView &v, const BatchV
         auto bs = [](bool shared, long long per) { return shared ? 0LL : per; };
 
         // ---- state FC + action/state bias of enc3
+        const StepIo io = step_io(h, vd, v, s);
         SaParams sp; memset(&sp, 0, sizeof(sp));
-        if (s < nc - 1) { sp.action = h->ctx_actions + (size_t)s * c.adim; sp.action_bstride = 0; }
-        else { sp.action = v.actions + (size_t)(s - (nc - 1)) * c.adim; sp.action_bstride = (long long)T * c.adim; }
-        if (s < nc) { sp.state = h->ctx_states + (size_t)s * c.sdim; sp.state_bstride = 0; }
-        else { sp.state = v.states_all + (size_t)(s - nc) * c.sdim; sp.state_bstride = (long long)T * c.sdim; }
+        sp.action = io.action; sp.action_bstride = io.action_bs; sp.state = io.state; sp.state_bstride = io.state_bs;
         sp.adim = c.adim; sp.sdim = c.sdim; sp.B = BD;
         sp.w_state = vd.w_state; sp.b_state = vd.b_state; sp.w_sa = vd.w_sa; sp.n_out = h->enc3.Cout;
-        sp.state_out = produce ? v.states_all + (size_t)t_out * c.sdim : nullptr;
-        sp.state_out_bstride = (long long)T * c.sdim;
+        sp.state_out = io.state_out; sp.state_out_bstride = io.state_out_bs;
         sp.sbias = D.sbias;
         VF_EMIT_SH(u_sa, all_sh, sink.sa(sp, {last}))
 
@@ -1997,16 +2055,12 @@ static int emit_rollout(vf_handle *h, int view, const BatchView &v, const BatchV
         auto emit_cond = [&](const int sc, const int u_state, int (&out)[7]) -> int {
             for (int k = 0; k < 7; ++k) out[k] = -1;
             if (!h->cond || sc >= h->S) return VF_OK;
-            const float *act, *sta; long long act_bs, sta_bs;
-            if (sc < nc - 1) { act = h->ctx_actions + (size_t)sc * c.adim; act_bs = 0; }
-            else { act = v.actions + (size_t)(sc - (nc - 1)) * c.adim; act_bs = (long long)T * c.adim; }
-            if (sc < nc) { sta = h->ctx_states + (size_t)sc * c.sdim; sta_bs = 0; }
-            else { sta = v.states_all + (size_t)(sc - nc) * c.sdim; sta_bs = (long long)T * c.sdim; }
+            const StepIo ic = step_io(h, vd, v, sc);
             for (int k = 0; k < 7; ++k) {
                 const bool shd = lstm_shared(k, sc);
                 CondParams cq; memset(&cq, 0, sizeof(cq));
-                cq.action = act; cq.action_bstride = act_bs;
-                cq.state = sta; cq.state_bstride = sta_bs;
+                cq.action = ic.action; cq.action_bstride = ic.action_bs;
+                cq.state = ic.state; cq.state_bstride = ic.state_bs;
                 cq.adim = c.adim; cq.sdim = c.sdim; cq.B = shd ? 1 : B;
                 cq.w = vd.w_cond[k]; cq.C4 = 4 * h->lstm[k].Cout;
                 cq.out = (shd ? sh : v).cond_bias[k][sc & 1];
@@ -2021,22 +2075,18 @@ static int emit_rollout(vf_handle *h, int view, const BatchView &v, const BatchV
         }
 
         // ---- encoder
-        const float *frame_in; long long frame_bs;
-        if (s < nc) { frame_in = vd.ctx_frames + (size_t)s * H * W * 3; frame_bs = 0; }
-        else { frame_in = v.frames_all + (size_t)(s - nc) * H * W * 3; frame_bs = (long long)T * H * W * 3; }
-
         ConvParams p;
         int u_enc00 = last;
         SegArg enc00_n = plain(nullptr, 0);
         if (h->savp) {      // extra encoder scale: enc00 = relu(LNa(conv5x5/2(frame))), applied on staging
-            p = params(h->enc00, BE0, plain(frame_in, frame_bs), nullptr);
+            p = params(h->enc00, BE0, plain(io.frame, io.frame_bs), nullptr);
             p.out = E0.enc00_o; p.stats = E0.st_enc00;
             VF_EMIT_SH(u_e00, enc0_sh, sink.conv(PH_CONV_RAW, h->enc00, p, {last}))
             u_enc00 = u_e00;
             enc00_n = normed(E0.enc00_o, bs(enc0_sh, h->per(base.enc00_o)), E0.st_enc00, h->enc00.stats_nparts,
                              h->enc00.stats_nparts, enc0_sh, h->per(base.enc00_o), vd.ln_g[9], vd.ln_b[9], kEnc00Ch, 1);
         }
-        p = params(h->enc0, BE0, h->savp ? enc00_n : plain(frame_in, frame_bs), nullptr);
+        p = params(h->enc0, BE0, h->savp ? enc00_n : plain(io.frame, io.frame_bs), nullptr);
         p.out = E0.enc0_o; p.stats = E0.st_enc0;
         VF_EMIT_SH(u_enc0, enc0_sh, sink.conv(PH_CONV_RAW, h->enc0, p, {u_enc00}))
 
@@ -2202,25 +2252,12 @@ static int emit_rollout(vf_handle *h, int view, const BatchView &v, const BatchV
             // DNA: every tap lies inside the tile's halo, as for CDNA, so the CDNA dependency rules hold as they are.
             if (h->flow || h->dna) { cp.w_flow = vd.w_flow; cp.b_flow = vd.b_flow; }
             else cp.kern = v.kern;
-            cp.prev_frame = frame_in; cp.prev_frame_bstride = frame_bs;
-            if (ND == 0) {      // frames-only: the tile neither reads nor writes a distribution or a block sum
-                cp.prev_distrib = nullptr; cp.prev_distrib_bstride = 0; cp.prev_sums = nullptr;
-            } else if (s < nc) {
-                cp.prev_distrib = vd.ctx_distrib + (size_t)s * H * W * ND; cp.prev_distrib_bstride = 0;
-                cp.prev_sums = nullptr;
-            } else {
-                cp.prev_distrib = v.distrib_all + (size_t)(s - nc) * H * W * ND;
-                cp.prev_distrib_bstride = (long long)T * H * W * ND;
-                cp.prev_sums = v.sums + (long long)(s - nc) * h->sums_step_stride;
-            }
-            cp.out_frame = v.frames_all + (size_t)t_out * H * W * 3; cp.out_frame_bstride = (long long)T * H * W * 3;
-            if (ND > 0) {
-                cp.out_distrib = v.distrib_all + (size_t)t_out * H * W * ND;
-                cp.out_distrib_bstride = (long long)T * H * W * ND;
-                cp.out_sums = v.sums + (long long)t_out * h->sums_step_stride;
-            }
-            if (goal_pix)
-                for (int d = 0; d < ND; ++d) { cp.goal[d][0] = goal_pix[2 * d]; cp.goal[d][1] = goal_pix[2 * d + 1]; }
+            // (frames-only: the tile neither reads nor writes a distribution or a block sum - step_io leaves them null)
+            cp.prev_frame = io.frame; cp.prev_frame_bstride = io.frame_bs;
+            cp.prev_distrib = io.prev_distrib; cp.prev_distrib_bstride = io.prev_distrib_bs; cp.prev_sums = io.prev_sums;
+            cp.out_frame = io.out_frame; cp.out_frame_bstride = io.out_frame_bs;
+            cp.out_distrib = io.out_distrib; cp.out_distrib_bstride = io.out_distrib_bs; cp.out_sums = io.out_sums;
+            set_goal(cp.goal, goal_pix, ND);
             VF_EMIT(u_comp, sink.top(*top_l, p, cp, h->ntiles, view, top_early, top_late, u_fin, h->fuse_top))
             last = u_comp;
         }
@@ -2690,6 +2727,17 @@ static bool shared_cache_hit(vf_handle *h, int cfg) {
     return h->dedup && h->cache_shared && h->shared_valid && h->shared_cfg == cfg;
 }
 
+// the caller's per-task weights [ncam][ND] as a kernel argument (null: every task weighs the same)
+static TaskWeights task_weights_of(const vf_handle *h, const float *task_weights) {
+    TaskWeights tw;
+    memset(&tw, 0, sizeof(tw));
+    if (task_weights) {
+        tw.use = 1;
+        for (int i = 0; i < h->ncam * h->ND; ++i) tw.w[i] = task_weights[i];
+    }
+    return tw;
+}
+
 template <int ND>
 static int launch_persistent_t(const Schedule &sc, int mode, int grid, size_t lds, hipStream_t st) {
     if (mode == COMP_DNA) hipLaunchKernelGGL((rollout_dna_kernel<ND>), dim3(grid), dim3(kConvThreads), lds, st, sc.phases, sc);
@@ -2789,35 +2837,18 @@ static int run_persistent(vf_handle *h, const float *d_actions, int B, const int
     const int by_lds = (int)std::max<size_t>(1, (160 * 1024) / lds);
     const int wgs_per_cu = std::min(h->persist_wgs_per_cu, by_lds);
     const int grid = std::min(sc_host.items, h->n_cu * wgs_per_cu);
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (h->profiling) {
-        while (h->ev_pool.size() < h->ev_used + 2) {
-            hipEvent_t e;
-            VF_HIP_CHECK(hipEventCreate(&e));
-            h->ev_pool.push_back(e);
-        }
-        e0 = h->ev_pool[h->ev_used]; e1 = h->ev_pool[h->ev_used + 1];
-        VF_HIP_CHECK(hipEventRecord(e0, st));
-    }
+    if (h->profiling && (rc = profile_begin(h, st))) return rc;
     const int mode = h->dna ? COMP_DNA : (h->flow ? COMP_FLOW : COMP_CDNA);
-    switch (h->ND) {
-        case 0:     // frames-only engines: kernels of their own names (vf_persistent.h)
-            if (mode == COMP_DNA) hipLaunchKernelGGL(rollout_dna_frames_kernel, dim3(grid), dim3(kConvThreads), lds, st, sc.phases, sc);
-            else if (mode == COMP_FLOW) hipLaunchKernelGGL(rollout_flow_frames_kernel, dim3(grid), dim3(kConvThreads), lds, st, sc.phases, sc);
-            else hipLaunchKernelGGL(rollout_frames_kernel, dim3(grid), dim3(kConvThreads), lds, st, sc.phases, sc);
-            rc = hipGetLastError() == hipSuccess ? VF_OK : fail(VF_ERR_HIP, "launch of the frames-only rollout kernel failed");
-            break;
-        case 1: rc = launch_persistent_t<1>(sc, mode, grid, lds, st); break;
-        case 2: rc = launch_persistent_t<2>(sc, mode, grid, lds, st); break;
-        case 3: rc = launch_persistent_t<3>(sc, mode, grid, lds, st); break;
-        default: rc = launch_persistent_t<4>(sc, mode, grid, lds, st); break;
+    if (h->ND == 0) {       // frames-only engines: kernels of their own names (vf_persistent.h)
+        if (mode == COMP_DNA) hipLaunchKernelGGL(rollout_dna_frames_kernel, dim3(grid), dim3(kConvThreads), lds, st, sc.phases, sc);
+        else if (mode == COMP_FLOW) hipLaunchKernelGGL(rollout_flow_frames_kernel, dim3(grid), dim3(kConvThreads), lds, st, sc.phases, sc);
+        else hipLaunchKernelGGL(rollout_frames_kernel, dim3(grid), dim3(kConvThreads), lds, st, sc.phases, sc);
+        rc = hipGetLastError() == hipSuccess ? VF_OK : fail(VF_ERR_HIP, "launch of the frames-only rollout kernel failed");
+    } else {
+        rc = with_nd(h->ND, [&](auto nd) { return launch_persistent_t<decltype(nd)::value>(sc, mode, grid, lds, st); });
     }
     if (rc) return rc;
-    if (h->profiling) {
-        VF_HIP_CHECK(hipEventRecord(e1, st));
-        h->ev_used += 2;
-        h->prof_flops += sc_host.flops;
-    }
+    if (h->profiling && (rc = profile_end(h, st, sc_host.flops))) return rc;
     h->shared_valid = h->dedup;
     h->shared_cfg = cfg;
     return VF_OK;
@@ -2859,12 +2890,7 @@ int vf_rollout(vf_handle *h, const float *d_actions, int32_t B, const int32_t *g
         h->last_goal.clear();
         return VF_OK;
     }
-    TaskWeights tw;
-    memset(&tw, 0, sizeof(tw));
-    if (task_weights) {
-        tw.use = 1;
-        for (int i = 0; i < h->ncam * h->ND; ++i) tw.w[i] = task_weights[i];
-    }
+    const TaskWeights tw = task_weights_of(h, task_weights);
     const int n_actions = B / h->n_draws;
     hipLaunchKernelGGL(scores_kernel, dim3(n_actions), dim3(64), 0, st, h->sums, h->sums_step_stride,
                        h->sums_view_stride, n_actions, h->n_draws, h->T, h->ND, h->ncam, h->nblocks, finalweight, tw,
@@ -2904,12 +2930,7 @@ int vf_ensemble_scores(vf_handle *const *members, int32_t n_members, float lambd
     memset(&em, 0, sizeof(em));
     em.n = n_members;
     for (int m = 0; m < n_members; ++m) { em.sums[m] = members[m]->sums; em.status[m] = members[m]->d_status; }
-    TaskWeights tw;
-    memset(&tw, 0, sizeof(tw));
-    if (task_weights) {
-        tw.use = 1;
-        for (int i = 0; i < h0->ncam * h0->ND; ++i) tw.w[i] = task_weights[i];
-    }
+    const TaskWeights tw = task_weights_of(h0, task_weights);
     const int n_actions = h0->last_B / h0->n_draws;
     hipLaunchKernelGGL(ensemble_scores_kernel, dim3(n_actions), dim3(64), 0, st, em, h0->sums_step_stride,
                        h0->sums_view_stride, n_actions, h0->n_draws, h0->T, h0->ND, h0->ncam, h0->nblocks,
@@ -2959,17 +2980,11 @@ int vf_render_plans(vf_handle *h, const int32_t *d_seq, int32_t K, const uint8_t
         VF_HIP_CHECK(hipGetLastError());
     }
     if (d_distrib_u8) {
-        auto launch = [&](auto kernel) {
-            hipLaunchKernelGGL(kernel, dim3((unsigned)(K * NV * T)), dim3(kRenderThreads), 0, st, h->distrib_all,
-                               view_rows * HW * h->ND, h->sums, h->sums_step_stride, h->sums_view_stride, h->nblocks, d_seq,
-                               h->last_B, NV, T, HW, d_lut, reinterpret_cast<uint32_t *>(d_distrib_u8));
-        };
-        switch (h->ND) {
-            case 1: launch(render_distrib_kernel<1>); break;
-            case 2: launch(render_distrib_kernel<2>); break;
-            case 3: launch(render_distrib_kernel<3>); break;
-            default: launch(render_distrib_kernel<4>); break;
-        }
+        with_nd(h->ND, [&](auto nd) {
+            hipLaunchKernelGGL(render_distrib_kernel<decltype(nd)::value>, dim3((unsigned)(K * NV * T)), dim3(kRenderThreads), 0, st,
+                               h->distrib_all, view_rows * HW * h->ND, h->sums, h->sums_step_stride, h->sums_view_stride,
+                               h->nblocks, d_seq, h->last_B, NV, T, HW, d_lut, reinterpret_cast<uint32_t *>(d_distrib_u8));
+        });
         VF_HIP_CHECK(hipGetLastError());
     }
     return VF_OK;
@@ -3066,10 +3081,7 @@ int vf_debug_lstm_layer(vf_handle *h, int32_t layer, int32_t B, const float *d_x
     VF_HIP_CHECK(hipSetDevice(h->cfg.device));
     const ConvLayer &l = h->lstm[layer];
     const long long px = (long long)l.Hin * l.Win;
-    SegArg sh, sx;
-    memset(&sh, 0, sizeof(sh)); memset(&sx, 0, sizeof(sx));
-    sh.ptr = d_h; sh.bstride = px * l.segC[0]; sh.gamma_mod = 1;       // (segment 0 is the recurrent input)
-    sx.ptr = d_x; sx.bstride = px * l.segC[1]; sx.gamma_mod = 1;
+    const SegArg sh = plain(d_h, px * l.segC[0]), sx = plain(d_x, px * l.segC[1]);      // (segment 0 is the recurrent input)
     ConvParams q = make_params(l, h->views[0].lw[l.id], B, sh, &sx, h->pad_skip);
     q.out = d_h_out; q.cstate = d_c_out; q.cstate_in = d_c; q.cin_bstride = px * l.Cout;
     q.stats = h->base.st_h[layer]; q.stats_nparts = h->st_rows[layer];

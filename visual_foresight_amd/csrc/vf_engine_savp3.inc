@@ -514,25 +514,16 @@ static int emit_rollout_s3(vf_handle *h, int view, int B, const float *d_actions
     Savp3 *s = h->s3;
     const ViewData &vd = h->views[view];
     const S3ViewW &vw = s->vw[view];
-    const int H = h->H, W = h->W, T = h->T, ND = h->ND, nc = c.n_context, ncond = s->ncond;
+    const int H = h->H, W = h->W, ND = h->ND, nc = c.n_context, ncond = s->ncond;
     const size_t BV = (size_t)c.max_batch * h->ncam;
     const size_t row = (size_t)view * c.max_batch;         // first row of this view in every [ncam][max_batch] buffer
     const long long HW = (long long)H * W;
     const BatchView bv = make_view(h, view, d_actions);
-    float *frames_all = bv.frames_all, *distrib_all = bv.distrib_all, *states_all = bv.states_all;
-    double *sums = bv.sums;
-    const float *actions = d_actions;
 
-    auto plain = [](const float *ptr, long long bs) {
-        SegArg a; memset(&a, 0, sizeof(a)); a.ptr = ptr; a.bstride = bs; a.gamma_mod = 1; return a;
-    };
     auto params = [&](const ConvLayer &l, const SegArg &s0, const SegArg *s1) { return make_params(l, vd.lw[l.id], B, s0, s1, h->pad_skip); };
     auto ew_base = [&](int op, int gx, int spi) {
         EwParams e; memset(&e, 0, sizeof(e)); e.op = op; e.B = B; e.gx = gx; e.spi = spi; return e;
     };
-#define S3_EMIT(var, expr)                 \
-    const int var = (expr);                \
-    if (Sink::failed(var)) return var;
 
     int last = -1, last2 = -1;          // terminal unit of the previous step / of the one before
     int u_sa_prev = -1;
@@ -544,21 +535,16 @@ static int emit_rollout_s3(vf_handle *h, int view, int B, const float *d_actions
     // whose element-wise items were the last readers of that parity's tables.
     auto emit_cond = [&](const int sx, const int guard) -> int {
         const int par = sx & 1;
-        const bool produce = sx >= nc - 1;
-        const int t_out = sx - (nc - 1);
+        const StepIo ic = step_io(h, vd, bv, sx);
         EwParams e = ew_base(EW_SA3, 0, kSaPerItem);
-        if (sx < nc - 1) { e.sa.action = h->ctx_actions + (size_t)sx * c.adim; e.sa.action_bs = 0; }
-        else { e.sa.action = actions + (size_t)(sx - (nc - 1)) * c.adim; e.sa.action_bs = (long long)T * c.adim; }
-        if (sx < nc) { e.sa.state = h->ctx_states + (size_t)sx * c.sdim; e.sa.state_bs = 0; }
-        else { e.sa.state = states_all + (size_t)(sx - nc) * c.sdim; e.sa.state_bs = (long long)T * c.sdim; }
+        e.sa.action = ic.action; e.sa.action_bs = ic.action_bs; e.sa.state = ic.state; e.sa.state_bs = ic.state_bs;
         e.sa.adim = c.adim; e.sa.sdim = c.sdim; e.sa.zdim = c.zdim;
         e.sa.w_state = vd.w_state; e.sa.b_state = vd.b_state; e.sa.w_rnnz = vw.w_rnnz; e.sa.b_rnnz = vw.b_rnnz;
         e.sa.rnn_state = s->rnn_state + row * 2 * c.zdim; e.sa.first = sx == 0;
         float *condvec = s->condvec + ((size_t)sx * BV + row) * ncond;
         e.sa.condvec = condvec;
-        e.sa.state_out = produce ? states_all + (size_t)t_out * c.sdim : nullptr;
-        e.sa.state_out_bs = (long long)T * c.sdim;
-        S3_EMIT(u_sa, sink.ew(e, view, {u_sa_prev}))
+        e.sa.state_out = ic.state_out; e.sa.state_out_bs = ic.state_out_bs;
+        VF_EMIT(u_sa, sink.ew(e, view, {u_sa_prev}))
         u_sa_prev = u_sa;
         for (int i = 0; i < s->nl; ++i) {
             const S3Layer &l = s->L[i];
@@ -566,13 +552,13 @@ static int emit_rollout_s3(vf_handle *h, int view, int B, const float *d_actions
             q.cond.condvec = condvec; q.cond.ncond = ncond; q.cond.w = vw.wc_conv[i]; q.cond.Ctot = l.C; q.cond.KH = l.conv.KH;
             if (l.dec) s3_ftab_up(q.cond.f); else s3_ftab_pool(q.cond.f, l.k);
             q.cond.out = l.cb_conv + ((size_t)par * BV + row) * 25 * l.C;
-            S3_EMIT(ucc, sink.ew(q, view, {u_sa, guard}))
+            VF_EMIT(ucc, sink.ew(q, view, {u_sa, guard}))
             u_cc_all[par][i] = ucc; u_cl_all[par][i] = -1;
             if (!l.rnn) continue;
             q.cond.w = vw.wc_lstm[i]; q.cond.Ctot = 4 * l.C; q.cond.KH = 5;
             s3_ftab_lstm(q.cond.f);
             q.cond.out = l.cb_lstm + ((size_t)par * BV + row) * 25 * 4 * l.C;
-            S3_EMIT(ucl, sink.ew(q, view, {u_sa, guard}))
+            VF_EMIT(ucl, sink.ew(q, view, {u_sa, guard}))
             u_cl_all[par][i] = ucl;
         }
         return VF_OK;
@@ -584,13 +570,9 @@ static int emit_rollout_s3(vf_handle *h, int view, int B, const float *d_actions
     for (int st = 0; st < h->S; ++st) {
         const int cur = st & 1, nxt = cur ^ 1, par = st & 1;
         const bool produce = st >= nc - 1;
-        const int t_out = st - (nc - 1);
+        const StepIo io = step_io(h, vd, bv, st);
         const int *u_cc = u_cc_all[par], *u_cl = u_cl_all[par];
         const int last_at_entry = last;     // terminal unit of step st - 1: the guard of step st + 1's tables
-
-        const float *frame_in; long long frame_bs;
-        if (st < nc) { frame_in = vd.ctx_frames + (size_t)st * HW * 3; frame_bs = 0; }
-        else { frame_in = frames_all + (size_t)(st - nc) * HW * 3; frame_bs = (long long)T * HW * 3; }
 
         // ---- encoder / decoder
         const float *x = nullptr; long long x_bs = 0; int u_x = last;      // output of the previous layer, its producer
@@ -605,12 +587,12 @@ static int emit_rollout_s3(vf_handle *h, int view, int B, const float *d_actions
                 ConvParams p;
                 if (i == 0) {
                     SegArg s1 = plain(vd.ctx_frames, 0);        // the FIRST context frame, shared by every sample
-                    p = params(l.conv, plain(frame_in, frame_bs), &s1);
+                    p = params(l.conv, plain(io.frame, io.frame_bs), &s1);
                 } else {
                     p = params(l.conv, plain(x, x_bs), nullptr);
                 }
                 p.out = ebuf;
-                S3_EMIT(uc, sink.conv(l.conv.G == 4 ? PH_CONV_RAW3G4 : (l.conv.G == 2 ? PH_CONV_RAW3G2 : PH_CONV_RAW3), l.conv, p, {u_x}))
+                VF_EMIT(uc, sink.conv(l.conv.G == 4 ? PH_CONV_RAW3G4 : (l.conv.G == 2 ? PH_CONV_RAW3G2 : PH_CONV_RAW3), l.conv, p, {u_x}))
                 u_conv = uc;
             } else {
                 float *ubuf = l.u + row * px * l.cin;
@@ -618,10 +600,10 @@ static int emit_rollout_s3(vf_handle *h, int view, int B, const float *d_actions
                 q.up.in0 = x; q.up.in0_bs = x_bs; q.up.C0 = l.c_prev;
                 q.up.in1 = l.skip >= 0 ? out_ptr[l.skip] : nullptr; q.up.in1_bs = l.skip >= 0 ? out_bs[l.skip] : 0; q.up.C1 = l.c_skip;
                 q.up.out = ubuf; q.up.out_bs = px * l.cin; q.up.h = l.hi; q.up.w = l.wi; q.up.rows = l.up_rows;
-                S3_EMIT(uu, sink.ew(q, view, {u_x, l.skip >= 0 ? u_out[l.skip] : -1}))
+                VF_EMIT(uu, sink.ew(q, view, {u_x, l.skip >= 0 ? u_out[l.skip] : -1}))
                 ConvParams p = params(l.conv, plain(ubuf, px * l.cin), nullptr);
                 p.out = ebuf;
-                S3_EMIT(uc, sink.conv(l.conv.G == 4 ? PH_CONV_RAW3G4 : (l.conv.G == 2 ? PH_CONV_RAW3G2 : PH_CONV_RAW3), l.conv, p, {uu}))
+                VF_EMIT(uc, sink.conv(l.conv.G == 4 ? PH_CONV_RAW3G4 : (l.conv.G == 2 ? PH_CONV_RAW3G2 : PH_CONV_RAW3), l.conv, p, {uu}))
                 u_conv = uc;
             }
             EwParams q = ew_base(EW_INORM, l.C / l.cpi_n, 0);
@@ -629,7 +611,7 @@ static int emit_rollout_s3(vf_handle *h, int view, int B, const float *d_actions
             q.norm.cond = l.cb_conv + ((size_t)par * BV + row) * 25 * l.C; q.norm.cond_bs = 25LL * l.C;
             q.norm.g0 = vw.ng[i]; q.norm.b0 = vw.nb[i];
             q.norm.H = l.ho; q.norm.W = l.wo; q.norm.C = l.C; q.norm.cpi = l.cpi_n; q.norm.relu = 1; q.norm.eps = kS3Eps;
-            S3_EMIT(un, sink.ew(q, view, {u_conv, u_cc[i]}))
+            VF_EMIT(un, sink.ew(q, view, {u_conv, u_cc[i]}))
             x = ebuf; x_bs = px * l.C; u_x = un;
             // The class-bias tables of step st + 1 (fourteen phases of four-sample items; their producers - this step's state
             // FC, the frames of step st - 1 - are long done): behind the smallest encoder layer's conv in ticket order, where a
@@ -647,7 +629,7 @@ static int emit_rollout_s3(vf_handle *h, int view, int B, const float *d_actions
                 ConvParams p = params(l.lstm, hs, &xs);         // recurrent input first (early start)
                 p.out = gates;
                 if (st == 0) p.chunk_begin = l.lstm.nchunk[0];      // h(-1) = 0: the recurrent chunks multiply zeros
-                S3_EMIT(ug, sink.conv_late(PH_GATES_RAW, l.lstm, p, u_cell_prev[i], un))
+                VF_EMIT(ug, sink.conv_late(PH_GATES_RAW, l.lstm, p, u_cell_prev[i], un))
                 EwParams r = ew_base(EW_INCELL, l.C / l.cpi_c, 0);
                 r.norm.in = gates; r.norm.in_bs = px * 4 * l.C;
                 r.norm.cond = l.cb_lstm + ((size_t)par * BV + row) * 25 * 4 * l.C; r.norm.cond_bs = 25LL * 4 * l.C;
@@ -655,7 +637,7 @@ static int emit_rollout_s3(vf_handle *h, int view, int B, const float *d_actions
                 r.norm.cprev = st == 0 ? nullptr : cbuf; r.norm.cprev_bs = px * l.C;
                 r.norm.out = h_out; r.norm.out_bs = px * l.C; r.norm.cout = cbuf; r.norm.cout_bs = px * l.C;
                 r.norm.H = l.ho; r.norm.W = l.wo; r.norm.C = l.C; r.norm.cpi = l.cpi_c; r.norm.eps = kS3Eps;
-                S3_EMIT(ucell, sink.ew(r, view, {ug, u_cl[i]}))
+                VF_EMIT(ucell, sink.ew(r, view, {ug, u_cl[i]}))
                 u_cell_prev[i] = ucell;
                 x = h_out; x_bs = px * l.C; u_x = ucell;
             }
@@ -670,11 +652,11 @@ static int emit_rollout_s3(vf_handle *h, int view, int B, const float *d_actions
         const ConvLayer &fc_l = Sink::fc_plan(h);
         ConvParams pf = params(fc_l, plain(out_ptr[ib], out_bs[ib]), nullptr);
         pf.out = bv.fc_part;
-        S3_EMIT(u_fc, sink.conv(PH_FC_PARTIAL, fc_l, pf, {u_out[ib]}))
+        VF_EMIT(u_fc, sink.conv(PH_FC_PARTIAL, fc_l, pf, {u_out[ib]}))
         FinParams fp;
         fp.partial = pf.out; fp.nsplit = h->fc.nsplit; fp.B = B; fp.K = h->K;
         fp.bias = vd.b_fc; fp.kern = bv.kern;
-        S3_EMIT(u_fin, sink.fin(fp, {u_fc}))
+        VF_EMIT(u_fin, sink.fin(fp, {u_fc}))
 
         // ---- heads
         const float *top = x; const long long top_bs = x_bs; const int u_top = u_x;
@@ -684,23 +666,16 @@ static int emit_rollout_s3(vf_handle *h, int view, int B, const float *d_actions
         float *hmhs_raw = s->hmhs_raw + row * HW * 2 * kS3Ngf;
         ConvParams ph = params(s->hmhs, plain(top, top_bs), nullptr);
         ph.out = hmhs_raw;
-        S3_EMIT(u_hc, sink.conv(PH_CONV_RAW3G2, s->hmhs, ph, {u_top}))
+        VF_EMIT(u_hc, sink.conv(PH_CONV_RAW3G2, s->hmhs, ph, {u_top}))
         EwParams tq = ew_base(EW_TRANSFORM, h->ntiles, 0);
         tq.top.H = H; tq.top.W = W; tq.top.ND = ND;
-        tq.top.prev_frame = frame_in; tq.top.prev_frame_bs = frame_bs;
-        if (st < nc) {
-            tq.top.prev_distrib = vd.ctx_distrib + (size_t)st * HW * ND; tq.top.prev_distrib_bs = 0; tq.top.prev_sums = nullptr;
-        } else {
-            tq.top.prev_distrib = distrib_all + (size_t)(st - nc) * HW * ND; tq.top.prev_distrib_bs = (long long)T * HW * ND;
-            tq.top.prev_sums = sums + (long long)(st - nc) * h->sums_step_stride;
-        }
+        tq.top.prev_frame = io.frame; tq.top.prev_frame_bs = io.frame_bs;
+        tq.top.prev_distrib = io.prev_distrib; tq.top.prev_distrib_bs = io.prev_distrib_bs; tq.top.prev_sums = io.prev_sums;
         tq.top.first_frame = vd.ctx_frames; tq.top.first_distrib = vd.ctx_distrib;
         tq.top.kern = fp.kern; tq.top.scr_raw = scr; tq.top.trans = trans; tq.top.transd = transd; tq.top.mlog = mlog;
-        tq.top.out_frame = frames_all + (size_t)t_out * HW * 3; tq.top.out_frame_bs = (long long)T * HW * 3;
-        tq.top.out_distrib = distrib_all + (size_t)t_out * HW * ND; tq.top.out_distrib_bs = (long long)T * HW * ND;
-        tq.top.out_sums = sums + (long long)t_out * h->sums_step_stride;
-        if (goal_pix)
-            for (int d = 0; d < ND; ++d) { tq.top.goal[d][0] = goal_pix[2 * d]; tq.top.goal[d][1] = goal_pix[2 * d + 1]; }
+        tq.top.out_frame = io.out_frame; tq.top.out_frame_bs = io.out_frame_bs;
+        tq.top.out_distrib = io.out_distrib; tq.top.out_distrib_bs = io.out_distrib_bs; tq.top.out_sums = io.out_sums;
+        set_goal(tq.top.goal, goal_pix, ND);
         const int cpi_h = s3_cpi(H * W, kS3Ngf);
         EwParams nq = ew_base(EW_INORM, 2 * kS3Ngf / cpi_h, 0);
         nq.norm.in = hmhs_raw; nq.norm.in_bs = HW * 2 * kS3Ngf;
@@ -711,33 +686,32 @@ static int emit_rollout_s3(vf_handle *h, int view, int B, const float *d_actions
             // layers only takes its statistics (table of 64 (scale, shift) pairs per sample), the item normalises while staging
             nq.norm.out = hmhs_raw; nq.norm.out_bs = HW * 2 * kS3Ngf;      // (not written: statistics only)
             nq.norm.tab = s->norm_tab + row * 128;
-            S3_EMIT(u_tab, sink.ew(nq, view, {u_hc}))
+            VF_EMIT(u_tab, sink.ew(nq, view, {u_hc}))
             EwParams f3 = tq;
             f3.op = EW_TOP3;
             f3.gx = ((H + kT3H - 1) / kT3H) * ((W + kT3W - 1) / kT3W);
             f3.top.hmhs_raw = hmhs_raw; f3.top.norm_tab = nq.norm.tab;
             f3.top.w_scr = vw.w_scr_v; f3.top.b_scr = vw.b_scr_v; f3.top.w_msk = vw.w_msk_v; f3.top.b_msk = vw.b_msk_v;
-            S3_EMIT(u_f3, sink.ew(f3, view, {u_tab, u_fin, last2}))
+            VF_EMIT(u_f3, sink.ew(f3, view, {u_tab, u_fin, last2}))
             last = u_f3;
             continue;
         }
         // (vf_set_fuse_top(0): the four-phase form - scratch conv, layers, mask conv, composition - through memory)
         nq.norm.out = hm_o; nq.norm.out2 = hs_o; nq.norm.split = kS3Ngf; nq.norm.out_bs = HW * kS3Ngf;
-        S3_EMIT(u_hn, sink.ew(nq, view, {u_hc}))
+        VF_EMIT(u_hn, sink.ew(nq, view, {u_hc}))
         ConvParams ps = params(s->scratch, plain(hs_o, HW * kS3Ngf), nullptr);
         ps.out = scr;
-        S3_EMIT(u_scr, sink.conv(PH_CONV_RAW3, s->scratch, ps, {u_hn}))
-        S3_EMIT(u_tr, sink.ew(tq, view, {u_scr, u_fin, last2}))
+        VF_EMIT(u_scr, sink.conv(PH_CONV_RAW3, s->scratch, ps, {u_hn}))
+        VF_EMIT(u_tr, sink.ew(tq, view, {u_scr, u_fin, last2}))
         SegArg ts = plain(trans, HW * kTransCh);
         ConvParams pm = params(s->masks, plain(hm_o, HW * kS3Ngf), &ts);
         pm.out = mlog;
-        S3_EMIT(u_m, sink.conv(PH_CONV_RAW3, s->masks, pm, {u_hn, u_tr}))
+        VF_EMIT(u_m, sink.conv(PH_CONV_RAW3, s->masks, pm, {u_hn, u_tr}))
         EwParams cq = tq;
         cq.op = EW_COMPOSE;
-        S3_EMIT(u_comp, sink.ew(cq, view, {u_m, u_tr}))
+        VF_EMIT(u_comp, sink.ew(cq, view, {u_m, u_tr}))
         last = u_comp;
     }
-#undef S3_EMIT
     return VF_OK;
 }
 
