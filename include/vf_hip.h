@@ -9,7 +9,7 @@
  * the calling thread.  No exception crosses this boundary.  Every device buffer - packed
  * weights, activations, predictions, schedules - is sized from the config and allocated in
  * vf_create(); no later call allocates device memory (vf_load_weights refills the same
- * buffers).  vf_set_context / vf_rollout / vf_export / vf_register / vf_allgather_scores only
+ * buffers).  vf_set_context / vf_rollout / vf_export / vf_register(_hw) / vf_resize_area / vf_allgather_scores only
  * enqueue work on the caller's HIP stream (hipStream_t passed as void*; NULL = the default
  * stream) and never synchronise it; a handle is driven from one stream at a time.
  * vf_load_weights, vf_device_status and the debug hooks are the blocking calls.
@@ -385,6 +385,40 @@ int vf_export(vf_handle *h, int32_t first, int32_t count, float *d_frames, float
 int vf_register(vf_handle *h, const float *d_current, const float *d_reference, const float *d_flow,
                 const int32_t *d_pix, int32_t ntask, int32_t region, int32_t clip_sub,
                 float *d_warped, float *d_warp_pts, float *d_desig, float *d_err, void *stream);
+
+/* vf_register at a size of the caller's.  The reference registers at the AGENT's resolution and predicts at the
+ * network's: the medium-resolution pixel tables of register_gtruth_controller.py:183,191, get_warp_err :121-128 on the
+ * agent-size frames, the window clipped with the agent's dimensions (:144-155), the tracked pixels scaled back by
+ * img_height / image_height (:172).  Same kernels and arguments as vf_register, the handle's ncam and device, but every
+ * image and the flow are [ncam][H][W][.] with the caller's H, W (each at least 8, H * W <= 2^22), the pixels d_pix and
+ * the results d_desig are in those coordinates and the window is clipped to [0, H - clip_sub] x [0, W - clip_sub].
+ * Called with the handle's own size it gives vf_register's bits.  VF_ERR_INVALID (nothing launched): vf_register's
+ * refusals, H < 8 or W < 8. */
+int vf_register_hw(vf_handle *h, int32_t H, int32_t W, const float *d_current, const float *d_reference,
+                   const float *d_flow, const int32_t *d_pix, int32_t ntask, int32_t region, int32_t clip_sub,
+                   float *d_warped, float *d_warp_pts, float *d_desig, float *d_err, void *stream);
+
+/* Area resampling: shrink n NHWC images [n][Hs][Ws][C] to [n][Hd][Wd][C] on the device (reference
+ * visual_mpc/utils/im_utils.py:6-15 and agent/general_agent.py:128: every observation goes through
+ * cv2.resize(..., INTER_AREA) before the policy sees it; goal_im_controller.py:89 the goal picture;
+ * register_gtruth_controller.py:44-51 the context of the two-resolution registration controller).  Handle-free: `device`
+ * is the HIP ordinal; one kernel is enqueued on `stream`, nothing is allocated, nothing synchronises.  dtype 0 = uint8,
+ * 1 = float32 (source and destination alike); C in 1..4; Hd <= Hs and Wd <= Ws, any ratio; equal sizes give a copy (below).
+ * The result is the EXACT area average (csrc/vf_resize.h; this project's own specification - it is meant to be
+ * INTER_AREA for shrinking, but cv2 was not available to pin that, and OpenCV's integer-factor fast path may round ties
+ * differently).  Per axis the weights are integers: destination row i covers [i*Hs, (i+1)*Hs), source row r covers
+ * [r*Hd, (r+1)*Hd), wy[i][r] = the length of the overlap (sum_r wy = Hs), wx likewise (sum_c wx = Ws), A = Hs*Ws.
+ *   uint8:   S = sum_r sum_c wy*wx*v (an exact integer);  out = S / A rounded half to even.
+ *   float32: one float64 sum per output element, source rows ascending and columns ascending within a row, every term
+ *            (double)(wy*wx) * (double)v (exact), additions rounded to nearest and never contracted; then one float64
+ *            division by A and one rounding to float32.
+ * An image's output depends on that image and the two sizes alone - not on n, its slot, the stream or the alignment.
+ * VF_ERR_INVALID (nothing launched, the device is not touched): a NULL pointer, dtype not 0 / 1, n < 1, C outside 1..4,
+ * a destination larger than the source on either axis, Hs*Ws > 2^22 (the uint8 sum must fit 31 bits), float32 pointers
+ * that are not 4-byte aligned, n * Hd > 2^30 (the grid of the one launch).  Equal sizes: uint8 is copied exactly; float32
+ * keeps every value but not every bit (-0.0 comes back as +0.0: the sum starts at +0.0). */
+int vf_resize_area(int32_t device, const void *d_src, void *d_dst, int32_t dtype /*0 = uint8, 1 = float32*/,
+                   int32_t n, int32_t Hs, int32_t Ws, int32_t C, int32_t Hd, int32_t Wd, void *stream);
 
 /* The one collective of multi-GPU planning: all-gather every rank's n_local score values (float64)
  * (n_local equal on all ranks: pad ragged shards) into d_all [world * n_local] with RCCL over

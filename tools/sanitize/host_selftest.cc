@@ -342,6 +342,43 @@ int main() {
             }
             std::printf("  inverse model: four shapes from 16x16 / adim 1 to 96x128 / adim 8, refusals: %s\n", rc ? "FAILED" : "ok");
         }
+        // area resampling and registration at a size of the caller's: the refusals come before the device is touched
+        {
+            alignas(16) static float img[8];
+            void *p = img, *odd = reinterpret_cast<char *>(img) + 2;
+            struct { const void *src; void *dst; int dtype, n, Hs, Ws, C, Hd, Wd; const char *msg; } refusals[] = {
+                {nullptr, p, 0, 1, 8, 8, 3, 4, 4, "null argument"}, {p, nullptr, 0, 1, 8, 8, 3, 4, 4, "null argument"},
+                {p, p, 2, 1, 8, 8, 3, 4, 4, "dtype"},               {p, p, -1, 1, 8, 8, 3, 4, 4, "dtype"},
+                {p, p, 0, 0, 8, 8, 3, 4, 4, "n = 0"},               {p, p, 0, 1, 8, 8, 0, 4, 4, "C = 0"},
+                {p, p, 0, 1, 8, 8, 5, 4, 4, "C = 5"},               {p, p, 0, 1, 8, 8, 3, 9, 4, "Hd x Wd"},
+                {p, p, 1, 1, 8, 8, 3, 4, 9, "Hd x Wd"},             {p, p, 0, 1, 8, 8, 3, 0, 4, "at least 1"},
+                {p, p, 0, 1, 2049, 2048, 3, 4, 4, "Hs*Ws"},         {p, p, 0, 1, 1 << 30, 1 << 30, 3, 4, 4, "Hs*Ws"},
+                {odd, p, 1, 1, 8, 8, 3, 4, 4, "4-byte aligned"},    {p, odd, 1, 1, 8, 8, 3, 4, 4, "4-byte aligned"},
+                {p, p, 0, 1 << 21, 1024, 4, 1, 1024, 4, "n * Hd"},  {p, p, 1, (1 << 30) + 1, 1, 1, 1, 1, 1, "n * Hd"}};
+            for (const auto &c : refusals) {
+                const int r = vf_resize_area(0, c.src, c.dst, c.dtype, c.n, c.Hs, c.Ws, c.C, c.Hd, c.Wd, nullptr);
+                if (r != VF_ERR_INVALID || std::string(vf_last_error()).find(c.msg) == std::string::npos) {
+                    std::fprintf(stderr, "vf_resize_area: want refusal '%s', got rc %d '%s'\n", c.msg, r, vf_last_error()); rc = 1;
+                }
+            }
+            if (vf_resize_area(-1, p, p, 0, 1, 8, 8, 3, 4, 4, nullptr) != VF_ERR_INVALID) rc = 1;
+            // (an odd uint8 pointer is served: everything is through, and this build launches nothing)
+            if (vf_resize_area(0, odd, p, 0, 1, 8, 8, 3, 4, 4, nullptr) != VF_ERR_HIP) { std::fprintf(stderr, "vf_resize_area: odd uint8 pointer refused\n"); rc = 1; }
+            int32_t pix[2] = {0, 0};
+            float out2[2];
+            struct { vf_handle *h; int H, W; const float *cur; int ntask, region, clip; const char *msg; } reg[] = {
+                {hh, 4, 64, img, 1, 0, 1, "H x W"},      {hh, 64, 7, img, 1, 0, 1, "H x W"},       {nullptr, 4, 4, img, 1, 0, 1, "H x W"},
+                {hh, 4096, 4096, img, 1, 0, 1, "H x W"}, {nullptr, 64, 64, img, 1, 0, 1, "null argument"},
+                {hh, 64, 64, nullptr, 1, 0, 1, "null argument"}, {hh, 64, 64, img, 0, 0, 1, "ntask"},
+                {hh, 64, 64, img, 1, 6, 1, "region"},    {hh, 64, 64, img, 1, 0, 2, "clip_sub"}};
+            for (const auto &c : reg) {
+                const int r = vf_register_hw(c.h, c.H, c.W, c.cur, img, img, pix, c.ntask, c.region, c.clip, nullptr, nullptr, out2, out2, nullptr);
+                if (r != VF_ERR_INVALID || std::string(vf_last_error()).find(c.msg) == std::string::npos) {
+                    std::fprintf(stderr, "vf_register_hw: want refusal '%s', got rc %d '%s'\n", c.msg, r, vf_last_error()); rc = 1;
+                }
+            }
+            std::printf("  area resampling / registration at the caller's size: refusals: %s\n", rc ? "FAILED" : "ok");
+        }
         if (hh && vf_destroy(hh)) { std::fprintf(stderr, "vf_destroy after the injected failures failed\n"); rc = 1; }
         std::printf("  injected failures (bad_alloc, std::exception, foreign) in vf_create / vf_load_weights / build_schedule: %s\n",
                     rc ? "FAILED" : "status codes returned, handle reusable");

@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(_HERE)
 LIB_PATH = os.environ.get('VF_LIBRARY') or os.path.join(_HERE, 'libvf_hip.so')     # override: experiments only
 SOURCES = [os.path.join(_HERE, 'csrc', f) for f in
-           ('vf_engine.hip', 'vf_conv_mfma.h', 'vf_conv_gsplit.h', 'vf_small_kernels.h', 'vf_goal_image.h', 'vf_plan_render.h', 'vf_net_conv.h',
+           ('vf_engine.hip', 'vf_conv_mfma.h', 'vf_conv_gsplit.h', 'vf_small_kernels.h', 'vf_goal_image.h', 'vf_plan_render.h', 'vf_resize.h', 'vf_net_conv.h',
             'vf_frame_scorer.h', 'vf_engine_sidenet.inc', 'vf_engine_scorer.inc', 'vf_registration_net.h', 'vf_engine_regnet.inc', 'vf_inverse_model.h', 'vf_engine_invmodel.inc', 'vf_persistent.h',
             'vf_conv_bf16x6.h', 'vf_conv_bf16.h', 'vf_fused_top.h', 'vf_fc_tile.h', 'vf_conv_first.h', 'vf_savp3.h', 'vf_engine_savp3.inc')] + \
           [os.path.join(REPO, 'include', 'vf_hip.h')]
@@ -31,7 +31,7 @@ EXPORTS = ('vf_abi_version', 'vf_last_error', 'vf_weight_count', 'vf_create', 'v
            'vf_scorer_scores',
            'vf_regnet_weight_count', 'vf_regnet_create', 'vf_regnet_destroy', 'vf_regnet_load_weights', 'vf_regnet_flow',
            'vf_invmodel_weight_count', 'vf_invmodel_create', 'vf_invmodel_destroy', 'vf_invmodel_load_weights',
-           'vf_invmodel_infer', 'vf_debug_lstm_layer')
+           'vf_invmodel_infer', 'vf_debug_lstm_layer', 'vf_register_hw', 'vf_resize_area')
 ABI_VERSION = 7
 
 
@@ -145,6 +145,8 @@ def load_library():
     lib.vf_invmodel_load_weights.argtypes = [P, P, ctypes.c_size_t]
     lib.vf_invmodel_infer.argtypes = [P, P, P, P, P, ctypes.c_int32, P, P, P]
     lib.vf_register.argtypes = [P, P, P, P, P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, P, P, P, P, P]
+    lib.vf_register_hw.argtypes = [P, ctypes.c_int32, ctypes.c_int32] + lib.vf_register.argtypes[1:]
+    lib.vf_resize_area.argtypes = [ctypes.c_int32, P, P] + [ctypes.c_int32] * 7 + [P]
     lib.vf_allgather_scores.argtypes = [P, P, P, ctypes.c_int32, P, P]
     lib.vf_comm_init_all.argtypes = [ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(P)]
     lib.vf_comm_destroy.argtypes = [P]
@@ -176,7 +178,7 @@ def load_library():
                  'vf_scorer_load_weights', 'vf_scorer_embed', 'vf_scorer_scores',
                  'vf_regnet_create', 'vf_regnet_destroy', 'vf_regnet_load_weights', 'vf_regnet_flow',
                  'vf_invmodel_create', 'vf_invmodel_destroy', 'vf_invmodel_load_weights', 'vf_invmodel_infer',
-                 'vf_export', 'vf_register', 'vf_allgather_scores', 'vf_comm_init_all', 'vf_comm_destroy',
+                 'vf_export', 'vf_register', 'vf_register_hw', 'vf_resize_area', 'vf_allgather_scores', 'vf_comm_init_all', 'vf_comm_destroy',
                  'vf_allgather_scores_group', 'vf_set_phase_stats',
                  'vf_debug_phase_stats', 'vf_debug_poison_status', 'vf_debug_lstm_layer'):
         getattr(lib, name).restype = ctypes.c_int

@@ -41,6 +41,7 @@
 #include "vf_registration_net.h"
 #include "vf_inverse_model.h"
 #include "vf_plan_render.h"
+#include "vf_resize.h"
 #include "vf_conv_bf16x6.h"
 #include "vf_conv_bf16.h"
 #include "vf_persistent.h"
@@ -2412,6 +2413,49 @@ static int render_plans_check(const vf_handle *h, const int32_t *d_seq, int32_t 
     return VF_OK;
 }
 
+// the refusals of vf_resize_area (host work only, as above: nothing of the device is touched before they are through)
+static int resize_area_check(int32_t device, const void *d_src, const void *d_dst, int32_t dtype, int32_t n, int32_t Hs,
+                             int32_t Ws, int32_t C, int32_t Hd, int32_t Wd) {
+    if (!d_src || !d_dst) return fail(VF_ERR_INVALID, "vf_resize_area: null argument (d_src, d_dst)");
+    if (device < 0) return fail(VF_ERR_INVALID, "vf_resize_area: device = " + std::to_string(device) + " is negative");
+    if (dtype != 0 && dtype != 1)
+        return fail(VF_ERR_INVALID, "vf_resize_area: dtype = " + std::to_string(dtype) + " is neither 0 (uint8) nor 1 (float32)");
+    if (n < 1) return fail(VF_ERR_INVALID, "vf_resize_area: n = " + std::to_string(n) + " images, need at least one");
+    if (C < 1 || C > 4) return fail(VF_ERR_INVALID, "vf_resize_area: C = " + std::to_string(C) + " channels outside 1..4");
+    if (Hd < 1 || Wd < 1 || Hs < 1 || Ws < 1)
+        return fail(VF_ERR_INVALID, "vf_resize_area: Hs, Ws, Hd, Wd must be at least 1");
+    if (Hd > Hs || Wd > Ws)
+        return fail(VF_ERR_INVALID, "vf_resize_area: destination Hd x Wd = " + std::to_string(Hd) + " x " + std::to_string(Wd) +
+                                        " is larger than the source " + std::to_string(Hs) + " x " + std::to_string(Ws) +
+                                        " (it shrinks only)");
+    if ((long long)Hs * Ws > kResizeMaxArea)
+        return fail(VF_ERR_INVALID, "vf_resize_area: Hs*Ws = " + std::to_string((long long)Hs * Ws) + " exceeds 2^22");
+    if (dtype == 1 && (reinterpret_cast<uintptr_t>(d_src) % 4 || reinterpret_cast<uintptr_t>(d_dst) % 4))
+        return fail(VF_ERR_INVALID, "vf_resize_area: float32 d_src and d_dst must be 4-byte aligned");
+    if ((long long)n * Hd > (1LL << 30))        // one workgroup per (image, band of at least one row): the grid of one launch
+        return fail(VF_ERR_INVALID, "vf_resize_area: n * Hd = " + std::to_string((long long)n * Hd) + " exceeds 2^30 (one launch)");
+    return VF_OK;
+}
+
+// the refusals of vf_register, and of vf_register_hw: the same and the caller's size
+static int register_check(const vf_handle *h, const float *d_current, const float *d_reference, const float *d_flow,
+                          const int32_t *d_pix, int32_t ntask, int32_t region, int32_t clip_sub, const float *d_desig,
+                          const float *d_err) {
+    if (!h || !d_current || !d_reference || !d_flow || !d_pix || !d_desig || !d_err)
+        return fail(VF_ERR_INVALID, "null argument");
+    if (ntask < 1 || region < 0 || (2 * region + 1) * (2 * region + 1) > kRegMaxWin || (clip_sub != 0 && clip_sub != 1))
+        return fail(VF_ERR_INVALID, "need ntask >= 1, 0 <= region <= 5 and clip_sub in {0, 1}");
+    return VF_OK;
+}
+static int register_hw_check(const vf_handle *h, int32_t H, int32_t W, const float *d_current, const float *d_reference,
+                             const float *d_flow, const int32_t *d_pix, int32_t ntask, int32_t region, int32_t clip_sub,
+                             const float *d_desig, const float *d_err) {
+    if (H < 8 || W < 8 || (long long)H * W > kResizeMaxArea)
+        return fail(VF_ERR_INVALID, "vf_register_hw: H x W = " + std::to_string(H) + " x " + std::to_string(W) +
+                                        ", need H >= 8, W >= 8 and H*W <= 2^22");
+    return register_check(h, d_current, d_reference, d_flow, d_pix, ntask, region, clip_sub, d_desig, d_err);
+}
+
 #ifdef VF_HOST_SELFTEST
 // ------------------------------------------------------------------ host self-test hooks
 // (tools/host_selftest.cc; ASan/UBSan build).  Checks the invariants the device relies on.
@@ -2663,7 +2707,23 @@ extern "C" int vf_render_plans(vf_handle *h, const int32_t *d_seq, int32_t K, co
     return fail(VF_ERR_HIP, "the host self-test build launches nothing");
     VF_API_CATCH(int)
 }
-#else   // ------------------------------------------------------------------ device execution
+extern "C" int vf_resize_area(int32_t device, const void *d_src, void *d_dst, int32_t dtype, int32_t n, int32_t Hs, int32_t Ws,
+                              int32_t C, int32_t Hd, int32_t Wd, void *) {       // (refusal paths only, as above)
+    VF_API_TRY
+    if (int rc = resize_area_check(device, d_src, d_dst, dtype, n, Hs, Ws, C, Hd, Wd)) return rc;
+    return fail(VF_ERR_HIP, "the host self-test build launches nothing");
+    VF_API_CATCH(int)
+}
+extern "C" int vf_register_hw(vf_handle *h, int32_t H, int32_t W, const float *d_current, const float *d_reference,
+                              const float *d_flow, const int32_t *d_pix, int32_t ntask, int32_t region, int32_t clip_sub,
+                              float *, float *, float *d_desig, float *d_err, void *) {      // (refusal paths only, as above)
+    VF_API_TRY
+    if (int rc = register_hw_check(h, H, W, d_current, d_reference, d_flow, d_pix, ntask, region, clip_sub, d_desig, d_err))
+        return rc;
+    return fail(VF_ERR_HIP, "the host self-test build launches nothing");
+    VF_API_CATCH(int)
+}
+#else  // ------------------------------------------------------------------ device execution
 
 // the zero initial LSTM state is one shared image per layer
 static int zero_shared_state(vf_handle *h, const BatchView &sh, hipStream_t st) {
@@ -3188,26 +3248,95 @@ int vf_export(vf_handle *h, int32_t first, int32_t count, float *d_frames, float
     VF_API_CATCH(int)
 }
 
+// the launches of vf_register (H, W = the handle's) and of vf_register_hw (the caller's), behind their refusals
+static int register_launch(vf_handle *h, int H, int W, const float *d_current, const float *d_reference, const float *d_flow,
+                           const int32_t *d_pix, int32_t ntask, int32_t region, int32_t clip_sub, float *d_warped,
+                           float *d_warp_pts, float *d_desig, float *d_err, void *stream) {
+    VF_HIP_CHECK(hipSetDevice(h->cfg.device));
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (d_warped || d_warp_pts) {
+        const int n = h->ncam * H * W;
+        hipLaunchKernelGGL(warp_image_kernel, dim3((n + 255) / 256), dim3(256), 0, st, d_current, d_flow, h->ncam, H, W,
+                           d_warped, d_warp_pts);
+        VF_HIP_CHECK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(register_kernel, dim3(h->ncam * ntask), dim3(128), 0, st, d_current, d_reference, d_flow, d_pix,
+                       h->ncam, ntask, H, W, region, clip_sub, d_desig, d_err);
+    VF_HIP_CHECK(hipGetLastError());
+    return VF_OK;
+}
+
 int vf_register(vf_handle *h, const float *d_current, const float *d_reference, const float *d_flow,
                 const int32_t *d_pix, int32_t ntask, int32_t region, int32_t clip_sub, float *d_warped,
                 float *d_warp_pts, float *d_desig, float *d_err, void *stream) {
     VF_API_TRY
-    if (!h || !d_current || !d_reference || !d_flow || !d_pix || !d_desig || !d_err)
-        return fail(VF_ERR_INVALID, "null argument");
-    if (ntask < 1 || region < 0 || (2 * region + 1) * (2 * region + 1) > kRegMaxWin || (clip_sub != 0 && clip_sub != 1))
-        return fail(VF_ERR_INVALID, "need ntask >= 1, 0 <= region <= 5 and clip_sub in {0, 1}");
-    VF_HIP_CHECK(hipSetDevice(h->cfg.device));
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (d_warped || d_warp_pts) {
-        const int n = h->ncam * h->H * h->W;
-        hipLaunchKernelGGL(warp_image_kernel, dim3((n + 255) / 256), dim3(256), 0, st, d_current, d_flow, h->ncam,
-                           h->H, h->W, d_warped, d_warp_pts);
-        VF_HIP_CHECK(hipGetLastError());
+    if (int rc = register_check(h, d_current, d_reference, d_flow, d_pix, ntask, region, clip_sub, d_desig, d_err)) return rc;
+    return register_launch(h, h->H, h->W, d_current, d_reference, d_flow, d_pix, ntask, region, clip_sub, d_warped, d_warp_pts,
+                           d_desig, d_err, stream);
+    VF_API_CATCH(int)
+}
+
+// vf_register at a size of the caller's: the same launches (both kernels take the size as arguments), the handle's ncam
+// and device.  The reference registers at the agent's resolution and predicts at the network's
+// (register_gtruth_controller.py:121-128,144-155,183,191).
+int vf_register_hw(vf_handle *h, int32_t H, int32_t W, const float *d_current, const float *d_reference,
+                   const float *d_flow, const int32_t *d_pix, int32_t ntask, int32_t region, int32_t clip_sub,
+                   float *d_warped, float *d_warp_pts, float *d_desig, float *d_err, void *stream) {
+    VF_API_TRY
+    if (int rc = register_hw_check(h, H, W, d_current, d_reference, d_flow, d_pix, ntask, region, clip_sub, d_desig, d_err))
+        return rc;
+    return register_launch(h, H, W, d_current, d_reference, d_flow, d_pix, ntask, region, clip_sub, d_warped, d_warp_pts, d_desig,
+                           d_err, stream);
+    VF_API_CATCH(int)
+}
+
+// Area resampling (vf_resize.h).  Integer ratios take resize_int_kernel; every other ratio resize_frac_kernel, which
+// stages a band's source rows in LDS when they fit.  A band is as many destination rows as give every thread about two
+// outputs, fewer when the stage would overflow.  A uint8 footprint of an integer ratio is split over up to 16 lanes by rows
+// (kResizeMaxSplit: a power of two that divides the wave, so the lanes of a pixel never straddle two waves).
+}   // extern "C"
+template <class T> static int launch_resize(const ResizeParams &base, int n, hipStream_t st) {
+    ResizeParams p = base;
+    const bool integer = p.Hs % p.Hd == 0 && p.Ws % p.Wd == 0;
+    p.stage = 0;
+    p.split = 1;
+    if (integer && std::is_same<T, uint8_t>::value)
+        while (p.split * 2 <= std::min(p.Hs / p.Hd, kResizeMaxSplit)) p.split *= 2;
+    // threads a destination row asks for: one per element (fractional ratios), p.split per pixel (integer ratios)
+    const long long per_row = integer ? (long long)p.Wd * p.split : (long long)p.Wd * p.C;
+    p.band = (int)std::min<long long>(p.Hd, std::max<long long>(1, (2 * kResizeThreads + per_row - 1) / per_row));
+    if (!integer) {
+        const long long row_bytes = (long long)p.Ws * p.C * (long long)sizeof(T);
+        // source rows of a band: at most ceil(band * Hs / Hd) + 1; 16 bytes for the offset from a 16-byte boundary
+        auto stage_bytes = [&](int band) { return (((long long)band * p.Hs + p.Hd - 1) / p.Hd + 1) * row_bytes + 16; };
+        while (p.band > 1 && stage_bytes(p.band) > kResizeStageBytes) p.band = (p.band + 1) / 2;
+        p.stage = stage_bytes(p.band) <= kResizeStageBytes;
     }
-    hipLaunchKernelGGL(register_kernel, dim3(h->ncam * ntask), dim3(128), 0, st, d_current, d_reference, d_flow,
-                       d_pix, h->ncam, ntask, h->H, h->W, region, clip_sub, d_desig, d_err);
+    p.n_bands = (p.Hd + p.band - 1) / p.band;
+    const dim3 grid((unsigned)((long long)n * p.n_bands)), block(kResizeThreads);
+    if (!integer) {
+        hipLaunchKernelGGL((resize_frac_kernel<T>), grid, block, 0, st, p);
+    } else {
+        switch (p.C) {
+        case 1: hipLaunchKernelGGL((resize_int_kernel<T, 1>), grid, block, 0, st, p); break;
+        case 2: hipLaunchKernelGGL((resize_int_kernel<T, 2>), grid, block, 0, st, p); break;
+        case 3: hipLaunchKernelGGL((resize_int_kernel<T, 3>), grid, block, 0, st, p); break;
+        default: hipLaunchKernelGGL((resize_int_kernel<T, 4>), grid, block, 0, st, p); break;
+        }
+    }
     VF_HIP_CHECK(hipGetLastError());
     return VF_OK;
+}
+extern "C" {
+
+int vf_resize_area(int32_t device, const void *d_src, void *d_dst, int32_t dtype, int32_t n, int32_t Hs, int32_t Ws,
+                   int32_t C, int32_t Hd, int32_t Wd, void *stream) {
+    VF_API_TRY
+    if (int rc = resize_area_check(device, d_src, d_dst, dtype, n, Hs, Ws, C, Hd, Wd)) return rc;
+    VF_HIP_CHECK(hipSetDevice(device));
+    const ResizeParams p = {d_src, d_dst, Hs, Ws, C, Hd, Wd, 1, 1, 0, 1};
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    return dtype == 0 ? launch_resize<uint8_t>(p, n, st) : launch_resize<float>(p, n, st);
     VF_API_CATCH(int)
 }
 

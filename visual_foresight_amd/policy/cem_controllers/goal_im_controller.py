@@ -31,16 +31,18 @@ With one view and the default hyper-parameters the score is the reference's: the
 import numpy as np
 
 from .cem_base_controller import CEMBaseController
-from .pixel_cost_controller import _default_predictor_class, build_predictor, context_states
+from .pixel_cost_controller import (_default_predictor_class, build_predictor, context_frames, context_states,
+                                    model_image_size, page_start_images)
 
 
-def prepare_goal_image(goal_image, ncam, height, width, raw=False):
+def prepare_goal_image(goal_image, ncam, height, width, raw=False, camera_size=None):
     """-> ``[ncam, H, W, 3]`` in the scale it is compared in: uint8 / 255 as float32 (``raw``: the bytes' values as
-    float32, the reference's literal arithmetic); floating-point goals are taken as they are."""
+    float32, the reference's literal arithmetic); floating-point goals are taken as they are.  ``camera_size``: a second
+    ``(H, W)`` the picture may come at (it is shrunk later, in that scale)."""
     g = np.asarray(goal_image)
     if g.ndim == 3 and ncam == 1:
         g = g[None]
-    if g.shape != (ncam, height, width, 3):
+    if g.shape != (ncam, height, width, 3) and (camera_size is None or g.shape != (ncam,) + tuple(camera_size) + (3,)):
         raise ValueError('goal_image must be [%d, %d, %d, 3], got %s' % (ncam, height, width, g.shape))
     if g.dtype == np.uint8:
         g = g.astype(np.float32)
@@ -83,10 +85,14 @@ class GoalImController(CEMBaseController):
         # no designated pixel is planned on: the network carries one distribution channel, switched on at the centre
         self.predictor = build_predictor(self, predictor_class, ag_params, gpu_id, ngpu, 1, horizon)
         self._net_context = self.predictor.n_context
-        self._img_height, self._img_width = [ag_params['image_height'], ag_params['image_width']]
+        self._img_height, self._img_width = model_image_size(ag_params)
+        self._camera_size = (ag_params['image_height'], ag_params['image_width'])
+        if self._camera_size == (self._img_height, self._img_width):
+            self._camera_size = None
         self._n_cam = getattr(self.predictor, 'n_cam', 1)
         self._images = None
         self._goal_image = None
+        self._n_act = 0                 # act() calls so far: the goal picture's name towards the predictor's goal cache
         self.cost_perstep = None        # [M, ncam, T] MSE of the last scoring call
 
     def _default_hparams(self):
@@ -110,20 +116,26 @@ class GoalImController(CEMBaseController):
     def evaluate_rollouts(self, actions, cem_itr):
         hp = self._hp
         context = {
-            "context_frames": self._images,
+            "context_frames": context_frames(self),
             "context_actions": self._sampler.chosen_actions,
             "context_states": context_states(self),
         }
         if hasattr(self.predictor, 'score_goal_image'):
+            # (a camera-size goal is shrunk once per act(): the call count names the picture to the predictor)
+            key = {'goal_key': ('act', id(self), self._n_act)} if self._camera_size is not None else {}
             scores, per_view = self.predictor.score_goal_image(
                 context, {'actions': actions}, self._goal_image, steps=hp.goal_cost_steps,
-                finalweight=hp.finalweight, first_view_only=hp.only_take_first_view)
+                finalweight=hp.finalweight, first_view_only=hp.only_take_first_view, **key)
             self.cost_perstep = self.predictor.last_goal_cost_per_step
         else:
             context = self._with_centre_distribution(context)
             prediction = self.predictor(context, {'actions': actions})
+            goal = self._goal_image
+            if goal.shape[1:3] != (self._img_height, self._img_width):      # a camera-size goal (reference :89), on the host
+                from visual_foresight_amd.video_prediction.resample import area_resize_host
+                goal = area_resize_host(goal, (self._img_height, self._img_width))
             scores, per_view, self.cost_perstep = goal_image_cost(
-                prediction['predicted_frames'], self._goal_image, hp.goal_cost_steps, hp.finalweight,
+                prediction['predicted_frames'], goal, hp.goal_cost_steps, hp.finalweight,
                 hp.only_take_first_view)
         bestind = scores.argsort()[0]
         for icam in range(per_view.shape[1]):
@@ -152,7 +164,7 @@ class GoalImController(CEMBaseController):
         rendered = plan_page.render_for_page(self.predictor, self.visualize_indices,
                                              self._with_centre_distribution(context), actions, want_distributions=False)
         for message in plan_page.build_plan_messages(
-                self._t, cem_itr, self._images[-1], scores[self.visualize_indices], rendered['frames'],
+                self._t, cem_itr, page_start_images(self), scores[self.visualize_indices], rendered['frames'],
                 goal_images=self._goal_bytes, img_height=self._hp.verbose_img_height,
                 extensions=plan_page.asset_extensions(self._verbose_worker)):
             self._verbose_worker.put(message)
@@ -162,10 +174,13 @@ class GoalImController(CEMBaseController):
         :param t: the controller's time step
         :param images: uint8 history ``[t+1, ncam, H, W, 3]``
         :param state: state history ``[t+1, sdim]``
-        :param goal_image: ``[ncam, H, W, 3]`` or ``[H, W, 3]`` (one view), uint8 or float, at the predictor's size
+        :param goal_image: ``[ncam, H, W, 3]`` or ``[H, W, 3]`` (one view), uint8 or float, at the predictor's size - or,
+            with ``model_image_height`` / ``model_image_width`` in ``ag_params``, at the camera's: it is then shrunk once per
+            ``act()``, on the device where the predictor scores there (reference :89)
         """
+        self._n_act += 1
         self._goal_image = prepare_goal_image(goal_image, self._n_cam, self._img_height, self._img_width,
-                                              raw=self._hp.goal_image_raw)
+                                              raw=self._hp.goal_image_raw, camera_size=self._camera_size)
         self._images = images
         self._verbose_worker = verbose_worker
         if verbose_worker is not None:      # the goal as the plan page shows it: the caller's bytes, or a float goal's

@@ -39,6 +39,51 @@ def context_states(ctrl):
     return np.concatenate((state, tail), axis=-1)
 
 
+def model_image_size(ag_params):
+    """``(height, width)`` the network runs at.  The agent's ``image_height`` / ``image_width`` unless the two free-form keys
+    ``model_image_height`` / ``model_image_width`` of ``ag_params`` name a smaller size of the same aspect ratio: the images
+    then arrive at the camera's resolution and are shrunk to the model's (``video_prediction/resample.py``; the reference's
+    agent does that itself, ``utils/im_utils.py:6-15``, and its registration controller works at both sizes).  This is the
+    reference's meaning of the controllers' ``_img_height`` / ``_img_width``."""
+    camera = (ag_params['image_height'], ag_params['image_width'])
+    keys = ('model_image_height' in ag_params, 'model_image_width' in ag_params)
+    if not any(keys):
+        return camera
+    if not all(keys):
+        raise ValueError("ag_params: 'model_image_height' and 'model_image_width' come as a pair")
+    model = (int(ag_params['model_image_height']), int(ag_params['model_image_width']))
+    from visual_foresight_amd.video_prediction.resample import check_aspect
+    check_aspect(camera, model)
+    return model
+
+
+def context_frames(ctrl):
+    """The image history as the predictor takes it.  A predictor that was told the camera's size (``camera_size``:
+    ``HipVPredEvaluation`` with ``camera_height`` / ``camera_width``) shrinks the frames on its device; for any other the
+    last ``n_context`` frames are shrunk here, on the host (reference ``register_gtruth_controller.py:50-51``)."""
+    images = ctrl._images
+    if ctrl._camera_size is None or getattr(ctrl.predictor, 'camera_size', None) is not None:
+        return images           # (no model-size keys: the default path hands the history on untouched)
+    model = (ctrl._img_height, ctrl._img_width)
+    if tuple(np.shape(images)[-3:-1]) == model:
+        return images
+    from visual_foresight_amd.video_prediction.resample import area_resize_host
+    return area_resize_host(np.asarray(images)[-ctrl._net_context:], model)
+
+
+def page_start_images(ctrl):
+    """The newest observed frame as the plan page shows it: at the model's size, like the predicted frames beside it and
+    the designated / goal pixels marked on it."""
+    if ctrl._camera_size is None:
+        return ctrl._images[-1]
+    newest = np.asarray(ctrl._images[-1])
+    model = (ctrl._img_height, ctrl._img_width)
+    if tuple(newest.shape[-3:-1]) == model:
+        return ctrl._images[-1]
+    from visual_foresight_amd.video_prediction.resample import area_resize_host
+    return area_resize_host(newest, model)
+
+
 def build_predictor(ctrl, predictor_class, ag_params, gpu_id, ngpu, designated_pixel_count, horizon):
     """Construct and restore the video predictor of a CEM controller (reference ``pixel_cost_controller.py:29-36``) and
     raise the controller's ``start_planning`` to the network's context.  Shared by the controllers that plan on
@@ -57,6 +102,11 @@ def build_predictor(ctrl, predictor_class, ag_params, gpu_id, ngpu, designated_p
             image_height=ag_params['image_height'], image_width=ag_params['image_width'],
             ncam=ag_params.get('ncam', 1),
             sequence_length=horizon + predictor_class.n_context_default)
+        model = model_image_size(ag_params)
+        if model != (ag_params['image_height'], ag_params['image_width']):
+            # the predictor runs at the model's size and shrinks the camera-size context itself
+            predictor_hparams.update(image_height=model[0], image_width=model[1],
+                                     camera_height=ag_params['image_height'], camera_width=ag_params['image_width'])
     predictor = predictor_class(hp.model_path, predictor_hparams, n_gpus=ngpu, first_gpu=gpu_id)
     predictor.restore()
     if hp.start_planning < predictor.n_context - 1:
@@ -81,7 +131,11 @@ class PixelCostController(CEMBaseController):
         self._net_context = self.predictor.n_context
 
         self._n_desig = self._hp.designated_pixel_count
-        self._img_height, self._img_width = [ag_params['image_height'], ag_params['image_width']]
+        self._img_height, self._img_width = model_image_size(ag_params)
+        # the agent's image size when the model's differs from it (the two ag_params keys), else None
+        self._camera_size = (ag_params['image_height'], ag_params['image_width'])
+        if self._camera_size == (self._img_height, self._img_width):
+            self._camera_size = None
         # the reference hard-codes 1 here (:43); multi-view predictors announce their view count
         self._n_cam = getattr(self.predictor, 'n_cam', 1)
 
@@ -125,7 +179,7 @@ class PixelCostController(CEMBaseController):
     # ------------------------------------------------------------------ rollout scoring
     def evaluate_rollouts(self, actions, cem_itr):
         context = {
-            "context_frames": self._images,
+            "context_frames": context_frames(self),
             "context_actions": self._sampler.chosen_actions,
             "context_pixel_distributions": self._make_input_distrib(cem_itr),
             "context_states": context_states(self),
@@ -171,7 +225,7 @@ class PixelCostController(CEMBaseController):
         self.visualize_indices = scores.argsort()[:plan_page.N_PLANS]
         rendered = plan_page.render_for_page(self.predictor, self.visualize_indices, context, actions)
         for message in plan_page.build_plan_messages(
-                self._t, cem_itr, self._images[-1], scores[self.visualize_indices], rendered['frames'],
+                self._t, cem_itr, page_start_images(self), scores[self.visualize_indices], rendered['frames'],
                 rendered['distributions'], desig_pix=self._desig_pix, goal_pix=self._goal_pix,
                 img_height=self._hp.verbose_img_height, extensions=plan_page.asset_extensions(worker)):
             worker.put(message)

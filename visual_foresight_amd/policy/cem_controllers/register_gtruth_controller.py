@@ -26,11 +26,19 @@ warper only has to supply the flow field.  With ``HipRegistrationNet``
 (``video_prediction/registration_net.py``) as the warper the flow fields of all registrations come
 from one ``flow_device`` call on the predictor's device and never visit the host.  Any other
 predictor takes the NumPy path of ``registration.py`` on the warper's own ``(warped, flow, warp_pts)``.
+
+Two resolutions (``model_image_height`` / ``model_image_width`` in ``ag_params``, the reference's ``:44-51,121-128,172,
+183,191`` - its one shipped registration experiment runs a 96 x 128 agent on a 48 x 64 predictor): ``desig_pix`` /
+``goal_pix`` arrive in MODEL coordinates; registration runs at the CAMERA's resolution - camera-size current frame, start
+frame and goal image, a warper built at that size, the medium-resolution pixel tables ``(pix * image_height /
+img_height).astype(int)``, the window ``5 if image_height >= 96 else 2`` clipped with the camera's dimensions
+(``vf_register_hw``, or ``registration.get_warp_err`` on the NumPy path) - and the tracked pixels are multiplied by
+``img_height / image_height`` before they become the designated pixels of the rollout, which runs at the model's size.
 """
 import numpy as np
 
 from .pixel_cost_controller import PixelCostController
-from .registration import get_warp_err, tradeoff_weights
+from .registration import get_warp_err, medium_res_pixels, model_res_pixels, tradeoff_weights
 
 
 class RegisterGtruthController(PixelCostController):
@@ -43,6 +51,9 @@ class RegisterGtruthController(PixelCostController):
         self.goal_image_warper = self._hp.registration_warper
         self.reg_tradeoff = np.ones([self._n_cam, self._n_desig]) / self._n_cam / self._n_desig
         self.start_image = None
+        # the agent's (camera's) height; self._img_height is the model's (pixel_cost_controller.model_image_size)
+        self._image_height = ag_params['image_height']
+        self._two_res = self._image_height != self._img_height
 
     def _default_hparams(self):
         params = super(RegisterGtruthController, self)._default_hparams()
@@ -61,11 +72,13 @@ class RegisterGtruthController(PixelCostController):
             raise ValueError("RegisterGtruthController needs the 'registration_warper' hyper-parameter")
         regs = self._hp.register_gtruth
         H = start_image.shape[1]
+        # registration runs at the agent's resolution, on the medium-resolution tables when the model's differs (:121-128)
+        pix_t0, goal_pix = (self.desig_pix_t0_med, self.goal_pix_med) if self._two_res else (self.desig_pix_t0, self.goal_pix_sel)
         if hasattr(self.predictor, 'register') and self._hp.registration_on_device:
             region = (5 if H >= 96 else 2) if self._hp.register_region else 0
             per_reg = []
             targets = [(ref, pix, clip) for name, ref, pix, clip in
-                       (('start', start_image, self.desig_pix_t0, 1), ('goal', self.goal_image, self.goal_pix_sel, 0))
+                       (('start', start_image, pix_t0, 1), ('goal', self.goal_image, goal_pix, 0))
                        if name in regs]
             if hasattr(self.goal_image_warper, 'flow_device'):
                 # a registration network on the device: one call for all registrations, the flow stays on the card
@@ -86,6 +99,8 @@ class RegisterGtruthController(PixelCostController):
                     per_reg.append(self.predictor.register(current_image, ref, flow, pix, region=region, clip_sub=clip))
             desig = [np.stack([d[icam] for d, _ in per_reg], axis=1) for icam in range(self._n_cam)]   # [ntask, nreg, 2]
             errs = [np.stack([e[icam] for _, e in per_reg], axis=1) for icam in range(self._n_cam)]    # [ntask, nreg]
+            if self._two_res:       # camera coordinates -> the model's (:172)
+                desig = [model_res_pixels(d, self._img_height, self._image_height) for d in desig]
         else:
             warped_start = start_pts = warped_goal = goal_pts = None
             if 'start' in regs:
@@ -94,9 +109,10 @@ class RegisterGtruthController(PixelCostController):
                 warped_goal, _, goal_pts = self.goal_image_warper(current_image, self.goal_image)
             errs, desig = [], []
             for icam in range(self._n_cam):
-                e, d = get_warp_err(icam, self.desig_pix_t0[icam], self.goal_pix_sel[icam], start_image,
+                e, d = get_warp_err(icam, pix_t0[icam], goal_pix[icam], start_image,
                                     self.goal_image, start_pts, goal_pts, warped_start, warped_goal,
-                                    register_gtruth=regs, register_region=self._hp.register_region)
+                                    register_gtruth=regs, register_region=self._hp.register_region,
+                                    pred_height=self._img_height if self._two_res else None)
                 errs.append(e)
                 desig.append(d)
         warperrs = np.stack(errs, 0)                                    # [ncam, ntask, nreg]
@@ -116,13 +132,16 @@ class RegisterGtruthController(PixelCostController):
 
     def act(self, goal_image=None, t=None, i_tr=None, desig_pix=None, goal_pix=None, images=None, state=None,
             verbose_worker=None):
-        """``goal_image`` [.., ncam, H, W, 3] float in [0,1] (the last entry is used, ``:186``)."""
+        """``goal_image`` [.., ncam, H, W, 3] float in [0,1] (the last entry is used, ``:186``), at the agent's size;
+        ``desig_pix`` / ``goal_pix`` in the model's coordinates."""
         nreg = len(self._hp.register_gtruth)
         self.goal_pix_sel = np.array(goal_pix).reshape((self._n_cam, self.ntask, 2))
         goal_tiled = np.tile(self.goal_pix_sel[:, :, None, :], [1, 1, nreg, 1])
+        self.goal_pix_med = medium_res_pixels(self.goal_pix_sel, self._image_height, self._img_height)     # (:183)
         self.goal_image = np.asarray(goal_image)[-1]
         if t == 0:
             self.desig_pix_t0 = np.array(desig_pix).reshape((self._n_cam, self.ntask, 2))
+            self.desig_pix_t0_med = medium_res_pixels(self.desig_pix_t0, self._image_height, self._img_height)     # (:191)
             self.start_image = np.asarray(images)[0].astype(np.float32) / 255.
         desig_tiled = np.tile(self.desig_pix_t0[:, :, None, :], [1, 1, nreg, 1])
         return super(RegisterGtruthController, self).act(

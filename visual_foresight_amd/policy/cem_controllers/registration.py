@@ -75,6 +75,19 @@ def get_warp_err(icam, pix_t0, goal_pix, start_image, goal_image, start_warp_pts
     return warperrs, desig
 
 
+def medium_res_pixels(pix, image_height, img_height):
+    """Pixels in the model's coordinates -> the agent's (medium-resolution) table the registration runs on: the
+    reference's ``(pix * agentparams['image_height'] / self._img_height).astype(np.int)`` (``:183,191``), truncation
+    included.  One ratio for rows and columns."""
+    return (np.asarray(pix) * image_height / img_height).astype(int)
+
+
+def model_res_pixels(desig, img_height, image_height):
+    """Tracked pixels in the agent's coordinates -> the model's: ``desig * self._img_height / agentparams['image_height']``
+    (``:172``), not rounded."""
+    return np.asarray(desig) * img_height / image_height
+
+
 def tradeoff_weights(warperrs):
     """``warperrs [ncam, ntask, nreg]`` -> weights of the same shape, each task's summing to 1.
 

@@ -68,6 +68,13 @@ class InvModelBaseController(Policy):
         predictor_class = hp.predictor_class if hp.predictor_class is not None else _default_predictor_class()
         predictor_hparams = {'adim': self._adim, 'n_context': hp.num_context, 'n_actions': hp.T}
         predictor_hparams.update({k: ag_params[k] for k in ('image_height', 'image_width') if k in ag_params})
+        if 'model_image_height' in ag_params or 'model_image_width' in ag_params:
+            # the network is built at the model's size; the camera-size start image, goal image and context frames are
+            # shrunk before every inference (video_prediction/resample.py; the reference's agent shrinks its observations)
+            from visual_foresight_amd.policy.cem_controllers.pixel_cost_controller import model_image_size
+            model = model_image_size(ag_params)
+            predictor_hparams.update(image_height=model[0], image_width=model[1],
+                                     camera_height=ag_params['image_height'], camera_width=ag_params['image_width'])
         self.predictor = predictor_class(hp.model_params_path, predictor_hparams, n_gpus=ngpu, first_gpu=gpu_id)
         self.predictor.restore()
         self._clear_plan()

@@ -42,6 +42,7 @@ import os
 import numpy as np
 
 from visual_foresight_amd import _lib
+from visual_foresight_amd.video_prediction import resample
 from visual_foresight_amd.video_prediction.cdna_arch import CdnaConfig, CdnaWeights
 from visual_foresight_amd.video_prediction.savp_arch import SavpConfig, Savp2Config
 from visual_foresight_amd.video_prediction.savp3_arch import Savp3Config
@@ -180,6 +181,18 @@ class HipVPredEvaluation(object):
                            ndesig=self.ndesig_of(hp), n_context=self.n_context,
                            sequence_length=self.sequence_length, **extra)
         self.frames_only = self.cfg.ndesig == 0
+        # 'camera_height' / 'camera_width': the context frames (and a goal picture, and what register() is given) arrive at
+        # the CAMERA's resolution and are shrunk on the device to the model's (resample.py; the reference's agent does it on
+        # the host, utils/im_utils.py:6-15).  None (default) = the model's size: nothing is resampled.  Everything downstream -
+        # distributions, goal pixels, exported frames, render_plans - stays at the model's size.
+        cam = (hp.get('camera_height'), hp.get('camera_width'))
+        if (cam[0] is None) != (cam[1] is None):
+            raise ValueError("'camera_height' and 'camera_width' come as a pair, got %r x %r" % cam)
+        self.camera_size = None
+        if cam[0] is not None and (int(cam[0]), int(cam[1])) != (self.cfg.height, self.cfg.width):
+            resample.check_aspect(cam, (self.cfg.height, self.cfg.width))
+            self.camera_size = (int(cam[0]), int(cam[1]))
+        self._goal_cache = None         # (goal_key, the shrunk goal picture on this device) of the last keyed goal-image call
         # the image centre as goal pixels [ncam, ndesig, 2]: what the frame costs hand the rollout entry, which wants some
         self._centre_pix = np.tile(np.array([self.cfg.height // 2, self.cfg.width // 2], np.int32),
                                    (self.n_cam, self.cfg.ndesig, 1))
@@ -385,7 +398,13 @@ class HipVPredEvaluation(object):
         torch, nc, c = self._torch, self.n_context, self.cfg
         ncam = self.n_cam
         frames = np.ascontiguousarray(np.asarray(context['context_frames'])[-nc:, :ncam])
-        if frames.dtype != np.uint8 or frames.shape != (nc, ncam, c.height, c.width, 3):
+        if self.camera_size is not None:
+            if frames.dtype != np.uint8 or frames.shape != (nc, ncam) + self.camera_size + (3,):
+                raise ValueError('context_frames must be uint8 [>=%d, %d, %d, %d, 3] at the camera size %d x %d (the model '
+                                 'size is %d x %d: they are shrunk on the device), got %s %s'
+                                 % ((nc, ncam) + self.camera_size + self.camera_size + (c.height, c.width, frames.dtype,
+                                                                                       frames.shape)))
+        elif frames.dtype != np.uint8 or frames.shape != (nc, ncam, c.height, c.width, 3):
             raise ValueError('context_frames must be uint8 [>=%d, %d, %d, %d, 3], got %s %s'
                              % (nc, ncam, c.height, c.width, frames.dtype, frames.shape))
         if self.frames_only:
@@ -414,6 +433,9 @@ class HipVPredEvaluation(object):
         self._ctx_key = tuple(a.copy() for a in key)
         dev = self.device
         self._ctx = [torch.from_numpy(a).to(dev) for a in (frames, states, acts, distrib)]
+        if self.camera_size is not None:        # uploaded once at the camera's size, shrunk into the buffer the engine reads
+            with torch.cuda.device(dev):
+                self._ctx[0] = resample.area_resize_device(self._ctx[0], (c.height, c.width))
         f, s, a, d = self._ctx
         _lib.check(self._libh.vf_set_context(self._handle, f.data_ptr(), s.data_ptr(), a.data_ptr(),
                                              None if self.frames_only else d.data_ptr(), self._stream()))
@@ -564,25 +586,46 @@ class HipVPredEvaluation(object):
         g = np.asarray(goal_image)
         if g.ndim == 3 and self.n_cam == 1:
             g = g[None]
-        if g.shape != (self.n_cam, c.height, c.width, 3):
-            raise ValueError('goal_image must be [%d, %d, %d, 3]%s, got %s'
-                             % (self.n_cam, c.height, c.width, ' or [H, W, 3]' if self.n_cam == 1 else '', g.shape))
+        sizes = [(c.height, c.width)] + ([self.camera_size] if self.camera_size is not None else [])
+        if g.shape not in [(self.n_cam,) + sz + (3,) for sz in sizes]:
+            raise ValueError('goal_image must be [%d, %s, 3]%s, got %s'
+                             % (self.n_cam, ' or '.join('%d, %d' % sz for sz in sizes),
+                                ' or [H, W, 3]' if self.n_cam == 1 else '', g.shape))
         if g.dtype == np.uint8:
             return np.ascontiguousarray(g.astype(np.float32) / np.float32(255.))
         if not np.issubdtype(g.dtype, np.floating):
             raise ValueError('goal_image must be uint8 or floating point, got %s' % g.dtype)
         return np.ascontiguousarray(g, dtype=np.float32)
 
+    def _goal_on_device(self, goal, goal_key=None):
+        """``goal`` (float32, from ``_check_goal_image``) on this engine's device at the model's size.  A goal picture at the
+        camera's size is shrunk there with the float32 path of ``vf_resize_area`` (reference ``goal_im_controller.py:89``).
+        ``goal_key``: the caller's name for this picture (``GoalImController`` counts its ``act()`` calls); a call with the key
+        of the previous one finds the shrunk copy - no upload, no launch, and the pictures are never compared.  Without a
+        key the picture is uploaded and shrunk in every call."""
+        torch, c = self._torch, self.cfg
+        if goal.shape[1:3] == (c.height, c.width):
+            return torch.from_numpy(goal).to(self.device)
+        if goal_key is not None and self._goal_cache is not None and self._goal_cache[0] == goal_key:
+            return self._goal_cache[1]
+        with torch.cuda.device(self.device):
+            small = resample.area_resize_device(torch.from_numpy(goal).to(self.device), (c.height, c.width))
+        self._goal_cache = None if goal_key is None else (goal_key, small)
+        return small
+
     @_scoring_entry
-    def score_goal_image(self, context, inputs, goal_image, steps='last', finalweight=10., first_view_only=False):
+    def score_goal_image(self, context, inputs, goal_image, steps='last', finalweight=10., first_view_only=False,
+                         goal_key=None):
         """Fused rollout + goal-image cost (reference ``policy/cem_controllers/goal_im_controller.py:93``): the mean
         squared error between predicted frames and ``goal_image``, reduced on the GPU from the frames resident in the
         engine.  Returns (scores[M], scores_per_view[M, ncam]) float64; ``last_goal_cost_per_step`` ``[M, ncam, T]``
         keeps the per-step MSE (averaged over latent draws).
 
         ``goal_image``: ``[ncam, H, W, 3]`` (or ``[H, W, 3]`` with one view); uint8 is scaled by 1/255 like the
-        context frames, floating point is compared as it is.  ``steps='last'`` scores the last predicted frame,
-        ``'weighted'`` the time-weighted mean with ``w = (1, ..., 1, finalweight)``.  ``first_view_only`` takes view 0's
+        context frames, floating point is compared as it is.  With ``camera_height`` / ``camera_width`` it may also come at
+        the camera's size: it is then shrunk on the device (after the scaling, in float32) - in every call, or, with a
+        ``goal_key`` (any hashable the caller changes with the picture), once per key.
+        ``steps='last'`` scores the last predicted frame, ``'weighted'`` the time-weighted mean with ``w = (1, ..., 1, finalweight)``.  ``first_view_only`` takes view 0's
         cost as the score instead of the mean over views (``scores_per_view`` keeps every view).
 
         Sharding, chunking, lanes and latent draws are those of ``score``.  The rollout entry still wants goal pixels
@@ -600,7 +643,7 @@ class HipVPredEvaluation(object):
         self._last_prepared = (ctx_p, seqs, M)
 
         def rows_of(lane, share, n, lo):        # [score | per view | cost per step]
-            goal_dev = self._torch.from_numpy(goal).to(lane.device)
+            goal_dev = lane._goal_on_device(goal, goal_key)
 
             def reduce(c_s, c_pv, c_cps):
                 _lib.check(lane._libh.vf_goal_image_scores(
@@ -917,9 +960,18 @@ class HipVPredEvaluation(object):
 
         cur, ref, fl = as_input(current), as_input(reference), as_input(flow)
         px = np.ascontiguousarray(pix, dtype=np.int32).reshape(self.n_cam, -1, 2)
-        if tuple(cur.shape) != (self.n_cam, c.height, c.width, 3) or tuple(ref.shape) != tuple(cur.shape) or \
-                tuple(fl.shape) != (self.n_cam, c.height, c.width, 2):
-            raise ValueError('register: need [ncam, H, W, 3] images and a [ncam, H, W, 2] flow field')
+        # at the model's size vf_register; at the camera's (camera_height / camera_width) vf_register_hw, whose pixels and
+        # results are in camera coordinates (the reference registers at the agent's resolution, :121-128,144-155)
+        size = (c.height, c.width)
+        if self.camera_size is not None and tuple(cur.shape[1:3]) == self.camera_size:
+            size = self.camera_size
+        if tuple(cur.shape) != (self.n_cam,) + size + (3,) or tuple(ref.shape) != tuple(cur.shape) or \
+                tuple(fl.shape) != (self.n_cam,) + size + (2,):
+            raise ValueError('register: need [ncam, H, W, 3] images and a [ncam, H, W, 2] flow field%s'
+                             % (' at the model size %d x %d or the camera size %d x %d' % ((c.height, c.width) + self.camera_size)
+                                if self.camera_size is not None else ''))
+        entry = (self._libh.vf_register, (self._handle,)) if size == (c.height, c.width) else \
+            (self._libh.vf_register_hw, (self._handle,) + size)
         ntask = px.shape[1]
         with torch.cuda.device(self.device):
             d_cur, d_ref, d_fl, d_px = (a if torch.is_tensor(a) else torch.from_numpy(a).to(self.device)
@@ -928,8 +980,8 @@ class HipVPredEvaluation(object):
             err = torch.empty((self.n_cam, ntask), dtype=torch.float32, device=self.device)
             warped = torch.empty_like(d_cur) if want_warped else None
             pts = torch.empty_like(d_fl) if want_warped else None
-            _lib.check(self._libh.vf_register(
-                self._handle, d_cur.data_ptr(), d_ref.data_ptr(), d_fl.data_ptr(), d_px.data_ptr(), ntask,
+            _lib.check(entry[0](
+                *entry[1], d_cur.data_ptr(), d_ref.data_ptr(), d_fl.data_ptr(), d_px.data_ptr(), ntask,
                 int(region), int(clip_sub), warped.data_ptr() if want_warped else None,
                 pts.data_ptr() if want_warped else None, desig.data_ptr(), err.data_ptr(), self._stream()))
             out = desig.cpu().numpy().astype(np.float64), err.cpu().numpy().astype(np.float64)

@@ -18,6 +18,7 @@ import ctypes
 import numpy as np
 
 from visual_foresight_amd import _lib
+from visual_foresight_amd.video_prediction import resample
 from visual_foresight_amd.video_prediction.inverse_model_arch import UNITS, InverseModelConfig, InverseModelWeights
 
 MAX_HOST_THREADS = 16
@@ -51,6 +52,21 @@ class _ActionInference(object):
         self.n_gpus, self.first_gpu = int(n_gpus), int(first_gpu)
         self.max_batch = int(self._hp.get('max_batch', 1))
         self.weights, self.cfg = None, None
+        # 'camera_height' / 'camera_width': images arrive at the camera's resolution and are shrunk to the network's
+        # (resample.py) before every inference; None (default) = the network's size, and any other size is refused
+        cam = (self._hp.get('camera_height'), self._hp.get('camera_width'))
+        if (cam[0] is None) != (cam[1] is None):
+            raise ValueError("'camera_height' and 'camera_width' come as a pair, got %r x %r" % cam)
+        self.camera_size = None if cam[0] is None else (int(cam[0]), int(cam[1]))
+
+    def _at_camera_size(self, start, goal, ctx_frames):
+        """True when all three image inputs are at the camera's size (they are then shrunk); at the network's size they go
+        in as they are, and ``_check`` refuses everything else."""
+        c = self.cfg
+        if c is None or self.camera_size is None or self.camera_size == (c.height, c.width):
+            return False
+        resample.check_aspect(self.camera_size, (c.height, c.width))
+        return all(tuple(x.shape[-3:-1]) == self.camera_size for x in (start, goal, ctx_frames))
 
     def _check(self, start, goal, ctx_actions, ctx_frames):
         c = self.cfg
@@ -132,6 +148,15 @@ class HipActionInference(_ActionInference):
         device) -> device ``[n, n_actions, adim]`` (and ``[n, n_context + n_actions, 2, 128]`` = h, c after every step)."""
         torch = self._torch
         start, goal, ctx_actions, ctx_frames = (self._tensor(x) for x in (start, goal, ctx_actions, ctx_frames))
+        if self._at_camera_size(start, goal, ctx_frames) and start.dim() == 4 and goal.shape == start.shape and \
+                ctx_frames.dim() == 5 and ctx_frames.shape[0] == start.shape[0]:
+            # camera-size images: one vf_resize_area call (float32 path) for the start images, the goals and the context
+            c, n = self.cfg, int(start.shape[0])
+            with torch.cuda.device(self.device):
+                small = resample.area_resize_device(
+                    torch.cat([start, goal, ctx_frames.reshape((-1,) + tuple(ctx_frames.shape[2:]))]), (c.height, c.width))
+            start, goal = small[:n], small[n:2 * n]
+            ctx_frames = small[2 * n:].reshape((n, -1) + tuple(small.shape[1:]))
         self._check(start, goal, ctx_actions, ctx_frames)
         c, n = self.cfg, int(start.shape[0])
         out = torch.empty((n, c.n_actions, c.adim), dtype=torch.float32, device=self.device)
@@ -185,8 +210,12 @@ class HostActionInference(_ActionInference):
 
     def infer(self, start, goal, ctx_actions, ctx_frames, want_hidden=False):
         import torch
-        start, goal, ctx_actions, ctx_frames = (torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
+        start, goal, ctx_actions, ctx_frames = (np.ascontiguousarray(x, dtype=np.float32)
                                                 for x in (start, goal, ctx_actions, ctx_frames))
+        if self._at_camera_size(start, goal, ctx_frames):
+            size = (self.cfg.height, self.cfg.width)
+            start, goal, ctx_frames = (resample.area_resize_host(x, size) for x in (start, goal, ctx_frames))
+        start, goal, ctx_actions, ctx_frames = (torch.from_numpy(x) for x in (start, goal, ctx_actions, ctx_frames))
         self._check(start, goal, ctx_actions, ctx_frames)
         cfg, p, n = self.cfg, self._params, start.shape[0]
         scale = np.float32(cfg.input_scale)
