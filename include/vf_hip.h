@@ -113,7 +113,11 @@ typedef struct vf_config {
                                  * the CDNA FC and kernels; tensors flow/w, flow/b where cdna/w, cdna/b sit), 3 = the survey
                                  * table with DNA compositing (selector: arch 0, layer_spec 3, num_masks 1 - a 1x1 head predicts
                                  * a normalised 5x5 kernel per pixel; no rgb head, two mask channels, tensors dna/w [1][1][32][25],
-                                 * dna/b where cdna/w, cdna/b sit); 1, 2 and 3 are exact fp32 only (precision 0).  0 for arch 1 - 2 */
+                                 * dna/b where cdna/w, cdna/b sit), 4 = the survey
+                                 * table with STP compositing (selector: arch 0, layer_spec 4, num_masks 10 - a two-layer FC head on
+                                 * the bottleneck predicts nine affine transforms per sample, each a clamped bilinear warp of the
+                                 * whole previous frame; tensors stp_fc/w [fc_in][100], stp_fc/b where cdna/w, cdna/b sit, then
+                                 * stp/w [100][54], stp/b); 1 - 4 are exact fp32 only (precision 0).  0 for arch 1 - 2 */
 } vf_config;
 
 typedef struct vf_handle vf_handle;

@@ -109,6 +109,16 @@ int main() {
     for (int spec : {0, 3}) rc |= run_case(40, 56, 5, 5, 4, 2, 2, 16, 0, 2, 1, b_small, 3, 0, 0, spec);
     for (int spec : {0, 3}) rc |= run_case(32, 32, 5, 5, 1, 1, 2, 16, 0, 1, 1, b_small, 3, 0, 0, spec);
     for (int spec : {0, 3}) rc |= run_case(64, 64, 5, 3, 1, 2, 13, 200, 0, 1, 1, b_c2, 3, 0, 0, spec);
+    // arch 0 with STP compositing (layer_spec 4, num_masks 10: nine affine warps per sample from a two-layer FC head - the
+    // first layer on the CDNA FC's plan, one PH_STP_FIN item per sample, a table of transforms where the kernel table sits;
+    // the self-test refuses such a schedule without the finish dependency, without the table, or with a flow / dna head or a
+    // CDNA kernel-finish item): the four shapes of the DNA block, each behind the cdna table of the same shape, from which
+    // its item count does not differ - the same K splits of the FC and one finish item per sample (tests/test_stp.py).
+    // Appended behind every other shape, under shape lines of their own (adim 9).
+    for (int spec : {0, 4}) rc |= run_case(64, 64, 9, 5, 2, 2, 3, 37, 0, 1, 1, b_small, 4, 0, 0, spec);
+    for (int spec : {0, 4}) rc |= run_case(40, 56, 9, 5, 4, 2, 2, 16, 0, 2, 1, b_small, 3, 0, 0, spec);
+    for (int spec : {0, 4}) rc |= run_case(32, 32, 9, 5, 1, 1, 2, 16, 0, 1, 1, b_small, 3, 0, 0, spec);
+    for (int spec : {0, 4}) rc |= run_case(64, 64, 9, 3, 1, 2, 13, 200, 0, 1, 1, b_c2, 3, 0, 0, spec);
     // invalid configurations are refused, not crashed on
     vf_config bad = {60, 64, 4, 5, 1, 2, 15, 10, 8, 0, 0, 1, 1, 0};
     vf_handle *h = nullptr;
@@ -137,6 +147,14 @@ int main() {
     if (vf_create(&bad12, &h) == 0) { std::fprintf(stderr, "DNA with num_masks 10 accepted\n"); rc = 1; }
     vf_config bad13 = {128, 128, 12, 5, 1, 2, 15, 1, 8, 0, 0, 1, 1, 1, 0, 3};   // ... and belongs to arch 0
     if (vf_create(&bad13, &h) == 0) { std::fprintf(stderr, "DNA with arch 1 accepted\n"); rc = 1; }
+    vf_config bad14 = {64, 64, 4, 5, 1, 2, 15, 10, 8, 0, 1, 1, 1, 0, 0, 4};     // STP is fp32 only
+    if (vf_create(&bad14, &h) == 0) { std::fprintf(stderr, "STP in the split-bf16 mode accepted\n"); rc = 1; }
+    vf_config bad15 = {64, 64, 4, 5, 1, 2, 15, 1, 8, 0, 0, 1, 1, 0, 0, 4};      // ... has nine transforms
+    if (vf_create(&bad15, &h) == 0) { std::fprintf(stderr, "STP with num_masks 1 accepted\n"); rc = 1; }
+    vf_config bad16 = {128, 128, 12, 5, 1, 2, 15, 10, 8, 0, 0, 1, 1, 1, 0, 4};  // ... and belongs to arch 0
+    if (vf_create(&bad16, &h) == 0) { std::fprintf(stderr, "STP with arch 1 accepted\n"); rc = 1; }
+    vf_config bad17 = {64, 64, 4, 5, 1, 2, 15, 10, 8, 0, 0, 1, 1, 0, 0, 5};     // no fifth table
+    if (vf_create(&bad17, &h) == 0) { std::fprintf(stderr, "layer_spec 5 accepted\n"); rc = 1; }
     // "No exception crosses this boundary" (include/vf_hip.h): a std::bad_alloc / std::exception / foreign throw inside the
     // schedule builder, the weight packer or vf_create comes back as a status code with vf_last_error() set, leaks nothing
     // (ASan's leak check runs at exit) and leaves the handle usable and destroyable

@@ -114,14 +114,19 @@ enum Epilogue {
                               // enc3, the 8 x 8 bottleneck; G = 2: both 32-channel groups of the first conv in one workgroup)
     EPI_RAW = 31,             // acc + bias, nothing else (arch 3: instance norm needs the whole image's statistics first; the
                               // element-wise items of vf_savp3.h normalise)
-    EPI_CONVT_FUSED_FRAMES = 32   // the fused top of a frames-only engine (no designated pixel): + 0 CDNA,
+    EPI_CONVT_FUSED_FRAMES = 32,  // the fused top of a frames-only engine (no designated pixel): + 0 CDNA,
                               // + 1 with the first-frame layer (arch 1), + 2 the six-kernel compositing of arch 2,
                               // + 3 appearance flow, + 4 DNA (fused_epi_frames)
+    EPI_CONVT_FUSED_STP = 37  // the fused top of an STP engine (the range in front of EPI_CONV_PAIR is full):
+                              // + designated pixels, + 0 frames-only (fused_epi_stp)
 };
 __host__ __device__ constexpr bool is_top_fused_frames(int epi) { return epi >= EPI_CONVT_FUSED_FRAMES && epi < EPI_CONVT_FUSED_FRAMES + 5; }
+__host__ __device__ constexpr bool is_top_fused_stp(int epi) { return epi >= EPI_CONVT_FUSED_STP && epi <= EPI_CONVT_FUSED_STP + 4; }
 __host__ __device__ constexpr bool is_top_fused(int epi) {
-    return (epi >= EPI_CONVT_FUSED && epi < EPI_CONV_PAIR) || is_top_fused_frames(epi);
+    return (epi >= EPI_CONVT_FUSED && epi < EPI_CONV_PAIR) || is_top_fused_frames(epi) || is_top_fused_stp(epi);
 }
+__host__ __device__ constexpr int fused_epi_stp(int nd) { return EPI_CONVT_FUSED_STP + nd; }
+static_assert(EPI_CONVT_FUSED_STP == EPI_CONVT_FUSED_FRAMES + 5, "the STP epilogues follow the frames-only ones");
 // frames-only fused epilogue of compositing mode `mode` (CompMode of vf_small_kernels.h: 0 CDNA, 1 flow, 2 DNA)
 __host__ __device__ constexpr int fused_epi_frames(int mode, bool first = false, bool k6 = false) {
     return EPI_CONVT_FUSED_FRAMES + (mode == 1 ? 3 : (mode == 2 ? 4 : (k6 ? 2 : (first ? 1 : 0))));
@@ -1875,6 +1880,9 @@ __device__ __forceinline__ void conv_tile(const PT &p, const int bx_, const int 
     // (the 32-row tile: wave w = gate w of its one row block - the gate-split exchange with one row block, and with it the
     // vectorised cell update: 16-byte loads and stores instead of 48 scalar ones per lane)
     if constexpr (GSPLIT || ROW32) lstm_gsplit_epilogue<MR>(p, acc, bx, by, smem);
+    else if constexpr (is_top_fused_stp(EPI))
+        // <ND (0: frames-only), no first-frame layer, ten masks, COMP_STP>
+        convt_fused_epilogue<EPI - EPI_CONVT_FUSED_STP, false, 10, 3>(p, acc, bx, red, smem);
     else if constexpr (is_top_fused_frames(EPI))
         // <ND = 0, first-frame layer, kernels K, CompMode>
         convt_fused_epilogue<0, EPI - EPI_CONVT_FUSED_FRAMES == 1 || EPI - EPI_CONVT_FUSED_FRAMES == 2,

@@ -134,6 +134,8 @@ static int a_of(const vf_config &c) { return c.adim + c.sdim; }
 static bool is_flow(const vf_config &c) { return c.arch == 0 && c.layer_spec == 2; }
 // arch 0, layer_spec 3: DNA compositing - a 5x5 kernel per pixel from a 1x1 head (dna_arch.py)
 static bool is_dna(const vf_config &c) { return c.arch == 0 && c.layer_spec == 3; }
+// arch 0, layer_spec 4: STP compositing - nine affine warps per sample from a two-layer FC head (stp_arch.py)
+static bool is_stp(const vf_config &c) { return c.arch == 0 && c.layer_spec == 4; }
 
 // arch 3 (the published SAVP generator): vf_engine_savp3.inc
 struct Savp3;
@@ -177,7 +179,9 @@ static std::vector<TensorDesc> tensor_table(const vf_config &c) {
     // transformation='flow'): flow/w [1][1][32][2 * kFlowWarps], flow/b where cdna/w, cdna/b sat
     // arch 0 with layer_spec = 3: the survey widths with the DNA head (dna_arch.py): no rgb head, two mask channels
     // (num_masks = 1), dna/w [1][1][32][kTaps], dna/b where cdna/w, cdna/b sat
-    const bool pub = c.arch == 0 && c.layer_spec == 1, flow = is_flow(c), dna = is_dna(c);
+    // arch 0 with layer_spec = 4: the survey widths with the STP head (stp_arch.py): stp_fc/w [fc_in][kStpHidden], stp_fc/b
+    // where cdna/w, cdna/b sat, then stp/w [kStpHidden][6 * kStpWarps], stp/b
+    const bool pub = c.arch == 0 && c.layer_spec == 1, flow = is_flow(c), dna = is_dna(c), stp = is_stp(c);
     const int c_t2 = pub ? L[5] + L[1] : L[5], c_top = pub ? L[6] + 32 : 32;
     if (savp) { conv("enc00", 5, 5, 3, kEnc00Ch); ln("lna", kEnc00Ch); }
     conv("enc0", 5, 5, savp ? kEnc00Ch : 3, 32); ln("ln1", 32);
@@ -201,7 +205,12 @@ static std::vector<TensorDesc> tensor_table(const vf_config &c) {
     const int KF = c.arch == 2 ? K - 2 : K;
     if (flow) conv("flow", 1, 1, c_top, 2 * kFlowWarps);
     else if (dna) conv("dna", 1, 1, c_top, kTaps);
-    else {
+    else if (stp) {
+        add("stp_fc/w", {fc_in, kStpHidden});
+        add("stp_fc/b", {kStpHidden});
+        add("stp/w", {kStpHidden, kStpRow * kStpWarps});
+        add("stp/b", {kStpRow * kStpWarps});
+    } else {
         add("cdna/w", {fc_in, kTaps * KF});
         add("cdna/b", {kTaps * KF});
     }
@@ -521,7 +530,8 @@ struct ViewData {
     float *ln_g[kNumLn] = {nullptr}, *ln_b[kNumLn] = {nullptr};    // ln1..ln9, lna (enc00), lnb (convt4)
     float *w_rgb = nullptr, *b_rgb = nullptr, *w_mask = nullptr, *b_mask = nullptr;
     float *w_state = nullptr, *b_state = nullptr, *w_sa = nullptr, *b_fc = nullptr;
-    float *w_flow = nullptr, *b_flow = nullptr;     // appearance-flow engines: the flow head (no CDNA FC, no b_fc)
+    float *w_flow = nullptr, *b_flow = nullptr;     // appearance-flow engines: the flow head (no CDNA FC, no b_fc); DNA engines:
+                                                    // the dna head; STP engines: stp/w, stp/b (b_fc holds stp_fc/b there)
     float *w_cond[7] = {nullptr};       // arch 2: conditioning rows of every conv-LSTM's weights, [25][adim + sdim][4C]
     float *ctx_frames = nullptr, *ctx_distrib = nullptr;
 };
@@ -540,6 +550,9 @@ struct vf_handle {
                                         // kernels (composite_flow_kernel, rollout_flow_kernel) run in place of the CDNA ones
     bool dna = false;                   // arch 0, layer_spec 3: DNA compositing - no CDNA FC, no kernel table, no rgb head; the
                                         // head lives in ViewData::w_flow / b_flow; composite_dna_kernel, rollout_dna_kernel run
+    bool stp = false;                   // arch 0, layer_spec 4: STP compositing - the FC plan runs the head's first layer, a finish
+                                        // item per sample (PH_STP_FIN) writes nine affine transforms where the kernel table
+                                        // sits; composite_stp_kernel, rollout_stp_kernel run
     int Hc, Wc;                         // input size of the three-scale conv-LSTM core (H, W; arch 1: H/2, W/2)
     int c_t2 = 64, c_top = 32;          // output channels of convt2 / convt3 (arch 0, layer_spec 1 - the public table: 96 / 64)
     int ncam = 1, n_draws = 1;
@@ -718,9 +731,9 @@ static int validate(const vf_config *c) {
         return s3_validate(c);
     }
     if (c->zdim != 0) return fail(VF_ERR_INVALID, "zdim belongs to arch 3 (must be 0 otherwise)");
-    if (c->layer_spec != 0 && !(c->arch == 0 && c->layer_spec >= 1 && c->layer_spec <= 3))
+    if (c->layer_spec != 0 && !(c->arch == 0 && c->layer_spec >= 1 && c->layer_spec <= 4))
         return fail(VF_ERR_INVALID, "layer_spec: arch 3's layer table, or with arch 0 1 (the public CDNA decoder widths), 2 "
-                                    "(appearance-flow compositing) or 3 (DNA compositing); 0 otherwise");
+                                    "(appearance-flow compositing), 3 (DNA compositing) or 4 (STP compositing); 0 otherwise");
     if (c->arch == 0 && c->layer_spec == 1 && c->precision != 0)
         return fail(VF_ERR_INVALID, "the public decoder table (arch 0, layer_spec 1) is built for precision 0 (exact fp32) only");
     if (is_flow(*c) && c->precision != 0)
@@ -730,6 +743,11 @@ static int validate(const vf_config *c) {
             return fail(VF_ERR_INVALID, "the DNA table (arch 0, layer_spec 3) is built for precision 0 (exact fp32) only");
         if (c->num_masks != 1)
             return fail(VF_ERR_INVALID, "the DNA table (arch 0, layer_spec 3) has one transform: num_masks must be 1");
+    } else if (is_stp(*c)) {
+        if (c->precision != 0)
+            return fail(VF_ERR_INVALID, "the STP table (arch 0, layer_spec 4) is built for precision 0 (exact fp32) only");
+        if (c->num_masks != 10)
+            return fail(VF_ERR_INVALID, "the STP table (arch 0, layer_spec 4) has nine transforms: num_masks must be 10");
     } else if (c->arch == 2 ? c->num_masks != 6 : c->num_masks != 10)
         return fail(VF_ERR_INVALID, "num_masks must be 10 (arch 0 / 1), 6 (arch 2: four CDNA warps + previous + first + scratch) or 4 (arch 3)");
     if (c->max_batch < 1) return fail(VF_ERR_INVALID, "max_batch must be >= 1");
@@ -839,6 +857,11 @@ static int configure_kernels(vf_handle *h) {
     if ((rc = allow_lds(&rollout_dna_kernel<2>, np))) return rc;
     if ((rc = allow_lds(&rollout_dna_kernel<3>, np))) return rc;
     if ((rc = allow_lds(&rollout_dna_kernel<4>, np))) return rc;
+    if ((rc = allow_lds(&rollout_stp_kernel<1>, np))) return rc;
+    if ((rc = allow_lds(&rollout_stp_kernel<2>, np))) return rc;
+    if ((rc = allow_lds(&rollout_stp_kernel<3>, np))) return rc;
+    if ((rc = allow_lds(&rollout_stp_kernel<4>, np))) return rc;
+    if ((rc = allow_lds(&rollout_stp_frames_kernel, np))) return rc;
     if ((rc = allow_lds(&rollout_frames_kernel, np))) return rc;
     if ((rc = allow_lds(&rollout_flow_frames_kernel, np))) return rc;
     if ((rc = allow_lds(&rollout_dna_frames_kernel, np))) return rc;
@@ -1091,10 +1114,11 @@ static void set_goal(int (&goal)[kMaxDesig][2], const int32_t *goal_pix, int ND)
     for (int d = 0; d < ND && goal_pix; ++d) { goal[d][0] = goal_pix[2 * d]; goal[d][1] = goal_pix[2 * d + 1]; }
 }
 
-// The CDNA FC as a K-split GEMM over 1x1 "images": k_in inputs, the taps of n_kern kernels out
-static void plan_fc(vf_handle *h, int k_in, int n_kern) {
+// The CDNA FC as a K-split GEMM over 1x1 "images": k_in inputs, the taps of n_kern kernels out.  (An STP engine runs the
+// first layer of its head on this plan: tensor stp_fc, kStpHidden = 4 * kTaps columns.)
+static void plan_fc(vf_handle *h, int k_in, int n_kern, const char *name = "cdna") {
     ConvLayer &f = h->fc;
-    init_layer(f, "cdna", PACK_PLAIN, 1, 1, 1, 1, 1, 1, 1, 0, k_in, 0, kTaps * n_kern, false, true, 256);
+    init_layer(f, name, PACK_PLAIN, 1, 1, 1, 1, 1, 1, 1, 0, k_in, 0, kTaps * n_kern, false, true, 256);
     const int total = f.nchunk[0];
     f.nsplit = std::min(32, total);
     f.chunks_per_split = (total + f.nsplit - 1) / f.nsplit;
@@ -1186,7 +1210,7 @@ double vf_macs_per_sample_step(const vf_config *cfg) {
         if (!d) continue;               // arch 0 has no enc00 / convt4
         macs += (double)r.h * r.w * d->shape[0] * d->shape[1] * d->shape[2] * d->shape[3];
     }
-    const TensorDesc *fc = find_tensor(t, "cdna/w"), *sw = find_tensor(t, "state/w");
+    const TensorDesc *fc = find_tensor(t, is_stp(*cfg) ? "stp_fc/w" : "cdna/w"), *sw = find_tensor(t, "state/w");
     macs += (double)sw->shape[0] * sw->shape[1];
     if (is_flow(*cfg)) {        // the flow head, and four bilinear taps per warp and channel in place of the FC and the 5 x 5 warps
         const TensorDesc *fw = find_tensor(t, "flow/w");
@@ -1198,6 +1222,12 @@ double vf_macs_per_sample_step(const vf_config *cfg) {
         const TensorDesc *dw = find_tensor(t, "dna/w");
         macs += (double)HF * WF * dw->shape[2] * dw->shape[3];
         macs += (double)HF * WF * kTaps * (3 + cfg->ndesig);
+        return macs;
+    }
+    if (is_stp(*cfg)) {         // the two FC layers of the head, and four bilinear taps per warp and channel
+        const TensorDesc *w2 = find_tensor(t, "stp/w");
+        macs += (double)fc->shape[0] * fc->shape[1] + (double)w2->shape[0] * w2->shape[1];
+        macs += (double)HF * WF * 4 * (3 + cfg->ndesig) * kStpWarps;
         return macs;
     }
     macs += (double)fc->shape[0] * fc->shape[1];
@@ -1259,7 +1289,9 @@ static int cdna_create(vf_handle *h) {
     init_layer(h->lstm[6], "lstm7", PACK_LSTM, H2, W2, H2, W2, 5, 5, 1, 2, h->c_t2, L[6], L[6], true, false, 128, cfg->precision, false, ccond);
     init_layer(h->convt3, "convt3", PACK_CONVT, H2, W2, H2, W2, 2, 2, 1, 1, L[6], 32, h->c_top, true, false, 128, 0, true);
     // CDNA FC as a K-split GEMM over 1x1 "images"
-    plan_fc(h, H8 * W8 * L[4], h->dna ? 10 : h->K);     // (a DNA engine never runs the FC: its unused plan is sized as the cdna table's)
+    static_assert(kStpHidden == 4 * kTaps, "the first FC of the STP head is planned as four kernels' taps");
+    if (h->stp) plan_fc(h, H8 * W8 * L[4], kStpHidden / kTaps, "stp_fc");
+    else plan_fc(h, H8 * W8 * L[4], h->dna ? 10 : h->K);     // (a DNA engine never runs the FC: its unused plan is sized as the cdna table's)
     h->layers = {&h->enc0, &h->lstm[0], &h->lstm[1], &h->enc1, &h->lstm[2], &h->lstm[3], &h->enc2, &h->enc3,
                  &h->lstm[4], &h->convt1, &h->lstm[5], &h->convt2, &h->lstm[6], &h->convt3};
     if (!h->flow && !h->dna) h->layers.push_back(&h->fc);   // (a flow / DNA engine has no CDNA FC: the plan above exists, nothing is packed or run)
@@ -1320,6 +1352,10 @@ static int cdna_create(vf_handle *h) {
         VF_ALLOC(vd.w_sa, (size_t)nsa * L[3]);
         if (h->flow) { VF_ALLOC(vd.w_flow, (size_t)h->c_top * 2 * kFlowWarps); VF_ALLOC(vd.b_flow, 2 * kFlowWarps); }
         else if (h->dna) { VF_ALLOC(vd.w_flow, (size_t)h->c_top * kTaps); VF_ALLOC(vd.b_flow, kTaps); }
+        else if (h->stp) {
+            VF_ALLOC(vd.b_fc, kStpHidden);
+            VF_ALLOC(vd.w_flow, (size_t)kStpHidden * kStpRow * kStpWarps); VF_ALLOC(vd.b_flow, kStpRow * kStpWarps);
+        }
         else VF_ALLOC(vd.b_fc, kTaps * h->K);
         if (h->cond)
             for (int k = 0; k < 7; ++k) VF_ALLOC(vd.w_cond[k], (size_t)kTaps * nsa * 4 * L[k]);
@@ -1352,8 +1388,9 @@ static int cdna_create(vf_handle *h) {
     row_spec(h, b.st_enc6, (size_t)h->convt3.stats_nparts * 2, false);
     row_spec(h, b.sbias, (size_t)h->enc3.Cout, true);
     // (a flow / DNA engine computes no CDNA kernels: rows of no elements, one unused element in all)
-    row_spec(h, b.fc_part, h->flow || h->dna ? 0 : (size_t)h->fc.nsplit * kTaps * h->K, false);
-    row_spec(h, b.kern, h->flow || h->dna ? 0 : (size_t)kTaps * h->K, false);
+    // (an STP engine: the first FC's kStpHidden sums per split, and nine 6-float transforms where the kernels sit)
+    row_spec(h, b.fc_part, h->flow || h->dna ? 0 : (size_t)h->fc.nsplit * (h->stp ? kStpHidden : kTaps * h->K), false);
+    row_spec(h, b.kern, h->flow || h->dna ? 0 : (h->stp ? (size_t)kStpRow * kStpWarps : (size_t)kTaps * h->K), false);
     if ((rc = alloc_common(h, 32))) return rc;          // (arch 2: up to 29 phases per step)
     h->shared_views.resize(NV);
     for (BatchView &sv : h->shared_views)
@@ -1390,6 +1427,7 @@ int vf_create(const vf_config *cfg, vf_handle **out) {
     h->cond = cfg->arch == 2;
     h->flow = is_flow(*cfg);
     h->dna = is_dna(*cfg);
+    h->stp = is_stp(*cfg);
     h->Hc = h->savp ? h->H / 2 : h->H; h->Wc = h->savp ? h->W / 2 : h->W;
     const int H = h->H, W = h->W;
     h->ntiles = ((H + kCompTile - 1) / kCompTile) * ((W + kCompTile - 1) / kCompTile);
@@ -1496,9 +1534,9 @@ int vf_load_weights(vf_handle *h, const float *blob_all, size_t n_floats) {
                             wide[((size_t)r * kTaps + tap) * h->K + k] = (blob + w->offset)[((size_t)r * kTaps + tap) * KF + k];
                 wp = pack_weights(l, wide.data(), 1, 1, fc_in, kTaps * h->K);
                 bp.assign(l.packed_b(), 0.f);
-            } else if (l.name == "cdna") {
+            } else if (l.name == "cdna" || l.name == "stp_fc") {
                 wp = pack_weights(l, blob + w->offset, 1, 1, w->shape[0], w->shape[1]);
-                bp.assign(l.packed_b(), 0.f);       // bias is added by cdna_finalize
+                bp.assign(l.packed_b(), 0.f);       // bias is added by cdna_finalize / stp_finalize
             } else if (l.name == "enc3") {
                 // only the enc2 rows go through the GEMM; the action/state rows become a per-sample bias
                 wp = pack_weights(l, blob + w->offset, 1, 1, w->shape[2], w->shape[3]);
@@ -1572,6 +1610,11 @@ int vf_load_weights(vf_handle *h, const float *blob_all, size_t n_floats) {
             const TensorDesc *dw = T("dna/w"), *db = T("dna/b");
             if ((rc = dev_write(h, vd.w_flow, blob + dw->offset, dw->size() * sizeof(float)))) return rc;
             if ((rc = dev_write(h, vd.b_flow, blob + db->offset, db->size() * sizeof(float)))) return rc;
+        } else if (h->stp) {
+            const TensorDesc *fb = T("stp_fc/b"), *sw = T("stp/w"), *sb = T("stp/b");
+            if ((rc = dev_write(h, vd.b_fc, blob + fb->offset, fb->size() * sizeof(float)))) return rc;
+            if ((rc = dev_write(h, vd.w_flow, blob + sw->offset, sw->size() * sizeof(float)))) return rc;
+            if ((rc = dev_write(h, vd.b_flow, blob + sb->offset, sb->size() * sizeof(float)))) return rc;
         } else if (h->cond) {
             std::vector<float> bw((size_t)kTaps * h->K, 0.f);
             for (int tap = 0; tap < kTaps; ++tap)
@@ -1723,9 +1766,16 @@ struct LaunchSink {
         hipLaunchKernelGGL(cdna_finalize_kernel, dim3(p.B), dim3(256), 0, st, p);
         return VF_OK;
     }
+    int stp_fin(const StpFinParams &p, std::initializer_list<int>) {
+        hipLaunchKernelGGL(stp_finalize_kernel, dim3(p.B), dim3(256), 0, st, p);
+        return VF_OK;
+    }
     int composite(const CompositeParams &p, int ntiles, int /*view*/, std::initializer_list<int>) {
         dim3 grid(ntiles, p.B);
-        if (p.ND == 0) {                // frames-only engines: one kernel per compositing mode (vf_small_kernels.h)
+        if (h->stp) {                   // STP: the transforms travel in the kernel table's field
+            if (p.ND == 0) hipLaunchKernelGGL(composite_stp_frames_kernel, grid, dim3(256), 0, st, p);
+            else with_nd(p.ND, [&](auto nd) { hipLaunchKernelGGL(composite_stp_kernel<decltype(nd)::value>, grid, dim3(256), 0, st, p); });
+        } else if (p.ND == 0) {         // frames-only engines: one kernel per compositing mode (vf_small_kernels.h)
             if (p.w_flow && p.K == 1) hipLaunchKernelGGL(composite_dna_frames_kernel, grid, dim3(256), 0, st, p);
             else if (p.w_flow) hipLaunchKernelGGL(composite_flow_frames_kernel, grid, dim3(256), 0, st, p);
             else if (p.K == 6) hipLaunchKernelGGL(composite_frames_kernel<6>, grid, dim3(256), 0, st, p);
@@ -1766,7 +1816,7 @@ struct ScheduleSink {
         else {
             dp.mode = (Q.B == 1) ? 1 : 0;       // a batch-1 producer is shared by every sample
             switch (Q.type) {
-                case PH_SA: case PH_CDNA_FIN: case PH_COND: dp.expect = 1; break;
+                case PH_SA: case PH_CDNA_FIN: case PH_COND: case PH_STP_FIN: dp.expect = 1; break;
                 case PH_COMPOSITE: dp.expect = Q.gx; break;
                 case PH_EW: dp.expect = Q.ew.spi > 0 ? 1 : Q.gx; break;
                 default: dp.expect = (Q.NI == 1 ? Q.tiles_per_img : 1) * Q.gy;
@@ -1878,6 +1928,14 @@ struct ScheduleSink {
     int fin(const FinParams &p, std::initializer_list<int> deps) {
         PhaseDesc P = phase(PH_CDNA_FIN, p.B);
         P.fin = p;
+        return add(P, p.B, p.B, deps);
+    }
+    // the finish item of an STP sample's transforms: one item per sample (NI = tiles_per_img = gy = 1: the device maps item
+    // i to sample i by the conv rule of item_samples, so no kernel but rollout_stp_kernel knows the phase type)
+    int stp_fin(const StpFinParams &p, std::initializer_list<int> deps) {
+        PhaseDesc P = phase(PH_STP_FIN, p.B);
+        P.stp = p;
+        P.NI = 1; P.tiles_per_img = 1; P.gx = p.B; P.gy = 1;
         return add(P, p.B, p.B, deps);
     }
     int composite(const CompositeParams &p, int ntiles, int view, std::initializer_list<int> deps) {
@@ -2208,10 +2266,18 @@ static int emit_rollout(vf_handle *h, int view, const BatchView &v, const BatchV
             for (int k = 0; k < 7; ++k) u_prev[k] = now[k];
         }
         if (produce && !h->flow && !h->dna) {      // the (tiny) finalise step of the CDNA kernels: behind lstm7, by when the FC has long finished
-            FinParams fp;
-            fp.partial = v.fc_part; fp.nsplit = h->fc.nsplit; fp.B = B; fp.K = h->K;
-            fp.bias = vd.b_fc; fp.kern = v.kern;
-            u_fin = sink.fin(fp, {u_fc});
+            if (h->stp) {       // STP: relu, the second FC and the nine transforms in pixel units, where the kernels would sit
+                StpFinParams sp2; memset(&sp2, 0, sizeof(sp2));
+                sp2.partial = v.fc_part; sp2.nsplit = h->fc.nsplit; sp2.B = B;
+                sp2.bias = vd.b_fc; sp2.w2 = vd.w_flow; sp2.b2 = vd.b_flow; sp2.theta = v.kern;
+                sp2.H = H; sp2.W = W;
+                u_fin = sink.stp_fin(sp2, {u_fc});
+            } else {
+                FinParams fp;
+                fp.partial = v.fc_part; fp.nsplit = h->fc.nsplit; fp.B = B; fp.K = h->K;
+                fp.bias = vd.b_fc; fp.kern = v.kern;
+                u_fin = sink.fin(fp, {u_fc});
+            }
             if (Sink::failed(u_fin)) return u_fin;
         }
 
@@ -2251,6 +2317,8 @@ static int emit_rollout(vf_handle *h, int view, const BatchView &v, const BatchV
             // top are released by this step's first conv (top_early), every tile of which waited for EVERY compositing tile of
             // the previous step (`last`, dep_on: all tiles of the sample), so the gathers find the frame complete.
             // DNA: every tap lies inside the tile's halo, as for CDNA, so the CDNA dependency rules hold as they are.
+            // STP: both - the top waits for the sample's finish item (u_fin) as a CDNA top does, and its affine warps gather from
+            // the whole previous frame as the flow warps do; cp.kern is the table of transforms.
             if (h->flow || h->dna) { cp.w_flow = vd.w_flow; cp.b_flow = vd.b_flow; }
             else cp.kern = v.kern;
             // (frames-only: the tile neither reads nor writes a distribution or a block sum - step_io leaves them null)
@@ -2485,6 +2553,10 @@ extern "C" int vf_selftest_schedule(vf_handle *h, int32_t B, int32_t skip_shared
         if ((h->flow || h->dna) && (P.type == PH_FC_PARTIAL || P.type == PH_CDNA_FIN))
             return fail(VF_ERR_INVALID, "phase " + std::to_string(i) + ": a CDNA kernel item in " +
                                         (h->dna ? "a DNA schedule" : "an appearance-flow schedule"));
+        // an STP schedule finishes its parameters with PH_STP_FIN, never with the CDNA kernels' item - and nobody else does
+        if (h->stp ? P.type == PH_CDNA_FIN : P.type == PH_STP_FIN)
+            return fail(VF_ERR_INVALID, "phase " + std::to_string(i) + (h->stp ? ": a CDNA kernel-finish item (a 5 x 5 kernel table) in an STP schedule"
+                                                                              : ": an STP finish item outside an STP schedule"));
         for (int d = 0; d < P.ndep; ++d) {
             // a dependency must point at the counters of a phase with smaller tickets
             bool found = false;
@@ -2610,14 +2682,31 @@ extern "C" int vf_selftest_schedule(vf_handle *h, int32_t B, int32_t skip_shared
             ok = ok && in_allocs(h, c.out_frame, ((size_t)(P.B - 1) * c.out_frame_bstride + hw * 3) * 4);
             ok = ok && in_allocs(h, c.out_distrib, ((size_t)(P.B - 1) * c.out_distrib_bstride + hw * c.ND) * 4);
             ok = ok && in_allocs(h, c.out_sums, (size_t)P.B * c.ND * h->nblocks * 2 * 8);
-            ok = ok && in_allocs(h, c.kern, (size_t)P.B * kTaps * c.K * 4);
+            ok = ok && in_allocs(h, c.kern, h->stp ? (size_t)P.B * kStpRow * kStpWarps * 4 : (size_t)P.B * kTaps * c.K * 4);
+            if (h->stp) {
+                // an STP engine: the table of transforms in `kern`, no flow / dna head, the survey table's ten masks; the phase
+                // waits for the finish item that writes exactly that table (an affine warp needs its sample's parameters; the
+                // whole previous frame is complete through the step's first conv, as for appearance flow)
+                if (!c.kern) return fail(VF_ERR_INVALID, "phase " + std::to_string(i) + ": a compositing phase without the parameter table in an STP schedule");
+                if (c.w_flow || c.b_flow || c.first_frame || !c.w_rgb || !c.b_rgb || c.K != kStpWarps + 1 || c.CF != 32)
+                    return fail(VF_ERR_INVALID, "phase " + std::to_string(i) + ": a flow / dna head or another table's compositing in an STP schedule");
+                bool fin_dep = false, fin_table = false;
+                for (size_t j = 0; j < i; ++j) {
+                    const PhaseDesc &Q = bs.phases[j];
+                    if (Q.type != PH_STP_FIN || Q.stp.theta != c.kern) continue;
+                    fin_table = true;
+                    for (int d = 0; d < P.ndep; ++d) fin_dep = fin_dep || (P.dep[d].cnt_base == Q.cnt_base && P.dep[d].expect == 1);
+                }
+                if (!fin_table) return fail(VF_ERR_INVALID, "phase " + std::to_string(i) + ": the kernel field of an STP compositing phase is not a table of transforms (a 5 x 5 kernel table?)");
+                if (!fin_dep) return fail(VF_ERR_INVALID, "phase " + std::to_string(i) + ": an STP compositing phase without the finish dependency");
+            }
             // an appearance-flow engine: the flow head instead of kernels, on the survey table's compositing only
             // a DNA engine: the per-pixel kernel head in the same two fields, no rgb head, one transform
             const size_t head_n = h->dna ? kTaps : 2 * kFlowWarps;
             if (h->dna && !(c.w_flow && c.b_flow && !c.kern && !c.first_frame && !c.w_rgb && !c.b_rgb && c.K == 1 && c.CF == 32))
                 return fail(VF_ERR_INVALID, "phase " + std::to_string(i) + ": a compositing phase without the dna head in a DNA schedule");
-            ok = ok && (h->dna || (h->flow ? (c.w_flow && c.b_flow && !c.kern && !c.first_frame && c.K == kFlowWarps + 1 && c.CF == 32)
-                                           : (!c.w_flow && !c.b_flow && c.kern)));
+            ok = ok && (h->dna || h->stp || (h->flow ? (c.w_flow && c.b_flow && !c.kern && !c.first_frame && c.K == kFlowWarps + 1 && c.CF == 32)
+                                                     : (!c.w_flow && !c.b_flow && c.kern)));
             ok = ok && in_allocs(h, c.w_flow, (size_t)32 * head_n * 4) && in_allocs(h, c.b_flow, head_n * 4);
             ok = ok && in_allocs(h, c.first_frame, hw * 3 * 4) && in_allocs(h, c.first_distrib, hw * c.ND * 4);
         } else if (P.type == PH_SA) {
@@ -2628,6 +2717,21 @@ extern "C" int vf_selftest_schedule(vf_handle *h, int32_t B, int32_t skip_shared
                  in_allocs(h, P.cond.w, (size_t)kTaps * (P.cond.adim + P.cond.sdim) * P.cond.C4 * 4) &&
                  in_allocs(h, P.cond.action, 4) && in_allocs(h, P.cond.state, 4);
         } else if (P.type == PH_CONV_PAIR) {
+        } else if (P.type == PH_STP_FIN) {
+            const StpFinParams &q = P.stp;
+            ok = ok && q.nsplit == h->fc.nsplit && q.B == P.B && q.H == h->H && q.W == h->W && P.n_items == P.B &&
+                 P.NI == 1 && P.tiles_per_img == 1 && P.gy == 1;       // (the device's item -> sample rule)
+            ok = ok && in_allocs(h, q.partial, (size_t)q.nsplit * P.B * kStpHidden * 4) && in_allocs(h, q.bias, kStpHidden * 4) &&
+                 in_allocs(h, q.w2, (size_t)kStpHidden * kStpRow * kStpWarps * 4) && in_allocs(h, q.b2, kStpRow * kStpWarps * 4) &&
+                 in_allocs(h, q.theta, (size_t)P.B * kStpRow * kStpWarps * 4) && q.partial && q.bias && q.w2 && q.b2 && q.theta;
+            // the first FC's sums must be complete: the whole-phase counter of a PH_FC_PARTIAL phase that writes `partial`
+            bool fc_dep = false;
+            for (size_t j = 0; j < i; ++j) {
+                const PhaseDesc &Q = bs.phases[j];
+                if (Q.type != PH_FC_PARTIAL || Q.conv.out != q.partial) continue;
+                for (int d = 0; d < P.ndep; ++d) fc_dep = fc_dep || (P.dep[d].cnt_base == Q.cnt_base && P.dep[d].expect == Q.n_items);
+            }
+            if (!fc_dep) return fail(VF_ERR_INVALID, "phase " + std::to_string(i) + ": an STP finish item that does not wait for its FC");
         } else {
             ok = ok && in_allocs(h, P.fin.partial, (size_t)P.fin.nsplit * P.B * kTaps * P.fin.K * 4) &&
                  in_allocs(h, P.fin.kern, (size_t)P.B * kTaps * P.fin.K * 4);
@@ -2800,7 +2904,8 @@ static TaskWeights task_weights_of(const vf_handle *h, const float *task_weights
 
 template <int ND>
 static int launch_persistent_t(const Schedule &sc, int mode, int grid, size_t lds, hipStream_t st) {
-    if (mode == COMP_DNA) hipLaunchKernelGGL((rollout_dna_kernel<ND>), dim3(grid), dim3(kConvThreads), lds, st, sc.phases, sc);
+    if (mode == COMP_STP) hipLaunchKernelGGL((rollout_stp_kernel<ND>), dim3(grid), dim3(kConvThreads), lds, st, sc.phases, sc);
+    else if (mode == COMP_DNA) hipLaunchKernelGGL((rollout_dna_kernel<ND>), dim3(grid), dim3(kConvThreads), lds, st, sc.phases, sc);
     else if (mode == COMP_FLOW) hipLaunchKernelGGL((rollout_flow_kernel<ND>), dim3(grid), dim3(kConvThreads), lds, st, sc.phases, sc);
     else hipLaunchKernelGGL((rollout_persistent_kernel<ND>), dim3(grid), dim3(kConvThreads), lds, st, sc.phases, sc);
     VF_HIP_CHECK(hipGetLastError());
@@ -2898,9 +3003,10 @@ static int run_persistent(vf_handle *h, const float *d_actions, int B, const int
     const int wgs_per_cu = std::min(h->persist_wgs_per_cu, by_lds);
     const int grid = std::min(sc_host.items, h->n_cu * wgs_per_cu);
     if (h->profiling && (rc = profile_begin(h, st))) return rc;
-    const int mode = h->dna ? COMP_DNA : (h->flow ? COMP_FLOW : COMP_CDNA);
+    const int mode = h->stp ? COMP_STP : (h->dna ? COMP_DNA : (h->flow ? COMP_FLOW : COMP_CDNA));
     if (h->ND == 0) {       // frames-only engines: kernels of their own names (vf_persistent.h)
-        if (mode == COMP_DNA) hipLaunchKernelGGL(rollout_dna_frames_kernel, dim3(grid), dim3(kConvThreads), lds, st, sc.phases, sc);
+        if (mode == COMP_STP) hipLaunchKernelGGL(rollout_stp_frames_kernel, dim3(grid), dim3(kConvThreads), lds, st, sc.phases, sc);
+        else if (mode == COMP_DNA) hipLaunchKernelGGL(rollout_dna_frames_kernel, dim3(grid), dim3(kConvThreads), lds, st, sc.phases, sc);
         else if (mode == COMP_FLOW) hipLaunchKernelGGL(rollout_flow_frames_kernel, dim3(grid), dim3(kConvThreads), lds, st, sc.phases, sc);
         else hipLaunchKernelGGL(rollout_frames_kernel, dim3(grid), dim3(kConvThreads), lds, st, sc.phases, sc);
         rc = hipGetLastError() == hipSuccess ? VF_OK : fail(VF_ERR_HIP, "launch of the frames-only rollout kernel failed");

@@ -36,10 +36,13 @@ __host__ __device__ inline size_t fused_top_lds_floats(int TH, int TW, int ND) {
 // distributions - and step 5 gathers the warps from the sample's whole previous frame in global memory.  The item was released
 // by the first conv of the step, every tile of which waited for every compose tile of the previous step: the frame is complete.
 // MODE COMP_DNA (DNA engines): step 3 stages the halo as for CDNA but no kernel table; step 5 runs the per-pixel 5x5 kernels.
+// MODE COMP_STP (STP engines): step 3 stages the sample's nine affine transforms where the kernel table sits and no halo;
+// step 5 gathers the warps from the whole previous frame as FLOW does (same release rule: the frame is complete).
 template <int ND, bool FIRST, int K, class PT, class CT, int MODE = COMP_CDNA>
 __device__ __forceinline__ void fused_top_body(const PT &p, const CT &c, f32x16 (&acc)[1][4], const int bx,
                                                long long *red, float *smem, const int *goal) {
-    constexpr bool FLOW = MODE == COMP_FLOW, DNA = MODE == COMP_DNA;
+    // (GATHER: the warps read the sample's whole previous frame from global memory - no halo tile)
+    constexpr bool FLOW = MODE == COMP_FLOW, DNA = MODE == COMP_DNA, STP = MODE == COMP_STP, GATHER = FLOW || STP;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int n = lane & 31, kh = lane >> 5;
     const int tiles_per_img = p.tilesY * p.tilesX;
@@ -177,7 +180,9 @@ __device__ __forceinline__ void fused_top_body(const PT &p, const CT &c, f32x16 
             kv[j] = i < kTaps * K ? c.kern[(long long)b * kTaps * K + i] : 0.f;
         }
     }
-    if constexpr (!FLOW) halo_request(tid);
+    // (STP: the sample's nine transforms, written by its finish item - a dependency of this item - in the kernels' place)
+    if constexpr (STP) kv[0] = tid < kStpWarps * kStpRow ? c.kern[(long long)b * (kStpWarps * kStpRow) + tid] : 0.f;
+    if constexpr (!GATHER) halo_request(tid);
 #pragma unroll
     for (int j = 0; j < (ND + 3) / 4; ++j) {
         const int d = ((wave + 3) & 3) + 4 * j;
@@ -194,8 +199,10 @@ __device__ __forceinline__ void fused_top_body(const PT &p, const CT &c, f32x16 
             if (i < kTaps * K) s_kern[(i / K) * kCompKernPad + i % K] = kv[j];
         }
     }
+    if constexpr (STP)
+        if (tid < kStpWarps * kStpRow) s_kern[(tid / kStpRow) * kStpRowPad + tid % kStpRow] = kv[0];
     __syncthreads();
-    if constexpr (!FLOW) {
+    if constexpr (!GATHER) {
         halo_store(tid);
         for (int i0 = tid + kHaloU * 256; i0 < HH_ * HW_; i0 += kHaloU * 256) { halo_request(i0); halo_store(i0); }
     }
@@ -249,7 +256,7 @@ __device__ __forceinline__ void fused_top_body(const PT &p, const CT &c, f32x16 
         // registers across composite_pixel, which has none to spare for ND > 2 - laundering the row base keeps the
         // handful of index instructions inside the pass)
         int row0 = wave * 32 + 4 * kh;
-        if constexpr (ND > 2 || (FLOW && ND > 1)) asm volatile("" : "+v"(row0));      // (the flow pass spills at ND 2 without it)
+        if constexpr (ND > 2 || (GATHER && ND > 1)) asm volatile("" : "+v"(row0));      // (the flow pass spills at ND 2 without it)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int row = row0 + (r & 3) + 8 * (r >> 2);
@@ -279,6 +286,10 @@ __device__ __forceinline__ void fused_top_body(const PT &p, const CT &c, f32x16 
             if (valid)
                 composite_pixel_values_flow<ND>(c, y, x, &s_enc[tid * kCompEncPad], mean, rstd, pf, pd, s_dscale, goal, cost,
                                                 of, od);
+        } else if constexpr (STP) {
+            if (valid)
+                composite_pixel_values_stp<ND>(c, y, x, &s_enc[tid * kCompEncPad], mean, rstd, s_kern, pf, pd, s_dscale, goal,
+                                               cost, of, od);
         } else if constexpr (DNA) {
             if (valid)
                 composite_pixel_values_dna<ND>(c, y, x, &s_enc[tid * kCompEncPad], mean, rstd, s_px, HW_, hy, hx, goal, cost,

@@ -41,8 +41,11 @@ enum PhaseType {
     PH_EW,                  // state FC / class biases / instance norm / cell / up-sampling / compositing layers (EwParams::op)
     PH_CONV_RAW3G2,         // two 32-channel groups of a conv as the two "gates" of one item (the hidden layers of the mask and
                             // scratch heads; every 64-channel conv): conv_tile<2, EPI_RAW>, output [pixel][.. 2 x 32 ..]
-    PH_CONV_RAW3G4          // four 32-channel groups per item (convs of 128 / 256 channels: the input tile is staged once for
+    PH_CONV_RAW3G4,         // four 32-channel groups per item (convs of 128 / 256 channels: the input tile is staged once for
                             // 128 output channels instead of once per 32): conv_tile<4, EPI_RAW, 1>
+    PH_STP_FIN              // STP engines (stp_arch.py): the finish item of a sample's nine affine transforms (stp_finalize_sample);
+                            // dispatched by rollout_stp_kernel only.  Its descriptor carries NI = tiles_per_img = gy = 1, so
+                            // item_samples() maps item i to sample i through its default rule
 };
 __host__ __device__ constexpr bool ph_is_conv(const int t) {
     return t <= PH_CONVT_RAW || t == PH_CONV_RAW3 || t == PH_GATES_RAW || t == PH_CONV_RAW3G2 || t == PH_CONV_RAW3G4;
@@ -111,6 +114,7 @@ struct PhaseDesc {
     CompositeParams comp;
     CondParams cond;
     EwParams ew;            // PH_EW
+    StpFinParams stp;       // PH_STP_FIN
 };
 
 constexpr int kCtlWords = 64;               // LDS control block: [0..3] scheduler, [8..8+32) goal pixels, [40..44) state words
@@ -245,6 +249,30 @@ static __device__ __noinline__ __attribute__((not_tail_called)) void composite_f
 static __device__ __noinline__ __attribute__((not_tail_called)) void composite_dna_frames_tile_call(const CompositeParams *p, int tile, int b) {
     composite_tile<0, 1, false, const VF_CONST_AS CompositeParams, 32, COMP_DNA>(const_params(p), tile, b, nullptr, tile_lds());
 }
+// the STP compositing tiles and finish item (vf_small_kernels.h; rollout_stp_kernel / rollout_stp_frames_kernel only)
+template <int ND>
+static __device__ __noinline__ __attribute__((not_tail_called)) void composite_stp_tile_call(const CompositeParams *p, int tile, int b, int view) {
+    extern __shared__ __attribute__((aligned(16))) float smem_all[];
+    const int *goal = reinterpret_cast<const int *>(smem_all) + kCtlGoal + view * ND * 2;
+    composite_tile<ND, kStpWarps + 1, false, const VF_CONST_AS CompositeParams, 32, COMP_STP>(const_params(p), tile, b, goal, tile_lds());
+}
+static __device__ __noinline__ __attribute__((not_tail_called)) void composite_stp_frames_tile_call(const CompositeParams *p, int tile, int b) {
+    composite_tile<0, kStpWarps + 1, false, const VF_CONST_AS CompositeParams, 32, COMP_STP>(const_params(p), tile, b, nullptr, tile_lds());
+}
+// ... and its fused tops (EPI_CONVT_FUSED_STP + ND): bodies of their own names too - the instances of conv_tile_call are
+// counted per epilogue, and no template counted per designated-pixel count is instantiated for zero
+// (tests/test_kernel_lint_frames_only.py)
+template <int ND>
+static __device__ __noinline__ __attribute__((not_tail_called)) void top_stp_tile_call(const ConvParams *p, int bx) {
+    static_assert(ND >= 1, "the frames-only form is top_stp_frames_tile_call");
+    conv_tile<4, fused_epi_stp(ND), 1>(const_params(p), bx, 0, 0, tile_lds());
+}
+static __device__ __noinline__ __attribute__((not_tail_called)) void top_stp_frames_tile_call(const ConvParams *p, int bx) {
+    conv_tile<4, fused_epi_stp(0), 1>(const_params(p), bx, 0, 0, tile_lds());
+}
+static __device__ __noinline__ __attribute__((not_tail_called)) void stp_finalize_call(const StpFinParams *p, int b) {
+    stp_finalize_sample(const_params(p), b, tile_lds());
+}
 static __device__ __noinline__ __attribute__((not_tail_called)) void gates_raw_tile_call(const ConvParams *p, int bx, int by) {
     conv_lstm_gsplit2_tile<4, const VF_CONST_AS ConvParams, true>(const_params(p), bx, by, tile_lds());
 }
@@ -293,7 +321,7 @@ static __device__ __noinline__ __attribute__((not_tail_called)) void small_item_
     }
 }
 
-// The scheduler loop, shared by the three kernels below.  MODE (CompMode) picks the compositing bodies at compile time: the
+// The scheduler loop, shared by the kernels below.  MODE (CompMode) picks the compositing bodies at compile time: the
 // production kernel carries no appearance-flow or DNA code and no run-time branch for them.
 template <int ND, int MODE>
 __device__ __forceinline__ void rollout_body(const PhaseDesc *__restrict__ phases, const Schedule sched) {
@@ -478,7 +506,11 @@ __device__ __forceinline__ void rollout_body(const PhaseDesc *__restrict__ phase
                 // (K = 6: the compositing of arch 2 - four CDNA warps + previous + first frame + scratch - always with
                 // the first-frame layer; K = 10 otherwise)
                 case PH_TOP_FUSED:
-                    if constexpr (ND == 0) {        // frames-only engines: the same dispatch over the frames-only epilogues
+                    if constexpr (MODE == COMP_STP) {
+                        if constexpr (ND == 0) top_stp_frames_tile_call(&P.conv, bx);
+                        else top_stp_tile_call<ND>(&P.conv, bx);
+                    }
+                    else if constexpr (ND == 0) {   // frames-only engines: the same dispatch over the frames-only epilogues
                         if constexpr (MODE != COMP_CDNA) conv_tile_call<4, fused_epi_frames(MODE), 1>(&P.conv, bx, 0, 0);
                         else if (P.comp.K == 6) conv_tile_call<4, fused_epi_frames(MODE, true, true), 1>(&P.conv, bx, 0, 0);
                         else if (P.comp.first_frame) conv_tile_call<4, fused_epi_frames(MODE, true), 1>(&P.conv, bx, 0, 0);
@@ -491,7 +523,11 @@ __device__ __forceinline__ void rollout_body(const PhaseDesc *__restrict__ phase
                     else conv_tile_call<4, fused_epi(ND, false), 1>(&P.conv, bx, 0, 0);
                     break;
                 case PH_COMPOSITE:
-                    if constexpr (ND == 0) {
+                    if constexpr (MODE == COMP_STP) {
+                        if constexpr (ND == 0) composite_stp_frames_tile_call(&P.comp, local % P.gx, b0);
+                        else composite_stp_tile_call<ND>(&P.comp, local % P.gx, b0, P.view);
+                    }
+                    else if constexpr (ND == 0) {
                         if constexpr (MODE == COMP_FLOW) composite_flow_frames_tile_call(&P.comp, local % P.gx, b0);
                         else if constexpr (MODE == COMP_DNA) composite_dna_frames_tile_call(&P.comp, local % P.gx, b0);
                         else if (P.comp.K == 6) composite_frames_tile_call<true, 6>(&P.comp, local % P.gx, b0);
@@ -533,7 +569,14 @@ __device__ __forceinline__ void rollout_body(const PhaseDesc *__restrict__ phase
                     }
                     break;
                 }
-                default: small_item_call(&P, P.type, b0, b1); break;
+                default:
+                    // (the STP finish item exists in STP schedules only: no other kernel tests for it)
+                    if constexpr (MODE == COMP_STP) {
+                        if (P.type == PH_STP_FIN) stp_finalize_call(&P.stp, b0);
+                        else small_item_call(&P, P.type, b0, b1);
+                    }
+                    else small_item_call(&P, P.type, b0, b1);
+                    break;
             }
         }
 
@@ -603,6 +646,15 @@ VF_GLOBAL VF_LAUNCH_BOUNDS(kConvThreads, 2) void rollout_dna_kernel(
     rollout_body<ND, COMP_DNA>(phases, sched);
 }
 
+// The rollout of an STP engine (stp_arch.py, vf_config arch 0 / layer_spec 4): the same schedule and tiles; a finish item
+// per sample turns the head's FC sums into nine affine transforms (PH_STP_FIN), and the compositing of the fused top and of
+// PH_COMPOSITE gathers the nine warps they describe from the whole previous frame.
+template <int ND>
+VF_GLOBAL VF_LAUNCH_BOUNDS(kConvThreads, 2) void rollout_stp_kernel(
+    const PhaseDesc *__restrict__ phases, const Schedule sched) {
+    rollout_body<ND, COMP_STP>(phases, sched);
+}
+
 // The rollouts of frames-only engines (vf_config.ndesig = 0): the same scheduler loop and tiles with ND = 0,
 // one kernel per compositing mode.  Names of their own: the three templates above are counted per designated-pixel count.
 VF_GLOBAL VF_LAUNCH_BOUNDS(kConvThreads, 2) void rollout_frames_kernel(
@@ -616,6 +668,10 @@ VF_GLOBAL VF_LAUNCH_BOUNDS(kConvThreads, 2) void rollout_flow_frames_kernel(
 VF_GLOBAL VF_LAUNCH_BOUNDS(kConvThreads, 2) void rollout_dna_frames_kernel(
     const PhaseDesc *__restrict__ phases, const Schedule sched) {
     rollout_body<0, COMP_DNA>(phases, sched);
+}
+VF_GLOBAL VF_LAUNCH_BOUNDS(kConvThreads, 2) void rollout_stp_frames_kernel(
+    const PhaseDesc *__restrict__ phases, const Schedule sched) {
+    rollout_body<0, COMP_STP>(phases, sched);
 }
 
 }  // namespace vf

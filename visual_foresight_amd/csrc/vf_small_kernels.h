@@ -2,6 +2,7 @@
 //   set_context      uint8 context frames -> float/255, context copies
 //   sa_kernel        state FC + the action/state part of enc3 as a per-sample bias
 //   cdna_finalize    sum K-split partials of the CDNA FC, relu-shift, L1-normalise each 5x5 kernel
+//   stp_finalize     sum K-split partials of the STP head's first FC, relu, second FC, the nine transforms in pixel units
 //   composite        LN9+relu -> rgb/mask heads -> softmax -> CDNA warp -> compositing of the next
 //                    frame and designated-pixel distributions + expected-distance partial sums
 //   scores / export  reduce per-step sums to costs (mean over tasks or trade-off weights, mean over
@@ -221,7 +222,7 @@ struct CompositeParams {
     const float *gamma, *beta;          // LN9 [32]
     const float *w_rgb, *b_rgb;         // [32][3], [3]
     const float *w_mask, *b_mask;       // [32][K+1], [K+1]
-    const float *kern;                  // [B][25][K]
+    const float *kern;                  // [B][25][K]; STP engines (stp_arch.py): the sample's transforms [B][kStpWarps][6]
     const float *prev_frame; long long prev_frame_bstride;      // [H][W][3]
     const float *prev_distrib; long long prev_distrib_bstride;  // [H][W][ND]
     const double *prev_sums;            // [B][ND][blocks][2] partial sums of prev_distrib, or null
@@ -660,15 +661,162 @@ __device__ __forceinline__ void composite_pixel_values_dna(const PT &p, const in
     composite_values_dna<ND>(p, y, x, o_m, o_a, s_px, halo_w, hy, hx, goal, cost, of, od);
 }
 
+// ------------------------------------------------------------------------------------------
+// STP compositing (stp_arch.py; arXiv:1605.07157 section 3.3).  A two-layer FC head on the bottleneck
+// predicts kStpWarps affine transforms per SAMPLE; warp k samples the whole previous frame and distributions at
+//     xs = sx + t0 cx + t1 (sx / sy) cy + t2 sx,   ys = sy + t3 (sy / sx) cx + t4 cy + t5 sy
+// (sx = (W - 1) / 2, sy = (H - 1) / 2, cx = x - sx, cy = y - sy) with the clamped bilinear taps of the flow path, and the
+// masks mix the warps as they mix the flow path's.  The parameters are a per-sample table as the CDNA kernels are
+// (PH_FC_PARTIAL + a finish item, CompositeParams::kern), the gathers reach any pixel as the flow path's do: the previous
+// frame must be complete, which the dependency of the step's first conv on every compositing tile gives (emit_rollout).
+constexpr int kStpWarps = 9;            // NF = num_masks - 1
+constexpr int kStpHidden = 100;         // hidden units of the head (= 4 * kTaps: the first FC runs on the CDNA FC's plan)
+constexpr int kStpRow = 6;              // floats per transform in global memory: [a0, a1, a2, b0, b1, b2]
+constexpr int kStpRowPad = 8;           // ... and in LDS (two 16-byte reads per transform, every lane the same address)
+static_assert(kStpWarps * kStpRowPad <= kTaps * kCompKernPad, "the transforms sit where the CDNA kernels sit in LDS");
+
+// The finish item.  hid_j = relu(stp_fc/b_j + sum_split partial_j) (splits ascending, as cdna_finalize), theta_o = one fma
+// chain over the hidden units ascending from stp/b_o, + the identity (1, 0, 0, 0, 1, 0), then the row in PIXEL units:
+//     a0 = t0, a1 = t1 * (sx / sy), a2 = fma(t2, sx, sx);   b0 = t3 * (sy / sx), b1 = t4, b2 = fma(t5, sy, sy)
+// so that a pixel computes xs = fma(a0, cx, fma(a1, cy, a2)), ys = fma(b0, cx, fma(b1, cy, b2)) (composite_values_stp).
+// With theta the identity a2 = sx and xs = cx + sx = x exactly; with (-1, 0, 0, 0, -1, 0) xs = sx - cx = W - 1 - x exactly.
+struct StpFinParams {
+    const float *partial; int nsplit; int B;    // [nsplit][B][kStpHidden] raw sums of the first FC
+    const float *bias;                          // stp_fc/b [kStpHidden]
+    const float *w2, *b2;                       // stp/w [kStpHidden][kStpWarps * 6], stp/b [kStpWarps * 6]
+    float *theta;                               // [B][kStpWarps][kStpRow], where the CDNA kernel table sits
+    int H, W;
+};
+
+// one sample per workgroup call; scratch: kStpHidden floats of LDS
+template <class PT>
+__device__ __forceinline__ void stp_finalize_sample(const PT &p, const int b, float *scratch) {
+    const int t = threadIdx.x;
+    constexpr int NO = kStpWarps * kStpRow;
+    if (t < kStpHidden) {
+        float acc = p.bias[t];
+        for (int z = 0; z < p.nsplit; ++z) acc += p.partial[((long long)z * p.B + b) * kStpHidden + t];
+        scratch[t] = fmaxf(acc, 0.f);
+    }
+    __syncthreads();
+    if (t < NO) {
+        float acc = p.b2[t];
+        for (int j = 0; j < kStpHidden; ++j) acc = fmaf(scratch[j], p.w2[j * NO + t], acc);
+        const int e = t % kStpRow;
+        const float sx = 0.5f * (float)(p.W - 1), sy = 0.5f * (float)(p.H - 1);
+        const float th = acc + ((e == 0 || e == 4) ? 1.0f : 0.0f);
+        float v = th;
+        if (e == 1) v = th * (sx / sy);
+        else if (e == 2) v = fmaf(th, sx, sx);
+        else if (e == 3) v = th * (sy / sx);
+        else if (e == 5) v = fmaf(th, sy, sy);
+        p.theta[(long long)b * NO + t] = v;
+    }
+}
+
+// the per-layer launch of the finish item
+VF_GLOBAL VF_LAUNCH_BOUNDS(256) void stp_finalize_kernel(const StpFinParams p) {
+    __shared__ float scratch[kStpHidden];
+    stp_finalize_sample(p, blockIdx.x, scratch);
+}
+
+// One output pixel (y, x) behind its rgb / mask head outputs: softmax, nine affine warps, next frame / distributions, cost
+// terms.  s_theta: the sample's transforms in LDS, [kStpWarps][kStpRowPad] in pixel units (above) - uniform over the
+// workgroup, so they cost LDS broadcasts and no per-lane register beyond the row in use.  pf / pd / dscale, the clamp, the
+// taps and the accumulation order are composite_values_flow's; there is no per-pixel head and no second pass over the
+// feature row.
+template <int ND, class PT>
+__device__ __forceinline__ void composite_values_stp(const PT &p, const int y, const int x, float (&o_rgb)[3],
+                                                     float (&o_m)[kStpWarps + 2], const float *s_theta, const float *pf,
+                                                     const float *pd, const float *dscale, const int *goal,
+                                                     double (&cost)[2 * nd_slots(ND)], float (&of)[3], float (&od)[nd_slots(ND)]) {
+    constexpr int NM = kStpWarps + 2;
+    float mx = o_m[0];
+#pragma unroll
+    for (int j = 1; j < NM; ++j) mx = fmaxf(mx, o_m[j]);
+    float den = 0.f;
+#pragma unroll
+    for (int j = 0; j < NM; ++j) { o_m[j] = __expf(o_m[j] - mx); den += o_m[j]; }
+    const float inv = 1.0f / den;
+#pragma unroll
+    for (int j = 0; j < NM; ++j) o_m[j] *= inv;
+
+    float sc[nd_slots(ND)];
+#pragma unroll
+    for (int d = 0; d < ND; ++d) sc[d] = dscale[d];
+    {
+        const long long o = (long long)y * p.W + x;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) of[c] = fmaf(o_m[0], pf[o * 3 + c], o_m[1] * sigmoidf_(o_rgb[c]));
+#pragma unroll
+        for (int d = 0; d < ND; ++d) od[d] = o_m[0] * (pd[o * ND + d] * sc[d]);
+    }
+    const float xmax = (float)(p.W - 1), ymax = (float)(p.H - 1);
+    const float cx = (float)x - 0.5f * xmax, cy = (float)y - 0.5f * ymax;
+#pragma unroll
+    for (int k = 0; k < kStpWarps; ++k) {
+        const f32x4 ta = *reinterpret_cast<const f32x4 *>(s_theta + k * kStpRowPad);
+        const f32x4 tb = *reinterpret_cast<const f32x4 *>(s_theta + k * kStpRowPad + 4);
+        const float xs = fmaf(ta[0], cx, fmaf(ta[1], cy, ta[2]));
+        const float ys = fmaf(ta[3], cx, fmaf(tb[0], cy, tb[1]));
+        // the taps of bilinear_clamped(), shared by the frame's channels and the distributions (a NaN clamps to 0)
+        const float sx = fminf(fmaxf(xs, 0.f), xmax);
+        const float sy = fminf(fmaxf(ys, 0.f), ymax);
+        const int x0 = (int)floorf(sx), y0 = (int)floorf(sy);
+        const int x1 = min(x0 + 1, p.W - 1), y1 = min(y0 + 1, p.H - 1);
+        const float fx = sx - (float)x0, fy = sy - (float)y0;
+        const int o00 = y0 * p.W + x0, o01 = y0 * p.W + x1, o10 = y1 * p.W + x0, o11 = y1 * p.W + x1;
+        const float m = o_m[k + 2];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float a = pf[o00 * 3 + c], b = pf[o01 * 3 + c], cc = pf[o10 * 3 + c], dd = pf[o11 * 3 + c];
+            const float top = fmaf(fx, b - a, a), bot = fmaf(fx, dd - cc, cc);
+            of[c] = fmaf(m, fmaf(fy, bot - top, top), of[c]);
+        }
+#pragma unroll
+        for (int d = 0; d < ND; ++d) {
+            const float a = pd[o00 * ND + d] * sc[d], b = pd[o01 * ND + d] * sc[d];
+            const float cc = pd[o10 * ND + d] * sc[d], dd = pd[o11 * ND + d] * sc[d];
+            const float top = fmaf(fx, b - a, a), bot = fmaf(fx, dd - cc, cc);
+            od[d] = fmaf(m, fmaf(fy, bot - top, top), od[d]);
+        }
+        // One warp's 4 x (3 + ND) gathers in flight at a time.  Every address of all nine warps is known up front (no
+        // per-pixel head stands between them, as the flow path's does), and left alone the scheduler hoists the loads of
+        // several warps: 226 VGPRs in the stand-alone tile, and spills in the fused top, which holds the conv tile's 64
+        // accumulators across this function.
+        __builtin_amdgcn_sched_barrier(0);
+    }
+#pragma unroll
+    for (int d = 0; d < ND; ++d) {
+        const float ry = (float)(y - goal[2 * d]), rx = (float)(x - goal[2 * d + 1]);
+        const float dist = sqrtf(fmaf(ry, ry, rx * rx));
+        cost[2 * d] = (double)od[d];
+        cost[2 * d + 1] = (double)od[d] * (double)dist;
+    }
+}
+// ... from the pixel's LDS feature row (the stand-alone tile and the fused top call this: same expressions, same bits)
+template <int ND, class PT>
+__device__ __forceinline__ void composite_pixel_values_stp(const PT &p, const int y, const int x, const float *feat,
+                                                           const float mean, const float rstd, const float *s_theta,
+                                                           const float *pf, const float *pd, const float *dscale,
+                                                           const int *goal, double (&cost)[2 * nd_slots(ND)], float (&of)[3],
+                                                           float (&od)[nd_slots(ND)]) {
+    float o_rgb[3], o_m[kStpWarps + 2];
+    composite_head_bias<kStpWarps + 1>(p, o_rgb, o_m);
+    composite_heads<kStpWarps + 1>(p, feat, mean, rstd, 0, o_rgb, o_m);
+    composite_values_stp<ND>(p, y, x, o_rgb, o_m, s_theta, pf, pd, dscale, goal, cost, of, od);
+}
+
 // compositing variants of composite_tile / fused_top_body / rollout_body (compile-time: the production kernel carries
-// neither appearance-flow nor DNA code and no run-time branch for them)
-enum CompMode { COMP_CDNA = 0, COMP_FLOW = 1, COMP_DNA = 2 };
+// neither appearance-flow, DNA nor STP code and no run-time branch for them)
+enum CompMode { COMP_CDNA = 0, COMP_FLOW = 1, COMP_DNA = 2, COMP_STP = 3 };
 
 // one 16x16 pixel tile of one sample.  FIRST (arch 1, savp_arch.py): the first context frame is one more compositing
 // layer - a template parameter, because a run-time branch around the mask bookkeeping costs the CDNA path 3.5 us per
 // tile (measured).
 // MODE COMP_FLOW (appearance flow, above): no halo tile and no kernel table are staged - the warps gather from global memory.
 // MODE COMP_DNA (above): the halo tile is staged, the kernel table is not.
+// MODE COMP_STP (above): no halo tile; the sample's nine transforms are staged where the kernel table sits.
 template <int ND, int K, bool FIRST, class PT, int CFT = 32, int MODE = COMP_CDNA>
 __device__ __forceinline__ void composite_tile(const PT &p, const int tile, const int b, const int *goal,
                                                float *smem) {
@@ -724,15 +872,18 @@ __device__ __forceinline__ void composite_tile(const PT &p, const int tile, cons
             if (lane_ == 0) s_dscale[d] = sc;
         }
     }
-    constexpr bool FLOW = MODE == COMP_FLOW, DNA = MODE == COMP_DNA;
+    constexpr bool FLOW = MODE == COMP_FLOW, DNA = MODE == COMP_DNA, STP = MODE == COMP_STP;
     if constexpr (MODE == COMP_CDNA)
         for (int i = tid; i < kTaps * K; i += 256) s_kern[(i / K) * kCompKernPad + i % K] = p.kern[(long long)b * kTaps * K + i];
+    if constexpr (STP)
+        if (tid < kStpWarps * kStpRow)
+            s_kern[(tid / kStpRow) * kStpRowPad + tid % kStpRow] = p.kern[(long long)b * (kStpWarps * kStpRow) + tid];
     __syncthreads();
 
     const float *pf = p.prev_frame + (long long)b * p.prev_frame_bstride;
     // (a frames-only tile, ND = 0: no distribution is staged, scaled or gathered; prev_distrib is null)
     const float *pd = ND > 0 ? p.prev_distrib + (long long)b * p.prev_distrib_bstride : nullptr;
-    for (int i = tid; i < (FLOW ? 0 : HS * HS); i += 256) {
+    for (int i = tid; i < (FLOW || STP ? 0 : HS * HS); i += 256) {
         const int ly = i / HS, lx = i % HS;
         const int y = ty0 + ly - 2, x = tx0 + lx - 2;
         const bool in = y >= 0 && y < p.H && x >= 0 && x < p.W;
@@ -762,6 +913,22 @@ __device__ __forceinline__ void composite_tile(const PT &p, const int tile, cons
             float of[3], od[nd_slots(ND)];
             composite_pixel_values_flow<ND>(p, y, x, &s_enc[tid * kCompEncPad], s_ln[0], s_ln[1], pf, pd, s_dscale, goal,
                                             cost, of, od);
+            const long long o = (long long)y * p.W + x;
+            float *fo = p.out_frame + (long long)b * p.out_frame_bstride + o * 3;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) fo[c] = of[c];
+            if constexpr (ND > 0) {
+                float *dout = p.out_distrib + (long long)b * p.out_distrib_bstride + o * ND;
+#pragma unroll
+                for (int d = 0; d < ND; ++d) dout[d] = od[d];
+            }
+        }
+    } else if constexpr (STP) {
+        static_assert(!STP || (CF == 32 && K == kStpWarps + 1 && !FIRST), "the stp table: survey decoder, ten masks");
+        if (valid) {
+            float of[3], od[nd_slots(ND)];
+            composite_pixel_values_stp<ND>(p, y, x, &s_enc[tid * kCompEncPad], s_ln[0], s_ln[1], s_kern, pf, pd, s_dscale,
+                                           goal, cost, of, od);
             const long long o = (long long)y * p.W + x;
             float *fo = p.out_frame + (long long)b * p.out_frame_bstride + o * 3;
 #pragma unroll
@@ -857,6 +1024,13 @@ VF_GLOBAL VF_LAUNCH_BOUNDS(256) void composite_dna_kernel(const CompositeParams 
     composite_tile<ND, 1, false, CompositeParams, 32, COMP_DNA>(p, blockIdx.x, blockIdx.y, &p.goal[0][0], smem);
 }
 
+// the per-layer launch of the STP compositing
+template <int ND>
+VF_GLOBAL VF_LAUNCH_BOUNDS(256) void composite_stp_kernel(const CompositeParams p) {
+    __shared__ __attribute__((aligned(16))) float smem[composite_lds_floats<ND, kStpWarps + 1>()];
+    composite_tile<ND, kStpWarps + 1, false, CompositeParams, 32, COMP_STP>(p, blockIdx.x, blockIdx.y, &p.goal[0][0], smem);
+}
+
 // Frames-only engines (vf_config.ndesig = 0): the same tile with ND = 0 - no distribution halo, no scale of
 // the previous distributions, no cost terms, no out_distrib / out_sums; a frame pixel runs the very fma chain of the ND = 1
 // instance.  Kernels of their own NAME, not a fifth instance of the templates above: those are counted per designated-pixel
@@ -877,6 +1051,10 @@ VF_GLOBAL VF_LAUNCH_BOUNDS(256) void composite_flow_frames_kernel(const Composit
 VF_GLOBAL VF_LAUNCH_BOUNDS(256) void composite_dna_frames_kernel(const CompositeParams p) {
     __shared__ __attribute__((aligned(16))) float smem[composite_lds_floats<0, 1>()];
     composite_tile<0, 1, false, CompositeParams, 32, COMP_DNA>(p, blockIdx.x, blockIdx.y, nullptr, smem);
+}
+VF_GLOBAL VF_LAUNCH_BOUNDS(256) void composite_stp_frames_kernel(const CompositeParams p) {
+    __shared__ __attribute__((aligned(16))) float smem[composite_lds_floats<0, kStpWarps + 1>()];
+    composite_tile<0, kStpWarps + 1, false, CompositeParams, 32, COMP_STP>(p, blockIdx.x, blockIdx.y, nullptr, smem);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -65,7 +65,9 @@ frame, scratch, then the warps with ``k`` ascending; head sums run over the chan
 only, ``'survey'`` decoder only.
 
 DNA (a 5x5 kernel per pixel from a 1x1 head; ``vf_config`` arch 0, layer_spec 3) has its own configuration class and
-manifest tag: ``dna_arch.py`` (``DnaConfig``).  ``CdnaConfig(transformation='dna')`` stays refused.
+manifest tag: ``dna_arch.py`` (``DnaConfig``).  ``CdnaConfig(transformation='dna')`` stays refused.  So has STP (nine
+affine warps per sample from an FC head; layer_spec 4): ``stp_arch.py`` (``StpConfig``), ``CdnaConfig(transformation='stp')``
+stays refused.
 """
 import json
 import os
@@ -292,6 +294,9 @@ class CdnaWeights(object):
         elif arch == 'dna':
             from visual_foresight_amd.video_prediction.dna_arch import DnaConfig
             file_cfg = DnaConfig(**manifest['config'])
+        elif arch == 'stp':
+            from visual_foresight_amd.video_prediction.stp_arch import StpConfig
+            file_cfg = StpConfig(**manifest['config'])
         else:
             raise ValueError('unknown architecture %r in %s' % (arch, model_dir))
         if cfg is not None and cfg.arch != arch:

@@ -76,6 +76,9 @@ def import_named_arrays(arrays, cfg, log=None):
     if getattr(cfg, 'transformation', 'cdna') == 'dna':
         raise ValueError("only transformation 'cdna' checkpoints can be imported: no TensorFlow name table exists for the "
                          "DNA head (transformation 'dna', tensors dna/w, dna/b)")
+    if getattr(cfg, 'transformation', 'cdna') == 'stp':
+        raise ValueError("only transformation 'cdna' checkpoints can be imported: no TensorFlow name table exists for the "
+                         "STP head (transformation 'stp', tensors stp_fc/w, stp_fc/b, stp/w, stp/b)")
     if getattr(cfg, 'transformation', 'cdna') != 'cdna':
         raise ValueError("only transformation 'cdna' checkpoints can be imported: no TensorFlow name table exists for the "
                          "appearance-flow head (transformation %r, tensors flow/w, flow/b)" % (cfg.transformation,))

@@ -54,7 +54,10 @@ def transformation_of(hparams):
     ``'flow'``, the appearance-flow compositing of ``cdna_arch.py``, or ``'dna'``, the per-pixel kernels of ``dna_arch.py``.
     The reference's legacy predictor configurations name it as ``'model': 'appflow'`` (``experiments/sawyer/*/conf.py``:
     "CDNA, DNA, or STP"); that key selects flow - and ``'model': 'DNA'``, in any letter case, dna - when
-    ``'transformation'`` itself is absent, and every other value of ``'model'`` is left to its other readers."""
+    ``'transformation'`` itself is absent, and every other value of ``'model'`` is left to its other readers.
+    ``'transformation': 'stp'`` selects the affine warps of ``stp_arch.py``; the legacy ``'model': 'STP'`` does NOT - it keeps
+    selecting ``'cdna'``, as it did before the STP table existed (``tests/test_dna.py`` pins that), so no existing
+    configuration changes the network it builds."""
     legacy = {'appflow': 'flow', 'dna': 'dna'}.get(str(hparams.get('model', '')).lower(), 'cdna')
     return str(hparams.get('transformation', legacy))
 
@@ -174,6 +177,9 @@ class HipVPredEvaluation(object):
             if transformation == 'dna':         # its own configuration class and manifest tag (dna_arch.py)
                 from visual_foresight_amd.video_prediction.dna_arch import DnaConfig
                 cfg_cls = DnaConfig
+            elif transformation == 'stp':       # likewise (stp_arch.py)
+                from visual_foresight_amd.video_prediction.stp_arch import StpConfig
+                cfg_cls = StpConfig
             else:
                 extra = dict(extra, transformation=transformation)
         self.cfg = cfg_cls(height=hp.get('image_height', 64), width=hp.get('image_width', 64),
