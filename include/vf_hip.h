@@ -9,7 +9,7 @@
  * the calling thread.  No exception crosses this boundary.  Every device buffer - packed
  * weights, activations, predictions, schedules - is sized from the config and allocated in
  * vf_create(); no later call allocates device memory (vf_load_weights refills the same
- * buffers).  vf_set_context / vf_rollout / vf_export / vf_register(_hw) / vf_resize_area / vf_allgather_scores only
+ * buffers).  vf_set_context / vf_rollout / vf_export / vf_register(_hw) / vf_resize_area / vf_cem_refit / vf_cem_sample / vf_allgather_scores only
  * enqueue work on the caller's HIP stream (hipStream_t passed as void*; NULL = the default
  * stream) and never synchronise it; a handle is driven from one stream at a time.
  * vf_load_weights, vf_device_status and the debug hooks are the blocking calls.
@@ -423,6 +423,52 @@ int vf_register_hw(vf_handle *h, int32_t H, int32_t W, const float *d_current, c
  * keeps every value but not every bit (-0.0 comes back as +0.0: the sum starts at +0.0). */
 int vf_resize_area(int32_t device, const void *d_src, void *d_dst, int32_t dtype /*0 = uint8, 1 = float32*/,
                    int32_t n, int32_t Hs, int32_t Ws, int32_t C, int32_t Hd, int32_t Wd, void *stream);
+
+/* Device-resident CEM iteration (csrc/vf_cem.h): pick the elites of a rollout's scores, refit the Gaussian proposal on them
+ * and draw the next candidates - all on the caller's stream, so that the iterations of one planning call (reference
+ * visual_mpc/policy/cem_controllers/cem_base_controller.py:85-116, samplers/gaussian_sampler.py:75-150, both host NumPy)
+ * need no download between rollouts.  The arithmetic is specified by the float64 class
+ * visual_foresight_amd/policy/cem_controllers/samplers/philox_gaussian_sampler.py: Philox4x32-10 under the key
+ * {seed_lo, seed_hi} with the counter {block j, trial n, sample i, call}; Box-Muller in float64; the proposal in factor
+ * form sigma = A A^T with the draw x_d = mean_d + sum_r A[d][r] z_r as one fma chain, r ascending.
+ * Handle-free like vf_resize_area: `device` is the HIP ordinal, nothing is allocated, nothing synchronises.
+ * D = nactions * adim <= 128, T = nactions * repeat, a row of d_actions holds adim + tail <= 8 floats, 2 <= n_elites <= 256.
+ * Workspace (caller-owned, vf_cem_workspace_bytes, 16-byte aligned): int32 R, int32 pad[3]; double mean[D];
+ * double A[max(D, n_elites)][D] with A[d][r] at [r][d].  The FIRST proposal of a planning call is uploaded by the caller
+ * in that layout (R = D, A = diag(std): any async copy on the same stream); vf_cem_refit writes the later ones. */
+typedef struct vf_cem_config {
+    int32_t nactions, repeat, adim, tail;
+    int32_t n_elites;
+    int32_t max_trials;         /* >= 1: draws per sample before the last one is clipped into rej_lim */
+    int32_t rejection;          /* 0: the first draw is taken as it is */
+    int32_t zero_first;         /* sample 0 becomes the zero action (its appended constants stay) */
+    int32_t discrete_mask;      /* bit c: column c becomes clip(floor(x), 0, 4) */
+    uint32_t seed_lo, seed_hi;
+    int32_t reserved;
+    double rej_lim[8];          /* per action column: |x| <= rej_lim accepts; +inf = no limit */
+    double trunc_lim[8];        /* per action column: clip to +-trunc_lim after discretisation; +inf = none */
+    double tail_value[8];       /* the constants written to columns adim .. adim + tail - 1 */
+} vf_cem_config;
+
+/* Bytes of the workspace for cfg; 0 (and vf_last_error) for an invalid cfg. */
+size_t vf_cem_workspace_bytes(const vf_cem_config *cfg);
+
+/* Elites and refit.  d_scores [M] float64 (as vf_rollout writes them), d_actions [M][T][adim + tail] float32 (the rollout's
+ * input), n_elites <= M <= 4096.  Writes d_elite_index [n_elites] (the n_elites smallest scores in ascending (score, index)
+ * order, NaN last), d_elite_score [n_elites], d_elite_plans [n_elites][T][adim + tail] (copies of the elites' rows) and,
+ * into the workspace, R = n_elites, mean_d = (sum over the elites in rank order of their value at the LAST step of held
+ * action d) / n_elites and A[d][k] = (e_kd - mean_d) / sqrt(n_elites - 1), float64, each operation rounded once.
+ * One kernel of one workgroup.  VF_ERR_INVALID (nothing launched): a NULL pointer, an invalid cfg, M outside the range. */
+int vf_cem_refit(int32_t device, const vf_cem_config *cfg, const double *d_scores, const float *d_actions, int32_t M,
+                 int32_t *d_elite_index, double *d_elite_score, float *d_elite_plans, void *d_workspace, void *stream);
+
+/* Draw M <= 4096 candidates from the workspace's proposal as sampling call number `call` (word 3 of the counter).  Writes
+ * d_actions [M][T][adim + tail] float32 - every sampled action held for `repeat` steps, the constants in the tail columns -
+ * d_trials [M] (draws taken) and d_capped [M] (1: max_trials draws were rejected and the last one was clipped).  One
+ * wavefront per sample; the only data-dependent loop is the trial loop, bounded by max_trials.
+ * VF_ERR_INVALID (nothing launched): a NULL pointer, an invalid cfg, M outside 1..4096. */
+int vf_cem_sample(int32_t device, const vf_cem_config *cfg, const void *d_workspace, uint32_t call, int32_t M,
+                  float *d_actions, int32_t *d_trials, int32_t *d_capped, void *stream);
 
 /* The one collective of multi-GPU planning: all-gather every rank's n_local score values (float64)
  * (n_local equal on all ranks: pad ragged shards) into d_all [world * n_local] with RCCL over

@@ -13,6 +13,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -382,6 +383,42 @@ int main() {
             if (vf_resize_area(-1, p, p, 0, 1, 8, 8, 3, 4, 4, nullptr) != VF_ERR_INVALID) rc = 1;
             // (an odd uint8 pointer is served: everything is through, and this build launches nothing)
             if (vf_resize_area(0, odd, p, 0, 1, 8, 8, 3, 4, 4, nullptr) != VF_ERR_HIP) { std::fprintf(stderr, "vf_resize_area: odd uint8 pointer refused\n"); rc = 1; }
+            // the device CEM entry points: configuration and argument refusals, the workspace size
+            {
+                const double inf = 1.0 / 0.0;
+                vf_cem_config good = {5, 3, 4, 0, 10, 256, 1, 0, 0, 1u, 2u, 0,
+                                      {0.075, 0.075, 0.225, inf, inf, inf, inf, inf}, {inf, inf, inf, inf, inf, inf, inf, inf}, {0}};
+                if (vf_cem_workspace_bytes(&good) != 16 + 8 * 20 * 21) { std::fprintf(stderr, "vf_cem_workspace_bytes: wrong size\n"); rc = 1; }
+                struct { int field, value; const char *msg; } bad_cem[] = {
+                    {0, 0, "nactions"}, {0, 33, "exceeds 128"}, {1, 0, "repeat"}, {2, 0, "adim"}, {3, 5, "adim + tail"},
+                    {4, 1, "n_elites"}, {4, 257, "n_elites"}, {5, 0, "max_trials"}, {8, 16, "discrete_mask"}};
+                for (const auto &c : bad_cem) {
+                    vf_cem_config b = good;
+                    int32_t words[9];       // the nine leading int32 fields, nactions .. discrete_mask
+                    std::memcpy(words, &b, sizeof words);
+                    words[c.field] = c.value;
+                    std::memcpy(&b, words, sizeof words);
+                    if (vf_cem_workspace_bytes(&b) != 0 || std::string(vf_last_error()).find(c.msg) == std::string::npos) {
+                        std::fprintf(stderr, "vf_cem_workspace_bytes: want refusal '%s', got '%s'\n", c.msg, vf_last_error()); rc = 1;
+                    }
+                }
+                vf_cem_config neg = good;
+                neg.rej_lim[1] = -1.0;
+                if (vf_cem_workspace_bytes(&neg) != 0 || vf_cem_workspace_bytes(nullptr) != 0) rc = 1;
+                double *pd = reinterpret_cast<double *>(img);
+                int32_t *pi = reinterpret_cast<int32_t *>(img);
+                if (vf_cem_sample(0, &good, nullptr, 0, 4, img, pi, pi, nullptr) != VF_ERR_INVALID) rc = 1;
+                if (vf_cem_sample(0, &good, odd, 0, 4, img, pi, pi, nullptr) != VF_ERR_INVALID) rc = 1;
+                if (vf_cem_sample(0, &good, p, 0, 0, img, pi, pi, nullptr) != VF_ERR_INVALID) rc = 1;
+                if (vf_cem_sample(0, &good, p, 0, 4097, img, pi, pi, nullptr) != VF_ERR_INVALID) rc = 1;
+                if (vf_cem_sample(-1, &good, p, 0, 4, img, pi, pi, nullptr) != VF_ERR_INVALID) rc = 1;
+                if (vf_cem_sample(0, &good, p, 0, 4, img, pi, pi, nullptr) != VF_ERR_HIP) rc = 1;      // all through: this build launches nothing
+                if (vf_cem_refit(0, &good, pd, img, 9, pi, pd, img, p, nullptr) != VF_ERR_INVALID) rc = 1;     // fewer candidates than elites
+                if (vf_cem_refit(0, &good, pd, img, 4097, pi, pd, img, p, nullptr) != VF_ERR_INVALID) rc = 1;
+                if (vf_cem_refit(0, &good, nullptr, img, 10, pi, pd, img, p, nullptr) != VF_ERR_INVALID) rc = 1;
+                if (vf_cem_refit(0, &good, pd, img, 10, pi, pd, img, p, nullptr) != VF_ERR_HIP) rc = 1;
+                std::printf("  device CEM: configuration and argument refusals: %s\n", rc ? "FAILED" : "ok");
+            }
             int32_t pix[2] = {0, 0};
             float out2[2];
             struct { vf_handle *h; int H, W; const float *cur; int ntask, region, clip; const char *msg; } reg[] = {

@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(_HERE)
 LIB_PATH = os.environ.get('VF_LIBRARY') or os.path.join(_HERE, 'libvf_hip.so')     # override: experiments only
 SOURCES = [os.path.join(_HERE, 'csrc', f) for f in
-           ('vf_engine.hip', 'vf_conv_mfma.h', 'vf_conv_gsplit.h', 'vf_small_kernels.h', 'vf_goal_image.h', 'vf_plan_render.h', 'vf_resize.h', 'vf_net_conv.h',
+           ('vf_engine.hip', 'vf_conv_mfma.h', 'vf_conv_gsplit.h', 'vf_small_kernels.h', 'vf_goal_image.h', 'vf_plan_render.h', 'vf_resize.h', 'vf_cem.h', 'vf_net_conv.h',
             'vf_frame_scorer.h', 'vf_engine_sidenet.inc', 'vf_engine_scorer.inc', 'vf_registration_net.h', 'vf_engine_regnet.inc', 'vf_inverse_model.h', 'vf_engine_invmodel.inc', 'vf_persistent.h',
             'vf_conv_bf16x6.h', 'vf_conv_bf16.h', 'vf_fused_top.h', 'vf_fc_tile.h', 'vf_conv_first.h', 'vf_savp3.h', 'vf_engine_savp3.inc')] + \
           [os.path.join(REPO, 'include', 'vf_hip.h')]
@@ -31,7 +31,8 @@ EXPORTS = ('vf_abi_version', 'vf_last_error', 'vf_weight_count', 'vf_create', 'v
            'vf_scorer_scores',
            'vf_regnet_weight_count', 'vf_regnet_create', 'vf_regnet_destroy', 'vf_regnet_load_weights', 'vf_regnet_flow',
            'vf_invmodel_weight_count', 'vf_invmodel_create', 'vf_invmodel_destroy', 'vf_invmodel_load_weights',
-           'vf_invmodel_infer', 'vf_debug_lstm_layer', 'vf_register_hw', 'vf_resize_area')
+           'vf_invmodel_infer', 'vf_debug_lstm_layer', 'vf_register_hw', 'vf_resize_area',
+           'vf_cem_workspace_bytes', 'vf_cem_refit', 'vf_cem_sample')
 ABI_VERSION = 7
 
 
@@ -52,6 +53,13 @@ class VfScorerConfig(ctypes.Structure):
 
 class VfRegnetConfig(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ('height', 'width', 'ncam', 'ch_mult', 'max_pairs', 'device')]
+
+
+class VfCemConfig(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ('nactions', 'repeat', 'adim', 'tail', 'n_elites', 'max_trials', 'rejection',
+                                              'zero_first', 'discrete_mask')] + \
+               [('seed_lo', ctypes.c_uint32), ('seed_hi', ctypes.c_uint32), ('reserved', ctypes.c_int32)] + \
+               [(n, ctypes.c_double * 8) for n in ('rej_lim', 'trunc_lim', 'tail_value')]
 
 
 class VfInvModelConfig(ctypes.Structure):
@@ -147,6 +155,11 @@ def load_library():
     lib.vf_register.argtypes = [P, P, P, P, P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, P, P, P, P, P]
     lib.vf_register_hw.argtypes = [P, ctypes.c_int32, ctypes.c_int32] + lib.vf_register.argtypes[1:]
     lib.vf_resize_area.argtypes = [ctypes.c_int32, P, P] + [ctypes.c_int32] * 7 + [P]
+    lib.vf_cem_workspace_bytes.restype = ctypes.c_size_t
+    lib.vf_cem_workspace_bytes.argtypes = [ctypes.POINTER(VfCemConfig)]
+    lib.vf_cem_refit.argtypes = [ctypes.c_int32, ctypes.POINTER(VfCemConfig), P, P, ctypes.c_int32, P, P, P, P, P]
+    lib.vf_cem_sample.argtypes = [ctypes.c_int32, ctypes.POINTER(VfCemConfig), P, ctypes.c_uint32, ctypes.c_int32, P, P, P, P]
+    lib.vf_cem_refit.restype = lib.vf_cem_sample.restype = ctypes.c_int
     lib.vf_allgather_scores.argtypes = [P, P, P, ctypes.c_int32, P, P]
     lib.vf_comm_init_all.argtypes = [ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(P)]
     lib.vf_comm_destroy.argtypes = [P]

@@ -42,6 +42,7 @@
 #include "vf_inverse_model.h"
 #include "vf_plan_render.h"
 #include "vf_resize.h"
+#include "vf_cem.h"
 #include "vf_conv_bf16x6.h"
 #include "vf_conv_bf16.h"
 #include "vf_persistent.h"
@@ -2505,6 +2506,67 @@ static int resize_area_check(int32_t device, const void *d_src, const void *d_ds
     return VF_OK;
 }
 
+// the refusals of vf_cem_workspace_bytes / vf_cem_refit / vf_cem_sample (host work only, as above)
+static int cem_config_check(const vf_cem_config *c, const char *who) {
+    const std::string w(who);
+    if (!c) return fail(VF_ERR_INVALID, w + ": null cfg");
+    if (c->nactions < 1 || c->repeat < 1 || c->adim < 1 || c->tail < 0 || c->adim + c->tail > kCemMaxWidth)
+        return fail(VF_ERR_INVALID, w + ": need nactions >= 1, repeat >= 1, adim >= 1, tail >= 0 and adim + tail <= 8");
+    if ((long long)c->nactions * c->adim > kCemMaxD)
+        return fail(VF_ERR_INVALID, w + ": D = nactions * adim = " + std::to_string((long long)c->nactions * c->adim) + " exceeds 128");
+    if ((long long)c->nactions * c->repeat > (1 << 16))
+        return fail(VF_ERR_INVALID, w + ": T = nactions * repeat exceeds 2^16");
+    if (c->n_elites < 2 || c->n_elites > kCemMaxK)
+        return fail(VF_ERR_INVALID, w + ": n_elites = " + std::to_string(c->n_elites) + " outside 2..256");
+    if (c->max_trials < 1) return fail(VF_ERR_INVALID, w + ": max_trials = " + std::to_string(c->max_trials) + ", need at least 1");
+    if (c->discrete_mask < 0 || c->discrete_mask >= (1 << c->adim))
+        return fail(VF_ERR_INVALID, w + ": discrete_mask names a column past adim");
+    for (int i = 0; i < c->adim; ++i)
+        if (!(c->rej_lim[i] >= 0.0) || !(c->trunc_lim[i] >= 0.0))
+            return fail(VF_ERR_INVALID, w + ": rej_lim and trunc_lim must be >= 0 (+inf = none)");
+    return VF_OK;
+}
+static CemParams cem_params(const vf_cem_config &c, int M) {
+    CemParams p = {};
+    p.nactions = c.nactions; p.repeat = c.repeat; p.adim = c.adim; p.tail = c.tail;
+    p.K = c.n_elites; p.M = M;
+    p.max_trials = c.max_trials; p.rejection = c.rejection != 0; p.zero_first = c.zero_first != 0;
+    p.discrete_mask = c.discrete_mask;
+    p.seed_lo = c.seed_lo; p.seed_hi = c.seed_hi;
+    for (int i = 0; i < kCemMaxWidth; ++i) {
+        p.rej_lim[i] = c.rej_lim[i]; p.trunc_lim[i] = c.trunc_lim[i]; p.tail_value[i] = c.tail_value[i];
+    }
+    return p;
+}
+static int cem_refit_check(int32_t device, const vf_cem_config *cfg, const double *d_scores, const float *d_actions, int32_t M,
+                           const int32_t *d_elite_index, const double *d_elite_score, const float *d_elite_plans,
+                           const void *d_workspace) {
+    if (int rc = cem_config_check(cfg, "vf_cem_refit")) return rc;
+    if (device < 0) return fail(VF_ERR_INVALID, "vf_cem_refit: device = " + std::to_string(device) + " is negative");
+    if (!d_scores || !d_actions || !d_elite_index || !d_elite_score || !d_elite_plans || !d_workspace)
+        return fail(VF_ERR_INVALID, "vf_cem_refit: null argument");
+    if (reinterpret_cast<uintptr_t>(d_workspace) % 16) return fail(VF_ERR_INVALID, "vf_cem_refit: d_workspace must be 16-byte aligned");
+    if (M < cfg->n_elites || M > kCemMaxM)
+        return fail(VF_ERR_INVALID, "vf_cem_refit: M = " + std::to_string(M) + " outside n_elites.." + std::to_string(kCemMaxM));
+    return VF_OK;
+}
+static int cem_sample_check(int32_t device, const vf_cem_config *cfg, const void *d_workspace, int32_t M, const float *d_actions,
+                            const int32_t *d_trials, const int32_t *d_capped) {
+    if (int rc = cem_config_check(cfg, "vf_cem_sample")) return rc;
+    if (device < 0) return fail(VF_ERR_INVALID, "vf_cem_sample: device = " + std::to_string(device) + " is negative");
+    if (!d_workspace || !d_actions || !d_trials || !d_capped) return fail(VF_ERR_INVALID, "vf_cem_sample: null argument");
+    if (reinterpret_cast<uintptr_t>(d_workspace) % 16) return fail(VF_ERR_INVALID, "vf_cem_sample: d_workspace must be 16-byte aligned");
+    if (M < 1 || M > kCemMaxM)
+        return fail(VF_ERR_INVALID, "vf_cem_sample: M = " + std::to_string(M) + " outside 1.." + std::to_string(kCemMaxM));
+    return VF_OK;
+}
+extern "C" size_t vf_cem_workspace_bytes(const vf_cem_config *cfg) {
+    VF_API_TRY
+    if (cem_config_check(cfg, "vf_cem_workspace_bytes")) return 0;
+    return cem_workspace_bytes(cfg->nactions * cfg->adim, cfg->n_elites);
+    VF_API_CATCH(size_t)
+}
+
 // the refusals of vf_register, and of vf_register_hw: the same and the caller's size
 static int register_check(const vf_handle *h, const float *d_current, const float *d_reference, const float *d_flow,
                           const int32_t *d_pix, int32_t ntask, int32_t region, int32_t clip_sub, const float *d_desig,
@@ -2824,6 +2886,21 @@ extern "C" int vf_register_hw(vf_handle *h, int32_t H, int32_t W, const float *d
     VF_API_TRY
     if (int rc = register_hw_check(h, H, W, d_current, d_reference, d_flow, d_pix, ntask, region, clip_sub, d_desig, d_err))
         return rc;
+    return fail(VF_ERR_HIP, "the host self-test build launches nothing");
+    VF_API_CATCH(int)
+}
+extern "C" int vf_cem_refit(int32_t device, const vf_cem_config *cfg, const double *d_scores, const float *d_actions, int32_t M,
+                            int32_t *d_elite_index, double *d_elite_score, float *d_elite_plans, void *d_workspace, void *) {
+    VF_API_TRY      // (refusal paths only, as above)
+    if (int rc = cem_refit_check(device, cfg, d_scores, d_actions, M, d_elite_index, d_elite_score, d_elite_plans, d_workspace))
+        return rc;
+    return fail(VF_ERR_HIP, "the host self-test build launches nothing");
+    VF_API_CATCH(int)
+}
+extern "C" int vf_cem_sample(int32_t device, const vf_cem_config *cfg, const void *d_workspace, uint32_t, int32_t M,
+                             float *d_actions, int32_t *d_trials, int32_t *d_capped, void *) {      // (refusal paths only, as above)
+    VF_API_TRY
+    if (int rc = cem_sample_check(device, cfg, d_workspace, M, d_actions, d_trials, d_capped)) return rc;
     return fail(VF_ERR_HIP, "the host self-test build launches nothing");
     VF_API_CATCH(int)
 }
@@ -3443,6 +3520,38 @@ int vf_resize_area(int32_t device, const void *d_src, void *d_dst, int32_t dtype
     const ResizeParams p = {d_src, d_dst, Hs, Ws, C, Hd, Wd, 1, 1, 0, 1};
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     return dtype == 0 ? launch_resize<uint8_t>(p, n, st) : launch_resize<float>(p, n, st);
+    VF_API_CATCH(int)
+}
+
+int vf_cem_refit(int32_t device, const vf_cem_config *cfg, const double *d_scores, const float *d_actions, int32_t M,
+                 int32_t *d_elite_index, double *d_elite_score, float *d_elite_plans, void *d_workspace, void *stream) {
+    VF_API_TRY
+    if (int rc = cem_refit_check(device, cfg, d_scores, d_actions, M, d_elite_index, d_elite_score, d_elite_plans, d_workspace))
+        return rc;
+    VF_HIP_CHECK(hipSetDevice(device));
+    CemParams p = cem_params(*cfg, M);
+    p.scores = d_scores; p.actions_in = d_actions;
+    p.elite_index = d_elite_index; p.elite_score = d_elite_score; p.elite_plans = d_elite_plans;
+    p.workspace = d_workspace;
+    hipLaunchKernelGGL(cem_refit_kernel, dim3(1), dim3(kCemThreads), 0, reinterpret_cast<hipStream_t>(stream), p);
+    VF_HIP_CHECK(hipGetLastError());
+    return VF_OK;
+    VF_API_CATCH(int)
+}
+
+int vf_cem_sample(int32_t device, const vf_cem_config *cfg, const void *d_workspace, uint32_t call, int32_t M,
+                  float *d_actions, int32_t *d_trials, int32_t *d_capped, void *stream) {
+    VF_API_TRY
+    if (int rc = cem_sample_check(device, cfg, d_workspace, M, d_actions, d_trials, d_capped)) return rc;
+    VF_HIP_CHECK(hipSetDevice(device));
+    CemParams p = cem_params(*cfg, M);
+    p.call = call;
+    p.actions_out = d_actions; p.trials = d_trials; p.capped = d_capped;
+    p.workspace = const_cast<void *>(d_workspace);
+    hipLaunchKernelGGL(cem_sample_kernel, dim3((M + kCemWaves - 1) / kCemWaves), dim3(kCemThreads), 0,
+                       reinterpret_cast<hipStream_t>(stream), p);
+    VF_HIP_CHECK(hipGetLastError());
+    return VF_OK;
     VF_API_CATCH(int)
 }
 

@@ -113,7 +113,8 @@ class CEMBaseController(Policy):
             assert scores.shape == (candidates.shape[0],), "score shape should be (n_actions,)"
             self.plan_stat['scores_itr{}'.format(itr)] = scores
 
-            self._best_indices = scores.argsort()[:n_elite]
+            select = getattr(self._sampler, 'select_elites', None)      # a sampler may define the order of the elites
+            self._best_indices = select(scores, n_elite) if select else scores.argsort()[:n_elite]
             self._best_actions = candidates[self._best_indices]
 
             if itr + 1 < self._n_iter:      # refit on the elites (without the appended constants)

@@ -105,6 +105,13 @@ class EnsembleHipPredictor(object):
         with m0._scoring_call(actions):
             return m0._prepare(context, actions)
 
+    def score_device_refusal(self):
+        """Why ``score_device`` cannot serve the ensemble (``HipVPredEvaluation.score_device_refusal``)."""
+        return 'score_device rolls the actions as they lie on the device: the ensemble prepares its sequences on the host'
+
+    def score_device(self, context, actions_dev, goal_pix, finalweight=10., only_take_first_view=False, task_weights=None):
+        raise ValueError(self.score_device_refusal())
+
     def score(self, context, inputs, goal_pix, finalweight=10., only_take_first_view=False, task_weights=None):
         """Ensemble cost of every action: (scores[M], scores_per_task[M, ncam*nd]) float64, as
         ``HipVPredEvaluation.score``.  ``last_cost_per_step`` [M, ncam*nd, T] holds the per-step ensemble cost

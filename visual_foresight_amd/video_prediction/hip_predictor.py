@@ -513,7 +513,10 @@ class HipVPredEvaluation(object):
         ntask = self.n_cam * self.cfg.ndesig
         nd = self.n_draws
         self._set_context(context)
-        local = torch.from_numpy(np.ascontiguousarray(seqs, dtype=np.float32)).to(self.device)
+        if torch.is_tensor(seqs):       # score_device: the sequences already lie on this device
+            local = seqs
+        else:
+            local = torch.from_numpy(np.ascontiguousarray(seqs, dtype=np.float32)).to(self.device)
         scores = torch.empty(n, dtype=torch.float64, device=self.device)
         per_task = torch.empty((n, ntask), dtype=torch.float64, device=self.device)
         bs = self.run_batch_size // nd          # actions per chunk
@@ -568,6 +571,49 @@ class HipVPredEvaluation(object):
 
         rows_np = score_rows(self, seqs, M, 1 + self.n_cam * self.cfg.ndesig, rows_of)
         return pixel_cost_columns(rows_np, only_take_first_view)
+
+    def score_device_refusal(self):
+        """Why ``score_device`` cannot serve this predictor, or None when it can (a planner asks before it commits a planning
+        call to the device route)."""
+        if self.frames_only:
+            return ('score_device needs pixel distributions; this predictor is frames-only (designated_pixel_count 0 / '
+                    'no_pix_distrib)')
+        if self._lanes:
+            return 'score_device drives one engine: this predictor has %d in-process lanes (n_gpus > 1)' % len(self._lanes)
+        if _dist_info()[1] > 1:
+            return 'score_device drives one engine: torch.distributed has %d ranks' % _dist_info()[1]
+        if type(self)._prepare is not HipVPredEvaluation._prepare or self.n_draws != 1:
+            return 'score_device rolls the actions as they lie on the device: %s prepares its sequences on the host' \
+                   % type(self).__name__
+        return None
+
+    def score_device(self, context, actions_dev, goal_pix, finalweight=10., only_take_first_view=False, task_weights=None):
+        """``score`` without the gather: roll ``actions_dev`` - a contiguous float32 tensor ``[M, T, adim]`` on this engine's
+        device - and return the device float64 ``scores [M]``.  Only enqueues (the context upload aside, when it changed);
+        the caller checks the downloaded scores with ``_check_scores``.  Chunked by ``run_batch_size`` like ``score``; the last
+        chunk stays resident for ``render_plans`` / ``fetch_pixel_distributions``, and ``actions_dev`` must stay untouched for
+        as long as those may be asked for.  The per-task scores of the call are kept in ``last_per_task_dev`` ``[M, tasks]``.
+        ValueError: lanes, a ``torch.distributed`` world, sequences prepared on the host, a frames-only engine."""
+        reason = self.score_device_refusal()
+        if reason:
+            raise ValueError(reason)
+        torch = self._torch
+        T = self.sequence_length - self.n_context
+        if not torch.is_tensor(actions_dev) or actions_dev.device != self.device or actions_dev.dtype != torch.float32 \
+                or not actions_dev.is_contiguous() or tuple(actions_dev.shape[1:]) != (T, self.cfg.adim) \
+                or actions_dev.shape[0] < 1:
+            raise ValueError('actions_dev must be a contiguous float32 tensor [M, %d, %d] on %s'
+                             % (T, self.cfg.adim, self.device))
+        M = int(actions_dev.shape[0])
+        self._last_prepared = (context, actions_dev, M)
+        with torch.cuda.device(self.device):
+            scores, per_task = self._score_prepared(context, actions_dev, M, goal_pix, finalweight, index_base=0,
+                                                    task_weights=task_weights)
+            if only_take_first_view:        # task 0 alone is the score (pixel_cost_columns)
+                per_task = per_task[:, :1]
+                scores = per_task[:, 0].contiguous()
+        self.last_per_task_dev = per_task
+        return scores
 
     def _refuse_frames_only(self, what):
         if self.frames_only:
@@ -859,7 +905,10 @@ class HipVPredEvaluation(object):
         n = len(indices)
         rows = (np.asarray(indices, dtype=np.int64)[:, None] * nd + np.arange(nd)[None]).reshape(-1)
         self._set_context(ctx_p)
-        seq = torch.from_numpy(np.ascontiguousarray(np.asarray(seqs)[rows], dtype=np.float32)).to(self.device)
+        if torch.is_tensor(seqs):       # the last call was score_device: its sequences never left the device
+            seq = seqs[torch.from_numpy(rows).to(self.device)].contiguous()
+        else:
+            seq = torch.from_numpy(np.ascontiguousarray(np.asarray(seqs)[rows], dtype=np.float32)).to(self.device)
         # (a frames-only rollout writes no pixel scores: zeros stand in, the failure word is read instead)
         scores = (torch.zeros if self.frames_only else torch.empty)(n, dtype=torch.float64, device=self.device)
         per_task = torch.empty((n, ntask), dtype=torch.float64, device=self.device)
