@@ -20,12 +20,14 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <cstdlib>
 #include <string>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include <dlfcn.h>
@@ -131,12 +133,60 @@ struct TensorDesc {
 };
 
 static int a_of(const vf_config &c) { return c.adim + c.sdim; }
-// arch 0, layer_spec 2: appearance-flow compositing (cdna_arch.py transformation='flow')
-static bool is_flow(const vf_config &c) { return c.arch == 0 && c.layer_spec == 2; }
-// arch 0, layer_spec 3: DNA compositing - a 5x5 kernel per pixel from a 1x1 head (dna_arch.py)
-static bool is_dna(const vf_config &c) { return c.arch == 0 && c.layer_spec == 3; }
-// arch 0, layer_spec 4: STP compositing - nine affine warps per sample from a two-layer FC head (stp_arch.py)
-static bool is_stp(const vf_config &c) { return c.arch == 0 && c.layer_spec == 4; }
+
+// ------------------------------------------------------------------ the compositing modes
+// What a compositing mode (CompMode, vf_small_kernels.h) is, once: the tensor table, validate, the MAC count, cdna_create,
+// vf_load_weights, emit_rollout and vf_selftest_schedule read a row of kCompSpecs where they would ask which mode this is.
+// What is code of a mode's own stays a `switch (h->comp)`: the STP finish parameters (emit_rollout) and what the self-test
+// demands of a compositing phase.  Which kernel runs a mode: rollout_for / composite_for, below.
+static const int kByArch = -1;          // a count the mode leaves to the architecture: num_masks (arch 0 / 1: 10, arch 2: 6)
+struct CompSpec {
+    int layer_spec;                     // the vf_config.layer_spec of arch 0 that selects the mode (comp_mode_of)
+    const char *article, *name;         // "an" "appearance-flow" table / schedule, in messages
+    int num_masks;                      // the num_masks it demands, or kByArch ...
+    const char *transforms;             // ... and how its refusal counts them
+    bool fp32_only;                     // built for precision 0 only
+    bool rgb;                           // an rgb head (the scratch image) next to the mask head
+    const char *head; int head_n;       // the head tensors <head>/w, <head>/b (ViewData::w_head / b_head) and their width; null: none
+    int head_in;                        // rows of <head>/w; 0: a 1x1 conv over the top's features, run by the compositing itself
+    const char *fc; int fc_kern;        // the FC tensors <fc>/w, <fc>/b (the plan h->fc; <fc>/b in ViewData::b_fc), null: no FC item,
+                                        // and the plan's width in kernels of kTaps columns.  fc_part has nsplit such rows a sample.
+    int kern_n;                         // floats per sample of BatchView::kern; 0: no such table, the compositing reads the head
+    int fin;                            // the phase type of the finish item that writes it behind the FC; -1: none
+    int K;                              // CompositeParams::K
+    int warps; bool gather;             // the MAC count: warps per pixel and channel, of four bilinear taps (gather) or kTaps
+};
+static_assert(kStpHidden == 4 * kTaps, "the first FC of the STP head is planned as four kernels' taps");
+static constexpr CompSpec kCompSpecs[4] = {
+    // COMP_CDNA (cdna_arch.py; savp_arch.py): an FC predicts num_masks 5x5 kernels per sample, cdna_finalize normalises them.
+    // arch 2: the FOUR CDNA kernels of the published generator (the engine pads them to its num_masks = 6 slots at load)
+    {0, "a", "CDNA", kByArch, nullptr, /*fp32_only*/ false, /*rgb*/ true, /*head*/ nullptr, 0, 0, /*fc*/ "cdna", kByArch,
+     /*kern_n*/ kByArch, PH_CDNA_FIN, /*K*/ kByArch, /*warps*/ kByArch, false},
+    // COMP_FLOW, arch 0 with layer_spec 2 (cdna_arch.py transformation='flow'): the survey widths with the appearance-flow head
+    // in place of the CDNA FC - flow/w [1][1][32][2 * kFlowWarps], flow/b where cdna/w, cdna/b sat.  No CDNA FC (its plan
+    // exists, nothing is packed or run), no b_fc, no kernels: rows of no elements, one unused element in all.
+    {2, "an", "appearance-flow", kByArch, nullptr, /*fp32_only*/ true, /*rgb*/ true, /*head*/ "flow", 2 * kFlowWarps, 0,
+     /*fc*/ nullptr, kByArch, /*kern_n*/ 0, -1, /*K*/ kFlowWarps + 1, /*warps*/ kFlowWarps, true},
+    // COMP_DNA, arch 0 with layer_spec 3 (dna_arch.py): the survey widths with the DNA head - a 5x5 kernel per pixel from a 1x1
+    // head, dna/w [1][1][32][kTaps], dna/b where cdna/w, cdna/b sat; no rgb head (the DNA table has no scratch image), two mask
+    // channels (num_masks = 1).  No CDNA FC, no kernel table (a DNA engine never runs the FC: its unused plan is sized as the
+    // cdna table's).
+    {3, "a", "DNA", 1, "one transform", /*fp32_only*/ true, /*rgb*/ false, /*head*/ "dna", kTaps, 0, /*fc*/ nullptr, 10,
+     /*kern_n*/ 0, -1, /*K*/ 1, /*warps*/ 1, false},
+    // COMP_STP, arch 0 with layer_spec 4 (stp_arch.py): the survey widths with the STP head - nine affine warps per sample from
+    // a two-layer FC head: stp_fc/w [fc_in][kStpHidden], stp_fc/b where cdna/w, cdna/b sat, then stp/w [kStpHidden][6 *
+    // kStpWarps], stp/b.  The FC plan runs the head's first layer (kStpHidden sums per split); a finish item per sample
+    // (PH_STP_FIN) writes nine 6-float transforms where the kernel table sits.
+    {4, "an", "STP", kStpWarps + 1, "nine transforms", /*fp32_only*/ true, /*rgb*/ true, /*head*/ "stp", kStpRow * kStpWarps,
+     kStpHidden, /*fc*/ "stp_fc", kStpHidden / kTaps, /*kern_n*/ kStpRow * kStpWarps, PH_STP_FIN, /*K*/ kStpWarps + 1,
+     /*warps*/ kStpWarps, true},
+};
+// arch 1, arch 2 and the public decoder table (arch 0, layer_spec 1) compose as the CDNA table does (arch 3: vf_engine_savp3.inc)
+static CompMode comp_mode_of(const vf_config &c) {
+    for (int m = COMP_FLOW; m <= COMP_STP; ++m)
+        if (c.arch == 0 && c.layer_spec == kCompSpecs[m].layer_spec) return (CompMode)m;
+    return COMP_CDNA;
+}
 
 // arch 3 (the published SAVP generator): vf_engine_savp3.inc
 struct Savp3;
@@ -176,13 +226,9 @@ static std::vector<TensorDesc> tensor_table(const vf_config &c) {
     // arch 0 with layer_spec = 1: the decoder widths of the PUBLIC CDNA prediction_model (arXiv:1605.07157's code keeps the
     // concatenated width through its transposed convs: convt2 96 -> 96, convt3 64 -> 64, so lstm7 reads 96 + 32 channels and
     // the heads 64); layer_spec = 0: the widths of SURVEY row a14 (convt2 96 -> 64, convt3 64 -> 32)
-    // arch 0 with layer_spec = 2: the survey widths with the appearance-flow head in place of the CDNA FC (cdna_arch.py
-    // transformation='flow'): flow/w [1][1][32][2 * kFlowWarps], flow/b where cdna/w, cdna/b sat
-    // arch 0 with layer_spec = 3: the survey widths with the DNA head (dna_arch.py): no rgb head, two mask channels
-    // (num_masks = 1), dna/w [1][1][32][kTaps], dna/b where cdna/w, cdna/b sat
-    // arch 0 with layer_spec = 4: the survey widths with the STP head (stp_arch.py): stp_fc/w [fc_in][kStpHidden], stp_fc/b
-    // where cdna/w, cdna/b sat, then stp/w [kStpHidden][6 * kStpWarps], stp/b
-    const bool pub = c.arch == 0 && c.layer_spec == 1, flow = is_flow(c), dna = is_dna(c), stp = is_stp(c);
+    // arch 0 with layer_spec = 2 / 3 / 4: the survey widths with another compositing mode's heads (kCompSpecs)
+    const bool pub = c.arch == 0 && c.layer_spec == 1;
+    const CompSpec &cs = kCompSpecs[comp_mode_of(c)];
     const int c_t2 = pub ? L[5] + L[1] : L[5], c_top = pub ? L[6] + 32 : 32;
     if (savp) { conv("enc00", 5, 5, 3, kEnc00Ch); ln("lna", kEnc00Ch); }
     conv("enc0", 5, 5, savp ? kEnc00Ch : 3, 32); ln("ln1", 32);
@@ -200,21 +246,12 @@ static std::vector<TensorDesc> tensor_table(const vf_config &c) {
     conv("lstm7", 5, 5, c_t2 + cc + L[6], 4 * L[6]); ln("ln8", L[6]);
     conv("convt3", 3, 3, L[6] + 32, c_top);     ln("ln9", c_top);
     if (savp) { conv("convt4", 3, 3, 32 + kEnc00Ch, 32); ln("lnb", 32); }
-    if (!dna) conv("rgb", 1, 1, c_top, 3);
+    if (cs.rgb) conv("rgb", 1, 1, c_top, 3);
     conv("masks", 1, 1, c_top, K + 1);
-    // arch 2: the FOUR CDNA kernels of the published generator (the engine pads them to its num_masks = 6 slots at load)
-    const int KF = c.arch == 2 ? K - 2 : K;
-    if (flow) conv("flow", 1, 1, c_top, 2 * kFlowWarps);
-    else if (dna) conv("dna", 1, 1, c_top, kTaps);
-    else if (stp) {
-        add("stp_fc/w", {fc_in, kStpHidden});
-        add("stp_fc/b", {kStpHidden});
-        add("stp/w", {kStpHidden, kStpRow * kStpWarps});
-        add("stp/b", {kStpRow * kStpWarps});
-    } else {
-        add("cdna/w", {fc_in, kTaps * KF});
-        add("cdna/b", {kTaps * KF});
-    }
+    auto dense = [&](const std::string &n, int rows, int cols) { add(n + "/w", {rows, cols}); add(n + "/b", {cols}); };
+    if (cs.fc) dense(cs.fc, fc_in, kTaps * (cs.fc_kern != kByArch ? cs.fc_kern : (c.arch == 2 ? K - 2 : K)));
+    if (cs.head && cs.head_in) dense(cs.head, cs.head_in, cs.head_n);
+    else if (cs.head) conv(cs.head, 1, 1, c_top, cs.head_n);
     add("state/w", {a, c.sdim});
     add("state/b", {c.sdim});
     return t;
@@ -531,8 +568,8 @@ struct ViewData {
     float *ln_g[kNumLn] = {nullptr}, *ln_b[kNumLn] = {nullptr};    // ln1..ln9, lna (enc00), lnb (convt4)
     float *w_rgb = nullptr, *b_rgb = nullptr, *w_mask = nullptr, *b_mask = nullptr;
     float *w_state = nullptr, *b_state = nullptr, *w_sa = nullptr, *b_fc = nullptr;
-    float *w_flow = nullptr, *b_flow = nullptr;     // appearance-flow engines: the flow head (no CDNA FC, no b_fc); DNA engines:
-                                                    // the dna head; STP engines: stp/w, stp/b (b_fc holds stp_fc/b there)
+    float *w_head = nullptr, *b_head = nullptr;     // the head of the compositing mode (CompSpec::head: flow, dna or stp), if any;
+                                                    // b_fc: the bias of its FC (CompSpec::fc: cdna/b or stp_fc/b), if any
     float *w_cond[7] = {nullptr};       // arch 2: conditioning rows of every conv-LSTM's weights, [25][adim + sdim][4C]
     float *ctx_frames = nullptr, *ctx_distrib = nullptr;
 };
@@ -547,13 +584,8 @@ struct vf_handle {
     vf::Savp3 *s3 = nullptr;            // vf_config.arch == 3: the published SAVP generator (vf_engine_savp3.inc)
     bool cond = false;                  // vf_config.arch == 2: [action, latent, state] conditions every conv-LSTM
                                         // ... through per-sample border-class biases (BatchView::cond_bias)
-    bool flow = false;                  // arch 0, layer_spec 2: appearance-flow compositing - no CDNA FC, no kernels; the flow
-                                        // kernels (composite_flow_kernel, rollout_flow_kernel) run in place of the CDNA ones
-    bool dna = false;                   // arch 0, layer_spec 3: DNA compositing - no CDNA FC, no kernel table, no rgb head; the
-                                        // head lives in ViewData::w_flow / b_flow; composite_dna_kernel, rollout_dna_kernel run
-    bool stp = false;                   // arch 0, layer_spec 4: STP compositing - the FC plan runs the head's first layer, a finish
-                                        // item per sample (PH_STP_FIN) writes nine affine transforms where the kernel table
-                                        // sits; composite_stp_kernel, rollout_stp_kernel run
+    CompMode comp = COMP_CDNA;          // comp_mode_of(cfg): what the mode has and runs is its row of kCompSpecs, which kernels
+                                        // run it rollout_for / composite_for
     int Hc, Wc;                         // input size of the three-scale conv-LSTM core (H, W; arch 1: H/2, W/2)
     int c_t2 = 64, c_top = 32;          // output channels of convt2 / convt3 (arch 0, layer_spec 1 - the public table: 96 / 64)
     int ncam = 1, n_draws = 1;
@@ -737,19 +769,12 @@ static int validate(const vf_config *c) {
                                     "(appearance-flow compositing), 3 (DNA compositing) or 4 (STP compositing); 0 otherwise");
     if (c->arch == 0 && c->layer_spec == 1 && c->precision != 0)
         return fail(VF_ERR_INVALID, "the public decoder table (arch 0, layer_spec 1) is built for precision 0 (exact fp32) only");
-    if (is_flow(*c) && c->precision != 0)
-        return fail(VF_ERR_INVALID, "the appearance-flow table (arch 0, layer_spec 2) is built for precision 0 (exact fp32) only");
-    if (is_dna(*c)) {
-        if (c->precision != 0)
-            return fail(VF_ERR_INVALID, "the DNA table (arch 0, layer_spec 3) is built for precision 0 (exact fp32) only");
-        if (c->num_masks != 1)
-            return fail(VF_ERR_INVALID, "the DNA table (arch 0, layer_spec 3) has one transform: num_masks must be 1");
-    } else if (is_stp(*c)) {
-        if (c->precision != 0)
-            return fail(VF_ERR_INVALID, "the STP table (arch 0, layer_spec 4) is built for precision 0 (exact fp32) only");
-        if (c->num_masks != 10)
-            return fail(VF_ERR_INVALID, "the STP table (arch 0, layer_spec 4) has nine transforms: num_masks must be 10");
-    } else if (c->arch == 2 ? c->num_masks != 6 : c->num_masks != 10)
+    const CompSpec &cs = kCompSpecs[comp_mode_of(*c)];
+    const std::string table = std::string("the ") + cs.name + " table (arch 0, layer_spec " + std::to_string(cs.layer_spec) + ")";
+    if (cs.fp32_only && c->precision != 0) return fail(VF_ERR_INVALID, table + " is built for precision 0 (exact fp32) only");
+    if (cs.num_masks != kByArch && c->num_masks != cs.num_masks)
+        return fail(VF_ERR_INVALID, table + " has " + cs.transforms + ": num_masks must be " + std::to_string(cs.num_masks));
+    if (cs.num_masks == kByArch && (c->arch == 2 ? c->num_masks != 6 : c->num_masks != 10))
         return fail(VF_ERR_INVALID, "num_masks must be 10 (arch 0 / 1), 6 (arch 2: four CDNA warps + previous + first + scratch) or 4 (arch 3)");
     if (c->max_batch < 1) return fail(VF_ERR_INVALID, "max_batch must be >= 1");
     if (c->precision < 0 || c->precision > 2)
@@ -821,6 +846,34 @@ static int allow_lds(K kernel, size_t bytes) {
 }
 
 #ifndef VF_HOST_SELFTEST
+// ---- which kernel runs a compositing mode with ND designated pixels: the one place that pairs (mode, ND) with a kernel name.
+// ND 0 is the frames-only kernel of the mode.  The run-time lookups are generated from the two selectors, so the allow_lds
+// loop of configure_kernels and the launches cannot list different kernels.  (The tables are built mode by mode, ND 1..4 within
+// a mode: an instance is compiled where a table first names it, and the code object lists its kernels in that order.)
+typedef void (*RolloutKernel)(const PhaseDesc *, Schedule);
+typedef void (*CompositeKernel)(CompositeParams);
+static const int kCompRows = 5;         // rows of the lookups: the four modes, and CDNA with the six masks of arch 2
+struct RolloutKernelOf { template <int MODE, int ND> static constexpr RolloutKernel get() {
+    if constexpr (MODE == COMP_CDNA) { if constexpr (ND == 0) return &rollout_frames_kernel; else return &rollout_persistent_kernel<ND>; }
+    else if constexpr (MODE == COMP_FLOW) { if constexpr (ND == 0) return &rollout_flow_frames_kernel; else return &rollout_flow_kernel<ND>; }
+    else if constexpr (MODE == COMP_DNA) { if constexpr (ND == 0) return &rollout_dna_frames_kernel; else return &rollout_dna_kernel<ND>; }
+    else { static_assert(MODE == COMP_STP, "no such compositing mode"); if constexpr (ND == 0) return &rollout_stp_frames_kernel; else return &rollout_stp_kernel<ND>; }
+} };
+// ROW: a mode, or kCompRows - 1 for COMP_CDNA with K = 6 (arch 2: four CDNA warps + previous + first frame + scratch)
+struct CompositeKernelOf { template <int ROW, int ND> static constexpr CompositeKernel get() {
+    constexpr int K = ROW == kCompRows - 1 ? 6 : 10;
+    if constexpr (ROW == COMP_CDNA || ROW == kCompRows - 1) { if constexpr (ND == 0) return &composite_frames_kernel<K>; else return &composite_kernel<ND, K>; }
+    else if constexpr (ROW == COMP_FLOW) { if constexpr (ND == 0) return &composite_flow_frames_kernel; else return &composite_flow_kernel<ND>; }
+    else if constexpr (ROW == COMP_DNA) { if constexpr (ND == 0) return &composite_dna_frames_kernel; else return &composite_dna_kernel<ND>; }
+    else { static_assert(ROW == COMP_STP, "no such compositing mode"); if constexpr (ND == 0) return &composite_stp_frames_kernel; else return &composite_stp_kernel<ND>; }
+} };
+// [row][ND 0..kMaxDesig] of a selector, row by row
+template <class Of, int... I>
+static constexpr auto kernel_table(std::integer_sequence<int, I...>) {
+    return std::array<decltype(Of::template get<0, 0>()), sizeof...(I)>{Of::template get<I / (kMaxDesig + 1), I % (kMaxDesig + 1)>()...};
+}
+static RolloutKernel rollout_for(int mode, int nd);     // (defined behind configure_kernels, for that order)
+
 static int configure_kernels(vf_handle *h) {
     const size_t n = h->max_lds;
     int rc;
@@ -846,27 +899,15 @@ static int configure_kernels(vf_handle *h) {
     if ((rc = allow_lds(&ew_kernel<3>, ew_lds_bytes(EW_TOP3, 3)))) return rc;
     if ((rc = allow_lds(&ew_kernel<4>, ew_lds_bytes(EW_TOP3, 4)))) return rc;
     const size_t np = n + kCtlWords * sizeof(int);
-    if ((rc = allow_lds(&rollout_persistent_kernel<1>, np))) return rc;
-    if ((rc = allow_lds(&rollout_persistent_kernel<2>, np))) return rc;
-    if ((rc = allow_lds(&rollout_persistent_kernel<3>, np))) return rc;
-    if ((rc = allow_lds(&rollout_persistent_kernel<4>, np))) return rc;
-    if ((rc = allow_lds(&rollout_flow_kernel<1>, np))) return rc;
-    if ((rc = allow_lds(&rollout_flow_kernel<2>, np))) return rc;
-    if ((rc = allow_lds(&rollout_flow_kernel<3>, np))) return rc;
-    if ((rc = allow_lds(&rollout_flow_kernel<4>, np))) return rc;
-    if ((rc = allow_lds(&rollout_dna_kernel<1>, np))) return rc;
-    if ((rc = allow_lds(&rollout_dna_kernel<2>, np))) return rc;
-    if ((rc = allow_lds(&rollout_dna_kernel<3>, np))) return rc;
-    if ((rc = allow_lds(&rollout_dna_kernel<4>, np))) return rc;
-    if ((rc = allow_lds(&rollout_stp_kernel<1>, np))) return rc;
-    if ((rc = allow_lds(&rollout_stp_kernel<2>, np))) return rc;
-    if ((rc = allow_lds(&rollout_stp_kernel<3>, np))) return rc;
-    if ((rc = allow_lds(&rollout_stp_kernel<4>, np))) return rc;
-    if ((rc = allow_lds(&rollout_stp_frames_kernel, np))) return rc;
-    if ((rc = allow_lds(&rollout_frames_kernel, np))) return rc;
-    if ((rc = allow_lds(&rollout_flow_frames_kernel, np))) return rc;
-    if ((rc = allow_lds(&rollout_dna_frames_kernel, np))) return rc;
+    for (int mode = COMP_CDNA; mode <= COMP_STP; ++mode)
+        for (int nd = 0; nd <= kMaxDesig; ++nd)
+            if ((rc = allow_lds(rollout_for(mode, nd), np))) return rc;
     return VF_OK;
+}
+
+static RolloutKernel rollout_for(int mode, int nd) {
+    static constexpr auto table = kernel_table<RolloutKernelOf>(std::make_integer_sequence<int, (COMP_STP + 1) * (kMaxDesig + 1)>());
+    return table[mode * (kMaxDesig + 1) + nd];
 }
 
 template <int G, int EPI, int MREP>
@@ -1211,28 +1252,15 @@ double vf_macs_per_sample_step(const vf_config *cfg) {
         if (!d) continue;               // arch 0 has no enc00 / convt4
         macs += (double)r.h * r.w * d->shape[0] * d->shape[1] * d->shape[2] * d->shape[3];
     }
-    const TensorDesc *fc = find_tensor(t, is_stp(*cfg) ? "stp_fc/w" : "cdna/w"), *sw = find_tensor(t, "state/w");
+    const CompSpec &cs = kCompSpecs[comp_mode_of(*cfg)];
+    const TensorDesc *sw = find_tensor(t, "state/w");
     macs += (double)sw->shape[0] * sw->shape[1];
-    if (is_flow(*cfg)) {        // the flow head, and four bilinear taps per warp and channel in place of the FC and the 5 x 5 warps
-        const TensorDesc *fw = find_tensor(t, "flow/w");
-        macs += (double)HF * WF * fw->shape[2] * fw->shape[3];
-        macs += (double)HF * WF * 4 * (3 + cfg->ndesig) * kFlowWarps;
-        return macs;
-    }
-    if (is_dna(*cfg)) {         // the DNA head, and one 5 x 5 kernel per pixel in place of the FC and the mixed CDNA kernels
-        const TensorDesc *dw = find_tensor(t, "dna/w");
-        macs += (double)HF * WF * dw->shape[2] * dw->shape[3];
-        macs += (double)HF * WF * kTaps * (3 + cfg->ndesig);
-        return macs;
-    }
-    if (is_stp(*cfg)) {         // the two FC layers of the head, and four bilinear taps per warp and channel
-        const TensorDesc *w2 = find_tensor(t, "stp/w");
-        macs += (double)fc->shape[0] * fc->shape[1] + (double)w2->shape[0] * w2->shape[1];
-        macs += (double)HF * WF * 4 * (3 + cfg->ndesig) * kStpWarps;
-        return macs;
-    }
-    macs += (double)fc->shape[0] * fc->shape[1];
-    macs += (double)HF * WF * kTaps * (3 + cfg->ndesig) * (cfg->arch == 2 ? cfg->num_masks - 2 : cfg->num_masks);
+    // the mode's FC (per sample) and head (a second FC per sample, or a 1x1 conv per pixel) ...
+    if (cs.fc) macs += (double)find_tensor(t, std::string(cs.fc) + "/w")->size();
+    if (cs.head) macs += (double)find_tensor(t, std::string(cs.head) + "/w")->size() * (cs.head_in ? 1.0 : (double)HF * WF);
+    // ... and its warps: four bilinear taps (flow, STP) or the 25 of a 5 x 5 kernel (CDNA: the sample's, mixed; DNA: one per pixel)
+    const int warps = cs.warps != kByArch ? cs.warps : (cfg->arch == 2 ? cfg->num_masks - 2 : cfg->num_masks);
+    macs += (double)HF * WF * (cs.gather ? 4 : kTaps) * (3 + cfg->ndesig) * warps;
     return macs;
     VF_API_CATCH(double)
 }
@@ -1290,12 +1318,11 @@ static int cdna_create(vf_handle *h) {
     init_layer(h->lstm[6], "lstm7", PACK_LSTM, H2, W2, H2, W2, 5, 5, 1, 2, h->c_t2, L[6], L[6], true, false, 128, cfg->precision, false, ccond);
     init_layer(h->convt3, "convt3", PACK_CONVT, H2, W2, H2, W2, 2, 2, 1, 1, L[6], 32, h->c_top, true, false, 128, 0, true);
     // CDNA FC as a K-split GEMM over 1x1 "images"
-    static_assert(kStpHidden == 4 * kTaps, "the first FC of the STP head is planned as four kernels' taps");
-    if (h->stp) plan_fc(h, H8 * W8 * L[4], kStpHidden / kTaps, "stp_fc");
-    else plan_fc(h, H8 * W8 * L[4], h->dna ? 10 : h->K);     // (a DNA engine never runs the FC: its unused plan is sized as the cdna table's)
+    const CompSpec &cs = kCompSpecs[h->comp];
+    plan_fc(h, H8 * W8 * L[4], cs.fc_kern != kByArch ? cs.fc_kern : h->K, cs.fc ? cs.fc : "cdna");
     h->layers = {&h->enc0, &h->lstm[0], &h->lstm[1], &h->enc1, &h->lstm[2], &h->lstm[3], &h->enc2, &h->enc3,
                  &h->lstm[4], &h->convt1, &h->lstm[5], &h->convt2, &h->lstm[6], &h->convt3};
-    if (!h->flow && !h->dna) h->layers.push_back(&h->fc);   // (a flow / DNA engine has no CDNA FC: the plan above exists, nothing is packed or run)
+    if (cs.fc) h->layers.push_back(&h->fc);     // (a mode without an FC: the plan above exists, nothing is packed or run)
     if (h->savp) { h->layers.push_back(&h->enc00); h->layers.push_back(&h->convt4); }
     h->small_plans = cfg->precision == 0;   // the split-bf16 and plain-bf16 tiles have 128 rows only
     for (int k = 0; k < 7; ++k) {
@@ -1351,13 +1378,8 @@ static int cdna_create(vf_handle *h) {
         VF_ALLOC(vd.w_mask, h->c_top * (h->K + 1)); VF_ALLOC(vd.b_mask, h->K + 1);
         VF_ALLOC(vd.w_state, (size_t)nsa * cfg->sdim); VF_ALLOC(vd.b_state, cfg->sdim);
         VF_ALLOC(vd.w_sa, (size_t)nsa * L[3]);
-        if (h->flow) { VF_ALLOC(vd.w_flow, (size_t)h->c_top * 2 * kFlowWarps); VF_ALLOC(vd.b_flow, 2 * kFlowWarps); }
-        else if (h->dna) { VF_ALLOC(vd.w_flow, (size_t)h->c_top * kTaps); VF_ALLOC(vd.b_flow, kTaps); }
-        else if (h->stp) {
-            VF_ALLOC(vd.b_fc, kStpHidden);
-            VF_ALLOC(vd.w_flow, (size_t)kStpHidden * kStpRow * kStpWarps); VF_ALLOC(vd.b_flow, kStpRow * kStpWarps);
-        }
-        else VF_ALLOC(vd.b_fc, kTaps * h->K);
+        if (cs.fc) VF_ALLOC(vd.b_fc, h->fc.n_valid);
+        if (cs.head) { VF_ALLOC(vd.w_head, (size_t)(cs.head_in ? cs.head_in : h->c_top) * cs.head_n); VF_ALLOC(vd.b_head, cs.head_n); }
         if (h->cond)
             for (int k = 0; k < 7; ++k) VF_ALLOC(vd.w_cond[k], (size_t)kTaps * nsa * 4 * L[k]);
     }
@@ -1388,10 +1410,9 @@ static int cdna_create(vf_handle *h) {
     row_spec(h, b.st_enc0, (size_t)h->enc0.stats_nparts * 2, true);
     row_spec(h, b.st_enc6, (size_t)h->convt3.stats_nparts * 2, false);
     row_spec(h, b.sbias, (size_t)h->enc3.Cout, true);
-    // (a flow / DNA engine computes no CDNA kernels: rows of no elements, one unused element in all)
-    // (an STP engine: the first FC's kStpHidden sums per split, and nine 6-float transforms where the kernels sit)
-    row_spec(h, b.fc_part, h->flow || h->dna ? 0 : (size_t)h->fc.nsplit * (h->stp ? kStpHidden : kTaps * h->K), false);
-    row_spec(h, b.kern, h->flow || h->dna ? 0 : (h->stp ? (size_t)kStpRow * kStpWarps : (size_t)kTaps * h->K), false);
+    // (a mode without an FC or a kernel table: rows of no elements, one unused element in all)
+    row_spec(h, b.fc_part, cs.fc ? (size_t)h->fc.nsplit * h->fc.n_valid : 0, false);
+    row_spec(h, b.kern, cs.kern_n != kByArch ? (size_t)cs.kern_n : (size_t)kTaps * h->K, false);
     if ((rc = alloc_common(h, 32))) return rc;          // (arch 2: up to 29 phases per step)
     h->shared_views.resize(NV);
     for (BatchView &sv : h->shared_views)
@@ -1426,9 +1447,7 @@ int vf_create(const vf_config *cfg, vf_handle **out) {
     h->blob_floats = h->table.back().offset + h->table.back().size();
     h->savp = cfg->arch == 1 || cfg->arch == 2;
     h->cond = cfg->arch == 2;
-    h->flow = is_flow(*cfg);
-    h->dna = is_dna(*cfg);
-    h->stp = is_stp(*cfg);
+    h->comp = comp_mode_of(*cfg);
     h->Hc = h->savp ? h->H / 2 : h->H; h->Wc = h->savp ? h->W / 2 : h->W;
     const int H = h->H, W = h->W;
     h->ntiles = ((H + kCompTile - 1) / kCompTile) * ((W + kCompTile - 1) / kCompTile);
@@ -1517,6 +1536,7 @@ int vf_load_weights(vf_handle *h, const float *blob_all, size_t n_floats) {
         return VF_OK;
     }
     auto T = [&](const std::string &name) { return find_tensor(h->table, name); };
+    const CompSpec &cs = kCompSpecs[h->comp];
     for (int view = 0; view < h->ncam; ++view) {
         const float *blob = blob_all + (size_t)view * h->blob_floats;
         ViewData &vd = h->views[view];
@@ -1524,7 +1544,7 @@ int vf_load_weights(vf_handle *h, const float *blob_all, size_t n_floats) {
             const ConvLayer &l = *lp;
             const TensorDesc *w = T(l.name + "/w"), *b = T(l.name + "/b");
             std::vector<float> wp, bp;
-            if (l.name == "cdna" && h->cond) {
+            if (lp == &h->fc && h->cond) {
                 // canonical [fc_in][25 x 4] -> the engine's [fc_in][25 x 6]: two dead kernels of zero weights (they meet a
                 // zero mask in the compositing), so every kernel-count-dependent stride stays num_masks
                 const int KF = h->K - 2, fc_in = w->shape[0];
@@ -1535,7 +1555,7 @@ int vf_load_weights(vf_handle *h, const float *blob_all, size_t n_floats) {
                             wide[((size_t)r * kTaps + tap) * h->K + k] = (blob + w->offset)[((size_t)r * kTaps + tap) * KF + k];
                 wp = pack_weights(l, wide.data(), 1, 1, fc_in, kTaps * h->K);
                 bp.assign(l.packed_b(), 0.f);
-            } else if (l.name == "cdna" || l.name == "stp_fc") {
+            } else if (lp == &h->fc) {
                 wp = pack_weights(l, blob + w->offset, 1, 1, w->shape[0], w->shape[1]);
                 bp.assign(l.packed_b(), 0.f);       // bias is added by cdna_finalize / stp_finalize
             } else if (l.name == "enc3") {
@@ -1569,7 +1589,7 @@ int vf_load_weights(vf_handle *h, const float *blob_all, size_t n_floats) {
             if ((rc = dev_write(h, vd.ln_b[i], blob + b->offset, b->size() * sizeof(float)))) return rc;
         }
         const TensorDesc *d;
-        if (!h->dna) {      // (the DNA table has no scratch image)
+        if (cs.rgb) {
             d = T("rgb/w");   if ((rc = dev_write(h, vd.w_rgb, blob + d->offset, d->size() * sizeof(float)))) return rc;
             d = T("rgb/b");   if ((rc = dev_write(h, vd.b_rgb, blob + d->offset, d->size() * sizeof(float)))) return rc;
         }
@@ -1602,26 +1622,20 @@ int vf_load_weights(vf_handle *h, const float *blob_all, size_t n_floats) {
         }
         d = T("state/w"); if ((rc = dev_write(h, vd.w_state, blob + d->offset, d->size() * sizeof(float)))) return rc;
         d = T("state/b"); if ((rc = dev_write(h, vd.b_state, blob + d->offset, d->size() * sizeof(float)))) return rc;
-        d = T("cdna/b");
-        if (h->flow) {
-            const TensorDesc *fw = T("flow/w"), *fb = T("flow/b");
-            if ((rc = dev_write(h, vd.w_flow, blob + fw->offset, fw->size() * sizeof(float)))) return rc;
-            if ((rc = dev_write(h, vd.b_flow, blob + fb->offset, fb->size() * sizeof(float)))) return rc;
-        } else if (h->dna) {
-            const TensorDesc *dw = T("dna/w"), *db = T("dna/b");
-            if ((rc = dev_write(h, vd.w_flow, blob + dw->offset, dw->size() * sizeof(float)))) return rc;
-            if ((rc = dev_write(h, vd.b_flow, blob + db->offset, db->size() * sizeof(float)))) return rc;
-        } else if (h->stp) {
-            const TensorDesc *fb = T("stp_fc/b"), *sw = T("stp/w"), *sb = T("stp/b");
-            if ((rc = dev_write(h, vd.b_fc, blob + fb->offset, fb->size() * sizeof(float)))) return rc;
-            if ((rc = dev_write(h, vd.w_flow, blob + sw->offset, sw->size() * sizeof(float)))) return rc;
-            if ((rc = dev_write(h, vd.b_flow, blob + sb->offset, sb->size() * sizeof(float)))) return rc;
-        } else if (h->cond) {
-            std::vector<float> bw((size_t)kTaps * h->K, 0.f);
-            for (int tap = 0; tap < kTaps; ++tap)
-                for (int k = 0; k < h->K - 2; ++k) bw[(size_t)tap * h->K + k] = (blob + d->offset)[(size_t)tap * (h->K - 2) + k];
-            if ((rc = dev_write(h, vd.b_fc, bw.data(), bw.size() * sizeof(float)))) return rc;
-        } else if ((rc = dev_write(h, vd.b_fc, blob + d->offset, d->size() * sizeof(float)))) return rc;
+        if (cs.fc) {        // the FC's bias, added by the finish item
+            d = T(std::string(cs.fc) + "/b");
+            if (h->cond) {  // (arch 2: padded to num_masks kernels as the FC's weights above)
+                std::vector<float> bw((size_t)kTaps * h->K, 0.f);
+                for (int tap = 0; tap < kTaps; ++tap)
+                    for (int k = 0; k < h->K - 2; ++k) bw[(size_t)tap * h->K + k] = (blob + d->offset)[(size_t)tap * (h->K - 2) + k];
+                if ((rc = dev_write(h, vd.b_fc, bw.data(), bw.size() * sizeof(float)))) return rc;
+            } else if ((rc = dev_write(h, vd.b_fc, blob + d->offset, d->size() * sizeof(float)))) return rc;
+        }
+        if (cs.head) {
+            const TensorDesc *hw = T(std::string(cs.head) + "/w"), *hb = T(std::string(cs.head) + "/b");
+            if ((rc = dev_write(h, vd.w_head, blob + hw->offset, hw->size() * sizeof(float)))) return rc;
+            if ((rc = dev_write(h, vd.b_head, blob + hb->offset, hb->size() * sizeof(float)))) return rc;
+        }
         // enc3 rows [L3 .. L3+adim+sdim) x 64: the smeared action/state inputs
         d = T("enc3/w");
         const int L3 = kLstmSizes[3];
@@ -1693,6 +1707,7 @@ static int profile_end(vf_handle *h, hipStream_t st, double flops) {
     return VF_OK;
 }
 
+static CompositeKernel composite_for(int mode, int nd, int K);      // (defined behind LaunchSink, for the same reason)
 struct LaunchSink {
     vf_handle *h;
     hipStream_t st;
@@ -1772,24 +1787,7 @@ struct LaunchSink {
         return VF_OK;
     }
     int composite(const CompositeParams &p, int ntiles, int /*view*/, std::initializer_list<int>) {
-        dim3 grid(ntiles, p.B);
-        if (h->stp) {                   // STP: the transforms travel in the kernel table's field
-            if (p.ND == 0) hipLaunchKernelGGL(composite_stp_frames_kernel, grid, dim3(256), 0, st, p);
-            else with_nd(p.ND, [&](auto nd) { hipLaunchKernelGGL(composite_stp_kernel<decltype(nd)::value>, grid, dim3(256), 0, st, p); });
-        } else if (p.ND == 0) {         // frames-only engines: one kernel per compositing mode (vf_small_kernels.h)
-            if (p.w_flow && p.K == 1) hipLaunchKernelGGL(composite_dna_frames_kernel, grid, dim3(256), 0, st, p);
-            else if (p.w_flow) hipLaunchKernelGGL(composite_flow_frames_kernel, grid, dim3(256), 0, st, p);
-            else if (p.K == 6) hipLaunchKernelGGL(composite_frames_kernel<6>, grid, dim3(256), 0, st, p);
-            else hipLaunchKernelGGL(composite_frames_kernel<10>, grid, dim3(256), 0, st, p);
-        } else if (p.w_flow && p.K == 1) {     // DNA: the per-pixel kernel head travels in the flow head's fields
-            with_nd(p.ND, [&](auto nd) { hipLaunchKernelGGL(composite_dna_kernel<decltype(nd)::value>, grid, dim3(256), 0, st, p); });
-        } else if (p.w_flow) {         // appearance flow
-            with_nd(p.ND, [&](auto nd) { hipLaunchKernelGGL(composite_flow_kernel<decltype(nd)::value>, grid, dim3(256), 0, st, p); });
-        } else if (p.K == 6) {         // arch 2: four CDNA warps + previous + first frame + scratch
-            with_nd(p.ND, [&](auto nd) { hipLaunchKernelGGL((composite_kernel<decltype(nd)::value, 6>), grid, dim3(256), 0, st, p); });
-        } else {
-            with_nd(p.ND, [&](auto nd) { hipLaunchKernelGGL((composite_kernel<decltype(nd)::value, 10>), grid, dim3(256), 0, st, p); });
-        }
+        hipLaunchKernelGGL(composite_for(h->comp, p.ND, p.K), dim3(ntiles, p.B), dim3(256), 0, st, p);
         VF_HIP_CHECK(hipGetLastError());
         return VF_OK;
     }
@@ -1801,6 +1799,12 @@ struct LaunchSink {
     }
     static bool failed(int rc) { return rc != VF_OK; }
 };
+
+// the per-layer compositing kernel of a mode (CompositeKernelOf, in front of configure_kernels)
+static CompositeKernel composite_for(int mode, int nd, int K) {
+    static constexpr auto table = kernel_table<CompositeKernelOf>(std::make_integer_sequence<int, kCompRows * (kMaxDesig + 1)>());
+    return table[(mode == COMP_CDNA && K == 6 ? kCompRows - 1 : mode) * (kMaxDesig + 1) + nd];
+}
 #endif
 
 struct ScheduleSink {
@@ -1998,6 +2002,7 @@ static int emit_rollout(vf_handle *h, int view, const BatchView &v, const BatchV
                         const int32_t *goal_pix, Sink &sink, bool skip_shared) {
     const vf_config &c = h->cfg;
     const ViewData &vd = h->views[view];
+    const CompSpec &cs = kCompSpecs[h->comp];
     const int H = h->H, W = h->W, ND = h->ND, nc = c.n_context;
     const BatchView &base = h->base;        // (names the buffer whose elements per sample h->per() returns)
     auto params = [&](const ConvLayer &l, int Bp, const SegArg &s0, const SegArg *s1) {
@@ -2247,7 +2252,7 @@ static int emit_rollout(vf_handle *h, int view, const BatchView &v, const BatchV
         // (An appearance-flow engine has no kernels: neither item is emitted, and the top depends on its two inputs alone.
         // A DNA engine likewise: its kernels come from a head of the top itself.)
         int u_fin = -1, u_fc = -1;
-        if (produce && !h->flow && !h->dna) {
+        if (produce && cs.fc) {
             SegArg flat = h5n;      // same LayerNorm, viewed as [B][1][1][H8*W8*128]
             const ConvLayer &fc_l = Sink::fc_plan(h);
             p = params(fc_l, B, flat, nullptr);
@@ -2266,18 +2271,22 @@ static int emit_rollout(vf_handle *h, int view, const BatchView &v, const BatchV
             const int now[7] = {u_l1, u_l2, u_l3, u_l4, u_l5, u_l6, u_l7};
             for (int k = 0; k < 7; ++k) u_prev[k] = now[k];
         }
-        if (produce && !h->flow && !h->dna) {      // the (tiny) finalise step of the CDNA kernels: behind lstm7, by when the FC has long finished
-            if (h->stp) {       // STP: relu, the second FC and the nine transforms in pixel units, where the kernels would sit
-                StpFinParams sp2; memset(&sp2, 0, sizeof(sp2));
-                sp2.partial = v.fc_part; sp2.nsplit = h->fc.nsplit; sp2.B = B;
-                sp2.bias = vd.b_fc; sp2.w2 = vd.w_flow; sp2.b2 = vd.b_flow; sp2.theta = v.kern;
-                sp2.H = H; sp2.W = W;
-                u_fin = sink.stp_fin(sp2, {u_fc});
-            } else {
-                FinParams fp;
-                fp.partial = v.fc_part; fp.nsplit = h->fc.nsplit; fp.B = B; fp.K = h->K;
-                fp.bias = vd.b_fc; fp.kern = v.kern;
-                u_fin = sink.fin(fp, {u_fc});
+        if (produce && cs.fin >= 0) {      // the (tiny) finalise step of the CDNA kernels: behind lstm7, by when the FC has long finished
+            switch (h->comp) {
+                case COMP_STP: {    // STP: relu, the second FC and the nine transforms in pixel units, where the kernels would sit
+                    StpFinParams sp2; memset(&sp2, 0, sizeof(sp2));
+                    sp2.partial = v.fc_part; sp2.nsplit = h->fc.nsplit; sp2.B = B;
+                    sp2.bias = vd.b_fc; sp2.w2 = vd.w_head; sp2.b2 = vd.b_head; sp2.theta = v.kern;
+                    sp2.H = H; sp2.W = W;
+                    u_fin = sink.stp_fin(sp2, {u_fc});
+                    break;
+                }
+                default: {
+                    FinParams fp;
+                    fp.partial = v.fc_part; fp.nsplit = h->fc.nsplit; fp.B = B; fp.K = h->K;
+                    fp.bias = vd.b_fc; fp.kern = v.kern;
+                    u_fin = sink.fin(fp, {u_fc});
+                }
             }
             if (Sink::failed(u_fin)) return u_fin;
         }
@@ -2312,7 +2321,7 @@ static int emit_rollout(vf_handle *h, int view, const BatchView &v, const BatchV
             }
             cp.ln_inv_n = (float)(1.0 / ((double)H * W * h->c_top));
             cp.CF = h->c_top;
-            if (!h->dna) { cp.w_rgb = vd.w_rgb; cp.b_rgb = vd.b_rgb; }
+            if (cs.rgb) { cp.w_rgb = vd.w_rgb; cp.b_rgb = vd.b_rgb; }
             cp.w_mask = vd.w_mask; cp.b_mask = vd.b_mask;
             // Appearance flow: the warps gather from the WHOLE previous frame / distributions of the sample.  Both routes of the
             // top are released by this step's first conv (top_early), every tile of which waited for EVERY compositing tile of
@@ -2320,7 +2329,7 @@ static int emit_rollout(vf_handle *h, int view, const BatchView &v, const BatchV
             // DNA: every tap lies inside the tile's halo, as for CDNA, so the CDNA dependency rules hold as they are.
             // STP: both - the top waits for the sample's finish item (u_fin) as a CDNA top does, and its affine warps gather from
             // the whole previous frame as the flow warps do; cp.kern is the table of transforms.
-            if (h->flow || h->dna) { cp.w_flow = vd.w_flow; cp.b_flow = vd.b_flow; }
+            if (cs.kern_n == 0) { cp.w_head = vd.w_head; cp.b_head = vd.b_head; }
             else cp.kern = v.kern;
             // (frames-only: the tile neither reads nor writes a distribution or a block sum - step_io leaves them null)
             cp.prev_frame = io.frame; cp.prev_frame_bstride = io.frame_bs;
@@ -2603,6 +2612,7 @@ extern "C" int vf_selftest_schedule(vf_handle *h, int32_t B, int32_t skip_shared
                                     uint64_t *out_upload_checksum) {
     VF_API_TRY
     if (!h) return fail(VF_ERR_INVALID, "null handle");
+    const CompSpec &cs = kCompSpecs[h->comp];
     BuiltSchedule bs;
     int rc = build_schedule(h, B, skip_shared != 0, bs);
     if (rc) return rc;
@@ -2612,13 +2622,12 @@ extern "C" int vf_selftest_schedule(vf_handle *h, int32_t B, int32_t skip_shared
         if (P.first_ticket != ticket || P.n_items <= 0) return fail(VF_ERR_INVALID, "tickets are not contiguous");
         ticket += P.n_items;
         if (P.ndep < 0 || P.ndep > kMaxDeps) return fail(VF_ERR_INVALID, "bad dependency count");
-        if ((h->flow || h->dna) && (P.type == PH_FC_PARTIAL || P.type == PH_CDNA_FIN))
-            return fail(VF_ERR_INVALID, "phase " + std::to_string(i) + ": a CDNA kernel item in " +
-                                        (h->dna ? "a DNA schedule" : "an appearance-flow schedule"));
+        if (!cs.fc && (P.type == PH_FC_PARTIAL || P.type == PH_CDNA_FIN))
+            return fail(VF_ERR_INVALID, "phase " + std::to_string(i) + ": a CDNA kernel item in " + cs.article + " " + cs.name + " schedule");
         // an STP schedule finishes its parameters with PH_STP_FIN, never with the CDNA kernels' item - and nobody else does
-        if (h->stp ? P.type == PH_CDNA_FIN : P.type == PH_STP_FIN)
-            return fail(VF_ERR_INVALID, "phase " + std::to_string(i) + (h->stp ? ": a CDNA kernel-finish item (a 5 x 5 kernel table) in an STP schedule"
-                                                                              : ": an STP finish item outside an STP schedule"));
+        if ((P.type == PH_CDNA_FIN || P.type == PH_STP_FIN) && P.type != cs.fin)
+            return fail(VF_ERR_INVALID, "phase " + std::to_string(i) + (P.type == PH_CDNA_FIN ? ": a CDNA kernel-finish item (a 5 x 5 kernel table) in an STP schedule"
+                                                                                              : ": an STP finish item outside an STP schedule"));
         for (int d = 0; d < P.ndep; ++d) {
             // a dependency must point at the counters of a phase with smaller tickets
             bool found = false;
@@ -2744,32 +2753,36 @@ extern "C" int vf_selftest_schedule(vf_handle *h, int32_t B, int32_t skip_shared
             ok = ok && in_allocs(h, c.out_frame, ((size_t)(P.B - 1) * c.out_frame_bstride + hw * 3) * 4);
             ok = ok && in_allocs(h, c.out_distrib, ((size_t)(P.B - 1) * c.out_distrib_bstride + hw * c.ND) * 4);
             ok = ok && in_allocs(h, c.out_sums, (size_t)P.B * c.ND * h->nblocks * 2 * 8);
-            ok = ok && in_allocs(h, c.kern, h->stp ? (size_t)P.B * kStpRow * kStpWarps * 4 : (size_t)P.B * kTaps * c.K * 4);
-            if (h->stp) {
-                // an STP engine: the table of transforms in `kern`, no flow / dna head, the survey table's ten masks; the phase
-                // waits for the finish item that writes exactly that table (an affine warp needs its sample's parameters; the
-                // whole previous frame is complete through the step's first conv, as for appearance flow)
-                if (!c.kern) return fail(VF_ERR_INVALID, "phase " + std::to_string(i) + ": a compositing phase without the parameter table in an STP schedule");
-                if (c.w_flow || c.b_flow || c.first_frame || !c.w_rgb || !c.b_rgb || c.K != kStpWarps + 1 || c.CF != 32)
-                    return fail(VF_ERR_INVALID, "phase " + std::to_string(i) + ": a flow / dna head or another table's compositing in an STP schedule");
-                bool fin_dep = false, fin_table = false;
-                for (size_t j = 0; j < i; ++j) {
-                    const PhaseDesc &Q = bs.phases[j];
-                    if (Q.type != PH_STP_FIN || Q.stp.theta != c.kern) continue;
-                    fin_table = true;
-                    for (int d = 0; d < P.ndep; ++d) fin_dep = fin_dep || (P.dep[d].cnt_base == Q.cnt_base && P.dep[d].expect == 1);
+            ok = ok && in_allocs(h, c.kern, (size_t)P.B * (cs.kern_n != kByArch ? cs.kern_n : kTaps * c.K) * 4);
+            // a mode with a head of the compositing's own (no kernel table): the head instead of kernels, on the survey table only
+            const bool own_head = c.w_head && c.b_head && !c.kern && !c.first_frame && c.K == cs.K && c.CF == 32;
+            switch (h->comp) {
+                case COMP_STP: {
+                    // an STP engine: the table of transforms in `kern`, no flow / dna head, the survey table's ten masks; the phase
+                    // waits for the finish item that writes exactly that table (an affine warp needs its sample's parameters; the
+                    // whole previous frame is complete through the step's first conv, as for appearance flow)
+                    if (!c.kern) return fail(VF_ERR_INVALID, "phase " + std::to_string(i) + ": a compositing phase without the parameter table in an STP schedule");
+                    if (c.w_head || c.b_head || c.first_frame || !c.w_rgb || !c.b_rgb || c.K != cs.K || c.CF != 32)
+                        return fail(VF_ERR_INVALID, "phase " + std::to_string(i) + ": a flow / dna head or another table's compositing in an STP schedule");
+                    bool fin_dep = false, fin_table = false;
+                    for (size_t j = 0; j < i; ++j) {
+                        const PhaseDesc &Q = bs.phases[j];
+                        if (Q.type != PH_STP_FIN || Q.stp.theta != c.kern) continue;
+                        fin_table = true;
+                        for (int d = 0; d < P.ndep; ++d) fin_dep = fin_dep || (P.dep[d].cnt_base == Q.cnt_base && P.dep[d].expect == 1);
+                    }
+                    if (!fin_table) return fail(VF_ERR_INVALID, "phase " + std::to_string(i) + ": the kernel field of an STP compositing phase is not a table of transforms (a 5 x 5 kernel table?)");
+                    if (!fin_dep) return fail(VF_ERR_INVALID, "phase " + std::to_string(i) + ": an STP compositing phase without the finish dependency");
+                    break;
                 }
-                if (!fin_table) return fail(VF_ERR_INVALID, "phase " + std::to_string(i) + ": the kernel field of an STP compositing phase is not a table of transforms (a 5 x 5 kernel table?)");
-                if (!fin_dep) return fail(VF_ERR_INVALID, "phase " + std::to_string(i) + ": an STP compositing phase without the finish dependency");
+                case COMP_DNA:      // the per-pixel kernel head, no rgb head, one transform
+                    if (!(own_head && !c.w_rgb && !c.b_rgb))
+                        return fail(VF_ERR_INVALID, "phase " + std::to_string(i) + ": a compositing phase without the dna head in a DNA schedule");
+                    break;
+                case COMP_FLOW: ok = ok && own_head; break;
+                case COMP_CDNA: ok = ok && !c.w_head && !c.b_head && c.kern; break;
             }
-            // an appearance-flow engine: the flow head instead of kernels, on the survey table's compositing only
-            // a DNA engine: the per-pixel kernel head in the same two fields, no rgb head, one transform
-            const size_t head_n = h->dna ? kTaps : 2 * kFlowWarps;
-            if (h->dna && !(c.w_flow && c.b_flow && !c.kern && !c.first_frame && !c.w_rgb && !c.b_rgb && c.K == 1 && c.CF == 32))
-                return fail(VF_ERR_INVALID, "phase " + std::to_string(i) + ": a compositing phase without the dna head in a DNA schedule");
-            ok = ok && (h->dna || h->stp || (h->flow ? (c.w_flow && c.b_flow && !c.kern && !c.first_frame && c.K == kFlowWarps + 1 && c.CF == 32)
-                                                     : (!c.w_flow && !c.b_flow && c.kern)));
-            ok = ok && in_allocs(h, c.w_flow, (size_t)32 * head_n * 4) && in_allocs(h, c.b_flow, head_n * 4);
+            ok = ok && in_allocs(h, c.w_head, (size_t)32 * cs.head_n * 4) && in_allocs(h, c.b_head, cs.head_n * 4);
             ok = ok && in_allocs(h, c.first_frame, hw * 3 * 4) && in_allocs(h, c.first_distrib, hw * c.ND * 4);
         } else if (P.type == PH_SA) {
             ok = ok && in_allocs(h, P.sa.sbias, (size_t)P.B * P.sa.n_out * 4) && in_allocs(h, P.sa.action, 4) &&
@@ -2979,16 +2992,6 @@ static TaskWeights task_weights_of(const vf_handle *h, const float *task_weights
     return tw;
 }
 
-template <int ND>
-static int launch_persistent_t(const Schedule &sc, int mode, int grid, size_t lds, hipStream_t st) {
-    if (mode == COMP_STP) hipLaunchKernelGGL((rollout_stp_kernel<ND>), dim3(grid), dim3(kConvThreads), lds, st, sc.phases, sc);
-    else if (mode == COMP_DNA) hipLaunchKernelGGL((rollout_dna_kernel<ND>), dim3(grid), dim3(kConvThreads), lds, st, sc.phases, sc);
-    else if (mode == COMP_FLOW) hipLaunchKernelGGL((rollout_flow_kernel<ND>), dim3(grid), dim3(kConvThreads), lds, st, sc.phases, sc);
-    else hipLaunchKernelGGL((rollout_persistent_kernel<ND>), dim3(grid), dim3(kConvThreads), lds, st, sc.phases, sc);
-    VF_HIP_CHECK(hipGetLastError());
-    return VF_OK;
-}
-
 // the whole rollout (every view) as one persistent launch (vf_persistent.h)
 static int run_persistent(vf_handle *h, const float *d_actions, int B, const int32_t *goal_pix, hipStream_t st) {
     int rc;
@@ -3080,17 +3083,10 @@ static int run_persistent(vf_handle *h, const float *d_actions, int B, const int
     const int wgs_per_cu = std::min(h->persist_wgs_per_cu, by_lds);
     const int grid = std::min(sc_host.items, h->n_cu * wgs_per_cu);
     if (h->profiling && (rc = profile_begin(h, st))) return rc;
-    const int mode = h->stp ? COMP_STP : (h->dna ? COMP_DNA : (h->flow ? COMP_FLOW : COMP_CDNA));
-    if (h->ND == 0) {       // frames-only engines: kernels of their own names (vf_persistent.h)
-        if (mode == COMP_STP) hipLaunchKernelGGL(rollout_stp_frames_kernel, dim3(grid), dim3(kConvThreads), lds, st, sc.phases, sc);
-        else if (mode == COMP_DNA) hipLaunchKernelGGL(rollout_dna_frames_kernel, dim3(grid), dim3(kConvThreads), lds, st, sc.phases, sc);
-        else if (mode == COMP_FLOW) hipLaunchKernelGGL(rollout_flow_frames_kernel, dim3(grid), dim3(kConvThreads), lds, st, sc.phases, sc);
-        else hipLaunchKernelGGL(rollout_frames_kernel, dim3(grid), dim3(kConvThreads), lds, st, sc.phases, sc);
-        rc = hipGetLastError() == hipSuccess ? VF_OK : fail(VF_ERR_HIP, "launch of the frames-only rollout kernel failed");
-    } else {
-        rc = with_nd(h->ND, [&](auto nd) { return launch_persistent_t<decltype(nd)::value>(sc, mode, grid, lds, st); });
-    }
-    if (rc) return rc;
+    hipLaunchKernelGGL(rollout_for(h->comp, h->ND), dim3(grid), dim3(kConvThreads), lds, st, sc.phases, sc);
+    // (frames-only engines: kernels of their own names, vf_persistent.h)
+    if (h->ND == 0 && hipGetLastError() != hipSuccess) return fail(VF_ERR_HIP, "launch of the frames-only rollout kernel failed");
+    VF_HIP_CHECK(hipGetLastError());
     if (h->profiling && (rc = profile_end(h, st, sc_host.flops))) return rc;
     h->shared_valid = h->dedup;
     h->shared_cfg = cfg;

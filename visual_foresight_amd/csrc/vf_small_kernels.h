@@ -236,9 +236,9 @@ struct CompositeParams {
                                         // does not depend on them
     int CF;                             // feature channels of enc6: 0 / 32, or 64 (the public CDNA decoder table, cdna_arch.py
                                         // decoder='public': the stand-alone compositing tile only, two 32-channel rounds)
-    const float *w_flow, *b_flow;       // appearance-flow engines (cdna_arch.py transformation='flow'): the 1x1 flow head
-                                        // [32][2 * kFlowWarps], [2 * kFlowWarps]; null = CDNA kernels (`kern` is null there).
-                                        // DNA engines (dna_arch.py, K == 1) pass their 1x1 kernel head here: [32][kTaps], [kTaps]
+    const float *w_head, *b_head;       // the mode's own 1x1 head (`kern` is null there): appearance-flow engines (cdna_arch.py
+                                        // transformation='flow') the flow head [32][2 * kFlowWarps], [2 * kFlowWarps]; DNA engines
+                                        // (dna_arch.py, K == 1) the kernel head [32][kTaps], [kTaps].  Null = CDNA kernels / STP.
 };
 
 // LDS floats needed by composite_tile<ND, K>
@@ -455,7 +455,7 @@ __device__ __forceinline__ void composite_flow_heads(const PT &p, const float *f
     typedef const __attribute__((address_space(4))) float cfloat;
     auto as_const = [](const float *q) { return (cfloat *)(unsigned long long)q; };
     cfloat *gam_ = as_const(p.gamma), *bet_ = as_const(p.beta);
-    cfloat *wfl_ = as_const(p.w_flow), *bfl_ = as_const(p.b_flow);
+    cfloat *wfl_ = as_const(p.w_head), *bfl_ = as_const(p.b_head);
 #pragma unroll
     for (int j = 0; j < NF2; ++j) o_fl[j] = bfl_[j];
     const f32x4 *src = reinterpret_cast<const f32x4 *>(feat);
@@ -556,7 +556,7 @@ __device__ __forceinline__ void composite_pixel_values_flow(const PT &p, const i
 // relu-shifted and normalised they are that pixel's own 5x5 kernel over the previous frame and distributions - where the
 // CDNA path mixes the sample's nine kernels by its masks.  One transform, two mask channels (previous frame | transformed),
 // no scratch image.  The halo tile in LDS is the CDNA path's; the kernel table is not staged.  The head reaches the device
-// through CompositeParams::w_flow / b_flow ([32][kTaps], [kTaps]) with K == 1.
+// through CompositeParams::w_head / b_head ([32][kTaps], [kTaps]) with K == 1.
 //
 // The two mask sums and the 25 tap sums of one pixel: each its own fma chain over the channels ascending from the bias, on
 // f_c = relu(LN9(enc6)_c), as composite_heads builds its sums (27 live accumulators, one pass over the LDS feature row).
@@ -567,7 +567,7 @@ __device__ __forceinline__ void composite_dna_heads(const PT &p, const float *fe
     auto as_const = [](const float *q) { return (cfloat *)(unsigned long long)q; };
     cfloat *gam_ = as_const(p.gamma), *bet_ = as_const(p.beta);
     cfloat *wmask_ = as_const(p.w_mask), *bmask_ = as_const(p.b_mask);
-    cfloat *wdna_ = as_const(p.w_flow), *bdna_ = as_const(p.b_flow);
+    cfloat *wdna_ = as_const(p.w_head), *bdna_ = as_const(p.b_head);
 #pragma unroll
     for (int j = 0; j < 2; ++j) o_m[j] = bmask_[j];
 #pragma unroll
