@@ -9,7 +9,7 @@
  * the calling thread.  No exception crosses this boundary.  Every device buffer - packed
  * weights, activations, predictions, schedules - is sized from the config and allocated in
  * vf_create(); no later call allocates device memory (vf_load_weights refills the same
- * buffers).  vf_set_context / vf_rollout / vf_export / vf_register(_hw) / vf_resize_area / vf_cem_refit / vf_cem_sample / vf_allgather_scores only
+ * buffers).  vf_set_context / vf_rollout / vf_export / vf_register(_hw) / vf_resize_area / vf_cem_refit / vf_cem_sample / vf_cem_soft_refit / vf_cem_sample_corr / vf_allgather_scores only
  * enqueue work on the caller's HIP stream (hipStream_t passed as void*; NULL = the default
  * stream) and never synchronise it; a handle is driven from one stream at a time.
  * vf_load_weights, vf_device_status and the debug hooks are the blocking calls.
@@ -469,6 +469,45 @@ int vf_cem_refit(int32_t device, const vf_cem_config *cfg, const double *d_score
  * VF_ERR_INVALID (nothing launched): a NULL pointer, an invalid cfg, M outside 1..4096. */
 int vf_cem_sample(int32_t device, const vf_cem_config *cfg, const void *d_workspace, uint32_t call, int32_t M,
                   float *d_actions, int32_t *d_trials, int32_t *d_capped, void *stream);
+
+/* The same for the time-correlated noise proposal of the RoboNet-era experiments (reference
+ * visual_mpc/policy/cem_controllers/samplers/correlated_noise.py:10-80): i.i.d. normals through an AR(1) filter along the
+ * action steps, refitted by an exponentially weighted soft mean of the elites.  The arithmetic is specified by the float64
+ * class visual_foresight_amd/policy/cem_controllers/samplers/philox_correlated_sampler.py: the white normal of sample i at
+ * d = a * adim + c is normal d of the counter {block d / 4, 0, sample i, call}; shaped s_d = w_d * std[c] + bias[c], or with
+ * refit_cov after a refit y_k = sum_d w_d A[d][k], s_d = sum_k A[d][k] y_k (two fma chains from 0, d then k ascending);
+ * filtered o_a = (beta_0 * s_a) + (beta_1 * prev), prev = o_{a-1}, for a = 0 the unfiltered s_{nactions-1} or, with
+ * has_first_prev, first_prev[c]; a candidate is o, plus centre once the workspace holds one.  No repeat: T = nactions.
+ * D = nactions * adim <= 128, adim + tail <= 8, 1 <= n_elites <= 256 (2 with refit_cov).
+ * Workspace (caller-owned, vf_cem_corr_workspace_bytes, 16-byte aligned): int32 R, int32 centre_valid, int32 pad[2];
+ * double centre[D]; double mean[D]; double soft[n_elites]; with refit_cov double A[n_elites][D], A[d][k] at [k][d].
+ * The caller starts a planning call by zeroing the 16-byte header (any async copy on the same stream): centre invalid, R 0. */
+typedef struct vf_cem_corr_config {
+    int32_t nactions, adim, tail, n_elites;
+    int32_t refit_cov;          /* the refit also fits A, which then colours the noise in place of std and bias */
+    int32_t has_first_prev;     /* step 0 is smoothed against first_prev, not against the last noise step */
+    uint32_t seed_lo, seed_hi;
+    double kappa, beta_0, beta_1;
+    double std[8], bias[8];     /* per action column */
+    double first_prev[8];
+    double tail_value[8];       /* the constants written to columns adim .. adim + tail - 1 */
+} vf_cem_corr_config;
+
+/* Bytes of the workspace for cfg; 0 (and vf_last_error) for an invalid cfg. */
+size_t vf_cem_corr_workspace_bytes(const vf_cem_corr_config *cfg);
+
+/* Elites and soft refit.  Arguments and elite outputs as vf_cem_refit, with T = nactions.  Into the workspace:
+ * soft_k = exp(kappa * (score_0 - score_k)) in rank order, centre_d = (sum_k e_kd * soft_k) / (sum_k soft_k + 1e-4),
+ * centre_valid = 1 and, with refit_cov, R = n_elites, the plain mean and A as vf_cem_refit fits them (else R = 0).
+ * One kernel of one workgroup.  VF_ERR_INVALID (nothing launched): a NULL pointer, an invalid cfg, M outside the range. */
+int vf_cem_soft_refit(int32_t device, const vf_cem_corr_config *cfg, const double *d_scores, const float *d_actions,
+                      int32_t M, int32_t *d_elite_index, double *d_elite_score, float *d_elite_plans, void *d_workspace,
+                      void *stream);
+
+/* Draw M <= 4096 candidates as sampling call number `call`: d_actions [M][nactions][adim + tail] float32.  One wavefront per
+ * sample, no data-dependent loop.  VF_ERR_INVALID (nothing launched): a NULL pointer, an invalid cfg, M outside 1..4096. */
+int vf_cem_sample_corr(int32_t device, const vf_cem_corr_config *cfg, const void *d_workspace, uint32_t call, int32_t M,
+                       float *d_actions, void *stream);
 
 /* The one collective of multi-GPU planning: all-gather every rank's n_local score values (float64)
  * (n_local equal on all ranks: pad ragged shards) into d_all [world * n_local] with RCCL over

@@ -418,6 +418,38 @@ int main() {
                 if (vf_cem_refit(0, &good, nullptr, img, 10, pi, pd, img, p, nullptr) != VF_ERR_INVALID) rc = 1;
                 if (vf_cem_refit(0, &good, pd, img, 10, pi, pd, img, p, nullptr) != VF_ERR_HIP) rc = 1;
                 std::printf("  device CEM: configuration and argument refusals: %s\n", rc ? "FAILED" : "ok");
+                // the same for the correlated-noise proposal
+                vf_cem_corr_config corr = {10, 4, 0, 20, 0, 0, 1u, 2u, 1.0, 0.5, 0.5,
+                                           {0.05, 0.05, 0.2, 0.3}, {0}, {0}, {0}};
+                if (vf_cem_corr_workspace_bytes(&corr) != 16 + 8 * (2 * 40 + 20)) { std::fprintf(stderr, "vf_cem_corr_workspace_bytes: wrong size\n"); rc = 1; }
+                corr.refit_cov = 1;
+                if (vf_cem_corr_workspace_bytes(&corr) != 16 + 8 * (2 * 40 + 20 + 20 * 40)) { std::fprintf(stderr, "vf_cem_corr_workspace_bytes: wrong size with refit_cov\n"); rc = 1; }
+                struct { int field, value; const char *msg; } bad_corr[] = {
+                    {0, 0, "nactions"}, {0, 33, "exceeds 128"}, {1, 0, "adim"}, {2, 5, "adim + tail"}, {2, -1, "tail"},
+                    {3, 1, "n_elites"}, {3, 257, "n_elites"}};
+                for (const auto &c : bad_corr) {
+                    vf_cem_corr_config b = corr;
+                    int32_t words[4];       // the four leading int32 fields, nactions .. n_elites
+                    std::memcpy(words, &b, sizeof words);
+                    words[c.field] = c.value;
+                    std::memcpy(&b, words, sizeof words);
+                    if (vf_cem_corr_workspace_bytes(&b) != 0 || std::string(vf_last_error()).find(c.msg) == std::string::npos) {
+                        std::fprintf(stderr, "vf_cem_corr_workspace_bytes: want refusal '%s', got '%s'\n", c.msg, vf_last_error()); rc = 1;
+                    }
+                }
+                if (vf_cem_corr_workspace_bytes(nullptr) != 0) rc = 1;
+                if (vf_cem_sample_corr(0, &corr, nullptr, 0, 4, img, nullptr) != VF_ERR_INVALID) rc = 1;
+                if (vf_cem_sample_corr(0, &corr, odd, 0, 4, img, nullptr) != VF_ERR_INVALID) rc = 1;
+                if (vf_cem_sample_corr(0, &corr, p, 0, 0, img, nullptr) != VF_ERR_INVALID) rc = 1;
+                if (vf_cem_sample_corr(0, &corr, p, 0, 4097, img, nullptr) != VF_ERR_INVALID) rc = 1;
+                if (vf_cem_sample_corr(-1, &corr, p, 0, 4, img, nullptr) != VF_ERR_INVALID) rc = 1;
+                if (vf_cem_sample_corr(0, &corr, p, 0, 4, img, nullptr) != VF_ERR_HIP) rc = 1;         // all through: this build launches nothing
+                if (vf_cem_soft_refit(0, &corr, pd, img, 19, pi, pd, img, p, nullptr) != VF_ERR_INVALID) rc = 1;   // fewer candidates than elites
+                if (vf_cem_soft_refit(0, &corr, pd, img, 4097, pi, pd, img, p, nullptr) != VF_ERR_INVALID) rc = 1;
+                if (vf_cem_soft_refit(0, &corr, nullptr, img, 20, pi, pd, img, p, nullptr) != VF_ERR_INVALID) rc = 1;
+                if (vf_cem_soft_refit(0, &corr, pd, img, 20, pi, pd, img, odd, nullptr) != VF_ERR_INVALID) rc = 1;
+                if (vf_cem_soft_refit(0, &corr, pd, img, 20, pi, pd, img, p, nullptr) != VF_ERR_HIP) rc = 1;
+                std::printf("  device CEM, correlated noise: configuration and argument refusals: %s\n", rc ? "FAILED" : "ok");
             }
             int32_t pix[2] = {0, 0};
             float out2[2];

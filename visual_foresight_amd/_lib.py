@@ -32,7 +32,8 @@ EXPORTS = ('vf_abi_version', 'vf_last_error', 'vf_weight_count', 'vf_create', 'v
            'vf_regnet_weight_count', 'vf_regnet_create', 'vf_regnet_destroy', 'vf_regnet_load_weights', 'vf_regnet_flow',
            'vf_invmodel_weight_count', 'vf_invmodel_create', 'vf_invmodel_destroy', 'vf_invmodel_load_weights',
            'vf_invmodel_infer', 'vf_debug_lstm_layer', 'vf_register_hw', 'vf_resize_area',
-           'vf_cem_workspace_bytes', 'vf_cem_refit', 'vf_cem_sample')
+           'vf_cem_workspace_bytes', 'vf_cem_refit', 'vf_cem_sample',
+           'vf_cem_corr_workspace_bytes', 'vf_cem_soft_refit', 'vf_cem_sample_corr')
 ABI_VERSION = 7
 
 
@@ -60,6 +61,13 @@ class VfCemConfig(ctypes.Structure):
                                               'zero_first', 'discrete_mask')] + \
                [('seed_lo', ctypes.c_uint32), ('seed_hi', ctypes.c_uint32), ('reserved', ctypes.c_int32)] + \
                [(n, ctypes.c_double * 8) for n in ('rej_lim', 'trunc_lim', 'tail_value')]
+
+
+class VfCemCorrConfig(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ('nactions', 'adim', 'tail', 'n_elites', 'refit_cov', 'has_first_prev')] + \
+               [('seed_lo', ctypes.c_uint32), ('seed_hi', ctypes.c_uint32)] + \
+               [(n, ctypes.c_double) for n in ('kappa', 'beta_0', 'beta_1')] + \
+               [(n, ctypes.c_double * 8) for n in ('std', 'bias', 'first_prev', 'tail_value')]
 
 
 class VfInvModelConfig(ctypes.Structure):
@@ -160,6 +168,11 @@ def load_library():
     lib.vf_cem_refit.argtypes = [ctypes.c_int32, ctypes.POINTER(VfCemConfig), P, P, ctypes.c_int32, P, P, P, P, P]
     lib.vf_cem_sample.argtypes = [ctypes.c_int32, ctypes.POINTER(VfCemConfig), P, ctypes.c_uint32, ctypes.c_int32, P, P, P, P]
     lib.vf_cem_refit.restype = lib.vf_cem_sample.restype = ctypes.c_int
+    lib.vf_cem_corr_workspace_bytes.restype = ctypes.c_size_t
+    lib.vf_cem_corr_workspace_bytes.argtypes = [ctypes.POINTER(VfCemCorrConfig)]
+    lib.vf_cem_soft_refit.argtypes = [ctypes.c_int32, ctypes.POINTER(VfCemCorrConfig), P, P, ctypes.c_int32, P, P, P, P, P]
+    lib.vf_cem_sample_corr.argtypes = [ctypes.c_int32, ctypes.POINTER(VfCemCorrConfig), P, ctypes.c_uint32, ctypes.c_int32, P, P]
+    lib.vf_cem_soft_refit.restype = lib.vf_cem_sample_corr.restype = ctypes.c_int
     lib.vf_allgather_scores.argtypes = [P, P, P, ctypes.c_int32, P, P]
     lib.vf_comm_init_all.argtypes = [ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(P)]
     lib.vf_comm_destroy.argtypes = [P]

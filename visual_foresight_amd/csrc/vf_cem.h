@@ -1,4 +1,5 @@
-// vf_cem.h - one CEM iteration on the device: elite selection + Gaussian refit, and sampling of the next candidates.
+// vf_cem.h - one CEM iteration on the device: elite selection + refit, and sampling of the next candidates, for the Gaussian
+// proposal (first half) and for the time-correlated noise proposal (second half, which has its own header comment).
 //
 // Specification: visual_foresight_amd/policy/cem_controllers/samplers/philox_gaussian_sampler.py (a float64 NumPy class that
 // is a sampler in its own right).  These kernels compute its numbers: elite indices, trial counts, mean and A bit for bit;
@@ -62,12 +63,12 @@ __device__ __forceinline__ bool cem_before(double a, int i, double b, int j) {
     return a < b || (a == b && i < j);
 }
 
-VF_GLOBAL VF_LAUNCH_BOUNDS(kCemThreads) void cem_refit_kernel(const CemParams p) {
-    __shared__ double s_score[kCemMaxM];
-    __shared__ int s_elite[kCemMaxK];
+// The elites of scores [M] by counting (one workgroup, all of it): stages the scores in s_score [M], leaves the index of
+// rank k in s_elite[k] and writes elite_index / elite_score [K].  Returns behind a barrier.
+__device__ __forceinline__ void cem_select_elites(const double *scores, int M, int K, double *s_score, int *s_elite,
+                                                  int *elite_index, double *elite_score) {
     const int tid = threadIdx.x;
-    const int D = p.nactions * p.adim, T = p.nactions * p.repeat, W = p.adim + p.tail, K = p.K, M = p.M;
-    for (int i = tid; i < M; i += kCemThreads) s_score[i] = p.scores[i];
+    for (int i = tid; i < M; i += kCemThreads) s_score[i] = scores[i];
     __syncthreads();
     for (int i = tid; i < M; i += kCemThreads) {
         const double mine = s_score[i];
@@ -75,11 +76,19 @@ VF_GLOBAL VF_LAUNCH_BOUNDS(kCemThreads) void cem_refit_kernel(const CemParams p)
         for (int j = 0; j < M; ++j) rank += cem_before(s_score[j], j, mine, i) ? 1 : 0;
         if (rank < K) {
             s_elite[rank] = i;
-            p.elite_index[rank] = i;
-            p.elite_score[rank] = mine;
+            elite_index[rank] = i;
+            elite_score[rank] = mine;
         }
     }
     __syncthreads();
+}
+
+VF_GLOBAL VF_LAUNCH_BOUNDS(kCemThreads) void cem_refit_kernel(const CemParams p) {
+    __shared__ double s_score[kCemMaxM];
+    __shared__ int s_elite[kCemMaxK];
+    const int tid = threadIdx.x;
+    const int D = p.nactions * p.adim, T = p.nactions * p.repeat, W = p.adim + p.tail, K = p.K, M = p.M;
+    cem_select_elites(p.scores, M, K, s_score, s_elite, p.elite_index, p.elite_score);
     char *ws = static_cast<char *>(p.workspace);
     double *mean = reinterpret_cast<double *>(ws + kCemHeaderBytes);
     double *A = mean + D;
@@ -198,6 +207,187 @@ VF_GLOBAL VF_LAUNCH_BOUNDS(kCemThreads) void cem_sample_kernel(const CemParams p
         for (int q = 0; q < p.repeat; ++q) out[(a * p.repeat + q) * W + c] = f;
     }
     for (int e = lane; e < T * p.tail; e += 64) {
+        const int t = e / p.tail, k = e % p.tail;
+        out[t * W + p.adim + k] = (float)p.tail_value[k];
+    }
+}
+
+// ------------------------------------------------------------------ the correlated-noise proposal
+// Specification: samplers/philox_correlated_sampler.py.  Elites, the plain mean and A bit for bit; soft and centre up to the
+// device's float64 exp, the actions up to its log / sin / cos.
+//
+// Workspace (caller-owned, cem_corr_workspace_bytes; the host uploads the header, cem_soft_refit_kernel writes the rest):
+//   int32  R, centre_valid, pad[2]     R: columns of A in use (K after a refit with refit_cov, else 0)
+//   double centre[D]                   the elites' soft mean
+//   double mean[D]                     their plain mean (refit_cov only; A is about it)
+//   double soft[K]                     their weights
+//   double A[K][D]                     refit_cov only: A[d, k] at [k][d]
+//
+//   cem_soft_refit_kernel   ONE workgroup: cem_select_elites, soft_k staged in LDS, then one thread per d.
+//   cem_sample_corr_kernel  one wavefront per sample, four per workgroup.  Lane l makes Philox block l (D <= 128: 32 blocks)
+//                           and owns d = l and d = l + 64; the shaped values go to the wave's LDS strip, lanes c < adim run
+//                           the serial AR(1) chain of their column in it, every lane adds the centre.  No data-dependent
+//                           loop; the only barriers are the wave's own.
+struct CemCorrParams {
+    int nactions, adim, tail, K, M;
+    int refit_cov, has_first_prev;
+    unsigned seed_lo, seed_hi, call;
+    double kappa, beta_0, beta_1;
+    double std[kCemMaxWidth], bias[kCemMaxWidth], first_prev[kCemMaxWidth], tail_value[kCemMaxWidth];
+    const double *scores;               // refit
+    const float *actions_in;            // refit
+    float *actions_out;                 // sample
+    int *elite_index;
+    double *elite_score;
+    float *elite_plans;
+    void *workspace;
+};
+
+__host__ __device__ inline size_t cem_corr_workspace_bytes(int D, int K, bool refit_cov) {
+    return (size_t)kCemHeaderBytes + sizeof(double) * ((size_t)2 * D + (size_t)K + (refit_cov ? (size_t)K * (size_t)D : 0));
+}
+
+VF_GLOBAL VF_LAUNCH_BOUNDS(kCemThreads) void cem_soft_refit_kernel(const CemCorrParams p) {
+    __shared__ double s_score[kCemMaxM];
+    __shared__ int s_elite[kCemMaxK];
+    __shared__ double s_soft[kCemMaxK];
+    const int tid = threadIdx.x;
+    const int D = p.nactions * p.adim, W = p.adim + p.tail, K = p.K, M = p.M;
+    const int plan = p.nactions * W;
+    cem_select_elites(p.scores, M, K, s_score, s_elite, p.elite_index, p.elite_score);
+    char *ws = static_cast<char *>(p.workspace);
+    double *centre = reinterpret_cast<double *>(ws + kCemHeaderBytes);
+    double *mean = centre + D;
+    double *soft = mean + D;
+    double *A = soft + K;
+    const double g0 = -s_score[s_elite[0]];
+    for (int k = tid; k < K; k += kCemThreads) {
+        const double v = exp(__dmul_rn(p.kappa, __dsub_rn(-s_score[s_elite[k]], g0)));
+        s_soft[k] = v;
+        soft[k] = v;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        int *head = reinterpret_cast<int *>(ws);
+        head[0] = p.refit_cov ? K : 0; head[1] = 1; head[2] = 0; head[3] = 0;
+    }
+    if (tid < D) {
+        const long long at = (long long)(tid / p.adim) * W + tid % p.adim;
+        double num = 0.0, den = 0.0, sum = 0.0;
+        for (int k = 0; k < K; ++k) {
+            const double e = (double)p.actions_in[(long long)s_elite[k] * plan + at];
+            num = __dadd_rn(num, __dmul_rn(e, s_soft[k]));
+            den = __dadd_rn(den, s_soft[k]);
+            sum = __dadd_rn(sum, e);
+        }
+        centre[tid] = __ddiv_rn(num, __dadd_rn(den, 1e-4));
+        if (p.refit_cov) {
+            const double m = __ddiv_rn(sum, (double)K);
+            const double scale = __dsqrt_rn((double)(K - 1));
+            mean[tid] = m;
+            for (int k = 0; k < K; ++k) {
+                const double e = (double)p.actions_in[(long long)s_elite[k] * plan + at];
+                A[(long long)k * D + tid] = __ddiv_rn(__dsub_rn(e, m), scale);
+            }
+        }
+    }
+    for (int e = tid; e < K * plan; e += kCemThreads) {
+        const int k = e / plan;
+        p.elite_plans[e] = p.actions_in[(long long)s_elite[k] * plan + (e - k * plan)];
+    }
+}
+
+// what the other lanes of the wave wrote to LDS is visible behind this
+__device__ __forceinline__ void cem_wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+VF_GLOBAL VF_LAUNCH_BOUNDS(kCemThreads) void cem_sample_corr_kernel(const CemCorrParams p) {
+    __shared__ double s_strip[kCemWaves][kCemMaxD];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int i = blockIdx.x * kCemWaves + wave;
+    if (i >= p.M) return;               // whole waves leave: nothing below waits for another wave
+    const int D = p.nactions * p.adim, W = p.adim + p.tail, K = p.K;
+    const char *ws = static_cast<const char *>(p.workspace);
+    const int *head = reinterpret_cast<const int *>(ws);
+    const double *centre = reinterpret_cast<const double *>(ws + kCemHeaderBytes);
+    const double *A = centre + 2 * D + K;
+    const int R = p.refit_cov ? max(0, min(head[0], K)) : 0;     // never past the workspace, whatever the header holds
+    const bool centred = head[1] != 0;
+    const int n_blocks = (D + 3) >> 2;          // <= 32: one per lane
+    const int d0 = lane, d1 = lane + 64;
+    const bool live0 = d0 < D, live1 = d1 < D;
+    const int c0 = live0 ? d0 % p.adim : 0, c1 = live1 ? d1 % p.adim : 0;
+    double z[4] = {0.0, 0.0, 0.0, 0.0};
+    if (lane < n_blocks) {
+        unsigned w[4];
+        cem_philox((unsigned)lane, 0u, (unsigned)i, p.call, p.seed_lo, p.seed_hi, w);
+        cem_pair(w[0], w[1], z[0], z[1]);
+        cem_pair(w[2], w[3], z[2], z[3]);
+    }
+    double s0 = 0.0, s1 = 0.0;
+    if (R == 0) {
+        double w0 = 0.0, w1 = 0.0;      // w_d lies in lane d / 4 as z[d % 4]
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const double v0 = __shfl(z[q], (d0 >> 2) & 63), v1 = __shfl(z[q], (d1 >> 2) & 63);
+            if ((d0 & 3) == q) w0 = v0;
+            if ((d1 & 3) == q) w1 = v1;
+        }
+        s0 = __dadd_rn(__dmul_rn(w0, p.std[c0]), p.bias[c0]);
+        s1 = __dadd_rn(__dmul_rn(w1, p.std[c1]), p.bias[c1]);
+    } else {
+        double y[4] = {0.0, 0.0, 0.0, 0.0};     // y_k of k = lane + 64 j (K <= 256)
+        for (int b = 0; b < n_blocks; ++b) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int d = 4 * b + q;
+                const double wd = __shfl(z[q], b);
+                if (d < D) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const int k = lane + 64 * j;
+                        if (k < R) y[j] = fma(wd, A[(long long)k * D + d], y[j]);
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            for (int l = 0; l < 64; ++l) {
+                const int k = 64 * j + l;
+                if (k >= R) break;              // (uniform)
+                const double yk = __shfl(y[j], l);
+                if (live0) s0 = fma(A[(long long)k * D + d0], yk, s0);
+                if (live1) s1 = fma(A[(long long)k * D + d1], yk, s1);
+            }
+        }
+    }
+    double *strip = s_strip[wave];
+    if (live0) strip[d0] = s0;
+    if (live1) strip[d1] = s1;
+    cem_wave_sync();
+    if (lane < p.adim) {                // the serial chain of column `lane`, in place: step a reads s_a before it writes o_a
+        double prev = p.has_first_prev ? p.first_prev[lane] : strip[(p.nactions - 1) * p.adim + lane];
+        for (int a = 0; a < p.nactions; ++a) {
+            const double o = __dadd_rn(__dmul_rn(p.beta_0, strip[a * p.adim + lane]), __dmul_rn(p.beta_1, prev));
+            strip[a * p.adim + lane] = o;
+            prev = o;
+        }
+    }
+    cem_wave_sync();
+    float *out = p.actions_out + (long long)i * p.nactions * W;
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+        const int d = half ? d1 : d0, c = half ? c1 : c0;
+        if (d >= D) continue;
+        double v = strip[d];
+        if (centred) v = __dadd_rn(v, centre[d]);
+        out[(d / p.adim) * W + c] = (float)v;
+    }
+    for (int e = lane; e < p.nactions * p.tail; e += 64) {
         const int t = e / p.tail, k = e % p.tail;
         out[t * W + p.adim + k] = (float)p.tail_value[k];
     }

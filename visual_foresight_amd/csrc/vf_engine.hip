@@ -2576,6 +2576,61 @@ extern "C" size_t vf_cem_workspace_bytes(const vf_cem_config *cfg) {
     VF_API_CATCH(size_t)
 }
 
+// the refusals of vf_cem_corr_workspace_bytes / vf_cem_soft_refit / vf_cem_sample_corr (host work only, as above)
+static int cem_corr_config_check(const vf_cem_corr_config *c, const char *who) {
+    const std::string w(who);
+    if (!c) return fail(VF_ERR_INVALID, w + ": null cfg");
+    if (c->nactions < 1 || c->adim < 1 || c->tail < 0 || c->adim + c->tail > kCemMaxWidth)
+        return fail(VF_ERR_INVALID, w + ": need nactions >= 1, adim >= 1, tail >= 0 and adim + tail <= 8");
+    if ((long long)c->nactions * c->adim > kCemMaxD)
+        return fail(VF_ERR_INVALID, w + ": D = nactions * adim = " + std::to_string((long long)c->nactions * c->adim) + " exceeds 128");
+    const int least = c->refit_cov ? 2 : 1;
+    if (c->n_elites < least || c->n_elites > kCemMaxK)
+        return fail(VF_ERR_INVALID, w + ": n_elites = " + std::to_string(c->n_elites) + " outside " + std::to_string(least) + "..256");
+    return VF_OK;
+}
+static CemCorrParams cem_corr_params(const vf_cem_corr_config &c, int M) {
+    CemCorrParams p = {};
+    p.nactions = c.nactions; p.adim = c.adim; p.tail = c.tail; p.K = c.n_elites; p.M = M;
+    p.refit_cov = c.refit_cov != 0; p.has_first_prev = c.has_first_prev != 0;
+    p.seed_lo = c.seed_lo; p.seed_hi = c.seed_hi;
+    p.kappa = c.kappa; p.beta_0 = c.beta_0; p.beta_1 = c.beta_1;
+    for (int i = 0; i < kCemMaxWidth; ++i) {
+        p.std[i] = c.std[i]; p.bias[i] = c.bias[i]; p.first_prev[i] = c.first_prev[i]; p.tail_value[i] = c.tail_value[i];
+    }
+    return p;
+}
+static int cem_soft_refit_check(int32_t device, const vf_cem_corr_config *cfg, const double *d_scores, const float *d_actions,
+                                int32_t M, const int32_t *d_elite_index, const double *d_elite_score,
+                                const float *d_elite_plans, const void *d_workspace) {
+    if (int rc = cem_corr_config_check(cfg, "vf_cem_soft_refit")) return rc;
+    if (device < 0) return fail(VF_ERR_INVALID, "vf_cem_soft_refit: device = " + std::to_string(device) + " is negative");
+    if (!d_scores || !d_actions || !d_elite_index || !d_elite_score || !d_elite_plans || !d_workspace)
+        return fail(VF_ERR_INVALID, "vf_cem_soft_refit: null argument");
+    if (reinterpret_cast<uintptr_t>(d_workspace) % 16)
+        return fail(VF_ERR_INVALID, "vf_cem_soft_refit: d_workspace must be 16-byte aligned");
+    if (M < cfg->n_elites || M > kCemMaxM)
+        return fail(VF_ERR_INVALID, "vf_cem_soft_refit: M = " + std::to_string(M) + " outside n_elites.." + std::to_string(kCemMaxM));
+    return VF_OK;
+}
+static int cem_sample_corr_check(int32_t device, const vf_cem_corr_config *cfg, const void *d_workspace, int32_t M,
+                                 const float *d_actions) {
+    if (int rc = cem_corr_config_check(cfg, "vf_cem_sample_corr")) return rc;
+    if (device < 0) return fail(VF_ERR_INVALID, "vf_cem_sample_corr: device = " + std::to_string(device) + " is negative");
+    if (!d_workspace || !d_actions) return fail(VF_ERR_INVALID, "vf_cem_sample_corr: null argument");
+    if (reinterpret_cast<uintptr_t>(d_workspace) % 16)
+        return fail(VF_ERR_INVALID, "vf_cem_sample_corr: d_workspace must be 16-byte aligned");
+    if (M < 1 || M > kCemMaxM)
+        return fail(VF_ERR_INVALID, "vf_cem_sample_corr: M = " + std::to_string(M) + " outside 1.." + std::to_string(kCemMaxM));
+    return VF_OK;
+}
+extern "C" size_t vf_cem_corr_workspace_bytes(const vf_cem_corr_config *cfg) {
+    VF_API_TRY
+    if (cem_corr_config_check(cfg, "vf_cem_corr_workspace_bytes")) return 0;
+    return cem_corr_workspace_bytes(cfg->nactions * cfg->adim, cfg->n_elites, cfg->refit_cov != 0);
+    VF_API_CATCH(size_t)
+}
+
 // the refusals of vf_register, and of vf_register_hw: the same and the caller's size
 static int register_check(const vf_handle *h, const float *d_current, const float *d_reference, const float *d_flow,
                           const int32_t *d_pix, int32_t ntask, int32_t region, int32_t clip_sub, const float *d_desig,
@@ -2914,6 +2969,22 @@ extern "C" int vf_cem_sample(int32_t device, const vf_cem_config *cfg, const voi
                              float *d_actions, int32_t *d_trials, int32_t *d_capped, void *) {      // (refusal paths only, as above)
     VF_API_TRY
     if (int rc = cem_sample_check(device, cfg, d_workspace, M, d_actions, d_trials, d_capped)) return rc;
+    return fail(VF_ERR_HIP, "the host self-test build launches nothing");
+    VF_API_CATCH(int)
+}
+extern "C" int vf_cem_soft_refit(int32_t device, const vf_cem_corr_config *cfg, const double *d_scores, const float *d_actions,
+                                 int32_t M, int32_t *d_elite_index, double *d_elite_score, float *d_elite_plans,
+                                 void *d_workspace, void *) {       // (refusal paths only, as above)
+    VF_API_TRY
+    if (int rc = cem_soft_refit_check(device, cfg, d_scores, d_actions, M, d_elite_index, d_elite_score, d_elite_plans, d_workspace))
+        return rc;
+    return fail(VF_ERR_HIP, "the host self-test build launches nothing");
+    VF_API_CATCH(int)
+}
+extern "C" int vf_cem_sample_corr(int32_t device, const vf_cem_corr_config *cfg, const void *d_workspace, uint32_t, int32_t M,
+                                  float *d_actions, void *) {       // (refusal paths only, as above)
+    VF_API_TRY
+    if (int rc = cem_sample_corr_check(device, cfg, d_workspace, M, d_actions)) return rc;
     return fail(VF_ERR_HIP, "the host self-test build launches nothing");
     VF_API_CATCH(int)
 }
@@ -3545,6 +3616,38 @@ int vf_cem_sample(int32_t device, const vf_cem_config *cfg, const void *d_worksp
     p.actions_out = d_actions; p.trials = d_trials; p.capped = d_capped;
     p.workspace = const_cast<void *>(d_workspace);
     hipLaunchKernelGGL(cem_sample_kernel, dim3((M + kCemWaves - 1) / kCemWaves), dim3(kCemThreads), 0,
+                       reinterpret_cast<hipStream_t>(stream), p);
+    VF_HIP_CHECK(hipGetLastError());
+    return VF_OK;
+    VF_API_CATCH(int)
+}
+
+int vf_cem_soft_refit(int32_t device, const vf_cem_corr_config *cfg, const double *d_scores, const float *d_actions, int32_t M,
+                      int32_t *d_elite_index, double *d_elite_score, float *d_elite_plans, void *d_workspace, void *stream) {
+    VF_API_TRY
+    if (int rc = cem_soft_refit_check(device, cfg, d_scores, d_actions, M, d_elite_index, d_elite_score, d_elite_plans, d_workspace))
+        return rc;
+    VF_HIP_CHECK(hipSetDevice(device));
+    CemCorrParams p = cem_corr_params(*cfg, M);
+    p.scores = d_scores; p.actions_in = d_actions;
+    p.elite_index = d_elite_index; p.elite_score = d_elite_score; p.elite_plans = d_elite_plans;
+    p.workspace = d_workspace;
+    hipLaunchKernelGGL(cem_soft_refit_kernel, dim3(1), dim3(kCemThreads), 0, reinterpret_cast<hipStream_t>(stream), p);
+    VF_HIP_CHECK(hipGetLastError());
+    return VF_OK;
+    VF_API_CATCH(int)
+}
+
+int vf_cem_sample_corr(int32_t device, const vf_cem_corr_config *cfg, const void *d_workspace, uint32_t call, int32_t M,
+                       float *d_actions, void *stream) {
+    VF_API_TRY
+    if (int rc = cem_sample_corr_check(device, cfg, d_workspace, M, d_actions)) return rc;
+    VF_HIP_CHECK(hipSetDevice(device));
+    CemCorrParams p = cem_corr_params(*cfg, M);
+    p.call = call;
+    p.actions_out = d_actions;
+    p.workspace = const_cast<void *>(d_workspace);
+    hipLaunchKernelGGL(cem_sample_corr_kernel, dim3((M + kCemWaves - 1) / kCemWaves), dim3(kCemThreads), 0,
                        reinterpret_cast<hipStream_t>(stream), p);
     VF_HIP_CHECK(hipGetLastError());
     return VF_OK;

@@ -1,8 +1,12 @@
-"""The device side of ``PhiloxGaussianCEMSampler``: buffers and launches of ``vf_cem_refit`` / ``vf_cem_sample``.
+"""The device side of the two Philox samplers: buffers and launches of ``vf_cem_refit`` / ``vf_cem_sample``
+(``DeviceCEM``, for ``PhiloxGaussianCEMSampler``) and of ``vf_cem_soft_refit`` / ``vf_cem_sample_corr``
+(``DeviceCorrelatedCEM``, for ``PhiloxCorrelatedNoiseSampler``).
 
-``DeviceCEM`` owns the workspace (the proposal in factor form) and the per-iteration candidate, elite and trial buffers of
-one controller, all allocated once.  Every method only enqueues on the current stream of its device; ``download`` is the one
-synchronisation of a planning call.  PyTorch carries the buffers, the arithmetic is ``csrc/vf_cem.h``.
+A driver owns the workspace (the proposal) and the per-iteration candidate and elite buffers of one controller, all
+allocated once.  Every method only enqueues on the current stream of its device; the controller's one download is the one
+synchronisation of a planning call.  PyTorch carries the buffers, the arithmetic is ``csrc/vf_cem.h``.  The controller
+drives either through ``begin`` / ``sample`` / ``refit`` / ``downloads`` / ``finish`` (a sampler names its driver:
+``device_cem_driver``).
 """
 import ctypes
 
@@ -81,6 +85,25 @@ class DeviceCEM(object):
     def _stream(self):
         return ctypes.c_void_p(self._torch.cuda.current_stream(self.device).cuda_stream)
 
+    # ------------------------------------------------------------------ one planning call, as the controller drives it
+    def begin(self, sampler, t, M, append_action=None):
+        """Start a planning call at time ``t`` that draws ``M`` sequences per iteration: the sampler's first proposal."""
+        self.cfg = cem_config(sampler, self.K, append_action)       # (reset() makes a new sampler: its key)
+        self._mean0, std = sampler.initial_proposal(t)
+        assert sampler.draws_for(self.max_samples) == M
+        self.upload(self._mean0, np.diag(std))
+
+    def downloads(self, M):
+        """What the call's one download carries besides scores, elite indices and the final elite plans."""
+        return [self.trials[:, :M], self.capped[:, :M]]
+
+    def finish(self, sampler, extras):
+        """The sampler's diagnostics and state after the download (``extras``: ``downloads`` on the host)."""
+        trials, capped = extras
+        sampler.last_trials, sampler.last_capped = trials[-1].astype(np.int32), capped[-1] != 0
+        sampler.n_capped += int(capped.sum())
+        sampler._mean, sampler._A = self._mean0, None       # (the fitted proposal stays on the device)
+
     def upload(self, mean, A):
         """Make ``(mean, A [D, R])`` the proposal: one asynchronous copy of the workspace image."""
         image = workspace_image(np.asarray(mean, np.float64), np.asarray(A, np.float64), self.rmax)
@@ -110,3 +133,104 @@ class DeviceCEM(object):
     def read_proposal(self):
         """(synchronises) -> ``(R, mean, A [D, R])`` of the workspace."""
         return read_workspace(self.workspace.cpu().numpy(), self.D)
+
+
+# ---------------------------------------------------------------------------------------------------- correlated noise
+def corr_workspace_bytes(D, K, refit_cov):
+    """Bytes of the workspace of ``vf_cem_soft_refit`` / ``vf_cem_sample_corr`` (header, centre, mean, soft, A)."""
+    return HEADER_BYTES + 8 * (2 * D + K + (K * D if refit_cov else 0))
+
+
+def corr_config(sampler, n_elites, append_action=None):
+    """The ``vf_cem_corr_config`` of a ``PhiloxCorrelatedNoiseSampler`` (its scales, key and the filter's first step)."""
+    hp, adim = sampler._hp, sampler._adim
+    tail = [float(v) for v in (append_action or ())]
+    std, bias, first = sampler.std(), sampler.bias(), sampler.first_predecessor()
+    cfg = _lib.VfCemCorrConfig()
+    cfg.nactions, cfg.adim, cfg.tail, cfg.n_elites = int(hp.nactions), int(adim), len(tail), int(n_elites)
+    cfg.refit_cov, cfg.has_first_prev = int(bool(hp.refit_cov)), int(first is not None)
+    cfg.seed_lo, cfg.seed_hi = sampler.key
+    cfg.kappa, cfg.beta_0, cfg.beta_1 = float(hp.kappa), float(hp.beta_0), float(hp.beta_1)
+    for i in range(8):
+        cfg.std[i] = float(std[i]) if i < adim else 0.0
+        cfg.bias[i] = float(bias[i]) if i < adim else 0.0
+        cfg.first_prev[i] = float(first[i]) if first is not None and i < adim else 0.0
+        cfg.tail_value[i] = tail[i] if i < len(tail) else 0.0
+    return cfg
+
+
+def read_corr_workspace(image, D, K, refit_cov):
+    """Workspace bytes (NumPy uint8) -> dict: ``R``, ``valid``, ``centre [D]``, ``mean [D]``, ``soft [K]``, ``A [D, R]``."""
+    image = np.ascontiguousarray(image)
+    head = image[:HEADER_BYTES].view(np.int32)
+    body = image[HEADER_BYTES:].view(np.float64)
+    R = int(head[0])
+    A = body[2 * D + K:2 * D + K + R * D].reshape(R, D).T.copy() if refit_cov else np.zeros((D, 0))
+    return dict(R=R, valid=bool(head[1]), centre=body[:D].copy(), mean=body[D:2 * D].copy(), soft=body[2 * D:2 * D + K].copy(),
+                A=A)
+
+
+class DeviceCorrelatedCEM(object):
+    def __init__(self, sampler, n_elites, n_iter, max_samples, device, append_action=None):
+        import torch
+        self._torch = torch
+        self.device = torch.device(device)
+        self._lib = _lib.load_library()
+        self.cfg = corr_config(sampler, n_elites, append_action)
+        hp = sampler._hp
+        self.D, self.K = int(hp.nactions) * sampler._adim, int(n_elites)
+        self.T, self.W = int(hp.nactions), sampler._adim + self.cfg.tail
+        self.refit_cov = bool(hp.refit_cov)
+        self.n_iter, self.max_samples = int(n_iter), int(max_samples)
+        nbytes = self._lib.vf_cem_corr_workspace_bytes(ctypes.byref(self.cfg))
+        if nbytes == 0:
+            raise ValueError('device CEM: %s' % self._lib.vf_last_error().decode())
+        assert nbytes == corr_workspace_bytes(self.D, self.K, self.refit_cov)
+        dev = self.device
+        self.workspace = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
+        self.actions = torch.zeros((self.n_iter, self.max_samples, self.T, self.W), dtype=torch.float32, device=dev)
+        self.scores = torch.zeros((self.n_iter, self.max_samples), dtype=torch.float64, device=dev)
+        self.elite_index = torch.zeros((self.n_iter, self.K), dtype=torch.int32, device=dev)
+        self.elite_score = torch.zeros((self.n_iter, self.K), dtype=torch.float64, device=dev)
+        self.elite_plans = torch.zeros((self.K, self.T, self.W), dtype=torch.float32, device=dev)
+
+    def _stream(self):
+        return ctypes.c_void_p(self._torch.cuda.current_stream(self.device).cuda_stream)
+
+    # ------------------------------------------------------------------ one planning call, as the controller drives it
+    def begin(self, sampler, t, M, append_action=None):
+        """Start a planning call: the first proposal has no centre, and the filter's first step is the sampler's."""
+        self.cfg = corr_config(sampler, self.K, append_action)      # (reset() makes a new sampler: its key)
+        sampler.start_planning_call()
+        self.upload()
+
+    def downloads(self, M):
+        return []
+
+    def finish(self, sampler, extras):
+        sampler.start_planning_call()       # (the fit stays on the device)
+
+    def upload(self):
+        """Make "no centre, no factor" the proposal: the workspace's header is zeroed on the stream."""
+        self.workspace[:HEADER_BYTES].zero_()
+
+    def sample(self, itr, M, call):
+        """Candidates of iteration ``itr`` -> the device tensor ``[M, nactions, adim + tail]`` the rollout reads."""
+        out = self.actions[itr, :M]
+        with self._torch.cuda.device(self.device):
+            _lib.check(self._lib.vf_cem_sample_corr(self.device.index, ctypes.byref(self.cfg), self.workspace.data_ptr(),
+                                                    int(call), int(M), out.data_ptr(), self._stream()))
+        return out
+
+    def refit(self, itr, scores_dev, actions_dev):
+        """Elites of ``scores_dev [M]`` (float64) over ``actions_dev [M, nactions, adim + tail]``, and the soft refit."""
+        M = int(scores_dev.shape[0])
+        with self._torch.cuda.device(self.device):
+            _lib.check(self._lib.vf_cem_soft_refit(self.device.index, ctypes.byref(self.cfg), scores_dev.data_ptr(),
+                                                   actions_dev.data_ptr(), M, self.elite_index[itr].data_ptr(),
+                                                   self.elite_score[itr].data_ptr(), self.elite_plans.data_ptr(),
+                                                   self.workspace.data_ptr(), self._stream()))
+
+    def read_proposal(self):
+        """(synchronises) -> the workspace as ``read_corr_workspace`` gives it."""
+        return read_corr_workspace(self.workspace.cpu().numpy(), self.D, self.K, self.refit_cov)

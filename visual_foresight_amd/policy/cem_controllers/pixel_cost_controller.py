@@ -216,12 +216,13 @@ class PixelCostController(CEMBaseController):
     keep_device_candidates = False      # debug: keep every iteration's candidates of a device-route call (device_candidates)
 
     def _device_cem_plan(self):
-        """``(K, M, tail)`` when this planning call can stay on the device, else None: the sampler is a
-        ``PhiloxGaussianCEMSampler`` with ``device_cem``, the predictor offers ``score_device`` and does not refuse it, the
-        rollouts are scored by ``PixelCostController.evaluate_rollouts`` itself and every iteration's page is not asked for."""
-        from .samplers.philox_gaussian_sampler import PhiloxGaussianCEMSampler, MAX_K, MAX_SAMPLES
+        """``(K, M, tail)`` when this planning call can stay on the device, else None: the sampler names a device driver
+        (``device_cem_driver``: the two Philox samplers) and has ``device_cem``, the predictor offers ``score_device`` and does
+        not refuse it, the rollouts are scored by ``PixelCostController.evaluate_rollouts`` itself and every iteration's page
+        is not asked for."""
+        from .samplers.philox_gaussian_sampler import MAX_K, MAX_SAMPLES
         hp, sampler, pred = self._hp, self._sampler, self.predictor
-        if not isinstance(sampler, PhiloxGaussianCEMSampler) or not hp.get('device_cem'):
+        if getattr(sampler, 'device_cem_driver', None) is None or not hp.get('device_cem'):
             return None
         if not hasattr(pred, 'score_device') or getattr(pred, 'score_device_refusal', lambda: None)():
             return None
@@ -234,9 +235,8 @@ class PixelCostController(CEMBaseController):
         if weights is not None and not getattr(pred, 'supports_task_weights', False):
             return None
         K = self._elite_count()
-        M = max(int(hp.num_samples * hp.reuse_factor), 1) if (
-            hp.reuse_mean and self._t >= hp.repeat - 1 and sampler._mean is not None) else hp.num_samples
-        if not (2 <= K <= min(MAX_K, M) and M <= MAX_SAMPLES) or pred.cfg.adim != self._adim + len(tail):
+        M = sampler.device_draws(self._t, hp.num_samples)
+        if not (2 <= K <= min(MAX_K, M) and M <= MAX_SAMPLES) or pred.cfg.adim != sampler._adim + len(tail):
             return None
         return K, M, tail
 
@@ -244,21 +244,19 @@ class PixelCostController(CEMBaseController):
         plan = self._device_cem_plan()
         if plan is None:
             return super(PixelCostController, self).perform_CEM(state)
-        from .device_cem import DeviceCEM, cem_config
+        from . import device_cem
         hp, sampler, pred = self._hp, self._sampler, self.predictor
         K, M, tail = plan
         torch = pred._torch
         self._logger.log('starting cem at t{} (device route)...'.format(self._t))
+        driver = getattr(device_cem, sampler.device_cem_driver)
         dc = getattr(self, '_device_cem', None)
-        if dc is None or (dc.K, dc.n_iter, dc.max_samples) != (K, self._n_iter, hp.num_samples):
-            dc = self._device_cem = DeviceCEM(sampler, K, self._n_iter, hp.num_samples, pred.device, tail)
-        dc.cfg = cem_config(sampler, K, tail)       # (reset() makes a new sampler: its key)
-        mean, std = sampler.initial_proposal(self._t)
-        assert sampler.draws_for(hp.num_samples) == M
+        if type(dc) is not driver or (dc.K, dc.n_iter, dc.max_samples) != (K, self._n_iter, hp.num_samples):
+            dc = self._device_cem = driver(sampler, K, self._n_iter, hp.num_samples, pred.device, tail)
         weights = self._task_weights()
         kw = {'task_weights': weights} if weights is not None else {}
         with torch.cuda.device(pred.device):
-            dc.upload(mean, np.diag(std))
+            dc.begin(sampler, self._t, M, tail)
             for itr in range(self._n_iter):
                 self._logger.log('iteration: ', itr)
                 candidates = dc.sample(itr, M, sampler.next_call())
@@ -272,24 +270,24 @@ class PixelCostController(CEMBaseController):
                                                only_take_first_view=hp.only_take_first_view, **kw)
                 dc.scores[itr, :M].copy_(scores_dev)
                 dc.refit(itr, scores_dev, candidates)       # (the last one names the final elites)
-            # the one download of the call: scores, elite indices, final elite plans, trial counts, capped flags
-            parts = [dc.scores[:, :M], dc.elite_index, dc.elite_plans, dc.trials[:, :M], dc.capped[:, :M]]
+            # the one download of the call: scores, elite indices, final elite plans, what the driver adds (trial counts,
+            # capped flags)
+            extra = dc.downloads(M)
+            parts = [dc.scores[:, :M], dc.elite_index, dc.elite_plans] + extra
             if self.keep_device_candidates:
                 parts.append(dc.actions[:, :M])
             packed = torch.cat([p.reshape(-1).to(torch.float64) for p in parts]).cpu().numpy()
         sizes = np.cumsum([0] + [p.numel() for p in parts])
         host = [packed[a:b].reshape(tuple(p.shape)) for p, a, b in zip(parts, sizes[:-1], sizes[1:])]
-        scores, elite_index, elite_plans, trials, capped = host[:5]
+        scores, elite_index, elite_plans = host[:3]
         pred._check_scores(scores.reshape(-1))
         for itr in range(self._n_iter):
             self.plan_stat['scores_itr{}'.format(itr)] = scores[itr].copy()
         self._best_indices = elite_index[-1].astype(np.int64)
         self._best_actions = elite_plans.copy()
-        sampler.last_trials, sampler.last_capped = trials[-1].astype(np.int32), capped[-1] != 0
-        sampler.n_capped += int(capped.sum())
-        sampler._mean, sampler._A = mean, None      # (the fitted proposal stays on the device)
+        dc.finish(sampler, host[3:3 + len(extra)])
         if self.keep_device_candidates:
-            self.device_candidates = [c.astype(np.float32) for c in host[5]]
+            self.device_candidates = [c.astype(np.float32) for c in host[3 + len(extra)]]
             self.device_elite_indices = elite_index.astype(np.int64)
         last = self._n_iter - 1
         if hp.predictor_propagation:

@@ -228,6 +228,14 @@ class PhiloxGaussianCEMSampler(CEMSampler):
             discrete[int(ind)] = True
         return rej, trunc, discrete
 
+    device_cem_driver = 'DeviceCEM'     # the class of device_cem.py that runs this sampler on the GPU
+
+    def device_draws(self, t, nsamples):
+        """How many sequences every sampling call of a planning call at time ``t`` draws (known before it starts)."""
+        hp = self._hp
+        reduced = hp.reuse_mean and t >= hp.repeat - 1 and self._mean is not None
+        return max(int(nsamples * hp.reuse_factor), 1) if reduced else nsamples
+
     def draws_for(self, M):
         """How many sequences a call asked for ``M`` draws (``reuse_factor`` after a reused mean)."""
         return max(int(M * self._hp.reuse_factor), 1) if self._last_reduce else M
