@@ -9,7 +9,7 @@
  * the calling thread.  No exception crosses this boundary.  Every device buffer - packed
  * weights, activations, predictions, schedules - is sized from the config and allocated in
  * vf_create(); no later call allocates device memory (vf_load_weights refills the same
- * buffers).  vf_set_context / vf_rollout / vf_export / vf_register(_hw) / vf_resize_area / vf_cem_refit / vf_cem_sample / vf_cem_soft_refit / vf_cem_sample_corr / vf_allgather_scores only
+ * buffers).  vf_set_context / vf_rollout / vf_export / vf_register(_hw) / vf_resize_area / vf_cem_refit / vf_cem_sample / vf_cem_soft_refit / vf_cem_sample_corr / vf_cem_sample_fold / vf_allgather_scores only
  * enqueue work on the caller's HIP stream (hipStream_t passed as void*; NULL = the default
  * stream) and never synchronise it; a handle is driven from one stream at a time.
  * vf_load_weights, vf_device_status and the debug hooks are the blocking calls.
@@ -507,6 +507,34 @@ int vf_cem_soft_refit(int32_t device, const vf_cem_corr_config *cfg, const doubl
 /* Draw M <= 4096 candidates as sampling call number `call`: d_actions [M][nactions][adim + tail] float32.  One wavefront per
  * sample, no data-dependent loop.  VF_ERR_INVALID (nothing launched): a NULL pointer, an invalid cfg, M outside 1..4096. */
 int vf_cem_sample_corr(int32_t device, const vf_cem_corr_config *cfg, const void *d_workspace, uint32_t call, int32_t M,
+                       float *d_actions, void *stream);
+
+/* The folding proposal of the towel experiments (reference visual_mpc/policy/cem_controllers/samplers/folding_sampler.py:7-132):
+ * besides plain Gaussian draws, two scripted families of "lift, carry to a place, put down" plans.  The arithmetic is
+ * specified by the float64 class visual_foresight_amd/policy/cem_controllers/samplers/philox_folding_sampler.py.  adim is 4.
+ * The proposal, its workspace and its refit are vf_cem_config's: size the workspace with vf_cem_workspace_bytes and refit with
+ * vf_cem_refit under a vf_cem_config of adim = 4 and the same nactions, repeat, tail and n_elites; upload the first proposal
+ * as for vf_cem_sample.  Sample i < n_scripted is TWO_PLACES (carry + up, down, up, carry + up, down; later steps zero),
+ * i < 2 n_scripted ONE_PLACE (up, carry + up, down, rest held to the end), the rest the plain draw of vf_cem_sample's trial
+ * 0.  Counter {block, trial, sample i, call}: trial 1, block 0 gives the places u_j = word_j / 2^32 (first (u_0, u_1), second
+ * (u_2, u_3)); trial 2 + s the R normals of scripted step s, v_c = m_c + g_c * sum_r A[c][r] z_r (an fma chain from 0 over
+ * rows 0..3 of A), g = 1 on a carry and (sqrt(.1), sqrt(.1), 1, sqrt(.5)) on the spot, m = (dx, dy, lift, 0) with the carry
+ * (end - start) / repeat.  Columns 0..2 are clipped to +-max_shift. */
+typedef struct vf_cem_fold_config {
+    int32_t nactions, repeat, tail;     /* 5 <= nactions <= 32; a row of d_actions holds 4 + tail <= 8 floats */
+    int32_t n_elites;
+    int32_t n_scripted;                 /* samples of each scripted family: 1 <= 2 * n_scripted <= M */
+    int32_t reserved;
+    uint32_t seed_lo, seed_hi;
+    double start_xy[2];                 /* the gripper's xy at the start of the planning call: where the carries start */
+    double max_shift[3];                /* clip of x, y, z; +inf = none */
+    double tail_value[8];               /* the constants written to columns 4 .. 4 + tail - 1 */
+} vf_cem_fold_config;
+
+/* Draw M <= 4096 candidates as sampling call number `call`: d_actions [M][nactions * repeat][4 + tail] float32.  One
+ * wavefront per sample, no data-dependent loop.  VF_ERR_INVALID (nothing launched): a NULL pointer, an invalid cfg, M outside
+ * 2 * n_scripted..4096. */
+int vf_cem_sample_fold(int32_t device, const vf_cem_fold_config *cfg, const void *d_workspace, uint32_t call, int32_t M,
                        float *d_actions, void *stream);
 
 /* The one collective of multi-GPU planning: all-gather every rank's n_local score values (float64)

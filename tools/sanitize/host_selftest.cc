@@ -450,6 +450,30 @@ int main() {
                 if (vf_cem_soft_refit(0, &corr, pd, img, 20, pi, pd, img, odd, nullptr) != VF_ERR_INVALID) rc = 1;
                 if (vf_cem_soft_refit(0, &corr, pd, img, 20, pi, pd, img, p, nullptr) != VF_ERR_HIP) rc = 1;
                 std::printf("  device CEM, correlated noise: configuration and argument refusals: %s\n", rc ? "FAILED" : "ok");
+                // the same for the folding proposal (its workspace and refit are vf_cem_config's)
+                vf_cem_fold_config fold = {5, 3, 0, 10, 2, 0, 1u, 2u, {0.9, 0.1}, {0.2, 0.2, 1.0 / 3}, {0}};
+                struct { int field, value; const char *msg; } bad_fold[] = {
+                    {0, 4, "nactions"}, {0, 33, "nactions"}, {1, 0, "repeat"}, {2, 5, "tail"}, {2, -1, "tail"},
+                    {3, 1, "n_elites"}, {3, 257, "n_elites"}, {4, 0, "n_scripted"}, {4, 10, "n_scripted"}};
+                for (const auto &c : bad_fold) {
+                    vf_cem_fold_config b = fold;
+                    int32_t words[5];       // the five leading int32 fields, nactions .. n_scripted
+                    std::memcpy(words, &b, sizeof words);
+                    words[c.field] = c.value;
+                    std::memcpy(&b, words, sizeof words);
+                    if (vf_cem_sample_fold(0, &b, p, 0, 18, img, nullptr) != VF_ERR_INVALID ||
+                        std::string(vf_last_error()).find(c.msg) == std::string::npos) {
+                        std::fprintf(stderr, "vf_cem_sample_fold: want refusal '%s', got '%s'\n", c.msg, vf_last_error()); rc = 1;
+                    }
+                }
+                if (vf_cem_sample_fold(0, nullptr, p, 0, 18, img, nullptr) != VF_ERR_INVALID) rc = 1;
+                if (vf_cem_sample_fold(0, &fold, nullptr, 0, 18, img, nullptr) != VF_ERR_INVALID) rc = 1;
+                if (vf_cem_sample_fold(0, &fold, odd, 0, 18, img, nullptr) != VF_ERR_INVALID) rc = 1;
+                if (vf_cem_sample_fold(0, &fold, p, 0, 3, img, nullptr) != VF_ERR_INVALID) rc = 1;          // 2 * n_scripted > M
+                if (vf_cem_sample_fold(0, &fold, p, 0, 4097, img, nullptr) != VF_ERR_INVALID) rc = 1;
+                if (vf_cem_sample_fold(-1, &fold, p, 0, 18, img, nullptr) != VF_ERR_INVALID) rc = 1;
+                if (vf_cem_sample_fold(0, &fold, p, 0, 18, img, nullptr) != VF_ERR_HIP) rc = 1;         // all through: this build launches nothing
+                std::printf("  device CEM, folding: configuration and argument refusals: %s\n", rc ? "FAILED" : "ok");
             }
             int32_t pix[2] = {0, 0};
             float out2[2];

@@ -33,7 +33,7 @@ EXPORTS = ('vf_abi_version', 'vf_last_error', 'vf_weight_count', 'vf_create', 'v
            'vf_invmodel_weight_count', 'vf_invmodel_create', 'vf_invmodel_destroy', 'vf_invmodel_load_weights',
            'vf_invmodel_infer', 'vf_debug_lstm_layer', 'vf_register_hw', 'vf_resize_area',
            'vf_cem_workspace_bytes', 'vf_cem_refit', 'vf_cem_sample',
-           'vf_cem_corr_workspace_bytes', 'vf_cem_soft_refit', 'vf_cem_sample_corr')
+           'vf_cem_corr_workspace_bytes', 'vf_cem_soft_refit', 'vf_cem_sample_corr', 'vf_cem_sample_fold')
 ABI_VERSION = 7
 
 
@@ -68,6 +68,12 @@ class VfCemCorrConfig(ctypes.Structure):
                [('seed_lo', ctypes.c_uint32), ('seed_hi', ctypes.c_uint32)] + \
                [(n, ctypes.c_double) for n in ('kappa', 'beta_0', 'beta_1')] + \
                [(n, ctypes.c_double * 8) for n in ('std', 'bias', 'first_prev', 'tail_value')]
+
+
+class VfCemFoldConfig(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ('nactions', 'repeat', 'tail', 'n_elites', 'n_scripted', 'reserved')] + \
+               [('seed_lo', ctypes.c_uint32), ('seed_hi', ctypes.c_uint32)] + \
+               [('start_xy', ctypes.c_double * 2), ('max_shift', ctypes.c_double * 3), ('tail_value', ctypes.c_double * 8)]
 
 
 class VfInvModelConfig(ctypes.Structure):
@@ -173,6 +179,8 @@ def load_library():
     lib.vf_cem_soft_refit.argtypes = [ctypes.c_int32, ctypes.POINTER(VfCemCorrConfig), P, P, ctypes.c_int32, P, P, P, P, P]
     lib.vf_cem_sample_corr.argtypes = [ctypes.c_int32, ctypes.POINTER(VfCemCorrConfig), P, ctypes.c_uint32, ctypes.c_int32, P, P]
     lib.vf_cem_soft_refit.restype = lib.vf_cem_sample_corr.restype = ctypes.c_int
+    lib.vf_cem_sample_fold.argtypes = [ctypes.c_int32, ctypes.POINTER(VfCemFoldConfig), P, ctypes.c_uint32, ctypes.c_int32, P, P]
+    lib.vf_cem_sample_fold.restype = ctypes.c_int
     lib.vf_allgather_scores.argtypes = [P, P, P, ctypes.c_int32, P, P]
     lib.vf_comm_init_all.argtypes = [ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(P)]
     lib.vf_comm_destroy.argtypes = [P]

@@ -1,5 +1,6 @@
 // vf_cem.h - one CEM iteration on the device: elite selection + refit, and sampling of the next candidates, for the Gaussian
-// proposal (first half) and for the time-correlated noise proposal (second half, which has its own header comment).
+// proposal (first part), for the time-correlated noise proposal (second part) and for the folding proposal (third part, which
+// shares the Gaussian workspace and refit and adds a sampling kernel); the later parts have header comments of their own.
 //
 // Specification: visual_foresight_amd/policy/cem_controllers/samplers/philox_gaussian_sampler.py (a float64 NumPy class that
 // is a sampler in its own right).  These kernels compute its numbers: elite indices, trial counts, mean and A bit for bit;
@@ -390,6 +391,125 @@ VF_GLOBAL VF_LAUNCH_BOUNDS(kCemThreads) void cem_sample_corr_kernel(const CemCor
     for (int e = lane; e < p.nactions * p.tail; e += 64) {
         const int t = e / p.tail, k = e % p.tail;
         out[t * W + p.adim + k] = (float)p.tail_value[k];
+    }
+}
+
+// ------------------------------------------------------------------ the folding proposal
+// Specification: samplers/philox_folding_sampler.py.  The proposal, its workspace and its refit are the Gaussian one's
+// (cem_refit_kernel with adim = 4); only the sampling differs.  The actions up to the device's log / sin / cos.
+//
+//   cem_sample_fold_kernel  one wavefront per sample, four per workgroup, no LDS, no barrier, no data-dependent loop.
+//                           Sample i < n_scripted is TWO_PLACES, i < 2 n_scripted ONE_PLACE, the rest plain (a wave-uniform
+//                           branch).  Lane l makes Philox block l of a trial and owns d = l and d = l + 64, both of channel
+//                           c = l & 3.  Plain: trial 0, the chain of cem_sample_kernel.  Scripted: the places from trial 1,
+//                           block 0 (every lane makes it); then per scripted step s (trial 2 + s) the chain
+//                           y_c = sum_r A[c, r] z_r from 0.0 over row c of A, v_c = m_c + g_c y_c, and a lane keeps the value
+//                           of the step its action index maps to (ONE_PLACE holds its last step, TWO_PLACES leaves zero).
+constexpr int kCemFoldAdim = 4;
+constexpr int kCemFoldSteps = 5;        // the longer script (TWO_PLACES); ONE_PLACE has 4
+
+struct CemFoldParams {
+    int nactions, repeat, tail, K, M, n_scripted;
+    unsigned seed_lo, seed_hi, call;
+    double start_xy[2], max_shift[3], tail_value[kCemMaxWidth];
+    float *actions_out;
+    const void *workspace;
+};
+
+VF_GLOBAL VF_LAUNCH_BOUNDS(kCemThreads) void cem_sample_fold_kernel(const CemFoldParams p) {
+    const int lane = threadIdx.x & 63;
+    const int i = blockIdx.x * kCemWaves + (threadIdx.x >> 6);
+    if (i >= p.M) return;               // whole waves leave: nothing below waits for another wave
+    const int D = p.nactions * kCemFoldAdim, T = p.nactions * p.repeat, W = kCemFoldAdim + p.tail;
+    const char *ws = static_cast<const char *>(p.workspace);
+    const double *mean = reinterpret_cast<const double *>(ws + kCemHeaderBytes);
+    const double *A = mean + D;
+    int R = *reinterpret_cast<const int *>(ws);
+    R = max(0, min(R, cem_rmax(D, p.K)));       // never past the workspace, whatever the header holds
+    const int n_blocks = (R + 3) >> 2;          // <= 64: one per lane
+    const int d0 = lane, d1 = lane + 64;
+    const bool live0 = d0 < D, live1 = d1 < D;
+    const int c = lane & 3, a0 = lane >> 2, a1 = a0 + 16;
+    double x0 = 0.0, x1 = 0.0;
+    if (i >= 2 * p.n_scripted) {                // plain: the Gaussian sampler's unrejected draw
+        double z[4] = {0.0, 0.0, 0.0, 0.0};
+        if (lane < n_blocks) {
+            unsigned w[4];
+            cem_philox((unsigned)lane, 0u, (unsigned)i, p.call, p.seed_lo, p.seed_hi, w);
+            cem_pair(w[0], w[1], z[0], z[1]);
+            cem_pair(w[2], w[3], z[2], z[3]);
+        }
+        x0 = live0 ? mean[d0] : 0.0;
+        x1 = live1 ? mean[d1] : 0.0;
+        for (int j = 0; j < n_blocks; ++j) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int r = 4 * j + q;
+                const double zr = __shfl(z[q], j);
+                if (r < R) {
+                    const double e0 = live0 ? A[(long long)r * D + d0] : 0.0;
+                    const double e1 = live1 ? A[(long long)r * D + d1] : 0.0;
+                    x0 = fma(e0, zr, x0);
+                    x1 = fma(e1, zr, x1);
+                }
+            }
+        }
+    } else {
+        const bool two = i < p.n_scripted;
+        unsigned pw[4];
+        cem_philox(0u, 1u, (unsigned)i, p.call, p.seed_lo, p.seed_hi, pw);
+        // the carries of this lane's channel (x or y; lift and rotation have none): start -> first place -> second place
+        const double start = p.start_xy[c & 1];
+        const double first = __ddiv_rn((double)pw[c & 1], 4294967296.0);
+        const double second = __ddiv_rn((double)pw[2 + (c & 1)], 4294967296.0);
+        const double rep = (double)p.repeat;
+        const double way0 = __ddiv_rn(__dsub_rn(first, start), rep);
+        const double way1 = __ddiv_rn(__dsub_rn(second, first), rep);
+        const int n_steps = two ? kCemFoldSteps : kCemFoldSteps - 1;
+        // the scripted step an action index takes: TWO_PLACES none past its script (-1), ONE_PLACE its last
+        const int s0 = a0 < n_steps ? a0 : (two ? -1 : n_steps - 1);
+        const int s1 = two ? -1 : n_steps - 1;  // (a1 >= 16 is past either script)
+        for (int s = 0; s < n_steps; ++s) {
+            double z[4] = {0.0, 0.0, 0.0, 0.0};
+            if (lane < n_blocks) {
+                unsigned w[4];
+                cem_philox((unsigned)lane, (unsigned)(2 + s), (unsigned)i, p.call, p.seed_lo, p.seed_hi, w);
+                cem_pair(w[0], w[1], z[0], z[1]);
+                cem_pair(w[2], w[3], z[2], z[3]);
+            }
+            double y = 0.0;
+            for (int j = 0; j < n_blocks; ++j) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int r = 4 * j + q;
+                    const double zr = __shfl(z[q], j);
+                    if (r < R) y = fma(A[(long long)r * D + c], zr, y);
+                }
+            }
+            const bool carry = two ? (s == 0 || s == 3) : s == 1;
+            const double lift = two ? ((s == 1 || s == 4) ? -1.0 : 1.0) : (s < 2 ? 1.0 : (s == 2 ? -1.0 : 0.0));
+            const double way = (two && s == 3) ? way1 : way0;
+            const double m = c < 2 ? (carry ? way : 0.0) : (c == 2 ? lift : 0.0);
+            const double g = (carry || c == 2) ? 1.0 : (c < 2 ? 0.31622776601683794 : 0.7071067811865476);   // sqrt(.1), sqrt(.5)
+            const double v = __dadd_rn(m, __dmul_rn(g, y));
+            if (s == s0) x0 = v;
+            if (s == s1) x1 = v;
+        }
+    }
+    float *out = p.actions_out + (long long)i * T * W;
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+        const int d = half ? d1 : d0;
+        if (d >= D) continue;
+        double v = half ? x1 : x0;
+        if (c < 3) v = cem_clip(v, -p.max_shift[c], p.max_shift[c]);
+        const float f = (float)v;
+        const int a = half ? a1 : a0;
+        for (int q = 0; q < p.repeat; ++q) out[(a * p.repeat + q) * W + c] = f;
+    }
+    for (int e = lane; e < T * p.tail; e += 64) {
+        const int t = e / p.tail, k = e % p.tail;
+        out[t * W + kCemFoldAdim + k] = (float)p.tail_value[k];
     }
 }
 

@@ -2576,6 +2576,30 @@ extern "C" size_t vf_cem_workspace_bytes(const vf_cem_config *cfg) {
     VF_API_CATCH(size_t)
 }
 
+// the refusals of vf_cem_sample_fold (host work only, as above); the workspace and the refit are vf_cem_config's with adim = 4
+static int cem_sample_fold_check(int32_t device, const vf_cem_fold_config *c, const void *d_workspace, int32_t M,
+                                 const float *d_actions) {
+    const std::string w("vf_cem_sample_fold");
+    if (!c) return fail(VF_ERR_INVALID, w + ": null cfg");
+    if (c->nactions < kCemFoldSteps || c->nactions * kCemFoldAdim > kCemMaxD)
+        return fail(VF_ERR_INVALID, w + ": nactions = " + std::to_string(c->nactions) + " outside 5..32");
+    if (c->repeat < 1 || (long long)c->nactions * c->repeat > (1 << 16))
+        return fail(VF_ERR_INVALID, w + ": need repeat >= 1 and T = nactions * repeat <= 2^16");
+    if (c->tail < 0 || kCemFoldAdim + c->tail > kCemMaxWidth) return fail(VF_ERR_INVALID, w + ": tail outside 0..4");
+    if (c->n_elites < 2 || c->n_elites > kCemMaxK)
+        return fail(VF_ERR_INVALID, w + ": n_elites = " + std::to_string(c->n_elites) + " outside 2..256");
+    for (int i = 0; i < 3; ++i)
+        if (!(c->max_shift[i] >= 0.0)) return fail(VF_ERR_INVALID, w + ": max_shift must be >= 0 (+inf = none)");
+    if (device < 0) return fail(VF_ERR_INVALID, w + ": device = " + std::to_string(device) + " is negative");
+    if (!d_workspace || !d_actions) return fail(VF_ERR_INVALID, w + ": null argument");
+    if (reinterpret_cast<uintptr_t>(d_workspace) % 16) return fail(VF_ERR_INVALID, w + ": d_workspace must be 16-byte aligned");
+    if (M < 1 || M > kCemMaxM) return fail(VF_ERR_INVALID, w + ": M = " + std::to_string(M) + " outside 1.." + std::to_string(kCemMaxM));
+    if (c->n_scripted < 1 || 2LL * c->n_scripted > M)
+        return fail(VF_ERR_INVALID, w + ": n_scripted = " + std::to_string(c->n_scripted) + ", need 1 <= 2 * n_scripted <= M = " +
+                                        std::to_string(M));
+    return VF_OK;
+}
+
 // the refusals of vf_cem_corr_workspace_bytes / vf_cem_soft_refit / vf_cem_sample_corr (host work only, as above)
 static int cem_corr_config_check(const vf_cem_corr_config *c, const char *who) {
     const std::string w(who);
@@ -2985,6 +3009,13 @@ extern "C" int vf_cem_sample_corr(int32_t device, const vf_cem_corr_config *cfg,
                                   float *d_actions, void *) {       // (refusal paths only, as above)
     VF_API_TRY
     if (int rc = cem_sample_corr_check(device, cfg, d_workspace, M, d_actions)) return rc;
+    return fail(VF_ERR_HIP, "the host self-test build launches nothing");
+    VF_API_CATCH(int)
+}
+extern "C" int vf_cem_sample_fold(int32_t device, const vf_cem_fold_config *cfg, const void *d_workspace, uint32_t, int32_t M,
+                                  float *d_actions, void *) {       // (refusal paths only, as above)
+    VF_API_TRY
+    if (int rc = cem_sample_fold_check(device, cfg, d_workspace, M, d_actions)) return rc;
     return fail(VF_ERR_HIP, "the host self-test build launches nothing");
     VF_API_CATCH(int)
 }
@@ -3648,6 +3679,27 @@ int vf_cem_sample_corr(int32_t device, const vf_cem_corr_config *cfg, const void
     p.actions_out = d_actions;
     p.workspace = const_cast<void *>(d_workspace);
     hipLaunchKernelGGL(cem_sample_corr_kernel, dim3((M + kCemWaves - 1) / kCemWaves), dim3(kCemThreads), 0,
+                       reinterpret_cast<hipStream_t>(stream), p);
+    VF_HIP_CHECK(hipGetLastError());
+    return VF_OK;
+    VF_API_CATCH(int)
+}
+
+int vf_cem_sample_fold(int32_t device, const vf_cem_fold_config *cfg, const void *d_workspace, uint32_t call, int32_t M,
+                       float *d_actions, void *stream) {
+    VF_API_TRY
+    if (int rc = cem_sample_fold_check(device, cfg, d_workspace, M, d_actions)) return rc;
+    VF_HIP_CHECK(hipSetDevice(device));
+    CemFoldParams p = {};
+    p.nactions = cfg->nactions; p.repeat = cfg->repeat; p.tail = cfg->tail; p.K = cfg->n_elites; p.M = M;
+    p.n_scripted = cfg->n_scripted;
+    p.seed_lo = cfg->seed_lo; p.seed_hi = cfg->seed_hi; p.call = call;
+    for (int i = 0; i < 2; ++i) p.start_xy[i] = cfg->start_xy[i];
+    for (int i = 0; i < 3; ++i) p.max_shift[i] = cfg->max_shift[i];
+    for (int i = 0; i < kCemMaxWidth; ++i) p.tail_value[i] = cfg->tail_value[i];
+    p.actions_out = d_actions;
+    p.workspace = d_workspace;
+    hipLaunchKernelGGL(cem_sample_fold_kernel, dim3((M + kCemWaves - 1) / kCemWaves), dim3(kCemThreads), 0,
                        reinterpret_cast<hipStream_t>(stream), p);
     VF_HIP_CHECK(hipGetLastError());
     return VF_OK;

@@ -98,6 +98,9 @@ class CEMBaseController(Policy):
         return np.concatenate((actions, tail), axis=-1)
 
     def perform_CEM(self, state):
+        plan = self._device_cem_plan()
+        if plan is not None:
+            return self._perform_device_CEM(state, plan)
         hp = self._hp
         self._logger.log('starting cem at t{}...'.format(self._t))
         n_elite = self._elite_count()
@@ -127,6 +130,104 @@ class CEMBaseController(Policy):
 
     def evaluate_rollouts(self, actions, cem_itr):
         raise NotImplementedError
+
+    # ------------------------------------------------------------------ device-resident CEM
+    keep_device_candidates = False      # debug: keep every iteration's candidates of a device-route call (device_candidates)
+
+    def _device_cem_plan(self):
+        """Hook: ``(K, M, tail)`` when this planning call can stay on the device, else None (the host route).  A controller
+        that scores on the device answers with ``_device_cem_shape``."""
+        return None
+
+    def _score_device_candidates(self, candidates, itr):
+        """Hook: score the device candidates ``[M, T, adim + tail]`` of iteration ``itr`` -> (device float64 scores ``[M]``,
+        the context the rollout saw).  Only enqueues."""
+        raise NotImplementedError
+
+    def _device_cem_downloads(self):
+        """Hook: device tensors of the last iteration that join the call's one download."""
+        return []
+
+    def _device_cem_finish(self, last, scores, context, downloaded):
+        """Hook, after the download: what the host route sets from the last iteration ``last`` (``scores [M]`` of it, the
+        host copies ``downloaded`` of ``_device_cem_downloads``)."""
+
+    def _device_cem_shape(self, entry, own_evaluate, pages_only=False):
+        """The refusals every device route shares -> ``(K, M, tail)`` or None: the sampler names a device driver
+        (``device_cem_driver``: the Philox samplers) and has ``device_cem``, the predictor offers ``entry`` and its refusal
+        (``<entry>_refusal``, or the one the frame entries share) is silent, the rollouts are scored by ``own_evaluate`` (the
+        controller class's own ``evaluate_rollouts``) and every iteration's page is not asked for: ``verbose_every_iter``, or,
+        with ``pages_only`` (a controller whose ``_device_cem_finish`` logs every iteration, ``_log_earlier_iterations``),
+        ``verbose_every_iter`` together with a verbose worker to put the pages on."""
+        from .samplers.philox_gaussian_sampler import MAX_K, MAX_SAMPLES
+        hp, sampler, pred = self._hp, self._sampler, self.predictor
+        if getattr(sampler, 'device_cem_driver', None) is None or not hp.get('device_cem'):
+            return None
+        refusal = 'score_device_refusal' if entry == 'score_device' else 'frame_score_device_refusal'
+        if not hasattr(pred, entry) or getattr(pred, refusal, lambda: None)():
+            return None
+        if type(self).evaluate_rollouts is not own_evaluate:
+            return None
+        if hp.verbose and hp.verbose_every_iter:    # only the last rollout is resident when the call is through
+            if not pages_only or getattr(self, '_verbose_worker', None) is not None:
+                return None
+        tail = list(hp.append_action) if hp.append_action else []
+        K = self._elite_count()
+        M = sampler.device_draws(self._t, hp.num_samples)
+        if not (2 <= K <= min(MAX_K, M) and M <= MAX_SAMPLES) or pred.cfg.adim != sampler._adim + len(tail):
+            return None
+        return K, M, tail
+
+    def _log_earlier_iterations(self, last):
+        """With ``verbose_every_iter``: the best-scores line of every iteration before ``last``, as the host route logs it."""
+        if self._hp.verbose and self._hp.verbose_every_iter:
+            for itr in range(last):
+                self._logger.log('best scores itr {}: {}'.format(itr, np.sort(self.plan_stat['scores_itr{}'.format(itr)])[:10]))
+
+    def _perform_device_CEM(self, state, plan):
+        """One planning call on the device: sample, score, select the elites and refit are enqueued for every iteration, then
+        one download."""
+        from . import device_cem
+        hp, sampler, pred = self._hp, self._sampler, self.predictor
+        K, M, tail = plan
+        torch = pred._torch
+        self._logger.log('starting cem at t{} (device route)...'.format(self._t))
+        driver = getattr(device_cem, sampler.device_cem_driver)
+        dc = getattr(self, '_device_cem', None)
+        if type(dc) is not driver or (dc.K, dc.n_iter, dc.max_samples) != (K, self._n_iter, hp.num_samples):
+            dc = self._device_cem = driver(sampler, K, self._n_iter, hp.num_samples, pred.device, tail)
+        with torch.cuda.device(pred.device):
+            dc.begin(sampler, self._t, M, tail, state[-1])
+            for itr in range(self._n_iter):
+                self._logger.log('iteration: ', itr)
+                candidates = dc.sample(itr, M, sampler.next_call())
+                scores_dev, context = self._score_device_candidates(candidates, itr)
+                dc.scores[itr, :M].copy_(scores_dev)
+                dc.refit(itr, scores_dev, candidates)       # (the last one names the final elites)
+            # the one download of the call: scores, elite indices, final elite plans, what the driver adds (trial counts,
+            # capped flags) and what the controller adds (the last iteration's cost rows)
+            extra = dc.downloads(M)
+            own = self._device_cem_downloads()
+            parts = [dc.scores[:, :M], dc.elite_index, dc.elite_plans] + extra + own
+            if self.keep_device_candidates:
+                parts.append(dc.actions[:, :M])
+            packed = torch.cat([p.reshape(-1).to(torch.float64) for p in parts]).cpu().numpy()
+        sizes = np.cumsum([0] + [p.numel() for p in parts])
+        host = [packed[a:b].reshape(tuple(p.shape)) for p, a, b in zip(parts, sizes[:-1], sizes[1:])]
+        scores, elite_index, elite_plans = host[:3]
+        pred._check_scores(scores.reshape(-1))
+        for itr in range(self._n_iter):
+            self.plan_stat['scores_itr{}'.format(itr)] = scores[itr].copy()
+        self._best_indices = elite_index[-1].astype(np.int64)
+        self._best_actions = elite_plans.copy()
+        dc.finish(sampler, host[3:3 + len(extra)])
+        n_own = 3 + len(extra) + len(own)
+        if self.keep_device_candidates:
+            self.device_candidates = [c.astype(np.float32) for c in host[n_own]]
+            self.device_elite_indices = elite_index.astype(np.int64)
+        last = self._n_iter - 1
+        self._device_cem_finish(last, scores[last], context, host[3 + len(extra):n_own])
+        self._t_since_replan = 0
 
     def _verbose_condition(self, cem_itr):
         if not self._hp.verbose:

@@ -1,6 +1,7 @@
-"""The device side of the two Philox samplers: buffers and launches of ``vf_cem_refit`` / ``vf_cem_sample``
-(``DeviceCEM``, for ``PhiloxGaussianCEMSampler``) and of ``vf_cem_soft_refit`` / ``vf_cem_sample_corr``
-(``DeviceCorrelatedCEM``, for ``PhiloxCorrelatedNoiseSampler``).
+"""The device side of the three Philox samplers: buffers and launches of ``vf_cem_refit`` / ``vf_cem_sample``
+(``DeviceCEM``, for ``PhiloxGaussianCEMSampler``), of ``vf_cem_soft_refit`` / ``vf_cem_sample_corr``
+(``DeviceCorrelatedCEM``, for ``PhiloxCorrelatedNoiseSampler``) and of ``vf_cem_refit`` / ``vf_cem_sample_fold``
+(``DeviceFoldingCEM``, for ``PhiloxFoldingCEMSampler``).
 
 A driver owns the workspace (the proposal) and the per-iteration candidate and elite buffers of one controller, all
 allocated once.  Every method only enqueues on the current stream of its device; the controller's one download is the one
@@ -86,8 +87,9 @@ class DeviceCEM(object):
         return ctypes.c_void_p(self._torch.cuda.current_stream(self.device).cuda_stream)
 
     # ------------------------------------------------------------------ one planning call, as the controller drives it
-    def begin(self, sampler, t, M, append_action=None):
-        """Start a planning call at time ``t`` that draws ``M`` sequences per iteration: the sampler's first proposal."""
+    def begin(self, sampler, t, M, append_action=None, state=None):
+        """Start a planning call at time ``t`` that draws ``M`` sequences per iteration: the sampler's first proposal.
+        ``state``: the state row the call starts from (the folding driver reads it)."""
         self.cfg = cem_config(sampler, self.K, append_action)       # (reset() makes a new sampler: its key)
         self._mean0, std = sampler.initial_proposal(t)
         assert sampler.draws_for(self.max_samples) == M
@@ -198,7 +200,7 @@ class DeviceCorrelatedCEM(object):
         return ctypes.c_void_p(self._torch.cuda.current_stream(self.device).cuda_stream)
 
     # ------------------------------------------------------------------ one planning call, as the controller drives it
-    def begin(self, sampler, t, M, append_action=None):
+    def begin(self, sampler, t, M, append_action=None, state=None):
         """Start a planning call: the first proposal has no centre, and the filter's first step is the sampler's."""
         self.cfg = corr_config(sampler, self.K, append_action)      # (reset() makes a new sampler: its key)
         sampler.start_planning_call()
@@ -234,3 +236,110 @@ class DeviceCorrelatedCEM(object):
     def read_proposal(self):
         """(synchronises) -> the workspace as ``read_corr_workspace`` gives it."""
         return read_corr_workspace(self.workspace.cpu().numpy(), self.D, self.K, self.refit_cov)
+
+
+# ---------------------------------------------------------------------------------------------------- folding
+def fold_refit_config(sampler, n_elites, append_action=None):
+    """The ``vf_cem_config`` under which ``vf_cem_workspace_bytes`` / ``vf_cem_refit`` serve a ``PhiloxFoldingCEMSampler``:
+    the Gaussian proposal with ``adim = 4``, nothing rejected, nothing limited."""
+    hp = sampler._hp
+    tail = [float(v) for v in (append_action or ())]
+    cfg = _lib.VfCemConfig()
+    cfg.nactions, cfg.repeat, cfg.adim, cfg.tail = int(hp.nactions), int(hp.repeat), 4, len(tail)
+    cfg.n_elites, cfg.max_trials = int(n_elites), 1
+    cfg.seed_lo, cfg.seed_hi = sampler.key
+    for i in range(8):
+        cfg.rej_lim[i] = cfg.trunc_lim[i] = float('inf')
+        cfg.tail_value[i] = tail[i] if i < len(tail) else 0.0
+    return cfg
+
+
+def fold_config(sampler, n_elites, M, append_action=None):
+    """The ``vf_cem_fold_config`` of a ``PhiloxFoldingCEMSampler`` whose calls draw ``M`` sequences."""
+    hp = sampler._hp
+    tail = [float(v) for v in (append_action or ())]
+    cfg = _lib.VfCemFoldConfig()
+    cfg.nactions, cfg.repeat, cfg.tail, cfg.n_elites = int(hp.nactions), int(hp.repeat), len(tail), int(n_elites)
+    cfg.n_scripted = int(sampler.check_draws(M))
+    cfg.seed_lo, cfg.seed_hi = sampler.key
+    start = sampler.start_xy()
+    for i in range(2):
+        cfg.start_xy[i] = float(start[i])
+    for i in range(3):
+        cfg.max_shift[i] = float(hp.max_shift[i])
+    for i in range(8):
+        cfg.tail_value[i] = tail[i] if i < len(tail) else 0.0
+    return cfg
+
+
+class DeviceFoldingCEM(object):
+    def __init__(self, sampler, n_elites, n_iter, max_samples, device, append_action=None):
+        import torch
+        self._torch = torch
+        self.device = torch.device(device)
+        self._lib = _lib.load_library()
+        self.refit_cfg = fold_refit_config(sampler, n_elites, append_action)
+        self.cfg = fold_config(sampler, n_elites, max_samples, append_action)
+        hp = sampler._hp
+        self.D, self.K = int(hp.nactions) * 4, int(n_elites)
+        self.T, self.W = int(hp.nactions) * int(hp.repeat), 4 + self.cfg.tail
+        self.n_iter, self.max_samples = int(n_iter), int(max_samples)
+        nbytes = self._lib.vf_cem_workspace_bytes(ctypes.byref(self.refit_cfg))
+        if nbytes == 0:
+            raise ValueError('device CEM: %s' % self._lib.vf_last_error().decode())
+        self.rmax = max(self.D, self.K)
+        dev = self.device
+        self.workspace = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
+        self.actions = torch.zeros((self.n_iter, self.max_samples, self.T, self.W), dtype=torch.float32, device=dev)
+        self.scores = torch.zeros((self.n_iter, self.max_samples), dtype=torch.float64, device=dev)
+        self.elite_index = torch.zeros((self.n_iter, self.K), dtype=torch.int32, device=dev)
+        self.elite_score = torch.zeros((self.n_iter, self.K), dtype=torch.float64, device=dev)
+        self.elite_plans = torch.zeros((self.K, self.T, self.W), dtype=torch.float32, device=dev)
+        self._staging = torch.zeros(nbytes, dtype=torch.uint8).pin_memory()
+
+    def _stream(self):
+        return ctypes.c_void_p(self._torch.cuda.current_stream(self.device).cuda_stream)
+
+    # ------------------------------------------------------------------ one planning call, as the controller drives it
+    def begin(self, sampler, t, M, append_action=None, state=None):
+        """Start a planning call at time ``t`` from the state row ``state``: the gripper's xy goes into the config, the first
+        proposal ``(0, diag(std))`` into the workspace."""
+        mean, std = sampler.initial_proposal(t, state)
+        self.refit_cfg = fold_refit_config(sampler, self.K, append_action)      # (reset() makes a new sampler: its key)
+        self.cfg = fold_config(sampler, self.K, M, append_action)
+        self.upload(mean, np.diag(std))
+
+    def downloads(self, M):
+        return []
+
+    def finish(self, sampler, extras):
+        pass        # (the fitted proposal stays on the device; the next call starts from the first proposal)
+
+    def upload(self, mean, A):
+        """Make ``(mean, A [D, R])`` the proposal: one asynchronous copy of the workspace image."""
+        image = workspace_image(np.asarray(mean, np.float64), np.asarray(A, np.float64), self.rmax)
+        # (the pinned stage may still feed the previous call's copy: wait for that one, it is long done)
+        self._torch.cuda.current_stream(self.device).synchronize()
+        self._staging.numpy()[:] = image
+        self.workspace.copy_(self._staging, non_blocking=True)
+
+    def sample(self, itr, M, call):
+        """Candidates of iteration ``itr`` -> the device tensor ``[M, T, 4 + tail]`` the rollout reads."""
+        out = self.actions[itr, :M]
+        with self._torch.cuda.device(self.device):
+            _lib.check(self._lib.vf_cem_sample_fold(self.device.index, ctypes.byref(self.cfg), self.workspace.data_ptr(),
+                                                    int(call), int(M), out.data_ptr(), self._stream()))
+        return out
+
+    def refit(self, itr, scores_dev, actions_dev):
+        """Elites of ``scores_dev [M]`` (float64) over ``actions_dev [M, T, 4 + tail]``, and the refit into the workspace."""
+        M = int(scores_dev.shape[0])
+        with self._torch.cuda.device(self.device):
+            _lib.check(self._lib.vf_cem_refit(self.device.index, ctypes.byref(self.refit_cfg), scores_dev.data_ptr(),
+                                              actions_dev.data_ptr(), M, self.elite_index[itr].data_ptr(),
+                                              self.elite_score[itr].data_ptr(), self.elite_plans.data_ptr(),
+                                              self.workspace.data_ptr(), self._stream()))
+
+    def read_proposal(self):
+        """(synchronises) -> ``(R, mean, A [D, R])`` of the workspace."""
+        return read_workspace(self.workspace.cpu().numpy(), self.D)

@@ -94,6 +94,7 @@ class GoalImController(CEMBaseController):
         self._goal_image = None
         self._n_act = 0                 # act() calls so far: the goal picture's name towards the predictor's goal cache
         self.cost_perstep = None        # [M, ncam, T] MSE of the last scoring call
+        self.goal_cost_per_view = None  # [M, ncam] cost of the last scoring call
 
     def _default_hparams(self):
         defaults = [
@@ -121,11 +122,9 @@ class GoalImController(CEMBaseController):
             "context_states": context_states(self),
         }
         if hasattr(self.predictor, 'score_goal_image'):
-            # (a camera-size goal is shrunk once per act(): the call count names the picture to the predictor)
-            key = {'goal_key': ('act', id(self), self._n_act)} if self._camera_size is not None else {}
             scores, per_view = self.predictor.score_goal_image(
                 context, {'actions': actions}, self._goal_image, steps=hp.goal_cost_steps,
-                finalweight=hp.finalweight, first_view_only=hp.only_take_first_view, **key)
+                finalweight=hp.finalweight, first_view_only=hp.only_take_first_view, **self._goal_key())
             self.cost_perstep = self.predictor.last_goal_cost_per_step
         else:
             context = self._with_centre_distribution(context)
@@ -137,15 +136,48 @@ class GoalImController(CEMBaseController):
             scores, per_view, self.cost_perstep = goal_image_cost(
                 prediction['predicted_frames'], goal, hp.goal_cost_steps, hp.finalweight,
                 hp.only_take_first_view)
+        self._log_and_page(cem_itr, scores, per_view, context, actions)
+        return scores
+
+    def _log_and_page(self, cem_itr, scores, per_view, context, actions):
+        """The per-view log lines of an iteration and, when it is the one to show, its best scores and plan page."""
         bestind = scores.argsort()[0]
         for icam in range(per_view.shape[1]):
             self._logger.log('best goal-image score cam{}  :{}'.format(icam, np.min(per_view[:, icam])))
             self._logger.log('goal-image score of best traj cam{} :{}'.format(icam, per_view[bestind, icam]))
+        self.goal_cost_per_view = per_view      # [M, ncam] of the last scoring call
         if self._verbose_condition(cem_itr):
             self._logger.log('best scores itr {}: {}'.format(cem_itr, np.sort(scores)[:10]))
             if self._verbose_worker is not None:
                 self._put_plan_page(cem_itr, scores, context, actions)
-        return scores
+
+    # ------------------------------------------------------------------ device-resident CEM (DESIGN.md 6.1.2)
+    def _goal_key(self):
+        # (a camera-size goal is shrunk once per act(): the call count names the picture to the predictor)
+        return {'goal_key': ('act', id(self), self._n_act)} if self._camera_size is not None else {}
+
+    def _device_cem_plan(self):
+        return self._device_cem_shape('score_goal_image_device', GoalImController.evaluate_rollouts, pages_only=True)
+
+    def _score_device_candidates(self, candidates, itr):
+        hp = self._hp
+        context = {
+            "context_frames": context_frames(self),
+            "context_actions": self._sampler.chosen_actions,
+            "context_states": context_states(self),
+        }
+        scores_dev = self.predictor.score_goal_image_device(
+            context, candidates, self._goal_image, steps=hp.goal_cost_steps, finalweight=hp.finalweight,
+            first_view_only=hp.only_take_first_view, **self._goal_key())
+        return scores_dev, context
+
+    def _device_cem_downloads(self):
+        return [self.predictor.last_goal_rows_dev]
+
+    def _device_cem_finish(self, last, scores, context, downloaded):
+        _, per_view, self.cost_perstep = self.predictor.split_goal_rows(downloaded[0])
+        self._log_earlier_iterations(last)
+        self._log_and_page(last, scores, per_view, context, None)
 
     def _with_centre_distribution(self, context):
         """``context`` plus the one distribution channel the network carries, switched on at the image centre - or, for a

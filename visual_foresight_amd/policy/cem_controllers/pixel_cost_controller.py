@@ -213,88 +213,34 @@ class PixelCostController(CEMBaseController):
         return None
 
     # ------------------------------------------------------------------ device-resident CEM
-    keep_device_candidates = False      # debug: keep every iteration's candidates of a device-route call (device_candidates)
-
     def _device_cem_plan(self):
-        """``(K, M, tail)`` when this planning call can stay on the device, else None: the sampler names a device driver
-        (``device_cem_driver``: the two Philox samplers) and has ``device_cem``, the predictor offers ``score_device`` and does
-        not refuse it, the rollouts are scored by ``PixelCostController.evaluate_rollouts`` itself and every iteration's page
-        is not asked for."""
-        from .samplers.philox_gaussian_sampler import MAX_K, MAX_SAMPLES
-        hp, sampler, pred = self._hp, self._sampler, self.predictor
-        if getattr(sampler, 'device_cem_driver', None) is None or not hp.get('device_cem'):
-            return None
-        if not hasattr(pred, 'score_device') or getattr(pred, 'score_device_refusal', lambda: None)():
-            return None
-        if type(self).evaluate_rollouts is not PixelCostController.evaluate_rollouts:
-            return None
-        if hp.verbose and hp.verbose_every_iter:    # only the last rollout is resident when the call is through
-            return None
-        tail = list(hp.append_action) if hp.append_action else []
+        """``(K, M, tail)`` when this planning call can stay on the device, else None: the refusals of
+        ``_device_cem_shape`` with the predictor's ``score_device``, and trade-off weights only where the predictor applies
+        them on the device."""
         weights = self._task_weights()
-        if weights is not None and not getattr(pred, 'supports_task_weights', False):
+        if weights is not None and not getattr(self.predictor, 'supports_task_weights', False):
             return None
-        K = self._elite_count()
-        M = sampler.device_draws(self._t, hp.num_samples)
-        if not (2 <= K <= min(MAX_K, M) and M <= MAX_SAMPLES) or pred.cfg.adim != sampler._adim + len(tail):
-            return None
-        return K, M, tail
+        return self._device_cem_shape('score_device', PixelCostController.evaluate_rollouts)
 
-    def perform_CEM(self, state):
-        plan = self._device_cem_plan()
-        if plan is None:
-            return super(PixelCostController, self).perform_CEM(state)
-        from . import device_cem
-        hp, sampler, pred = self._hp, self._sampler, self.predictor
-        K, M, tail = plan
-        torch = pred._torch
-        self._logger.log('starting cem at t{} (device route)...'.format(self._t))
-        driver = getattr(device_cem, sampler.device_cem_driver)
-        dc = getattr(self, '_device_cem', None)
-        if type(dc) is not driver or (dc.K, dc.n_iter, dc.max_samples) != (K, self._n_iter, hp.num_samples):
-            dc = self._device_cem = driver(sampler, K, self._n_iter, hp.num_samples, pred.device, tail)
+    def _score_device_candidates(self, candidates, itr):
+        hp = self._hp
         weights = self._task_weights()
         kw = {'task_weights': weights} if weights is not None else {}
-        with torch.cuda.device(pred.device):
-            dc.begin(sampler, self._t, M, tail)
-            for itr in range(self._n_iter):
-                self._logger.log('iteration: ', itr)
-                candidates = dc.sample(itr, M, sampler.next_call())
-                context = {
-                    "context_frames": context_frames(self),
-                    "context_actions": sampler.chosen_actions,
-                    "context_pixel_distributions": self._make_input_distrib(itr),
-                    "context_states": context_states(self),
-                }
-                scores_dev = pred.score_device(context, candidates, goal_pix=self._goal_pix, finalweight=hp.finalweight,
-                                               only_take_first_view=hp.only_take_first_view, **kw)
-                dc.scores[itr, :M].copy_(scores_dev)
-                dc.refit(itr, scores_dev, candidates)       # (the last one names the final elites)
-            # the one download of the call: scores, elite indices, final elite plans, what the driver adds (trial counts,
-            # capped flags)
-            extra = dc.downloads(M)
-            parts = [dc.scores[:, :M], dc.elite_index, dc.elite_plans] + extra
-            if self.keep_device_candidates:
-                parts.append(dc.actions[:, :M])
-            packed = torch.cat([p.reshape(-1).to(torch.float64) for p in parts]).cpu().numpy()
-        sizes = np.cumsum([0] + [p.numel() for p in parts])
-        host = [packed[a:b].reshape(tuple(p.shape)) for p, a, b in zip(parts, sizes[:-1], sizes[1:])]
-        scores, elite_index, elite_plans = host[:3]
-        pred._check_scores(scores.reshape(-1))
-        for itr in range(self._n_iter):
-            self.plan_stat['scores_itr{}'.format(itr)] = scores[itr].copy()
-        self._best_indices = elite_index[-1].astype(np.int64)
-        self._best_actions = elite_plans.copy()
-        dc.finish(sampler, host[3:3 + len(extra)])
-        if self.keep_device_candidates:
-            self.device_candidates = [c.astype(np.float32) for c in host[3 + len(extra)]]
-            self.device_elite_indices = elite_index.astype(np.int64)
-        last = self._n_iter - 1
-        if hp.predictor_propagation:
-            self._chosen_distrib = pred.fetch_pixel_distributions(int(self._best_indices[0]))
+        context = {
+            "context_frames": context_frames(self),
+            "context_actions": self._sampler.chosen_actions,
+            "context_pixel_distributions": self._make_input_distrib(itr),
+            "context_states": context_states(self),
+        }
+        scores_dev = self.predictor.score_device(context, candidates, goal_pix=self._goal_pix, finalweight=hp.finalweight,
+                                                 only_take_first_view=hp.only_take_first_view, **kw)
+        return scores_dev, context
+
+    def _device_cem_finish(self, last, scores, context, downloaded):
+        if self._hp.predictor_propagation:
+            self._chosen_distrib = self.predictor.fetch_pixel_distributions(int(self._best_indices[0]))
         if self._verbose_condition(last):
-            self._visualize(last, scores[last], context, None)
-        self._t_since_replan = 0
+            self._visualize(last, scores, context, None)
 
     def _visualize(self, cem_itr, scores, context=None, actions=None):
         """Plan visualisation (reference :88-131).  Without a ``verbose_worker`` (or without the rollout's inputs) the

@@ -125,11 +125,37 @@ class LearnedCostController(CEMBaseController):
         else:
             prediction = self.predictor(self._with_centre_distribution(context), {'actions': actions})
             scores = self._host_scores(prediction['predicted_frames'], goal_enc)
+        self._log_and_page(cem_itr, scores, context, actions)
+        return scores
+
+    def _log_and_page(self, cem_itr, scores, context, actions):
+        """When the iteration is the one to show: its best scores and plan page."""
         if self._verbose_condition(cem_itr):
             self._logger.log('best scores itr {}: {}'.format(cem_itr, np.sort(scores)[:10]))
             if self._verbose_worker is not None:
                 self._put_plan_page(cem_itr, scores, context, actions)
-        return scores
+
+    # ------------------------------------------------------------------ device-resident CEM (DESIGN.md 6.1.2)
+    def _device_cem_plan(self):
+        return self._device_cem_shape('score_frames_device', LearnedCostController.evaluate_rollouts, pages_only=True)
+
+    def _score_device_candidates(self, candidates, itr):
+        context = {
+            "context_frames": self._images,
+            "context_actions": self._sampler.chosen_actions,
+            "context_states": context_states(self),
+        }
+        scores_dev = self.predictor.score_frames_device(context, candidates, self.scorer, goal_enc=self._goal_enc(),
+                                                        finalweight=self._hp.finalweight)
+        return scores_dev, context
+
+    def _device_cem_downloads(self):
+        return [self.predictor.last_frame_rows_dev]
+
+    def _device_cem_finish(self, last, scores, context, downloaded):
+        self.cost_perstep = np.ascontiguousarray(downloaded[0][:, 1:])
+        self._log_earlier_iterations(last)
+        self._log_and_page(last, scores, context, None)
 
     def _host_scores(self, gen_images, goal_enc):
         """Host scoring of materialised frames ``[M, T, ncam, H, W, 3]`` (in [0, 1])."""

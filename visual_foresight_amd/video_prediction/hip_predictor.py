@@ -598,13 +598,7 @@ class HipVPredEvaluation(object):
         if reason:
             raise ValueError(reason)
         torch = self._torch
-        T = self.sequence_length - self.n_context
-        if not torch.is_tensor(actions_dev) or actions_dev.device != self.device or actions_dev.dtype != torch.float32 \
-                or not actions_dev.is_contiguous() or tuple(actions_dev.shape[1:]) != (T, self.cfg.adim) \
-                or actions_dev.shape[0] < 1:
-            raise ValueError('actions_dev must be a contiguous float32 tensor [M, %d, %d] on %s'
-                             % (T, self.cfg.adim, self.device))
-        M = int(actions_dev.shape[0])
+        M = self._check_actions_dev(actions_dev)
         self._last_prepared = (context, actions_dev, M)
         with torch.cuda.device(self.device):
             scores, per_task = self._score_prepared(context, actions_dev, M, goal_pix, finalweight, index_base=0,
@@ -614,6 +608,30 @@ class HipVPredEvaluation(object):
                 scores = per_task[:, 0].contiguous()
         self.last_per_task_dev = per_task
         return scores
+
+    def _check_actions_dev(self, actions_dev):
+        """The candidates of a ``score*_device`` entry: a contiguous float32 tensor ``[M, T, adim]`` on this engine's device
+        -> ``M``."""
+        torch = self._torch
+        T = self.sequence_length - self.n_context
+        if not torch.is_tensor(actions_dev) or actions_dev.device != self.device or actions_dev.dtype != torch.float32 \
+                or not actions_dev.is_contiguous() or tuple(actions_dev.shape[1:]) != (T, self.cfg.adim) \
+                or actions_dev.shape[0] < 1:
+            raise ValueError('actions_dev must be a contiguous float32 tensor [M, %d, %d] on %s'
+                             % (T, self.cfg.adim, self.device))
+        return int(actions_dev.shape[0])
+
+    def frame_score_device_refusal(self):
+        """Why ``score_goal_image_device`` / ``score_frames_device`` cannot serve this predictor, or None when they can: every
+        clause of ``score_device_refusal`` but the frames-only one - a frame cost needs no distribution."""
+        if self._lanes:
+            return 'the device entries drive one engine: this predictor has %d in-process lanes (n_gpus > 1)' % len(self._lanes)
+        if _dist_info()[1] > 1:
+            return 'the device entries drive one engine: torch.distributed has %d ranks' % _dist_info()[1]
+        if type(self)._prepare is not HipVPredEvaluation._prepare or self.n_draws != 1:
+            return 'the device entries roll the actions as they lie on the device: %s prepares its sequences on the host' \
+                   % type(self).__name__
+        return None
 
     def _refuse_frames_only(self, what):
         if self.frames_only:
@@ -684,29 +702,66 @@ class HipVPredEvaluation(object):
         and a distribution context: the image centre is passed for both (``context_pixel_distributions`` of
         ``context`` is not read) and its pixel scores are dropped - the price is the ``ndesig`` distribution
         channels the network carries anyway.  A frames-only predictor carries none and passes neither."""
-        goal = self._check_goal_image(goal_image)
-        if steps not in ('last', 'weighted'):
-            raise ValueError("steps must be 'last' or 'weighted', got %r" % (steps,))
-        mode = 1 if steps == 'weighted' else 0
+        goal, mode = self._check_goal_cost(goal_image, steps)
         actions = self._check_actions(inputs['actions'])
         M = actions.shape[0]
         ncam, T = self.n_cam, self.sequence_length - self.n_context
         ctx_p, seqs = self._prepare(self._centre_context(context), actions)
         self._last_prepared = (ctx_p, seqs, M)
 
-        def rows_of(lane, share, n, lo):        # [score | per view | cost per step]
-            goal_dev = lane._goal_on_device(goal, goal_key)
-
-            def reduce(c_s, c_pv, c_cps):
-                _lib.check(lane._libh.vf_goal_image_scores(
-                    lane._handle, goal_dev.data_ptr(), mode, ctypes.c_float(finalweight), int(bool(first_view_only)),
-                    c_s.data_ptr(), c_pv.data_ptr(), c_cps.data_ptr(), lane._stream()))
-
-            return lane._roll_and_reduce(ctx_p, share, n, lo, (1, ncam, ncam * T), reduce)
+        def rows_of(lane, share, n, lo):
+            return lane._goal_rows(ctx_p, share, n, lo, goal, goal_key, mode, finalweight, first_view_only)
 
         rows_np = score_rows(self, seqs, M, 1 + ncam + ncam * T, rows_of)
-        self.last_goal_cost_per_step = np.ascontiguousarray(rows_np[:, 1 + ncam:]).reshape(M, ncam, T)
-        return np.ascontiguousarray(rows_np[:, 0]), np.ascontiguousarray(rows_np[:, 1:1 + ncam])
+        scores, per_view, self.last_goal_cost_per_step = self.split_goal_rows(rows_np)
+        return scores, per_view
+
+    def _check_goal_cost(self, goal_image, steps):
+        """The argument checks of the goal-image entries -> (float32 goal, the kernel's mode)."""
+        goal = self._check_goal_image(goal_image)
+        if steps not in ('last', 'weighted'):
+            raise ValueError("steps must be 'last' or 'weighted', got %r" % (steps,))
+        return goal, 1 if steps == 'weighted' else 0
+
+    def _goal_rows(self, ctx_p, seqs, n, lo, goal, goal_key, mode, finalweight, first_view_only):
+        """Roll ``n`` actions on this engine and reduce them against ``goal`` -> device rows
+        ``[n, score | per view | cost per step]``."""
+        ncam, T = self.n_cam, self.sequence_length - self.n_context
+        goal_dev = self._goal_on_device(goal, goal_key)
+
+        def reduce(c_s, c_pv, c_cps):
+            _lib.check(self._libh.vf_goal_image_scores(
+                self._handle, goal_dev.data_ptr(), mode, ctypes.c_float(finalweight), int(bool(first_view_only)),
+                c_s.data_ptr(), c_pv.data_ptr(), c_cps.data_ptr(), self._stream()))
+
+        return self._roll_and_reduce(ctx_p, seqs, n, lo, (1, ncam, ncam * T), reduce)
+
+    def split_goal_rows(self, rows_np):
+        """Host rows of the goal-image cost -> (scores [M], per view [M, ncam], cost per step [M, ncam, T])."""
+        ncam, T = self.n_cam, self.sequence_length - self.n_context
+        M = rows_np.shape[0]
+        return (np.ascontiguousarray(rows_np[:, 0]), np.ascontiguousarray(rows_np[:, 1:1 + ncam]),
+                np.ascontiguousarray(rows_np[:, 1 + ncam:]).reshape(M, ncam, T))
+
+    def score_goal_image_device(self, context, actions_dev, goal_image, steps='last', finalweight=10., first_view_only=False,
+                                goal_key=None):
+        """``score_goal_image`` without the gather, as ``score_device`` is ``score`` without it: roll ``actions_dev`` - a
+        contiguous float32 tensor ``[M, T, adim]`` on this engine's device - and return the device float64 ``scores [M]``.
+        Only enqueues (the context and goal uploads aside); the caller checks the downloaded scores with ``_check_scores``.
+        Chunked by ``run_batch_size``; the last chunk stays resident for ``render_plans``.  The whole rows
+        ``[M, score | per view | cost per step]`` stay in ``last_goal_rows_dev`` (``split_goal_rows`` reads them on the host).
+        ValueError: ``frame_score_device_refusal``.  A frames-only engine serves."""
+        reason = self.frame_score_device_refusal()
+        if reason:
+            raise ValueError(reason)
+        goal, mode = self._check_goal_cost(goal_image, steps)
+        M = self._check_actions_dev(actions_dev)
+        ctx_p = self._centre_context(context)
+        self._last_prepared = (ctx_p, actions_dev, M)
+        with self._torch.cuda.device(self.device):
+            rows = self._goal_rows(ctx_p, actions_dev, M, 0, goal, goal_key, mode, finalweight, first_view_only)
+            self.last_goal_rows_dev = rows
+            return rows[:, 0].contiguous()
 
     # ------------------------------------------------------------------ learned cost (frame scorer)
     def _scorer_here(self, scorer):
@@ -752,38 +807,66 @@ class HipVPredEvaluation(object):
         Sharding, chunking, lanes and latent draws are those of ``score`` (with ``n_gpus > 1`` the scorer is copied to
         every lane's device once).  As in ``score_goal_image`` the image centre stands in for the goal pixels and
         the distribution context the rollout entry wants."""
-        c, ncam = self.cfg, self.n_cam
         T = self.sequence_length - self.n_context
-        if (scorer.cfg.height, scorer.cfg.width, scorer.n_cam) != (c.height, c.width, ncam):
-            raise ValueError('the scorer is built for %dx%d, %d view(s); the predictor rolls %dx%d, %d view(s)'
-                             % (scorer.cfg.height, scorer.cfg.width, scorer.n_cam, c.height, c.width, ncam))
-        if scorer.cfg.head == 'embedding':
-            if goal_enc is None:
-                raise ValueError('the embedding head needs goal_enc [ncam, D]')
-            goal_enc = np.ascontiguousarray(goal_enc, dtype=np.float32)
-            if goal_enc.shape != (ncam, scorer.cfg.out_dim):
-                raise ValueError('goal_enc must be [%d, %d], got %s' % (ncam, scorer.cfg.out_dim, goal_enc.shape))
-        else:
-            goal_enc = None
+        goal_enc = self._check_scorer(scorer, goal_enc)
         actions = self._check_actions(inputs['actions'])
         M = actions.shape[0]
         ctx_p, seqs = self._prepare(self._centre_context(context), actions)
         self._last_prepared = (ctx_p, seqs, M)
 
-        def rows_of(lane, share, n, lo):        # [score | cost per step]
-            here = lane._scorer_here(scorer)
-            goal_dev = None if goal_enc is None else self._torch.from_numpy(goal_enc).to(lane.device)
-
-            def reduce(c_s, c_cps):
-                _lib.check(lane._libh.vf_scorer_scores(
-                    here._handle, lane._handle, None if goal_dev is None else goal_dev.data_ptr(),
-                    ctypes.c_float(finalweight), c_s.data_ptr(), c_cps.data_ptr(), None, lane._stream()))
-
-            return lane._roll_and_reduce(ctx_p, share, n, lo, (1, T), reduce)
+        def rows_of(lane, share, n, lo):
+            return lane._frame_rows(ctx_p, share, n, lo, scorer, goal_enc, finalweight)
 
         rows_np = score_rows(self, seqs, M, 1 + T, rows_of)
         self.last_frame_cost_per_step = np.ascontiguousarray(rows_np[:, 1:])
         return np.ascontiguousarray(rows_np[:, 0])
+
+    def _check_scorer(self, scorer, goal_enc):
+        """The argument checks of the learned-cost entries -> ``goal_enc`` as the kernel takes it (None: classifier head)."""
+        c, ncam = self.cfg, self.n_cam
+        if (scorer.cfg.height, scorer.cfg.width, scorer.n_cam) != (c.height, c.width, ncam):
+            raise ValueError('the scorer is built for %dx%d, %d view(s); the predictor rolls %dx%d, %d view(s)'
+                             % (scorer.cfg.height, scorer.cfg.width, scorer.n_cam, c.height, c.width, ncam))
+        if scorer.cfg.head != 'embedding':
+            return None
+        if goal_enc is None:
+            raise ValueError('the embedding head needs goal_enc [ncam, D]')
+        goal_enc = np.ascontiguousarray(goal_enc, dtype=np.float32)
+        if goal_enc.shape != (ncam, scorer.cfg.out_dim):
+            raise ValueError('goal_enc must be [%d, %d], got %s' % (ncam, scorer.cfg.out_dim, goal_enc.shape))
+        return goal_enc
+
+    def _frame_rows(self, ctx_p, seqs, n, lo, scorer, goal_enc, finalweight):
+        """Roll ``n`` actions on this engine and score their frames with ``scorer`` -> device rows
+        ``[n, score | cost per step]``."""
+        T = self.sequence_length - self.n_context
+        here = self._scorer_here(scorer)
+        goal_dev = None if goal_enc is None else self._torch.from_numpy(goal_enc).to(self.device)
+
+        def reduce(c_s, c_cps):
+            _lib.check(self._libh.vf_scorer_scores(
+                here._handle, self._handle, None if goal_dev is None else goal_dev.data_ptr(),
+                ctypes.c_float(finalweight), c_s.data_ptr(), c_cps.data_ptr(), None, self._stream()))
+
+        return self._roll_and_reduce(ctx_p, seqs, n, lo, (1, T), reduce)
+
+    def score_frames_device(self, context, actions_dev, scorer, goal_enc=None, finalweight=100.):
+        """``score_frames`` without the gather: roll ``actions_dev`` - a contiguous float32 tensor ``[M, T, adim]`` on this
+        engine's device - and return the device float64 ``scores [M]``.  Only enqueues (the context and ``goal_enc`` uploads
+        aside); the caller checks the downloaded scores with ``_check_scores``.  Chunked by ``run_batch_size``; the last chunk
+        stays resident for ``render_plans``.  The whole rows ``[M, score | cost per step]`` stay in ``last_frame_rows_dev``.
+        ValueError: ``frame_score_device_refusal``.  A frames-only engine serves."""
+        reason = self.frame_score_device_refusal()
+        if reason:
+            raise ValueError(reason)
+        goal_enc = self._check_scorer(scorer, goal_enc)
+        M = self._check_actions_dev(actions_dev)
+        ctx_p = self._centre_context(context)
+        self._last_prepared = (ctx_p, actions_dev, M)
+        with self._torch.cuda.device(self.device):
+            rows = self._frame_rows(ctx_p, actions_dev, M, 0, scorer, goal_enc, finalweight)
+            self.last_frame_rows_dev = rows
+            return rows[:, 0].contiguous()
 
     # ------------------------------------------------------------------ in-process multi-GPU (n_gpus > 1)
     def _gather_lane_rows(self, packed, M):
