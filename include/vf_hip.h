@@ -9,7 +9,7 @@
  * the calling thread.  No exception crosses this boundary.  Every device buffer - packed
  * weights, activations, predictions, schedules - is sized from the config and allocated in
  * vf_create(); no later call allocates device memory (vf_load_weights refills the same
- * buffers).  vf_set_context / vf_rollout / vf_export / vf_register(_hw) / vf_resize_area / vf_cem_refit / vf_cem_sample / vf_cem_soft_refit / vf_cem_sample_corr / vf_cem_sample_fold / vf_allgather_scores only
+ * buffers).  vf_set_context / vf_rollout / vf_export / vf_register(_hw) / vf_resize_area / vf_cem_refit / vf_cem_sample / vf_cem_soft_refit / vf_cem_sample_corr / vf_cem_sample_fold / vf_cem_latents / vf_cem_fold_latents / vf_allgather_scores only
  * enqueue work on the caller's HIP stream (hipStream_t passed as void*; NULL = the default
  * stream) and never synchronise it; a handle is driven from one stream at a time.
  * vf_load_weights, vf_device_status and the debug hooks are the blocking calls.
@@ -536,6 +536,25 @@ typedef struct vf_cem_fold_config {
  * 2 * n_scripted..4096. */
 int vf_cem_sample_fold(int32_t device, const vf_cem_fold_config *cfg, const void *d_workspace, uint32_t call, int32_t M,
                        float *d_actions, void *stream);
+
+/* The latent draws of a stochastic predictor on the device (BASELINE config 5: every candidate is rolled n_latent times with
+ * common random numbers).  The arithmetic is specified by philox_latents / fold_latents of
+ * visual_foresight_amd/video_prediction/stochastic_predictor.py.  vf_cem_latents writes d_z [n_latent][T][zdim] float32:
+ * z[d][t][j] is normal t * zdim + j of the counter {block, 0xFFFFFFFF, d, call} under the key {seed_lo, seed_hi} - Philox
+ * and Box-Muller as in vf_cem_sample, with a trial word no sampler uses, so the latents share no counter with the candidates
+ * when the seeds and call numbers are equal.  One wavefront per draw, no data-dependent loop.
+ * VF_ERR_INVALID (nothing launched): a NULL or not 4-byte aligned pointer, a negative device, n_latent, T or zdim < 1,
+ * T * zdim > 2^30. */
+int vf_cem_latents(int32_t device, uint32_t seed_lo, uint32_t seed_hi, uint32_t call, int32_t n_latent, int32_t T,
+                   int32_t zdim, float *d_z, void *stream);
+
+/* Fold the draws into the sample axis, draw-minor: d_seqs [M * n_latent][T][width + zdim] float32, row a * n_latent + d =
+ * [d_actions[a] | d_z[d]] per step, from d_actions [M][T][width] (as vf_cem_sample* write them, width = adim + tail) and d_z
+ * [n_latent][T][zdim].  Pure copying; 16-byte accesses when width and zdim are multiples of four and the three pointers are
+ * 16-byte aligned.  VF_ERR_INVALID (nothing launched): a NULL or not 4-byte aligned pointer, a negative device, M, n_latent,
+ * T, width or zdim < 1, M * n_latent rows or T * (width + zdim) floats per row that do not fit in int32. */
+int vf_cem_fold_latents(int32_t device, const float *d_actions, const float *d_z, int32_t M, int32_t n_latent, int32_t T,
+                        int32_t width, int32_t zdim, float *d_seqs, void *stream);
 
 /* The one collective of multi-GPU planning: all-gather every rank's n_local score values (float64)
  * (n_local equal on all ranks: pad ragged shards) into d_all [world * n_local] with RCCL over

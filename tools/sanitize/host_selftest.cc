@@ -474,6 +474,30 @@ int main() {
                 if (vf_cem_sample_fold(-1, &fold, p, 0, 18, img, nullptr) != VF_ERR_INVALID) rc = 1;
                 if (vf_cem_sample_fold(0, &fold, p, 0, 18, img, nullptr) != VF_ERR_HIP) rc = 1;         // all through: this build launches nothing
                 std::printf("  device CEM, folding: configuration and argument refusals: %s\n", rc ? "FAILED" : "ok");
+                // the latent draws and their fold: plain arguments, no configuration
+                struct { int n_latent, T, zdim; const char *msg; } bad_latents[] = {
+                    {0, 3, 8, "n_latent"}, {2, 0, 8, "T = 0"}, {2, 3, 0, "zdim"}, {2, 1 << 20, 1 << 11, "2^30"}};
+                for (const auto &c : bad_latents)
+                    if (vf_cem_latents(0, 1u, 2u, 3u, c.n_latent, c.T, c.zdim, img, nullptr) != VF_ERR_INVALID ||
+                        std::string(vf_last_error()).find(c.msg) == std::string::npos) {
+                        std::fprintf(stderr, "vf_cem_latents: want refusal '%s', got '%s'\n", c.msg, vf_last_error()); rc = 1;
+                    }
+                if (vf_cem_latents(0, 1u, 2u, 3u, 2, 3, 8, nullptr, nullptr) != VF_ERR_INVALID) rc = 1;
+                if (vf_cem_latents(-1, 1u, 2u, 3u, 2, 3, 8, img, nullptr) != VF_ERR_INVALID) rc = 1;
+                if (vf_cem_latents(0, 1u, 2u, 3u, 2, 3, 8, img, nullptr) != VF_ERR_HIP) rc = 1;           // all through: this build launches nothing
+                struct { int M, n_latent, T, width, zdim; const char *msg; } bad_fold_latents[] = {
+                    {0, 2, 3, 4, 8, "M = 0"}, {4, 0, 3, 4, 8, "n_latent"}, {4, 2, 0, 4, 8, "T = 0"}, {4, 2, 3, 0, 8, "width"},
+                    {4, 2, 3, 4, 0, "zdim"}, {1 << 20, 1 << 11, 3, 4, 8, "rows do not fit"}, {4, 2, 1 << 28, 4, 4, "per row"}};
+                for (const auto &c : bad_fold_latents)
+                    if (vf_cem_fold_latents(0, img, img, c.M, c.n_latent, c.T, c.width, c.zdim, img, nullptr) != VF_ERR_INVALID ||
+                        std::string(vf_last_error()).find(c.msg) == std::string::npos) {
+                        std::fprintf(stderr, "vf_cem_fold_latents: want refusal '%s', got '%s'\n", c.msg, vf_last_error()); rc = 1;
+                    }
+                if (vf_cem_fold_latents(0, nullptr, img, 4, 2, 3, 4, 8, img, nullptr) != VF_ERR_INVALID) rc = 1;
+                if (vf_cem_fold_latents(0, img, img, 4, 2, 3, 4, 8, nullptr, nullptr) != VF_ERR_INVALID) rc = 1;
+                if (vf_cem_fold_latents(-1, img, img, 4, 2, 3, 4, 8, img, nullptr) != VF_ERR_INVALID) rc = 1;
+                if (vf_cem_fold_latents(0, img, img, 4, 2, 3, 4, 8, img, nullptr) != VF_ERR_HIP) rc = 1;
+                std::printf("  device CEM, latent draws: argument refusals: %s\n", rc ? "FAILED" : "ok");
             }
             int32_t pix[2] = {0, 0};
             float out2[2];

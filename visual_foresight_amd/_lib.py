@@ -33,7 +33,8 @@ EXPORTS = ('vf_abi_version', 'vf_last_error', 'vf_weight_count', 'vf_create', 'v
            'vf_invmodel_weight_count', 'vf_invmodel_create', 'vf_invmodel_destroy', 'vf_invmodel_load_weights',
            'vf_invmodel_infer', 'vf_debug_lstm_layer', 'vf_register_hw', 'vf_resize_area',
            'vf_cem_workspace_bytes', 'vf_cem_refit', 'vf_cem_sample',
-           'vf_cem_corr_workspace_bytes', 'vf_cem_soft_refit', 'vf_cem_sample_corr', 'vf_cem_sample_fold')
+           'vf_cem_corr_workspace_bytes', 'vf_cem_soft_refit', 'vf_cem_sample_corr', 'vf_cem_sample_fold',
+           'vf_cem_latents', 'vf_cem_fold_latents')
 ABI_VERSION = 7
 
 
@@ -181,6 +182,9 @@ def load_library():
     lib.vf_cem_soft_refit.restype = lib.vf_cem_sample_corr.restype = ctypes.c_int
     lib.vf_cem_sample_fold.argtypes = [ctypes.c_int32, ctypes.POINTER(VfCemFoldConfig), P, ctypes.c_uint32, ctypes.c_int32, P, P]
     lib.vf_cem_sample_fold.restype = ctypes.c_int
+    lib.vf_cem_latents.argtypes = [ctypes.c_int32] + [ctypes.c_uint32] * 3 + [ctypes.c_int32] * 3 + [P, P]
+    lib.vf_cem_fold_latents.argtypes = [ctypes.c_int32, P, P] + [ctypes.c_int32] * 5 + [P, P]
+    lib.vf_cem_latents.restype = lib.vf_cem_fold_latents.restype = ctypes.c_int
     lib.vf_allgather_scores.argtypes = [P, P, P, ctypes.c_int32, P, P]
     lib.vf_comm_init_all.argtypes = [ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(P)]
     lib.vf_comm_destroy.argtypes = [P]

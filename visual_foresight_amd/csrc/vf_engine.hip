@@ -2600,6 +2600,40 @@ static int cem_sample_fold_check(int32_t device, const vf_cem_fold_config *c, co
     return VF_OK;
 }
 
+// the refusals of vf_cem_latents / vf_cem_fold_latents (host work only, as above)
+static int cem_latents_check(int32_t device, int32_t n_latent, int32_t T, int32_t zdim, const float *d_z) {
+    const std::string w("vf_cem_latents");
+    if (n_latent < 1) return fail(VF_ERR_INVALID, w + ": n_latent = " + std::to_string(n_latent) + ", need at least 1");
+    if (T < 1) return fail(VF_ERR_INVALID, w + ": T = " + std::to_string(T) + ", need at least 1");
+    if (zdim < 1) return fail(VF_ERR_INVALID, w + ": zdim = " + std::to_string(zdim) + ", need at least 1");
+    if ((long long)T * zdim > (1LL << 30))
+        return fail(VF_ERR_INVALID, w + ": T * zdim = " + std::to_string((long long)T * zdim) + " exceeds 2^30");
+    if (device < 0) return fail(VF_ERR_INVALID, w + ": device = " + std::to_string(device) + " is negative");
+    if (!d_z) return fail(VF_ERR_INVALID, w + ": null argument");
+    if (reinterpret_cast<uintptr_t>(d_z) % 4) return fail(VF_ERR_INVALID, w + ": d_z must be 4-byte aligned");
+    return VF_OK;
+}
+static int cem_fold_latents_check(int32_t device, const float *d_actions, const float *d_z, int32_t M, int32_t n_latent,
+                                  int32_t T, int32_t width, int32_t zdim, const float *d_seqs) {
+    const std::string w("vf_cem_fold_latents");
+    if (M < 1) return fail(VF_ERR_INVALID, w + ": M = " + std::to_string(M) + ", need at least 1");
+    if (n_latent < 1) return fail(VF_ERR_INVALID, w + ": n_latent = " + std::to_string(n_latent) + ", need at least 1");
+    if (T < 1) return fail(VF_ERR_INVALID, w + ": T = " + std::to_string(T) + ", need at least 1");
+    if (width < 1) return fail(VF_ERR_INVALID, w + ": width = " + std::to_string(width) + ", need at least 1");
+    if (zdim < 1) return fail(VF_ERR_INVALID, w + ": zdim = " + std::to_string(zdim) + ", need at least 1");
+    if ((long long)M * n_latent > INT32_MAX)
+        return fail(VF_ERR_INVALID, w + ": M * n_latent = " + std::to_string((long long)M * n_latent) + " rows do not fit in int32");
+    if ((long long)T * ((long long)width + zdim) > INT32_MAX)
+        return fail(VF_ERR_INVALID, w + ": T * (width + zdim) = " + std::to_string((long long)T * ((long long)width + zdim)) +
+                                        " floats per row do not fit in int32");
+    if (device < 0) return fail(VF_ERR_INVALID, w + ": device = " + std::to_string(device) + " is negative");
+    if (!d_actions || !d_z || !d_seqs) return fail(VF_ERR_INVALID, w + ": null argument");
+    if (reinterpret_cast<uintptr_t>(d_actions) % 4 || reinterpret_cast<uintptr_t>(d_z) % 4 ||
+        reinterpret_cast<uintptr_t>(d_seqs) % 4)
+        return fail(VF_ERR_INVALID, w + ": d_actions, d_z and d_seqs must be 4-byte aligned");
+    return VF_OK;
+}
+
 // the refusals of vf_cem_corr_workspace_bytes / vf_cem_soft_refit / vf_cem_sample_corr (host work only, as above)
 static int cem_corr_config_check(const vf_cem_corr_config *c, const char *who) {
     const std::string w(who);
@@ -3016,6 +3050,20 @@ extern "C" int vf_cem_sample_fold(int32_t device, const vf_cem_fold_config *cfg,
                                   float *d_actions, void *) {       // (refusal paths only, as above)
     VF_API_TRY
     if (int rc = cem_sample_fold_check(device, cfg, d_workspace, M, d_actions)) return rc;
+    return fail(VF_ERR_HIP, "the host self-test build launches nothing");
+    VF_API_CATCH(int)
+}
+extern "C" int vf_cem_latents(int32_t device, uint32_t, uint32_t, uint32_t, int32_t n_latent, int32_t T, int32_t zdim,
+                              float *d_z, void *) {        // (refusal paths only, as above)
+    VF_API_TRY
+    if (int rc = cem_latents_check(device, n_latent, T, zdim, d_z)) return rc;
+    return fail(VF_ERR_HIP, "the host self-test build launches nothing");
+    VF_API_CATCH(int)
+}
+extern "C" int vf_cem_fold_latents(int32_t device, const float *d_actions, const float *d_z, int32_t M, int32_t n_latent,
+                                   int32_t T, int32_t width, int32_t zdim, float *d_seqs, void *) {     // (refusal paths only, as above)
+    VF_API_TRY
+    if (int rc = cem_fold_latents_check(device, d_actions, d_z, M, n_latent, T, width, zdim, d_seqs)) return rc;
     return fail(VF_ERR_HIP, "the host self-test build launches nothing");
     VF_API_CATCH(int)
 }
@@ -3701,6 +3749,46 @@ int vf_cem_sample_fold(int32_t device, const vf_cem_fold_config *cfg, const void
     p.workspace = d_workspace;
     hipLaunchKernelGGL(cem_sample_fold_kernel, dim3((M + kCemWaves - 1) / kCemWaves), dim3(kCemThreads), 0,
                        reinterpret_cast<hipStream_t>(stream), p);
+    VF_HIP_CHECK(hipGetLastError());
+    return VF_OK;
+    VF_API_CATCH(int)
+}
+
+int vf_cem_latents(int32_t device, uint32_t seed_lo, uint32_t seed_hi, uint32_t call, int32_t n_latent, int32_t T,
+                   int32_t zdim, float *d_z, void *stream) {
+    VF_API_TRY
+    if (int rc = cem_latents_check(device, n_latent, T, zdim, d_z)) return rc;
+    VF_HIP_CHECK(hipSetDevice(device));
+    CemLatentParams p = {};
+    p.n_latent = n_latent;
+    p.N = (long long)T * zdim;
+    p.n_blocks = (int)((p.N + 3) / 4);
+    p.seed_lo = seed_lo; p.seed_hi = seed_hi; p.call = call;
+    p.z = d_z;
+    hipLaunchKernelGGL(cem_latents_kernel, dim3((n_latent + kCemWaves - 1) / kCemWaves), dim3(kCemThreads), 0,
+                       reinterpret_cast<hipStream_t>(stream), p);
+    VF_HIP_CHECK(hipGetLastError());
+    return VF_OK;
+    VF_API_CATCH(int)
+}
+
+int vf_cem_fold_latents(int32_t device, const float *d_actions, const float *d_z, int32_t M, int32_t n_latent, int32_t T,
+                        int32_t width, int32_t zdim, float *d_seqs, void *stream) {
+    VF_API_TRY
+    if (int rc = cem_fold_latents_check(device, d_actions, d_z, M, n_latent, T, width, zdim, d_seqs)) return rc;
+    VF_HIP_CHECK(hipSetDevice(device));
+    // float4s where every piece of a row starts on a 16-byte boundary
+    const bool vec = width % 4 == 0 && zdim % 4 == 0 && reinterpret_cast<uintptr_t>(d_actions) % 16 == 0 &&
+                     reinterpret_cast<uintptr_t>(d_z) % 16 == 0 && reinterpret_cast<uintptr_t>(d_seqs) % 16 == 0;
+    CemFoldLatentParams p = {};
+    p.n_latent = n_latent; p.T = T; p.width = width; p.zdim = zdim;
+    p.total = (long long)M * n_latent * T * (((long long)width + zdim) / (vec ? 4 : 1));
+    p.actions = d_actions; p.z = d_z; p.seqs = d_seqs;
+    const long long blocks = (p.total + kCemThreads - 1) / kCemThreads;
+    const dim3 grid((unsigned)(blocks < kCemFoldMaxBlocks ? blocks : kCemFoldMaxBlocks)), block(kCemThreads);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (vec) hipLaunchKernelGGL(cem_fold_latents_kernel<true>, grid, block, 0, st, p);
+    else hipLaunchKernelGGL(cem_fold_latents_kernel<false>, grid, block, 0, st, p);
     VF_HIP_CHECK(hipGetLastError());
     return VF_OK;
     VF_API_CATCH(int)

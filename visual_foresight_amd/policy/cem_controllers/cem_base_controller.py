@@ -174,7 +174,9 @@ class CEMBaseController(Policy):
         tail = list(hp.append_action) if hp.append_action else []
         K = self._elite_count()
         M = sampler.device_draws(self._t, hp.num_samples)
-        if not (2 <= K <= min(MAX_K, M) and M <= MAX_SAMPLES) or pred.cfg.adim != sampler._adim + len(tail):
+        # (the caller's action width: a stochastic predictor's engine takes adim + zdim, the latents are folded in later)
+        width = pred._adim_in() if hasattr(pred, '_adim_in') else pred.cfg.adim
+        if not (2 <= K <= min(MAX_K, M) and M <= MAX_SAMPLES) or width != sampler._adim + len(tail):
             return None
         return K, M, tail
 

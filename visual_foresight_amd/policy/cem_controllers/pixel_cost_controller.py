@@ -214,13 +214,17 @@ class PixelCostController(CEMBaseController):
 
     # ------------------------------------------------------------------ device-resident CEM
     def _device_cem_plan(self):
+        return self._pixel_cost_device_plan(PixelCostController.evaluate_rollouts)
+
+    def _pixel_cost_device_plan(self, own_evaluate):
         """``(K, M, tail)`` when this planning call can stay on the device, else None: the refusals of
         ``_device_cem_shape`` with the predictor's ``score_device``, and trade-off weights only where the predictor applies
-        them on the device."""
+        them on the device.  ``own_evaluate``: the ``evaluate_rollouts`` of the class whose device hooks answer - a subclass
+        that overrides it again without them plans on the host."""
         weights = self._task_weights()
         if weights is not None and not getattr(self.predictor, 'supports_task_weights', False):
             return None
-        return self._device_cem_shape('score_device', PixelCostController.evaluate_rollouts)
+        return self._device_cem_shape('score_device', own_evaluate)
 
     def _score_device_candidates(self, candidates, itr):
         hp = self._hp

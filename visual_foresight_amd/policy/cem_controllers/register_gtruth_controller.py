@@ -122,10 +122,28 @@ class RegisterGtruthController(PixelCostController):
         return np.stack(desig, 0).reshape(self._n_cam, self._n_desig, 2), tradeoff
 
     def evaluate_rollouts(self, actions, cem_itr):
+        self._register_at_first_iteration(cem_itr)
+        return super(RegisterGtruthController, self).evaluate_rollouts(actions, cem_itr)
+
+    def _register_at_first_iteration(self, cem_itr):
         if self._hp.register_gtruth and cem_itr == 0:
             current = self._images[-1].astype(np.float32) / 255.
             self._desig_pix, self.reg_tradeoff = self.register_gtruth(self.start_image, current)
-        return super(RegisterGtruthController, self).evaluate_rollouts(actions, cem_itr)
+
+    # ------------------------------------------------------------------ device-resident CEM
+    def _device_cem_plan(self):
+        """The parent's refusals against this class's own ``evaluate_rollouts``, and registration through
+        ``predictor.register`` (``registration_on_device``): the NumPy path of ``registration.py`` plans on the host."""
+        if not (hasattr(self.predictor, 'register') and self._hp.registration_on_device):
+            return None
+        return self._pixel_cost_device_plan(RegisterGtruthController.evaluate_rollouts)
+
+    def _score_device_candidates(self, candidates, itr):
+        """Register before the first rollout - ``register()`` downloads the tracked pixels and warp errors, the one
+        synchronisation of the call besides its download - then score as the parent does (the trade-off weights reach the
+        rollout through ``_task_weights``)."""
+        self._register_at_first_iteration(itr)
+        return super(RegisterGtruthController, self)._score_device_candidates(candidates, itr)
 
     def _task_weights(self):
         return self.reg_tradeoff if self._hp.trade_off_reg else None

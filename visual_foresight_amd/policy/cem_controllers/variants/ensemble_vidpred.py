@@ -74,6 +74,27 @@ class CEM_Controller_Ensemble_Vidpred(PixelCostController):
             self._visualize(cem_itr, scores)
         return scores
 
+    # ------------------------------------------------------------------ device-resident CEM
+    def _device_cem_plan(self):
+        """The parent's refusals against this class's own ``evaluate_rollouts``, with a predictor that keeps the ensemble's
+        cost rows on the device (``EnsembleHipPredictor.score_device``)."""
+        if not hasattr(self.predictor, 'last_cost_rows_dev'):
+            return None
+        return self._pixel_cost_device_plan(CEM_Controller_Ensemble_Vidpred.evaluate_rollouts)
+
+    def _device_cem_downloads(self):
+        """The last iteration's rows ``[M, score | per task | per task x step]``: the per-step columns are ``cost_perstep``."""
+        return [self.predictor.last_cost_rows_dev]
+
+    def _device_cem_finish(self, last, scores, context, downloaded):
+        _, per_task, cps = self.predictor.split_cost_rows(downloaded[0])
+        if self._hp.only_take_first_view:
+            per_task = per_task[:, :1]
+        self.predictor.last_cost_per_step = cps
+        self.cost_perstep = cps.reshape(cps.shape[0], self._n_cam, self._n_desig, cps.shape[2])
+        self._log_task_scores(scores, per_task)
+        super(CEM_Controller_Ensemble_Vidpred, self)._device_cem_finish(last, scores, context, downloaded)
+
     def _visualize(self, cem_itr, scores, context=None, actions=None):
         """The reference's ensemble controller has no plan page: the best scores are logged."""
         self._logger.log('best scores itr {}: {}'.format(cem_itr, np.sort(scores)[:10]))

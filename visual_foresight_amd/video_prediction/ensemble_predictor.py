@@ -14,6 +14,10 @@ the ensemble scores on the device - no predicted video leaves the GPU.
 
 Multi-GPU: under ``torch.distributed`` every rank holds all E members on its own GPU, scores its action shard and the
 score rows are all-gathered unchanged.  In-process lanes (``n_gpus > 1`` without ``torch.distributed``) are refused.
+
+``score_device`` is ``score`` without the gather, for the device-resident CEM route: the members roll
+device candidates as they lie there.  Stochastic members need the counter-based latent stream for it (the member option
+``philox_latents=True`` selects ``PhiloxStochasticHipPredictor``; member 0 draws and folds once for all members).
 """
 import ctypes
 import os
@@ -23,7 +27,7 @@ import numpy as np
 from visual_foresight_amd import _lib
 from visual_foresight_amd.video_prediction.hip_predictor import HipVPredEvaluation, pixel_cost_columns, score_rows
 from visual_foresight_amd.video_prediction.sharding import dist_info as _dist_info
-from visual_foresight_amd.video_prediction.stochastic_predictor import StochasticHipPredictor
+from visual_foresight_amd.video_prediction.stochastic_predictor import PhiloxStochasticHipPredictor, StochasticHipPredictor
 
 
 class EnsembleHipPredictor(object):
@@ -56,7 +60,10 @@ class EnsembleHipPredictor(object):
         stochastic = hp.pop('stochastic', None)
         if stochastic is None:
             stochastic = 'n_latent' in hp or hp.get('arch', 'cdna') != 'cdna'
-        member_cls = StochasticHipPredictor if stochastic else HipVPredEvaluation
+        philox = bool(hp.pop('philox_latents', False))       # the latent stream the device entries can draw
+        if philox and not stochastic:
+            raise ValueError('philox_latents selects the latent stream of stochastic members: these members draw none')
+        member_cls = (PhiloxStochasticHipPredictor if philox else StochasticHipPredictor) if stochastic else HipVPredEvaluation
         self.model_path = model_path
         seed = int(hp.get('seed', 0))
         self.members = [member_cls('', dict(hp, seed=seed + 1000 * m), n_gpus=n_gpus, first_gpu=first_gpu)
@@ -67,6 +74,7 @@ class EnsembleHipPredictor(object):
             setattr(self, name, getattr(m0, name))
         self.weights = None
         self.last_cost_per_step = None
+        self.last_cost_rows_dev = None      # score_device: [M, score | per task | per task x step] on the device
         self._last_prepared = None
 
     # ------------------------------------------------------------------ weights
@@ -105,12 +113,79 @@ class EnsembleHipPredictor(object):
         with m0._scoring_call(actions):
             return m0._prepare(context, actions)
 
+    def _adim_in(self):
+        return self.members[0]._adim_in()
+
     def score_device_refusal(self):
-        """Why ``score_device`` cannot serve the ensemble (``HipVPredEvaluation.score_device_refusal``)."""
-        return 'score_device rolls the actions as they lie on the device: the ensemble prepares its sequences on the host'
+        """Why ``score_device`` cannot serve the ensemble, or None when it can: the members' own refusals
+        (``HipVPredEvaluation.score_device_refusal``: ranks, sequences prepared on the host)."""
+        m0 = self.members[0]
+        if m0._prepares_on_host():
+            return 'score_device rolls the actions as they lie on the device: the ensemble prepares its sequences on the host'
+        return m0.score_device_refusal()
+
+    def _member_rows(self, prepared, local, n, lo, goal_pix, finalweight, task_weights):
+        """Every member rolls the device sequences ``local [n * n_draws, T, engine adim]`` (actions ``[lo, lo + n)`` of the
+        call ``prepared = (context, sequences, M)``), chunk by chunk, and ``vf_ensemble_scores`` reduces each chunk -> device
+        float64 rows ``[n, score | per task | per task x step]``.  Only enqueues (the context upload aside)."""
+        torch = self._torch
+        m0 = self.members[0]
+        T = self.sequence_length - self.n_context
+        ntask = self.n_cam * self.cfg.ndesig
+        nd = self.n_draws
+        tw = m0._task_weights_c(task_weights)
+        handles = (ctypes.c_void_p * self.num_ensembles)(*[m._handle.value for m in self.members])
+        for member in self.members:
+            member._last_prepared = prepared
+            member._set_context(prepared[0])
+        rows = torch.empty((n, 1 + ntask + ntask * T), dtype=torch.float64, device=self.device)
+        scores, per_task, cps = rows[:, 0], rows[:, 1:1 + ntask], rows[:, 1 + ntask:]
+        bs = self.run_batch_size // nd
+        own_s = torch.empty(bs, dtype=torch.float64, device=self.device)
+        own_pt = torch.empty((bs, ntask), dtype=torch.float64, device=self.device)
+        c_s = torch.empty(bs, dtype=torch.float64, device=self.device)
+        c_pt = torch.empty((bs, ntask), dtype=torch.float64, device=self.device)
+        c_cps = torch.empty((bs, ntask * T), dtype=torch.float64, device=self.device)
+        for c0 in range(0, n, bs):
+            c1 = min(c0 + bs, n)
+            for member in self.members:
+                member._rollout_chunk(local[c0 * nd:c1 * nd], goal_pix, finalweight, own_s[:c1 - c0],
+                                      own_pt[:c1 - c0], task_weights)
+                member._last_lo, member._last_M = lo + c0, c1 - c0
+            _lib.check(m0._libh.vf_ensemble_scores(handles, self.num_ensembles, ctypes.c_float(self.lambda_variance),
+                                                   ctypes.c_float(finalweight), tw, c_s.data_ptr(), c_pt.data_ptr(),
+                                                   c_cps.data_ptr(), m0._stream()))
+            scores[c0:c1], per_task[c0:c1], cps[c0:c1] = c_s[:c1 - c0], c_pt[:c1 - c0], c_cps[:c1 - c0]
+        return rows
 
     def score_device(self, context, actions_dev, goal_pix, finalweight=10., only_take_first_view=False, task_weights=None):
-        raise ValueError(self.score_device_refusal())
+        """``score`` without the gather: every member rolls ``actions_dev`` - a contiguous float32 tensor ``[M, T, adim]`` on
+        the members' device - and the device float64 ensemble ``scores [M]`` come back.  Only enqueues (the context upload
+        aside, when it changed); the caller checks the downloaded scores with ``_check_scores``.  Chunked by
+        ``run_batch_size`` like ``score``; every member keeps its last chunk resident, and ``actions_dev`` must stay untouched
+        for as long as ``fetch_pixel_distributions`` may be asked.  With stochastic members, member 0 draws and folds the
+        call's latents once for all (one call number, as in ``score``).  The whole rows stay in ``last_cost_rows_dev``
+        ``[M, score | per task | per task x step]``.  ValueError: ``score_device_refusal``."""
+        reason = self.score_device_refusal()
+        if reason:
+            raise ValueError(reason)
+        torch = self._torch
+        m0 = self.members[0]
+        M = m0._check_actions_dev(actions_dev)
+        with torch.cuda.device(self.device):
+            ctx_p, seqs = m0._prepare_device(context, actions_dev)
+            self._last_prepared = (ctx_p, seqs, M)
+            rows = self._member_rows(self._last_prepared, seqs, M, 0, goal_pix, finalweight, task_weights)
+            self.last_cost_rows_dev = rows
+            # (only_take_first_view: task 0 alone is the score, pixel_cost_columns)
+            return rows[:, 1 if only_take_first_view else 0].contiguous()
+
+    def split_cost_rows(self, rows_np):
+        """Host rows of the ensemble cost -> (scores [M], per task [M, ncam*nd], cost per step [M, ncam*nd, T])."""
+        ntask = self.n_cam * self.cfg.ndesig
+        M = rows_np.shape[0]
+        return (np.ascontiguousarray(rows_np[:, 0]), np.ascontiguousarray(rows_np[:, 1:1 + ntask]),
+                np.ascontiguousarray(rows_np[:, 1 + ntask:]).reshape(M, ntask, -1))
 
     def score(self, context, inputs, goal_pix, finalweight=10., only_take_first_view=False, task_weights=None):
         """Ensemble cost of every action: (scores[M], scores_per_task[M, ncam*nd]) float64, as
@@ -122,36 +197,12 @@ class EnsembleHipPredictor(object):
         M = actions.shape[0]
         T = self.sequence_length - self.n_context
         ntask = self.n_cam * self.cfg.ndesig
-        nd = self.n_draws
         ctx_p, seqs = self._prepare(context, actions)
         self._last_prepared = (ctx_p, seqs, M)
-        tw = m0._task_weights_c(task_weights)
-        handles = (ctypes.c_void_p * self.num_ensembles)(*[m._handle.value for m in self.members])
 
         def rows_of(_, share, n, lo):       # [score | per task | per task x step]; the engines are the members
-            for member in self.members:
-                member._last_prepared = (ctx_p, seqs, M)
-                member._set_context(ctx_p)
             local = torch.from_numpy(np.ascontiguousarray(share, dtype=np.float32)).to(self.device)
-            rows = torch.empty((n, 1 + ntask + ntask * T), dtype=torch.float64, device=self.device)
-            scores, per_task, cps = rows[:, 0], rows[:, 1:1 + ntask], rows[:, 1 + ntask:]
-            bs = self.run_batch_size // nd
-            own_s = torch.empty(bs, dtype=torch.float64, device=self.device)
-            own_pt = torch.empty((bs, ntask), dtype=torch.float64, device=self.device)
-            c_s = torch.empty(bs, dtype=torch.float64, device=self.device)
-            c_pt = torch.empty((bs, ntask), dtype=torch.float64, device=self.device)
-            c_cps = torch.empty((bs, ntask * T), dtype=torch.float64, device=self.device)
-            for c0 in range(0, n, bs):
-                c1 = min(c0 + bs, n)
-                for member in self.members:
-                    member._rollout_chunk(local[c0 * nd:c1 * nd], goal_pix, finalweight, own_s[:c1 - c0],
-                                          own_pt[:c1 - c0], task_weights)
-                    member._last_lo, member._last_M = lo + c0, c1 - c0
-                _lib.check(m0._libh.vf_ensemble_scores(handles, self.num_ensembles, ctypes.c_float(self.lambda_variance),
-                                                       ctypes.c_float(finalweight), tw, c_s.data_ptr(), c_pt.data_ptr(),
-                                                       c_cps.data_ptr(), m0._stream()))
-                scores[c0:c1], per_task[c0:c1], cps[c0:c1] = c_s[:c1 - c0], c_pt[:c1 - c0], c_cps[:c1 - c0]
-            return rows
+            return self._member_rows((ctx_p, seqs, M), local, n, lo, goal_pix, finalweight, task_weights)
 
         rows_np = score_rows(self, seqs, M, 1 + ntask + ntask * T, rows_of)
         self.last_cost_per_step = np.ascontiguousarray(rows_np[:, 1 + ntask:]).reshape(M, ntask, T)

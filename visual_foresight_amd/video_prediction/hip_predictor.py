@@ -488,6 +488,19 @@ class HipVPredEvaluation(object):
         """(context, actions[n]) -> (engine context, sequences[n * n_draws])."""
         return context, actions
 
+    def _prepare_device(self, context, actions_dev):
+        """``_prepare`` for candidates that lie on this engine's device (the ``score*_device`` entries; only enqueues, under
+        this engine's device): nothing here.  A class that overrides ``_prepare`` brings its own or refuses the device entries
+        (``_prepares_on_host``)."""
+        return context, actions_dev
+
+    def _prepares_on_host(self):
+        """Whether the device entries cannot serve this class: its ``_prepare`` is overridden below the ``_prepare_device`` it
+        would run with (that hook prepares something else), or several draws per action meet the plain hook."""
+        mro = type(self).__mro__
+        host, device = (next(i for i, c in enumerate(mro) if name in vars(c)) for name in ('_prepare', '_prepare_device'))
+        return device > host or (type(self)._prepare_device is HipVPredEvaluation._prepare_device and self.n_draws != 1)
+
     def _scoring_call(self, actions):
         """Context manager around one scoring call on ``actions`` (``score*``; the ensemble enters member 0's): nothing here,
         the stochastic predictor holds the call's latent draws in it."""
@@ -582,7 +595,7 @@ class HipVPredEvaluation(object):
             return 'score_device drives one engine: this predictor has %d in-process lanes (n_gpus > 1)' % len(self._lanes)
         if _dist_info()[1] > 1:
             return 'score_device drives one engine: torch.distributed has %d ranks' % _dist_info()[1]
-        if type(self)._prepare is not HipVPredEvaluation._prepare or self.n_draws != 1:
+        if self._prepares_on_host():
             return 'score_device rolls the actions as they lie on the device: %s prepares its sequences on the host' \
                    % type(self).__name__
         return None
@@ -599,9 +612,10 @@ class HipVPredEvaluation(object):
             raise ValueError(reason)
         torch = self._torch
         M = self._check_actions_dev(actions_dev)
-        self._last_prepared = (context, actions_dev, M)
         with torch.cuda.device(self.device):
-            scores, per_task = self._score_prepared(context, actions_dev, M, goal_pix, finalweight, index_base=0,
+            ctx_p, seqs = self._prepare_device(context, actions_dev)
+            self._last_prepared = (ctx_p, seqs, M)
+            scores, per_task = self._score_prepared(ctx_p, seqs, M, goal_pix, finalweight, index_base=0,
                                                     task_weights=task_weights)
             if only_take_first_view:        # task 0 alone is the score (pixel_cost_columns)
                 per_task = per_task[:, :1]
@@ -615,10 +629,10 @@ class HipVPredEvaluation(object):
         torch = self._torch
         T = self.sequence_length - self.n_context
         if not torch.is_tensor(actions_dev) or actions_dev.device != self.device or actions_dev.dtype != torch.float32 \
-                or not actions_dev.is_contiguous() or tuple(actions_dev.shape[1:]) != (T, self.cfg.adim) \
+                or not actions_dev.is_contiguous() or tuple(actions_dev.shape[1:]) != (T, self._adim_in()) \
                 or actions_dev.shape[0] < 1:
             raise ValueError('actions_dev must be a contiguous float32 tensor [M, %d, %d] on %s'
-                             % (T, self.cfg.adim, self.device))
+                             % (T, self._adim_in(), self.device))
         return int(actions_dev.shape[0])
 
     def frame_score_device_refusal(self):
@@ -628,7 +642,7 @@ class HipVPredEvaluation(object):
             return 'the device entries drive one engine: this predictor has %d in-process lanes (n_gpus > 1)' % len(self._lanes)
         if _dist_info()[1] > 1:
             return 'the device entries drive one engine: torch.distributed has %d ranks' % _dist_info()[1]
-        if type(self)._prepare is not HipVPredEvaluation._prepare or self.n_draws != 1:
+        if self._prepares_on_host():
             return 'the device entries roll the actions as they lie on the device: %s prepares its sequences on the host' \
                    % type(self).__name__
         return None
@@ -756,10 +770,10 @@ class HipVPredEvaluation(object):
             raise ValueError(reason)
         goal, mode = self._check_goal_cost(goal_image, steps)
         M = self._check_actions_dev(actions_dev)
-        ctx_p = self._centre_context(context)
-        self._last_prepared = (ctx_p, actions_dev, M)
         with self._torch.cuda.device(self.device):
-            rows = self._goal_rows(ctx_p, actions_dev, M, 0, goal, goal_key, mode, finalweight, first_view_only)
+            ctx_p, seqs = self._prepare_device(self._centre_context(context), actions_dev)
+            self._last_prepared = (ctx_p, seqs, M)
+            rows = self._goal_rows(ctx_p, seqs, M, 0, goal, goal_key, mode, finalweight, first_view_only)
             self.last_goal_rows_dev = rows
             return rows[:, 0].contiguous()
 
@@ -861,10 +875,10 @@ class HipVPredEvaluation(object):
             raise ValueError(reason)
         goal_enc = self._check_scorer(scorer, goal_enc)
         M = self._check_actions_dev(actions_dev)
-        ctx_p = self._centre_context(context)
-        self._last_prepared = (ctx_p, actions_dev, M)
         with self._torch.cuda.device(self.device):
-            rows = self._frame_rows(ctx_p, actions_dev, M, 0, scorer, goal_enc, finalweight)
+            ctx_p, seqs = self._prepare_device(self._centre_context(context), actions_dev)
+            self._last_prepared = (ctx_p, seqs, M)
+            rows = self._frame_rows(ctx_p, seqs, M, 0, scorer, goal_enc, finalweight)
             self.last_frame_rows_dev = rows
             return rows[:, 0].contiguous()
 
