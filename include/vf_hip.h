@@ -9,7 +9,7 @@
  * the calling thread.  No exception crosses this boundary.  Every device buffer - packed
  * weights, activations, predictions, schedules - is sized from the config and allocated in
  * vf_create(); no later call allocates device memory (vf_load_weights refills the same
- * buffers).  vf_set_context / vf_rollout / vf_export / vf_register(_hw) / vf_resize_area / vf_cem_refit / vf_cem_sample / vf_cem_soft_refit / vf_cem_sample_corr / vf_cem_sample_fold / vf_cem_latents / vf_cem_fold_latents / vf_allgather_scores only
+ * buffers).  vf_set_context / vf_rollout / vf_export / vf_register(_hw) / vf_resize_area / vf_cem_refit / vf_cem_sample / vf_cem_soft_refit / vf_cem_sample_corr / vf_cem_sample_fold / vf_cem_sample_autograsp / vf_cem_latents / vf_cem_fold_latents / vf_allgather_scores only
  * enqueue work on the caller's HIP stream (hipStream_t passed as void*; NULL = the default
  * stream) and never synchronise it; a handle is driven from one stream at a time.
  * vf_load_weights, vf_device_status and the debug hooks are the blocking calls.
@@ -536,6 +536,42 @@ typedef struct vf_cem_fold_config {
  * 2 * n_scripted..4096. */
 int vf_cem_sample_fold(int32_t device, const vf_cem_fold_config *cfg, const void *d_workspace, uint32_t call, int32_t M,
                        float *d_actions, void *stream);
+
+/* The autograsp proposal (reference visual_mpc/policy/cem_controllers/samplers/autograsp_sampler.py:5-58): a Gaussian proposal
+ * over the moves whose last action column, the gripper command, is not sampled but derived from the planned height.  The
+ * arithmetic is specified by the float64 class visual_foresight_amd/policy/cem_controllers/samplers/philox_autograsp_sampler.py.
+ * The proposal, its workspace and its refit are vf_cem_config's: cfg->adim counts the MOVES (at least 3: column 2 is the
+ * lift), cfg->tail >= 1 counts the gripper column (column adim; tail_value[0] is not read) and the appended constants behind
+ * it (tail_value[1 ..]); size the workspace with vf_cem_workspace_bytes, refit with vf_cem_refit and upload the first
+ * proposal as for vf_cem_sample, all under that cfg.  The moves are vf_cem_sample's of the same cfg, counter and workspace.
+ * Height mode, per sample, from the float32 moves z_t that are stored: c_0 = float64(z_0) * action_norm_factor,
+ * c_t = c_(t-1) + float64(z_t) * action_norm_factor, shut_t = c_t + state_z < z_thresh, every operation rounded once; unless
+ * reopen the gripper stays shut from the first shut step on; then, with deviation_prob > 0, step t is flipped when
+ * u_t < deviation_prob, u_t = word (t % 4) / 2^32 of the counter {block t / 4, 0xFFFFFFFE, sample i, call} - a trial word no
+ * sampler and no latent draw uses.  Share mode (a refit that keeps the elites' gripper): share_t = float32(elites whose
+ * gripper value at step t is float32(close_cmd)) / float32(n_elites), shut_t = u_t < share_t; no latch, no deviation.
+ * The column holds float32(close_cmd) where shut, float32(open_cmd) elsewhere. */
+typedef struct vf_cem_grip_config {
+    int32_t mode;               /* 0: by height, 1: by the elites' share */
+    int32_t reopen;             /* height mode: the gripper may open again once it has shut */
+    double state_z;             /* the height the planning call starts from */
+    double action_norm_factor;  /* lift action -> height */
+    double z_thresh;            /* shut below this height */
+    double deviation_prob;      /* height mode: chance of flipping a step, in [0, 1] */
+    double close_cmd, open_cmd;
+} vf_cem_grip_config;
+
+/* Draw M <= 4096 candidates as sampling call number `call`: d_actions [M][nactions * repeat][adim + tail] float32 - moves,
+ * gripper, appended constants - d_trials [M] and d_capped [M] as vf_cem_sample.  Share mode first computes d_share [T]
+ * (float32, caller-owned scratch) from d_elite_plans [n_elites][T][adim + tail] (as vf_cem_refit wrote them) in a kernel of
+ * one workgroup on the same stream; height mode reads neither and both may be NULL.  One wavefront per sample; the only
+ * data-dependent loop is the trial loop, bounded by max_trials.
+ * VF_ERR_INVALID (nothing launched): a NULL cfg, grip or pointer, a workspace that is not 16-byte or another pointer that is
+ * not 4-byte aligned, an invalid cfg, adim < 3, tail < 1, M outside 1..4096, a mode other than 0 / 1, deviation_prob outside
+ * [0, 1] or NaN, share mode without d_elite_plans or d_share. */
+int vf_cem_sample_autograsp(int32_t device, const vf_cem_config *cfg, const vf_cem_grip_config *grip, const void *d_workspace,
+                            uint32_t call, int32_t M, const float *d_elite_plans, float *d_share, float *d_actions,
+                            int32_t *d_trials, int32_t *d_capped, void *stream);
 
 /* The latent draws of a stochastic predictor on the device (BASELINE config 5: every candidate is rolled n_latent times with
  * common random numbers).  The arithmetic is specified by philox_latents / fold_latents of

@@ -474,6 +474,36 @@ int main() {
                 if (vf_cem_sample_fold(-1, &fold, p, 0, 18, img, nullptr) != VF_ERR_INVALID) rc = 1;
                 if (vf_cem_sample_fold(0, &fold, p, 0, 18, img, nullptr) != VF_ERR_HIP) rc = 1;         // all through: this build launches nothing
                 std::printf("  device CEM, folding: configuration and argument refusals: %s\n", rc ? "FAILED" : "ok");
+                // the same for the autograsp proposal: the moves' vf_cem_config with the gripper column leading the tail
+                vf_cem_config ag = good;
+                ag.adim = 3; ag.tail = 1;
+                vf_cem_grip_config grip = {0, 0, 0.25, 1.0, 0.15, 0.0, 1.0, -1.0};
+                struct { int adim, tail, mode; double dev; int M; const char *msg; } bad_ag[] = {
+                    {2, 1, 0, 0.0, 4, "move channels"}, {3, 0, 0, 0.0, 4, "gripper column"}, {3, 6, 0, 0.0, 4, "adim + tail"},
+                    {3, 1, 2, 0.0, 4, "mode"}, {3, 1, 0, -0.5, 4, "deviation_prob"}, {3, 1, 0, 1.5, 4, "deviation_prob"},
+                    {3, 1, 0, inf - inf, 4, "deviation_prob"}, {3, 1, 0, 0.0, 0, "M = 0"}, {3, 1, 0, 0.0, 4097, "M = 4097"}};
+                for (const auto &c : bad_ag) {
+                    vf_cem_config b = ag;
+                    vf_cem_grip_config g = grip;
+                    b.adim = c.adim; b.tail = c.tail; g.mode = c.mode; g.deviation_prob = c.dev;
+                    if (vf_cem_sample_autograsp(0, &b, &g, p, 0, c.M, nullptr, nullptr, img, pi, pi, nullptr) != VF_ERR_INVALID ||
+                        std::string(vf_last_error()).find(c.msg) == std::string::npos) {
+                        std::fprintf(stderr, "vf_cem_sample_autograsp: want refusal '%s', got '%s'\n", c.msg, vf_last_error()); rc = 1;
+                    }
+                }
+                vf_cem_grip_config by_share = grip;
+                by_share.mode = 1;
+                if (vf_cem_sample_autograsp(0, nullptr, &grip, p, 0, 4, nullptr, nullptr, img, pi, pi, nullptr) != VF_ERR_INVALID) rc = 1;
+                if (vf_cem_sample_autograsp(0, &ag, nullptr, p, 0, 4, nullptr, nullptr, img, pi, pi, nullptr) != VF_ERR_INVALID) rc = 1;
+                if (vf_cem_sample_autograsp(0, &ag, &grip, nullptr, 0, 4, nullptr, nullptr, img, pi, pi, nullptr) != VF_ERR_INVALID) rc = 1;
+                if (vf_cem_sample_autograsp(0, &ag, &grip, odd, 0, 4, nullptr, nullptr, img, pi, pi, nullptr) != VF_ERR_INVALID) rc = 1;
+                if (vf_cem_sample_autograsp(0, &ag, &grip, p, 0, 4, nullptr, nullptr, nullptr, pi, pi, nullptr) != VF_ERR_INVALID) rc = 1;
+                if (vf_cem_sample_autograsp(0, &ag, &by_share, p, 0, 4, nullptr, img, img, pi, pi, nullptr) != VF_ERR_INVALID) rc = 1;
+                if (vf_cem_sample_autograsp(0, &ag, &by_share, p, 0, 4, img, nullptr, img, pi, pi, nullptr) != VF_ERR_INVALID) rc = 1;
+                if (vf_cem_sample_autograsp(-1, &ag, &grip, p, 0, 4, nullptr, nullptr, img, pi, pi, nullptr) != VF_ERR_INVALID) rc = 1;
+                if (vf_cem_sample_autograsp(0, &ag, &grip, p, 0, 4, nullptr, nullptr, img, pi, pi, nullptr) != VF_ERR_HIP) rc = 1;   // all through
+                if (vf_cem_sample_autograsp(0, &ag, &by_share, p, 0, 4, img, img, img, pi, pi, nullptr) != VF_ERR_HIP) rc = 1;
+                std::printf("  device CEM, autograsp: configuration and argument refusals: %s\n", rc ? "FAILED" : "ok");
                 // the latent draws and their fold: plain arguments, no configuration
                 struct { int n_latent, T, zdim; const char *msg; } bad_latents[] = {
                     {0, 3, 8, "n_latent"}, {2, 0, 8, "T = 0"}, {2, 3, 0, "zdim"}, {2, 1 << 20, 1 << 11, "2^30"}};

@@ -34,7 +34,7 @@ EXPORTS = ('vf_abi_version', 'vf_last_error', 'vf_weight_count', 'vf_create', 'v
            'vf_invmodel_infer', 'vf_debug_lstm_layer', 'vf_register_hw', 'vf_resize_area',
            'vf_cem_workspace_bytes', 'vf_cem_refit', 'vf_cem_sample',
            'vf_cem_corr_workspace_bytes', 'vf_cem_soft_refit', 'vf_cem_sample_corr', 'vf_cem_sample_fold',
-           'vf_cem_latents', 'vf_cem_fold_latents')
+           'vf_cem_sample_autograsp', 'vf_cem_latents', 'vf_cem_fold_latents')
 ABI_VERSION = 7
 
 
@@ -75,6 +75,12 @@ class VfCemFoldConfig(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ('nactions', 'repeat', 'tail', 'n_elites', 'n_scripted', 'reserved')] + \
                [('seed_lo', ctypes.c_uint32), ('seed_hi', ctypes.c_uint32)] + \
                [('start_xy', ctypes.c_double * 2), ('max_shift', ctypes.c_double * 3), ('tail_value', ctypes.c_double * 8)]
+
+
+class VfCemGripConfig(ctypes.Structure):
+    _fields_ = [('mode', ctypes.c_int32), ('reopen', ctypes.c_int32)] + \
+               [(n, ctypes.c_double) for n in ('state_z', 'action_norm_factor', 'z_thresh', 'deviation_prob', 'close_cmd',
+                                               'open_cmd')]
 
 
 class VfInvModelConfig(ctypes.Structure):
@@ -182,6 +188,9 @@ def load_library():
     lib.vf_cem_soft_refit.restype = lib.vf_cem_sample_corr.restype = ctypes.c_int
     lib.vf_cem_sample_fold.argtypes = [ctypes.c_int32, ctypes.POINTER(VfCemFoldConfig), P, ctypes.c_uint32, ctypes.c_int32, P, P]
     lib.vf_cem_sample_fold.restype = ctypes.c_int
+    lib.vf_cem_sample_autograsp.argtypes = [ctypes.c_int32, ctypes.POINTER(VfCemConfig), ctypes.POINTER(VfCemGripConfig), P,
+                                            ctypes.c_uint32, ctypes.c_int32, P, P, P, P, P, P]
+    lib.vf_cem_sample_autograsp.restype = ctypes.c_int
     lib.vf_cem_latents.argtypes = [ctypes.c_int32] + [ctypes.c_uint32] * 3 + [ctypes.c_int32] * 3 + [P, P]
     lib.vf_cem_fold_latents.argtypes = [ctypes.c_int32, P, P] + [ctypes.c_int32] * 5 + [P, P]
     lib.vf_cem_latents.restype = lib.vf_cem_fold_latents.restype = ctypes.c_int

@@ -1,7 +1,8 @@
 // vf_cem.h - one CEM iteration on the device: elite selection + refit, and sampling of the next candidates, for the Gaussian
 // proposal (first part), for the time-correlated noise proposal (second part) and for the folding proposal (third part, which
 // shares the Gaussian workspace and refit and adds a sampling kernel); the fourth part draws a stochastic predictor's latents
-// and folds them into the candidates.  The later parts have header comments of their own.
+// and folds them into the candidates; the fifth is the autograsp proposal, the Gaussian one with a derived gripper column.
+// The later parts have header comments of their own.
 //
 // Specification: visual_foresight_amd/policy/cem_controllers/samplers/philox_gaussian_sampler.py (a float64 NumPy class that
 // is a sampler in its own right).  These kernels compute its numbers: elite indices, trial counts, mean and A bit for bit;
@@ -144,22 +145,31 @@ __device__ __forceinline__ double cem_clip(double v, double lo, double hi) {    
     return v < lo ? lo : (v > hi ? hi : v);
 }
 
-VF_GLOBAL VF_LAUNCH_BOUNDS(kCemThreads) void cem_sample_kernel(const CemParams p) {
-    const int lane = threadIdx.x & 63;
-    const int i = blockIdx.x * kCemWaves + (threadIdx.x >> 6);
-    if (i >= p.M) return;               // whole waves leave: nothing below waits for another wave
-    const int D = p.nactions * p.adim, T = p.nactions * p.repeat, W = p.adim + p.tail;
+// What a lane holds of its sample after the trials: its two dimensions, their action columns and rejection limits, the
+// values of the accepted (or last) trial, the trials taken.  cem_sample_kernel and cem_sample_autograsp_kernel share it.
+struct CemLane {
+    int d0, d1, c0, c1;
+    double x0, x1, lim0, lim1;
+    int n;
+    bool accepted;
+};
+
+// The trials of sample i (every lane of its wave calls this: the shuffles and the vote are wave-wide).
+__device__ __forceinline__ CemLane cem_draw(const CemParams &p, int lane, int i) {
+    const int D = p.nactions * p.adim;
     const char *ws = static_cast<const char *>(p.workspace);
     const double *mean = reinterpret_cast<const double *>(ws + kCemHeaderBytes);
     const double *A = mean + D;
     int R = *reinterpret_cast<const int *>(ws);
     R = max(0, min(R, cem_rmax(D, p.K)));       // never past the workspace, whatever the header holds
     const int n_blocks = (R + 3) >> 2;          // <= 64: one per lane
-    const int d0 = lane, d1 = lane + 64;
+    CemLane s;
+    s.d0 = lane; s.d1 = lane + 64;
+    const int d0 = s.d0, d1 = s.d1;
     const bool live0 = d0 < D, live1 = d1 < D;
-    const int c0 = live0 ? d0 % p.adim : 0, c1 = live1 ? d1 % p.adim : 0;
+    s.c0 = live0 ? d0 % p.adim : 0; s.c1 = live1 ? d1 % p.adim : 0;
     const double m0 = live0 ? mean[d0] : 0.0, m1 = live1 ? mean[d1] : 0.0;
-    const double lim0 = p.rej_lim[c0], lim1 = p.rej_lim[c1];
+    const double lim0 = p.rej_lim[s.c0], lim1 = p.rej_lim[s.c1];
     double x0 = m0, x1 = m1;
     int n = 0;
     bool accepted = false;
@@ -188,23 +198,40 @@ VF_GLOBAL VF_LAUNCH_BOUNDS(kCemThreads) void cem_sample_kernel(const CemParams p
         const bool ok = (!live0 || fabs(x0) <= lim0) && (!live1 || fabs(x1) <= lim1);
         if (!p.rejection || __all(ok)) { accepted = true; break; }
     }
+    s.x0 = x0; s.x1 = x1; s.lim0 = lim0; s.lim1 = lim1;
+    s.n = n; s.accepted = accepted;
+    return s;
+}
+
+// The float32 value a lane stores for its dimension of `half`: clipped when capped, discretised, truncated, zeroed
+__device__ __forceinline__ float cem_emit(const CemParams &p, const CemLane &s, int half, int i) {
+    const int c = half ? s.c1 : s.c0;
+    double v = half ? s.x1 : s.x0;
+    const double lim = half ? s.lim1 : s.lim0;
+    if (!s.accepted) v = cem_clip(v, -lim, lim);
+    if ((p.discrete_mask >> c) & 1) v = cem_clip(floor(v), 0.0, 4.0);
+    const double tl = p.trunc_lim[c];
+    v = cem_clip(v, -tl, tl);
+    if (p.zero_first && i == 0) v = 0.0;
+    return (float)v;
+}
+
+VF_GLOBAL VF_LAUNCH_BOUNDS(kCemThreads) void cem_sample_kernel(const CemParams p) {
+    const int lane = threadIdx.x & 63;
+    const int i = blockIdx.x * kCemWaves + (threadIdx.x >> 6);
+    if (i >= p.M) return;               // whole waves leave: nothing below waits for another wave
+    const int D = p.nactions * p.adim, T = p.nactions * p.repeat, W = p.adim + p.tail;
+    const CemLane s = cem_draw(p, lane, i);
     if (lane == 0) {
-        p.trials[i] = accepted ? n + 1 : p.max_trials;
-        p.capped[i] = accepted ? 0 : 1;
+        p.trials[i] = s.accepted ? s.n + 1 : p.max_trials;
+        p.capped[i] = s.accepted ? 0 : 1;
     }
     float *out = p.actions_out + (long long)i * T * W;
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
-        const int d = half ? d1 : d0, c = half ? c1 : c0;
+        const int d = half ? s.d1 : s.d0, c = half ? s.c1 : s.c0;
         if (d >= D) continue;
-        double v = half ? x1 : x0;
-        const double lim = half ? lim1 : lim0;
-        if (!accepted) v = cem_clip(v, -lim, lim);
-        if ((p.discrete_mask >> c) & 1) v = cem_clip(floor(v), 0.0, 4.0);
-        const double tl = p.trunc_lim[c];
-        v = cem_clip(v, -tl, tl);
-        if (p.zero_first && i == 0) v = 0.0;
-        const float f = (float)v;
+        const float f = cem_emit(p, s, half, i);
         const int a = d / p.adim;
         for (int q = 0; q < p.repeat; ++q) out[(a * p.repeat + q) * W + c] = f;
     }
@@ -578,6 +605,108 @@ VF_GLOBAL VF_LAUNCH_BOUNDS(kCemThreads) void cem_fold_latents_kernel(const CemFo
         const float *from = q < W ? p.actions : p.z;
         if (VEC) reinterpret_cast<float4 *>(p.seqs)[g] = reinterpret_cast<const float4 *>(from)[src];
         else p.seqs[g] = from[src];
+    }
+}
+
+// ------------------------------------------------------------------ the autograsp proposal
+// Specification: samplers/philox_autograsp_sampler.py.  The moves (columns 0 .. adim - 1), their workspace and their refit are
+// the Gaussian proposal's: cem_draw / cem_emit above and cem_refit_kernel, under a CemParams whose adim counts the moves and
+// whose tail counts the gripper column (column adim) and the appended constants behind it.  The gripper column is derived
+// from the float32 moves the kernel stores, so it equals the specification's on those moves bit for bit whatever the
+// device's log / sin / cos did to them.
+//
+//   cem_grip_share_kernel        ONE workgroup, share mode only: share[t] = float32(count_t) / float32(K), count_t the
+//                                elites whose gripper value at step t is the close command - one thread per step in a loop,
+//                                so that the sampling kernel reads T floats, not K * T elite values per sample.
+//   cem_sample_autograsp_kernel  one wavefront per sample, four per workgroup, no LDS, no barrier.  The moves as
+//                                cem_sample_kernel; the trial loop, bounded by max_trials, stays the only data-dependent
+//                                loop.  Steps go in rounds of 64, lane l owning step 64 * round + l.  Height mode: EVERY lane
+//                                runs the serial chain c_t = c_(t-1) + float64(z_t) * norm, h_t = c_t + state_z (z_t fetched
+//                                by __shfl from the lane that owns the lift of step t's action, every operation rounded
+//                                once, the latch carried along) and keeps the decision of its own step - a shuffle scan
+//                                would round differently.  The uniform of step t is word t % 4 of Philox block t / 4 under
+//                                trial 0xFFFFFFFE (no sampler's trial, not the latents' 0xFFFFFFFF): it flips the step with
+//                                deviation_prob (none drawn when that is 0) or, in share mode, shuts it when u < share[t].
+constexpr unsigned kCemGripTrial = 0xFFFFFFFEu;
+constexpr int kCemGripHeight = 0, kCemGripShare = 1;
+constexpr int kCemGripLift = 2;         // the move channel the height follows
+
+struct CemGripParams {
+    int mode, reopen;
+    double state_z, norm, z_thresh, deviation_prob;
+    float close_cmd, open_cmd;
+    const float *elite_plans;           // share mode: [K][T][W]
+    float *share;                       // share mode: [T]
+};
+
+VF_GLOBAL VF_LAUNCH_BOUNDS(kCemThreads) void cem_grip_share_kernel(const CemGripParams g, int K, int T, int W, int col) {
+    for (int t = threadIdx.x; t < T; t += kCemThreads) {
+        int count = 0;
+        for (int k = 0; k < K; ++k) count += g.elite_plans[((long long)k * T + t) * W + col] == g.close_cmd ? 1 : 0;
+        g.share[t] = __fdiv_rn((float)count, (float)K);
+    }
+}
+
+VF_GLOBAL VF_LAUNCH_BOUNDS(kCemThreads) void cem_sample_autograsp_kernel(const CemParams p, const CemGripParams g) {
+    const int lane = threadIdx.x & 63;
+    const int i = blockIdx.x * kCemWaves + (threadIdx.x >> 6);
+    if (i >= p.M) return;               // whole waves leave: nothing below waits for another wave
+    const int D = p.nactions * p.adim, T = p.nactions * p.repeat, W = p.adim + p.tail;
+    const CemLane s = cem_draw(p, lane, i);
+    if (lane == 0) {
+        p.trials[i] = s.accepted ? s.n + 1 : p.max_trials;
+        p.capped[i] = s.accepted ? 0 : 1;
+    }
+    float *out = p.actions_out + (long long)i * T * W;
+    float f0 = 0.f, f1 = 0.f;           // what this lane stores for d0 and d1
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+        const int d = half ? s.d1 : s.d0, c = half ? s.c1 : s.c0;
+        if (d >= D) continue;
+        const float f = cem_emit(p, s, half, i);
+        if (half) f1 = f; else f0 = f;
+        const int a = d / p.adim;
+        for (int q = 0; q < p.repeat; ++q) out[(a * p.repeat + q) * W + c] = f;
+    }
+    const bool by_height = g.mode == kCemGripHeight;
+    const bool draws = !by_height || g.deviation_prob > 0.0;
+    double c = 0.0;
+    bool latched = false;
+    for (int base = 0; base < T; base += 64) {          // (uniform: every lane runs every round and every chain step)
+        bool shut = false;
+        if (by_height) {
+            const int steps = min(64, T - base);
+            for (int l = 0; l < steps; ++l) {
+                const int d = ((base + l) / p.repeat) * p.adim + kCemGripLift;      // < D: its lane stored a value
+                const float z0 = __shfl(f0, d & 63), z1 = __shfl(f1, d & 63);
+                const double step = __dmul_rn((double)(d < 64 ? z0 : z1), g.norm);
+                c = base + l == 0 ? step : __dadd_rn(c, step);
+                bool below = __dadd_rn(c, g.state_z) < g.z_thresh;
+                if (!g.reopen) {
+                    latched = latched || below;
+                    below = latched;
+                }
+                if (l == lane) shut = below;
+            }
+        }
+        const int t = base + lane;      // (no shuffle below: the lanes past T may idle)
+        if (t < T) {
+            if (draws) {
+                unsigned w[4];
+                cem_philox((unsigned)(t >> 2), kCemGripTrial, (unsigned)i, p.call, p.seed_lo, p.seed_hi, w);
+                const int q = t & 3;
+                const unsigned word = q == 0 ? w[0] : (q == 1 ? w[1] : (q == 2 ? w[2] : w[3]));
+                const double u = __ddiv_rn((double)word, 4294967296.0);
+                if (by_height) shut = shut != (u < g.deviation_prob);
+                else shut = u < (double)g.share[t];
+            }
+            out[t * W + p.adim] = shut ? g.close_cmd : g.open_cmd;
+        }
+    }
+    const int consts = p.tail - 1;      // the appended constants follow the gripper column: tail_value[1 ..]
+    for (int e = lane; e < T * consts; e += 64) {
+        const int t = e / consts, k = e % consts;
+        out[t * W + p.adim + 1 + k] = (float)p.tail_value[1 + k];
     }
 }
 

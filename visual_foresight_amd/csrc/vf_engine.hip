@@ -2600,6 +2600,33 @@ static int cem_sample_fold_check(int32_t device, const vf_cem_fold_config *c, co
     return VF_OK;
 }
 
+// the refusals of vf_cem_sample_autograsp (host work only, as above); cfg is the moves' vf_cem_config, its tail led by the gripper
+static int cem_sample_autograsp_check(int32_t device, const vf_cem_config *cfg, const vf_cem_grip_config *grip,
+                                      const void *d_workspace, int32_t M, const float *d_elite_plans, const float *d_share,
+                                      const float *d_actions, const int32_t *d_trials, const int32_t *d_capped) {
+    const std::string w("vf_cem_sample_autograsp");
+    if (int rc = cem_config_check(cfg, "vf_cem_sample_autograsp")) return rc;
+    if (cfg->adim < kCemGripLift + 1)
+        return fail(VF_ERR_INVALID, w + ": adim = " + std::to_string(cfg->adim) + " move channels, the height reads channel 2");
+    if (cfg->tail < 1) return fail(VF_ERR_INVALID, w + ": tail = 0 leaves no gripper column behind the moves");
+    if (!grip) return fail(VF_ERR_INVALID, w + ": null grip");
+    if (grip->mode != kCemGripHeight && grip->mode != kCemGripShare)
+        return fail(VF_ERR_INVALID, w + ": mode = " + std::to_string(grip->mode) + " is neither 0 (height) nor 1 (share)");
+    if (!(grip->deviation_prob >= 0.0 && grip->deviation_prob <= 1.0))
+        return fail(VF_ERR_INVALID, w + ": deviation_prob outside [0, 1]");
+    if (device < 0) return fail(VF_ERR_INVALID, w + ": device = " + std::to_string(device) + " is negative");
+    if (!d_workspace || !d_actions || !d_trials || !d_capped) return fail(VF_ERR_INVALID, w + ": null argument");
+    if (grip->mode == kCemGripShare && (!d_elite_plans || !d_share))
+        return fail(VF_ERR_INVALID, w + ": share mode needs d_elite_plans and d_share");
+    if (reinterpret_cast<uintptr_t>(d_workspace) % 16) return fail(VF_ERR_INVALID, w + ": d_workspace must be 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(d_actions) % 4 || reinterpret_cast<uintptr_t>(d_trials) % 4 ||
+        reinterpret_cast<uintptr_t>(d_capped) % 4 || reinterpret_cast<uintptr_t>(d_elite_plans) % 4 ||
+        reinterpret_cast<uintptr_t>(d_share) % 4)
+        return fail(VF_ERR_INVALID, w + ": d_actions, d_trials, d_capped, d_elite_plans and d_share must be 4-byte aligned");
+    if (M < 1 || M > kCemMaxM) return fail(VF_ERR_INVALID, w + ": M = " + std::to_string(M) + " outside 1.." + std::to_string(kCemMaxM));
+    return VF_OK;
+}
+
 // the refusals of vf_cem_latents / vf_cem_fold_latents (host work only, as above)
 static int cem_latents_check(int32_t device, int32_t n_latent, int32_t T, int32_t zdim, const float *d_z) {
     const std::string w("vf_cem_latents");
@@ -3050,6 +3077,15 @@ extern "C" int vf_cem_sample_fold(int32_t device, const vf_cem_fold_config *cfg,
                                   float *d_actions, void *) {       // (refusal paths only, as above)
     VF_API_TRY
     if (int rc = cem_sample_fold_check(device, cfg, d_workspace, M, d_actions)) return rc;
+    return fail(VF_ERR_HIP, "the host self-test build launches nothing");
+    VF_API_CATCH(int)
+}
+extern "C" int vf_cem_sample_autograsp(int32_t device, const vf_cem_config *cfg, const vf_cem_grip_config *grip,
+                                       const void *d_workspace, uint32_t, int32_t M, const float *d_elite_plans, float *d_share,
+                                       float *d_actions, int32_t *d_trials, int32_t *d_capped, void *) {   // (refusal paths only)
+    VF_API_TRY
+    if (int rc = cem_sample_autograsp_check(device, cfg, grip, d_workspace, M, d_elite_plans, d_share, d_actions, d_trials, d_capped))
+        return rc;
     return fail(VF_ERR_HIP, "the host self-test build launches nothing");
     VF_API_CATCH(int)
 }
@@ -3749,6 +3785,35 @@ int vf_cem_sample_fold(int32_t device, const vf_cem_fold_config *cfg, const void
     p.workspace = d_workspace;
     hipLaunchKernelGGL(cem_sample_fold_kernel, dim3((M + kCemWaves - 1) / kCemWaves), dim3(kCemThreads), 0,
                        reinterpret_cast<hipStream_t>(stream), p);
+    VF_HIP_CHECK(hipGetLastError());
+    return VF_OK;
+    VF_API_CATCH(int)
+}
+
+int vf_cem_sample_autograsp(int32_t device, const vf_cem_config *cfg, const vf_cem_grip_config *grip, const void *d_workspace,
+                            uint32_t call, int32_t M, const float *d_elite_plans, float *d_share, float *d_actions,
+                            int32_t *d_trials, int32_t *d_capped, void *stream) {
+    VF_API_TRY
+    if (int rc = cem_sample_autograsp_check(device, cfg, grip, d_workspace, M, d_elite_plans, d_share, d_actions, d_trials, d_capped))
+        return rc;
+    VF_HIP_CHECK(hipSetDevice(device));
+    CemParams p = cem_params(*cfg, M);
+    p.call = call;
+    p.actions_out = d_actions; p.trials = d_trials; p.capped = d_capped;
+    p.workspace = const_cast<void *>(d_workspace);
+    CemGripParams g = {};
+    g.mode = grip->mode; g.reopen = grip->reopen != 0;
+    g.state_z = grip->state_z; g.norm = grip->action_norm_factor; g.z_thresh = grip->z_thresh;
+    g.deviation_prob = grip->deviation_prob;
+    g.close_cmd = (float)grip->close_cmd; g.open_cmd = (float)grip->open_cmd;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (g.mode == kCemGripShare) {
+        g.elite_plans = d_elite_plans; g.share = d_share;
+        hipLaunchKernelGGL(cem_grip_share_kernel, dim3(1), dim3(kCemThreads), 0, st, g, cfg->n_elites,
+                           cfg->nactions * cfg->repeat, cfg->adim + cfg->tail, cfg->adim);
+        VF_HIP_CHECK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(cem_sample_autograsp_kernel, dim3((M + kCemWaves - 1) / kCemWaves), dim3(kCemThreads), 0, st, p, g);
     VF_HIP_CHECK(hipGetLastError());
     return VF_OK;
     VF_API_CATCH(int)

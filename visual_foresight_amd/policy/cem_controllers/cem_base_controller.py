@@ -176,7 +176,7 @@ class CEMBaseController(Policy):
         M = sampler.device_draws(self._t, hp.num_samples)
         # (the caller's action width: a stochastic predictor's engine takes adim + zdim, the latents are folded in later)
         width = pred._adim_in() if hasattr(pred, '_adim_in') else pred.cfg.adim
-        if not (2 <= K <= min(MAX_K, M) and M <= MAX_SAMPLES) or width != sampler._adim + len(tail):
+        if not (2 <= K <= min(MAX_K, M) and M <= MAX_SAMPLES) or width != sampler.action_width() + len(tail):
             return None
         return K, M, tail
 

@@ -1,7 +1,8 @@
-"""The device side of the three Philox samplers: buffers and launches of ``vf_cem_refit`` / ``vf_cem_sample``
+"""The device side of the four Philox samplers: buffers and launches of ``vf_cem_refit`` / ``vf_cem_sample``
 (``DeviceCEM``, for ``PhiloxGaussianCEMSampler``), of ``vf_cem_soft_refit`` / ``vf_cem_sample_corr``
-(``DeviceCorrelatedCEM``, for ``PhiloxCorrelatedNoiseSampler``) and of ``vf_cem_refit`` / ``vf_cem_sample_fold``
-(``DeviceFoldingCEM``, for ``PhiloxFoldingCEMSampler``).
+(``DeviceCorrelatedCEM``, for ``PhiloxCorrelatedNoiseSampler``), of ``vf_cem_refit`` / ``vf_cem_sample_fold``
+(``DeviceFoldingCEM``, for ``PhiloxFoldingCEMSampler``) and of ``vf_cem_refit`` / ``vf_cem_sample_autograsp``
+(``DeviceAutograspCEM``, for ``PhiloxAutograspSampler``).
 
 A driver owns the workspace (the proposal) and the per-iteration candidate and elite buffers of one controller, all
 allocated once.  Every method only enqueues on the current stream of its device; the controller's one download is the one
@@ -58,12 +59,14 @@ def read_workspace(image, D):
 
 
 class DeviceCEM(object):
+    config = staticmethod(cem_config)       # (sampler, n_elites, append_action) -> the vf_cem_config of workspace and refit
+
     def __init__(self, sampler, n_elites, n_iter, max_samples, device, append_action=None):
         import torch
         self._torch = torch
         self.device = torch.device(device)
         self._lib = _lib.load_library()
-        self.cfg = cem_config(sampler, n_elites, append_action)
+        self.cfg = self.config(sampler, n_elites, append_action)
         hp = sampler._hp
         self.D, self.K = int(hp.nactions) * sampler._adim, int(n_elites)
         self.T, self.W = int(hp.nactions) * int(hp.repeat), sampler._adim + self.cfg.tail
@@ -90,7 +93,7 @@ class DeviceCEM(object):
     def begin(self, sampler, t, M, append_action=None, state=None):
         """Start a planning call at time ``t`` that draws ``M`` sequences per iteration: the sampler's first proposal.
         ``state``: the state row the call starts from (the folding driver reads it)."""
-        self.cfg = cem_config(sampler, self.K, append_action)       # (reset() makes a new sampler: its key)
+        self.cfg = self.config(sampler, self.K, append_action)      # (reset() makes a new sampler: its key)
         self._mean0, std = sampler.initial_proposal(t)
         assert sampler.draws_for(self.max_samples) == M
         self.upload(self._mean0, np.diag(std))
@@ -343,3 +346,49 @@ class DeviceFoldingCEM(object):
     def read_proposal(self):
         """(synchronises) -> ``(R, mean, A [D, R])`` of the workspace."""
         return read_workspace(self.workspace.cpu().numpy(), self.D)
+
+
+# ---------------------------------------------------------------------------------------------------- autograsp
+def autograsp_config(sampler, n_elites, append_action=None):
+    """The ``vf_cem_config`` of a ``PhiloxAutograspSampler``: its parent's over the moves, the tail led by the gripper column
+    (``tail_value[0]`` is not read) with the appended constants behind it."""
+    return cem_config(sampler, n_elites, [0.0] + [float(v) for v in (append_action or ())])
+
+
+def grip_config(sampler, by_share):
+    """The ``vf_cem_grip_config`` of a sampling call of a ``PhiloxAutograspSampler``, by height or by the elites' share."""
+    hp = sampler._hp
+    cfg = _lib.VfCemGripConfig()
+    cfg.mode, cfg.reopen = int(bool(by_share)), int(bool(hp.reopen))
+    cfg.state_z, cfg.action_norm_factor, cfg.z_thresh = sampler.state_z(), float(hp.action_norm_factor), float(hp.z_thresh)
+    cfg.deviation_prob = float(hp.deviation_prob)
+    cfg.close_cmd, cfg.open_cmd = float(hp.gripper_close_cmd), float(hp.gripper_open_cmd)
+    return cfg
+
+
+class DeviceAutograspCEM(DeviceCEM):
+    """``DeviceCEM`` over the moves; rows of ``[moves | gripper | appended constants]``, and ``share [T]`` as scratch."""
+    config = staticmethod(autograsp_config)
+
+    def __init__(self, sampler, n_elites, n_iter, max_samples, device, append_action=None):
+        super(DeviceAutograspCEM, self).__init__(sampler, n_elites, n_iter, max_samples, device, append_action)
+        self.share = self._torch.zeros(self.T, dtype=self._torch.float32, device=self.device)
+        self._sampler = sampler
+
+    def begin(self, sampler, t, M, append_action=None, state=None):
+        """As ``DeviceCEM.begin``; the height the call starts from, ``state[2]``, goes into the grip config."""
+        sampler.start_planning_call(state)
+        self._sampler = sampler
+        super(DeviceAutograspCEM, self).begin(sampler, t, M, append_action, state)
+
+    def sample(self, itr, M, call):
+        """Candidates of iteration ``itr`` -> ``[M, T, adim + 1 + tail]``: by height, or by the share of the elites the last
+        ``refit`` left in ``elite_plans`` (``no_refit`` False, from the second iteration on)."""
+        out = self.actions[itr, :M]
+        grip = grip_config(self._sampler, self._sampler.by_share(itr))
+        with self._torch.cuda.device(self.device):
+            _lib.check(self._lib.vf_cem_sample_autograsp(
+                self.device.index, ctypes.byref(self.cfg), ctypes.byref(grip), self.workspace.data_ptr(), int(call), int(M),
+                self.elite_plans.data_ptr(), self.share.data_ptr(), out.data_ptr(), self.trials[itr].data_ptr(),
+                self.capped[itr].data_ptr(), self._stream()))
+        return out

@@ -21,6 +21,10 @@ class CEMSampler(object):
         """Hyper-parameters this sampler adds to the controller's (name -> default)."""
         return {}
 
+    def action_width(self):
+        """Columns of the sequences this sampler emits (a sampler may emit more than it proposes over)."""
+        return self._adim
+
     def sample_initial_actions(self, t, nsamples, current_state):
         """First proposal of a planning call at time ``t`` -> ``[nsamples, T, adim]``."""
         raise NotImplementedError
