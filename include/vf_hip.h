@@ -167,6 +167,38 @@ int vf_load_weights(vf_handle *h, const float *host_blob, size_t n_floats);
 int vf_set_context(vf_handle *h, const uint8_t *d_frames, const float *d_states,
                    const float *d_ctx_actions, const float *d_ctx_distrib, void *stream);
 
+/* Grouped contexts: G planning problems in one rollout.  Rows [g * rows_per_group, (g + 1) * rows_per_group) of every later vf_rollout read
+ * context g.  Layouts: vf_set_context's with a leading [n_groups] axis.  d_ctx_distrib NULL on a frames-only handle.
+ * Every context distribution plane is normalised, as vf_set_context expects.
+ * The contexts are converted and expanded into one copy per row; a step reads them with a row stride where it reads the
+ * broadcast context with stride 0, and the rollout is emitted as with vf_set_dedup(h, 0) whatever that switch says
+ * (nothing is shared between rows; every route gives the bits G single-context rollouts of rows_per_group rows give).
+ * While the handle is in this GROUPED MODE vf_rollout wants B == n_groups * rows_per_group and scores every row against
+ * the one goal_pix it is passed (vf_group_pixel_scores takes a goal per group); vf_export, vf_render_plans,
+ * vf_goal_image_scores, vf_scorer_scores and vf_device_status work on the rows unchanged.  A later vf_set_context
+ * returns the handle to the broadcast mode.  The FIRST call on a handle allocates the per-row buffers (for max_batch
+ * rows - the one exception to "no later call allocates"; vf_destroy frees them); every call enqueues one kernel on
+ * `stream` and never synchronises.  Returns VF_ERR_INVALID (nothing launched, the handle as it was; the message names
+ * "grouped contexts") for arch 1 .. 3, n_draws > 1, n_groups < 1, rows_per_group < 1, n_groups * rows_per_group >
+ * max_batch, a d_ctx_distrib that contradicts ndesig, or missing context actions with n_context > 1. */
+int vf_set_contexts(vf_handle *h, int32_t n_groups, int32_t rows_per_group, const uint8_t *d_frames,
+                    const float *d_states, const float *d_ctx_actions, const float *d_ctx_distrib, void *stream);
+
+/* Expected-distance cost of the handle's LAST vf_rollout against one goal per group, from the resident distributions.
+ * d_goal_pix: DEVICE int32 [n_groups][ncam][ndesig][2] (row, col; may lie off-image).  task_weights: HOST float
+ * [n_groups][ncam * ndesig] or NULL.  d_scores float64 [B], d_scores_per_task float64 [B][ncam * ndesig] (may be NULL).
+ * Per row b of group g, view c, pixel p, step t:  S1 = sum over pixels of x * || (row, col) - goal[g][c][p] ||  over the
+ * unnormalised distribution x (float64 root of the exact integer, float64 accumulation in an order that depends on H
+ * and W alone: a row's cost has the same bits in any batch, group count or position), S0 the divisor vf_export
+ * normalises with; then vf_rollout's reduction:  e = sum_t w_t (S1 / S0) / sum_t w_t,  w = (1, ..., 1, finalweight),
+ * and the plain mean over tasks or the group's task_weights sum.  If the handle's device status is raised every output
+ * is NaN.  Enqueues two kernels (with task_weights one more per 32 groups) on `stream`, allocates nothing, never
+ * synchronises.  Returns VF_ERR_INVALID (nothing launched; the message names "grouped contexts") for a NULL handle /
+ * d_goal_pix / d_scores, a frames-only handle, a handle outside grouped mode, or one that has not rolled since its
+ * vf_set_contexts. */
+int vf_group_pixel_scores(vf_handle *h, const int32_t *d_goal_pix, float finalweight, const float *task_weights,
+                          double *d_scores, double *d_scores_per_task, void *stream);
+
 /* Roll B (<= max_batch, a multiple of n_draws) action sequences through every view's predictor
  * for T steps and reduce the predicted designated-pixel distributions to costs on the device.
  * Replaces predictor_func()/sess.run, setup_predictor.py:164-200, the call at

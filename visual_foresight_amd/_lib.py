@@ -34,7 +34,8 @@ EXPORTS = ('vf_abi_version', 'vf_last_error', 'vf_weight_count', 'vf_create', 'v
            'vf_invmodel_infer', 'vf_debug_lstm_layer', 'vf_register_hw', 'vf_resize_area',
            'vf_cem_workspace_bytes', 'vf_cem_refit', 'vf_cem_sample',
            'vf_cem_corr_workspace_bytes', 'vf_cem_soft_refit', 'vf_cem_sample_corr', 'vf_cem_sample_fold',
-           'vf_cem_sample_autograsp', 'vf_cem_latents', 'vf_cem_fold_latents')
+           'vf_cem_sample_autograsp', 'vf_cem_latents', 'vf_cem_fold_latents',
+           'vf_set_contexts', 'vf_group_pixel_scores')
 ABI_VERSION = 7
 
 
@@ -148,6 +149,9 @@ def load_library():
     lib.vf_destroy.argtypes = [P]
     lib.vf_load_weights.argtypes = [P, P, ctypes.c_size_t]
     lib.vf_set_context.argtypes = [P, P, P, P, P, P]
+    lib.vf_set_contexts.argtypes = [P, ctypes.c_int32, ctypes.c_int32, P, P, P, P, P]
+    lib.vf_group_pixel_scores.argtypes = [P, P, ctypes.c_float, ctypes.POINTER(ctypes.c_float), P, P, P]
+    lib.vf_set_contexts.restype = lib.vf_group_pixel_scores.restype = ctypes.c_int
     lib.vf_rollout.argtypes = [P, P, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.c_float,
                                ctypes.POINTER(ctypes.c_float), P, P, P]
     lib.vf_ensemble_scores.argtypes = [ctypes.POINTER(P), ctypes.c_int32, ctypes.c_float, ctypes.c_float,

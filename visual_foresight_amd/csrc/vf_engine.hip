@@ -622,6 +622,19 @@ struct vf_handle {
     float *ctx_frames_all = nullptr, *ctx_distrib_all = nullptr;
     float *ctx_states = nullptr, *ctx_actions = nullptr;
 
+    // Grouped contexts (vf_set_contexts): n_groups planning problems of rows_per_group rows each in one rollout.  Their
+    // contexts are kept PER ROW - frames / distributions [ncam][rows][n_context][..], states [rows][n_context][sdim], actions
+    // [rows][n_context - 1][adim], rows = n_groups * rows_per_group - and step_io hands them out with their row strides where
+    // it hands out the broadcast context with stride 0.  Allocated by the first vf_set_contexts for max_batch rows (vf_create
+    // takes none of it), with the plane costs [max_batch][ncam][ND][T] of vf_group_pixel_scores.
+    bool grouped = false;
+    int n_groups = 0, rows_per_group = 0;
+    bool group_bufs = false;
+    float *gctx_frames = nullptr, *gctx_distrib = nullptr, *gctx_states = nullptr, *gctx_actions = nullptr;
+    double *group_cost = nullptr;
+    // nothing is shared between the rows of a grouped rollout: it is emitted as with dedup off
+    bool dedup_on() const { return dedup && !grouped; }
+
     // Activations, states, statistics and predictions, [ncam][max_batch] samples each: `base` holds the first row of every
     // buffer, `spec` its layout, slot by slot (row_spec / alloc_view / make_view).  The engine's
     // create function fills `spec` once, from its layer plans; nothing else writes a per-sample size.
@@ -652,7 +665,7 @@ struct vf_handle {
     struct SchedCache {                 // device copy of one schedule + the key it was built for
         PhaseDesc *d_phases = nullptr;
         int B = -1, items = 0, counters = 0, phases = 0;
-        bool dedup = true;
+        bool dedup = true, grouped = false;     // (grouped: the context inputs carry row strides, step_io)
         int xcd_queues = 0, nq = 1, total_q[kQueues] = {0};
         int options = -1;               // sched_options() the schedule was built with (every toggle build_schedule reads)
         double flops = 0.0;
@@ -1120,15 +1133,24 @@ struct StepIo {
     long long state_out_bs, out_frame_bs, out_distrib_bs;
     double *out_sums;
 };
-static StepIo step_io(const vf_handle *h, const ViewData &vd, const BatchView &v, int s) {
+static StepIo step_io(const vf_handle *h, int view_index, const BatchView &v, int s) {
+    const ViewData &vd = h->views[(size_t)view_index];
     const vf_config &c = h->cfg;
     const int T = h->T, ND = h->ND, nc = c.n_context;
     const size_t HW = (size_t)h->H * h->W;
     StepIo io;
     memset(&io, 0, sizeof(io));
-    if (s < nc - 1) io.action = h->ctx_actions + (size_t)s * c.adim;
+    // grouped contexts: row b of every context input is its own copy (of its group's context), view `view` of rows each
+    const bool grp = h->grouped;
+    const size_t rows = (size_t)h->n_groups * h->rows_per_group, view = (size_t)view_index;
+    if (s < nc - 1 && grp) { io.action = h->gctx_actions + (size_t)s * c.adim; io.action_bs = (long long)(nc - 1) * c.adim; }
+    else if (s < nc - 1) io.action = h->ctx_actions + (size_t)s * c.adim;
     else { io.action = v.actions + (size_t)(s - (nc - 1)) * c.adim; io.action_bs = (long long)T * c.adim; }
-    if (s < nc) {
+    if (s < nc && grp) {
+        io.state = h->gctx_states + (size_t)s * c.sdim; io.state_bs = (long long)nc * c.sdim;
+        io.frame = h->gctx_frames + (view * rows * nc + s) * HW * 3; io.frame_bs = (long long)nc * HW * 3;
+        if (ND > 0) { io.prev_distrib = h->gctx_distrib + (view * rows * nc + s) * HW * ND; io.prev_distrib_bs = (long long)nc * HW * ND; }
+    } else if (s < nc) {
         io.state = h->ctx_states + (size_t)s * c.sdim;
         io.frame = vd.ctx_frames + (size_t)s * HW * 3;
         if (ND > 0) io.prev_distrib = vd.ctx_distrib + (size_t)s * HW * ND;
@@ -1673,6 +1695,7 @@ int vf_set_context(vf_handle *h, const uint8_t *d_frames, const float *d_states,
                        d_ctx_actions, h->ctx_actions, n_a);
     VF_HIP_CHECK(hipGetLastError());
     h->have_context = true;
+    h->grouped = false;             // (back to the broadcast context from grouped contexts, vf_set_contexts)
     h->shared_valid = false;        // the shared units are functions of the context
     return VF_OK;
     VF_API_CATCH(int)
@@ -2048,8 +2071,8 @@ static int emit_rollout(vf_handle *h, int view, const BatchView &v, const BatchV
         const long long items = (long long)conv_items_x(reg, Bp) * reg.ncg;
         return items <= h->n_cu / 8 ? one : reg;
     };
-    auto all_shared = [&](int s) { return h->dedup && s < nc - 1; };
-    auto enc_shared = [&](int s) { return h->dedup && s < nc; };
+    auto all_shared = [&](int s) { return h->dedup_on() && s < nc - 1; };
+    auto enc_shared = [&](int s) { return h->dedup_on() && s < nc; };
     // (arch 2: the action conditions every conv-LSTM, so at step n_context - 1 only the convs in front of lstm1 still see
     // the same input for every sample)
     auto core_shared = [&](int s) { return h->cond ? all_shared(s) : enc_shared(s); };
@@ -2080,7 +2103,7 @@ static int emit_rollout(vf_handle *h, int view, const BatchView &v, const BatchV
         auto bs = [](bool shared, long long per) { return shared ? 0LL : per; };
 
         // ---- state FC + action/state bias of enc3
-        const StepIo io = step_io(h, vd, v, s);
+        const StepIo io = step_io(h, view, v, s);
         SaParams sp; memset(&sp, 0, sizeof(sp));
         sp.action = io.action; sp.action_bstride = io.action_bs; sp.state = io.state; sp.state_bstride = io.state_bs;
         sp.adim = c.adim; sp.sdim = c.sdim; sp.B = BD;
@@ -2120,7 +2143,7 @@ static int emit_rollout(vf_handle *h, int view, const BatchView &v, const BatchV
         auto emit_cond = [&](const int sc, const int u_state, int (&out)[7]) -> int {
             for (int k = 0; k < 7; ++k) out[k] = -1;
             if (!h->cond || sc >= h->S) return VF_OK;
-            const StepIo ic = step_io(h, vd, v, sc);
+            const StepIo ic = step_io(h, view, v, sc);
             for (int k = 0; k < 7; ++k) {
                 const bool shd = lstm_shared(k, sc);
                 CondParams cq; memset(&cq, 0, sizeof(cq));
@@ -2488,6 +2511,67 @@ static int render_plans_check(const vf_handle *h, const int32_t *d_seq, int32_t 
     if (h->ND == 0 && d_distrib_u8)
         return fail(VF_ERR_INVALID, "vf_render_plans: a frames-only handle (ndesig 0) has no distributions to render: d_distrib_u8 must be NULL");
     if (h->last_B < 1) return fail(VF_ERR_INVALID, "the handle has not rolled");
+    return VF_OK;
+}
+
+// the refusals of vf_set_contexts (host work only, as above)
+static int set_contexts_check(const vf_handle *h, int32_t n_groups, int32_t rows_per_group, const uint8_t *d_frames,
+                              const float *d_states, const float *d_ctx_actions, const float *d_ctx_distrib) {
+    if (!h || !d_frames || !d_states) return fail(VF_ERR_INVALID, "vf_set_contexts (grouped contexts): null argument");
+    if (h->cfg.arch != 0)
+        return fail(VF_ERR_INVALID, "vf_set_contexts: grouped contexts need arch 0, this handle has arch " + std::to_string(h->cfg.arch) +
+                                        " (its first-frame / context path reads one broadcast context)");
+    if (h->n_draws > 1)
+        return fail(VF_ERR_INVALID, "vf_set_contexts: grouped contexts need n_draws = 1, this handle has " + std::to_string(h->n_draws));
+    if (n_groups < 1 || rows_per_group < 1)
+        return fail(VF_ERR_INVALID, "vf_set_contexts: grouped contexts need n_groups >= 1 and rows_per_group >= 1, got " +
+                                        std::to_string(n_groups) + " x " + std::to_string(rows_per_group));
+    if ((long long)n_groups * rows_per_group > h->cfg.max_batch)
+        return fail(VF_ERR_INVALID, "vf_set_contexts: grouped contexts of " + std::to_string(n_groups) + " x " +
+                                        std::to_string(rows_per_group) + " rows exceed max_batch = " + std::to_string(h->cfg.max_batch));
+    if (h->ND == 0 && d_ctx_distrib)
+        return fail(VF_ERR_INVALID, "vf_set_contexts (grouped contexts): a frames-only handle (ndesig 0) takes no context "
+                                    "distributions: d_ctx_distrib must be NULL");
+    if (h->ND > 0 && !d_ctx_distrib)
+        return fail(VF_ERR_INVALID, "vf_set_contexts (grouped contexts): d_ctx_distrib is NULL on a handle with ndesig " + std::to_string(h->ND));
+    if (h->cfg.n_context > 1 && !d_ctx_actions)
+        return fail(VF_ERR_INVALID, "vf_set_contexts (grouped contexts): context actions required when n_context > 1");
+    return VF_OK;
+}
+
+// the per-row context buffers and the plane costs of a handle's grouped mode, at its first vf_set_contexts: sized for
+// max_batch rows and registered like every other allocation (vf_destroy frees them, vf_selftest_schedule finds them)
+static int alloc_grouped(vf_handle *h) {
+    if (h->group_bufs) return VF_OK;        // (a call that failed part-way left its buffers registered: they are kept)
+    const vf_config &c = h->cfg;
+    const size_t rows = (size_t)c.max_batch, nc = (size_t)c.n_context, HW = (size_t)h->H * h->W;
+    int rc;
+    if (!h->gctx_frames) VF_ALLOC(h->gctx_frames, h->ncam * rows * nc * HW * 3);
+    if (h->ND > 0 && !h->gctx_distrib) VF_ALLOC(h->gctx_distrib, h->ncam * rows * nc * HW * h->ND);
+    if (!h->gctx_states) VF_ALLOC(h->gctx_states, rows * nc * c.sdim);
+    if (!h->gctx_actions) VF_ALLOC(h->gctx_actions, rows * std::max<size_t>(nc - 1, 1) * c.adim);
+    if (h->ND > 0 && !h->group_cost) VF_ALLOC(h->group_cost, rows * h->ncam * h->ND * h->T);
+    h->group_bufs = true;
+    return VF_OK;
+}
+
+// the handle enters grouped mode (or changes its grouping): nothing cached for another context layout survives
+static void enter_grouped(vf_handle *h, int32_t n_groups, int32_t rows_per_group) {
+    h->grouped = true;
+    h->n_groups = n_groups; h->rows_per_group = rows_per_group;
+    h->have_context = true;
+    h->shared_valid = false;
+    h->last_B = 0;                  // (what is resident was not rolled from these contexts)
+}
+
+// the refusals of vf_group_pixel_scores (host work only, as above)
+static int group_pixel_scores_check(const vf_handle *h, const int32_t *d_goal_pix, const double *d_scores) {
+    if (!h || !d_goal_pix || !d_scores) return fail(VF_ERR_INVALID, "vf_group_pixel_scores (grouped contexts): null argument");
+    if (h->ND == 0)
+        return fail(VF_ERR_INVALID, "vf_group_pixel_scores (grouped contexts): a frames-only handle (ndesig 0) keeps no distributions to score");
+    if (!h->grouped)
+        return fail(VF_ERR_INVALID, "vf_group_pixel_scores: the handle holds no grouped contexts (vf_set_contexts)");
+    if (h->last_B < 1) return fail(VF_ERR_INVALID, "vf_group_pixel_scores (grouped contexts): the handle has not rolled");
     return VF_OK;
 }
 
@@ -3026,6 +3110,32 @@ extern "C" int vf_render_plans(vf_handle *h, const int32_t *d_seq, int32_t K, co
     return fail(VF_ERR_HIP, "the host self-test build launches nothing");
     VF_API_CATCH(int)
 }
+extern "C" int vf_set_contexts(vf_handle *h, int32_t n_groups, int32_t rows_per_group, const uint8_t *d_frames,
+                               const float *d_states, const float *d_ctx_actions, const float *d_ctx_distrib, void *) {
+    VF_API_TRY      // (the refusals, the buffers and the mode - what a schedule depends on; nothing is converted)
+    if (int rc = set_contexts_check(h, n_groups, rows_per_group, d_frames, d_states, d_ctx_actions, d_ctx_distrib)) return rc;
+    if (int rc = alloc_grouped(h)) return rc;
+    enter_grouped(h, n_groups, rows_per_group);
+    return VF_OK;
+    VF_API_CATCH(int)
+}
+extern "C" int vf_set_context(vf_handle *h, const uint8_t *d_frames, const float *d_states, const float *, const float *,
+                              void *) {     // (the way back from grouped mode: the mode alone, nothing is converted)
+    VF_API_TRY
+    if (!h || !d_frames || !d_states) return fail(VF_ERR_INVALID, "null argument");
+    h->have_context = true;
+    h->grouped = false;
+    h->shared_valid = false;
+    return VF_OK;
+    VF_API_CATCH(int)
+}
+extern "C" int vf_group_pixel_scores(vf_handle *h, const int32_t *d_goal_pix, float, const float *, double *d_scores, double *,
+                                     void *) {      // (refusal paths only, as above)
+    VF_API_TRY
+    if (int rc = group_pixel_scores_check(h, d_goal_pix, d_scores)) return rc;
+    return fail(VF_ERR_HIP, "the host self-test build launches nothing");
+    VF_API_CATCH(int)
+}
 extern "C" int vf_resize_area(int32_t device, const void *d_src, void *d_dst, int32_t dtype, int32_t n, int32_t Hs, int32_t Ws,
                               int32_t C, int32_t Hd, int32_t Wd, void *) {       // (refusal paths only, as above)
     VF_API_TRY
@@ -3164,7 +3274,7 @@ static int sched_options(const vf_handle *h, int B) {
 
 // Are the shared buffers of configuration `cfg` (launch mode and split) still valid?
 static bool shared_cache_hit(vf_handle *h, int cfg) {
-    return h->dedup && h->cache_shared && h->shared_valid && h->shared_cfg == cfg;
+    return h->dedup_on() && h->cache_shared && h->shared_valid && h->shared_cfg == cfg;
 }
 
 // the caller's per-task weights [ncam][ND] as a kernel argument (null: every task weighs the same)
@@ -3189,7 +3299,7 @@ static int run_persistent(vf_handle *h, const float *d_actions, int B, const int
     const int cfg = 1000;
     const bool skip_shared = shared_cache_hit(h, cfg);
     vf_handle::SchedCache &sc_host = h->sched[skip_shared ? 1 : 0];
-    if (sc_host.B != B || sc_host.dedup != h->dedup || sc_host.xcd_queues != h->xcd_queues ||
+    if (sc_host.B != B || sc_host.dedup != h->dedup || sc_host.grouped != h->grouped || sc_host.xcd_queues != h->xcd_queues ||
         sc_host.options != sched_options(h, B)) {
         BuiltSchedule bs;
         if ((rc = build_schedule(h, B, skip_shared, bs))) return rc;
@@ -3226,7 +3336,7 @@ static int run_persistent(vf_handle *h, const float *d_actions, int B, const int
                                     hipMemcpyHostToDevice, st));
         VF_HIP_CHECK(hipEventRecord(h->stage_done[slot], st));
         h->stage_used[slot] = true;
-        sc_host.B = B; sc_host.dedup = h->dedup;
+        sc_host.B = B; sc_host.dedup = h->dedup; sc_host.grouped = h->grouped;
         sc_host.xcd_queues = h->xcd_queues;
         sc_host.options = sched_options(h, B);
         sc_host.items = bs.items; sc_host.counters = bs.counters;
@@ -3274,7 +3384,7 @@ static int run_persistent(vf_handle *h, const float *d_actions, int B, const int
     if (h->ND == 0 && hipGetLastError() != hipSuccess) return fail(VF_ERR_HIP, "launch of the frames-only rollout kernel failed");
     VF_HIP_CHECK(hipGetLastError());
     if (h->profiling && (rc = profile_end(h, st, sc_host.flops))) return rc;
-    h->shared_valid = h->dedup;
+    h->shared_valid = h->dedup_on();
     h->shared_cfg = cfg;
     return VF_OK;
 }
@@ -3297,6 +3407,9 @@ int vf_rollout(vf_handle *h, const float *d_actions, int32_t B, const int32_t *g
     if (B % h->n_draws)
         return fail(VF_ERR_INVALID, "batch " + std::to_string(B) + " is not a multiple of n_draws = " +
                                         std::to_string(h->n_draws));
+    if (h->grouped && B != h->n_groups * h->rows_per_group)
+        return fail(VF_ERR_INVALID, "vf_rollout: the handle holds grouped contexts for " + std::to_string(h->n_groups) + " x " +
+                                        std::to_string(h->rows_per_group) + " rows, got batch " + std::to_string(B));
     VF_HIP_CHECK(hipSetDevice(h->cfg.device));
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     int rc;
@@ -3308,7 +3421,7 @@ int vf_rollout(vf_handle *h, const float *d_actions, int32_t B, const int32_t *g
         for (int v = 0; v < h->ncam; ++v) {
             if ((rc = run_steps(h, v, make_view(h, v, d_actions), h->shared_views[(size_t)v], B, goal_pix, st, skip))) return rc;
         }
-        h->shared_valid = h->dedup; h->shared_cfg = 1;
+        h->shared_valid = h->dedup_on(); h->shared_cfg = 1;
     }
     if (frames_only) {      // no block sums to reduce: the costs of such a handle come from vf_goal_image_scores / vf_scorer_scores
         h->last_B = B;
@@ -3385,6 +3498,60 @@ int vf_goal_image_scores(vf_handle *h, const float *d_goal, int32_t steps_mode, 
                        h->n_draws, NV, T, steps_mode, finalweight, first_view_only != 0, h->d_status, d_scores,
                        d_scores_per_view, d_cost_per_step);
     VF_HIP_CHECK(hipGetLastError());
+    return VF_OK;
+    VF_API_CATCH(int)
+}
+
+int vf_set_contexts(vf_handle *h, int32_t n_groups, int32_t rows_per_group, const uint8_t *d_frames, const float *d_states,
+                    const float *d_ctx_actions, const float *d_ctx_distrib, void *stream) {
+    VF_API_TRY
+    if (int rc = set_contexts_check(h, n_groups, rows_per_group, d_frames, d_states, d_ctx_actions, d_ctx_distrib)) return rc;
+    VF_HIP_CHECK(hipSetDevice(h->cfg.device));
+    if (int rc = alloc_grouped(h)) return rc;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const int nc = h->cfg.n_context, hw3 = h->H * h->W * 3, hwd = h->H * h->W * h->ND;
+    const int n_s = nc * h->cfg.sdim, n_a = (nc - 1) * h->cfg.adim;
+    const long long rows = (long long)n_groups * rows_per_group;
+    const long long n = std::max(std::max((long long)h->ncam * rows * nc * hw3, (long long)h->ncam * rows * nc * hwd),
+                                 rows * std::max(n_s, n_a));
+    hipLaunchKernelGGL(set_contexts_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_frames, h->gctx_frames,
+                       n_groups, rows_per_group, nc, h->ncam, hw3, d_ctx_distrib, h->gctx_distrib, hwd, d_states,
+                       h->gctx_states, n_s, d_ctx_actions, h->gctx_actions, n_a);
+    VF_HIP_CHECK(hipGetLastError());
+    enter_grouped(h, n_groups, rows_per_group);
+    return VF_OK;
+    VF_API_CATCH(int)
+}
+
+int vf_group_pixel_scores(vf_handle *h, const int32_t *d_goal_pix, float finalweight, const float *task_weights,
+                          double *d_scores, double *d_scores_per_task, void *stream) {
+    VF_API_TRY
+    if (int rc = group_pixel_scores_check(h, d_goal_pix, d_scores)) return rc;
+    VF_HIP_CHECK(hipSetDevice(h->cfg.device));
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const int B = h->last_B, T = h->T, NV = h->ncam, ND = h->ND, ntask = NV * ND;
+    const long long view_stride = (long long)h->cfg.max_batch * T * h->H * h->W * ND;
+    with_nd(ND, [&](auto nd) {
+        hipLaunchKernelGGL(group_pixel_cost_kernel<decltype(nd)::value>, dim3((unsigned)(B * NV * T)), dim3(kGroupCostThreads), 0,
+                           st, h->distrib_all, view_stride, h->sums, h->sums_step_stride, h->sums_view_stride, d_goal_pix,
+                           h->rows_per_group, NV, T, h->H, h->W, h->nblocks, h->group_cost);
+    });
+    VF_HIP_CHECK(hipGetLastError());
+    GroupWeights gw;
+    memset(&gw, 0, sizeof(gw));
+    // (the weights of kGroupWeightSets groups fit a launch's arguments; without weights one launch scores every row)
+    for (int g0 = 0; g0 < (task_weights ? h->n_groups : 1); g0 += kGroupWeightSets) {
+        int n_rows = B;
+        if (task_weights) {
+            gw.use = 1; gw.g0 = g0; gw.n = std::min(kGroupWeightSets, h->n_groups - g0);
+            for (int g = 0; g < gw.n; ++g)
+                for (int i = 0; i < ntask; ++i) gw.w[g][i] = task_weights[(size_t)(g0 + g) * ntask + i];
+            n_rows = gw.n * h->rows_per_group;
+        }
+        hipLaunchKernelGGL(group_scores_kernel, dim3((unsigned)((n_rows + 63) / 64)), dim3(64), 0, st, h->group_cost, B,
+                           h->rows_per_group, NV, ND, T, finalweight, gw, h->d_status, d_scores, d_scores_per_task);
+        VF_HIP_CHECK(hipGetLastError());
+    }
     return VF_OK;
     VF_API_CATCH(int)
 }

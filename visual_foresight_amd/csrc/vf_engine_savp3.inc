@@ -535,7 +535,7 @@ static int emit_rollout_s3(vf_handle *h, int view, int B, const float *d_actions
     // whose element-wise items were the last readers of that parity's tables.
     auto emit_cond = [&](const int sx, const int guard) -> int {
         const int par = sx & 1;
-        const StepIo ic = step_io(h, vd, bv, sx);
+        const StepIo ic = step_io(h, view, bv, sx);
         EwParams e = ew_base(EW_SA3, 0, kSaPerItem);
         e.sa.action = ic.action; e.sa.action_bs = ic.action_bs; e.sa.state = ic.state; e.sa.state_bs = ic.state_bs;
         e.sa.adim = c.adim; e.sa.sdim = c.sdim; e.sa.zdim = c.zdim;
@@ -570,7 +570,7 @@ static int emit_rollout_s3(vf_handle *h, int view, int B, const float *d_actions
     for (int st = 0; st < h->S; ++st) {
         const int cur = st & 1, nxt = cur ^ 1, par = st & 1;
         const bool produce = st >= nc - 1;
-        const StepIo io = step_io(h, vd, bv, st);
+        const StepIo io = step_io(h, view, bv, st);
         const int *u_cc = u_cc_all[par], *u_cl = u_cl_all[par];
         const int last_at_entry = last;     // terminal unit of step st - 1: the guard of step st + 1's tables
 

@@ -52,6 +52,31 @@ VF_GLOBAL void set_context_kernel(const uint8_t *frames_u8, float *frames_f, int
     if (i < n_a) dst_a[i] = src_a[i];
 }
 
+// Grouped contexts (vf_set_contexts): G contexts in the caller's layout, [G][nc][ncam][..], converted as above and EXPANDED
+// into one copy per row - row g * rpg + j of every buffer holds context g:
+//   frames_f [ncam][G * rpg][nc][HW3], dst_d [ncam][G * rpg][nc][HWD], dst_s [G * rpg][n_s], dst_a [G * rpg][n_a]
+// (n_s = nc * sdim, n_a = (nc - 1) * adim), so that a step reads its context as `ptr + row * stride` exactly where it reads
+// a rolled input.  One thread per OUTPUT element of the largest buffer; every value is the one set_context_kernel writes.
+VF_GLOBAL void set_contexts_kernel(const uint8_t *frames_u8, float *frames_f, int G, int rpg, int nc, int ncam, int hw3,
+                                    const float *src_d, float *dst_d, int hwd,
+                                    const float *src_s, float *dst_s, int n_s,
+                                    const float *src_a, float *dst_a, int n_a) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long long rows = (long long)G * rpg;
+    if (i < (long long)ncam * rows * nc * hw3) {
+        const int e = (int)(i % hw3), t = (int)((i / hw3) % nc);
+        const long long row = (i / ((long long)hw3 * nc)) % rows, v = i / ((long long)hw3 * nc * rows);
+        frames_f[i] = (float)frames_u8[(((row / rpg) * nc + t) * ncam + v) * hw3 + e] / 255.0f;
+    }
+    if (i < (long long)ncam * rows * nc * hwd) {
+        const int e = (int)(i % hwd), t = (int)((i / hwd) % nc);
+        const long long row = (i / ((long long)hwd * nc)) % rows, v = i / ((long long)hwd * nc * rows);
+        dst_d[i] = src_d[(((row / rpg) * nc + t) * ncam + v) * hwd + e];
+    }
+    if (i < rows * n_s) dst_s[i] = src_s[((i / n_s) / rpg) * n_s + i % n_s];
+    if (i < rows * n_a) dst_a[i] = src_a[((i / n_a) / rpg) * n_a + i % n_a];
+}
+
 // ------------------------------------------------------------------------------------------
 struct SaParams {
     const float *action; long long action_bstride;     // [adim] per sample (0 stride: shared)
@@ -1221,6 +1246,102 @@ VF_GLOBAL void export_distrib_kernel(const float *src, long long view_stride, co
                        ((long long)b * ND + d) * ntiles * 2;
     dst[i] = distrib_normalised(src[(long long)v * view_stride + ((long long)b * T + t) * HW * ND + e],
                                 distrib_s0(pp, ntiles));
+}
+
+// ------------------------------------------------------------------------------------------
+// Grouped pixel cost (vf_group_pixel_scores): the expected distance of the resident, UNNORMALISED distributions of the last
+// rollout to one goal per GROUP of rows (vf_set_contexts), where scores_kernel reduces the sums the rollout took against its
+// one goal.  Per row b of group g = b / rows_per_group, view v, pixel d, step t:
+//     S1 = sum over (r, c) of x[r][c] * sqrt((double)((r - gr)^2 + (c - gc)^2)),   (gr, gc) = goal[g][v][d]
+// The squared distance is an exact integer, the root a float64 one, products and sums float64.  One workgroup per plane
+// (b, v, t): thread k of 256 takes the pixel quads k, k + 256, ... in that order (a quad = 4 neighbours of one image row:
+// W is a multiple of 8), the lanes of a wave add up in wave_sum's butterfly and the four waves in wave order.  That order
+// depends on H and W alone, so a row's cost has the same bits in any batch, group count or position.  S0 is distrib_s0 of
+// the plane's block sums - the divisor vf_export normalises with - and the plane's cost S1 / S0 goes to
+// cost[b][v][d][t].  Traffic: ONE pass over the distributions, B * ncam * T * H * W * ND * 4 bytes in 16-byte loads - the
+// kernel is bound by the memory system (HBM, or the last-level cache where the rollout's stores still sit), not by its
+// float64 arithmetic (one root, one multiply and one add per value read).
+constexpr int kGroupCostThreads = 256;
+template <int ND>
+VF_GLOBAL VF_LAUNCH_BOUNDS(kGroupCostThreads) void group_pixel_cost_kernel(
+        const float *distrib, long long view_stride, const double *sums, long long step_stride, long long sums_view_stride,
+        const int32_t *goal_pix, int rows_per_group, int NV, int T, int H, int W, int ntiles, double *cost) {
+    __shared__ double s_part[kGroupCostThreads / 64][ND];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int t = blockIdx.x % T, v = (blockIdx.x / T) % NV, b = blockIdx.x / (T * NV);
+    const int g = b / rows_per_group;
+    long long gr[ND], gc[ND];
+    double acc[ND];
+#pragma unroll
+    for (int d = 0; d < ND; ++d) {
+        gr[d] = goal_pix[(((long long)g * NV + v) * ND + d) * 2];
+        gc[d] = goal_pix[(((long long)g * NV + v) * ND + d) * 2 + 1];
+        acc[d] = 0.0;
+    }
+    const long long HW = (long long)H * W;
+    const f32x4 *src = reinterpret_cast<const f32x4 *>(distrib + (long long)v * view_stride + ((long long)b * T + t) * HW * ND);
+    const int nquads = (int)(HW / 4);
+    for (int k = tid; k < nquads; k += kGroupCostThreads) {
+        float x[4 * ND];
+#pragma unroll
+        for (int i = 0; i < ND; ++i) {
+            const f32x4 q = src[(long long)k * ND + i];
+            x[4 * i] = q[0]; x[4 * i + 1] = q[1]; x[4 * i + 2] = q[2]; x[4 * i + 3] = q[3];
+        }
+        const int r = (4 * k) / W, c0 = (4 * k) % W;
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+#pragma unroll
+            for (int d = 0; d < ND; ++d) {
+                const long long dr = r - gr[d], dc = c0 + q - gc[d];
+                acc[d] += (double)x[q * ND + d] * sqrt((double)(dr * dr + dc * dc));
+            }
+    }
+#pragma unroll
+    for (int d = 0; d < ND; ++d) {
+        acc[d] = wave_sum(acc[d]);
+        if (lane == 0) s_part[wave][d] = acc[d];
+    }
+    __syncthreads();
+    if (tid < ND) {
+        double s1 = 0.0;
+#pragma unroll
+        for (int w = 0; w < kGroupCostThreads / 64; ++w) s1 += s_part[w][tid];
+        const double *pp = sums + (long long)t * step_stride + (long long)v * sums_view_stride +
+                           ((long long)b * ND + tid) * ntiles * 2;
+        cost[(((long long)b * NV + v) * ND + tid) * T + t] = s1 / distrib_s0(pp, ntiles);
+    }
+}
+
+// ... and scores_kernel's reduction of those plane costs, one thread per row: e = sum_t w_t cost / sum_t w_t with
+// w = (1, ..., 1, finalweight), then the plain mean over tasks or the weighted sum with the weights of the row's GROUP.  The
+// weights travel as a launch argument, kGroupWeightSets groups at a time: a launch scores the rows of the groups
+// [gw.g0, gw.g0 + gw.n) (without weights one launch scores every row).  A raised *status poisons every output with NaN.
+constexpr int kGroupWeightSets = 32;
+struct GroupWeights { int use, g0, n; float w[kGroupWeightSets][kMaxCam * kMaxDesig]; };
+VF_GLOBAL void group_scores_kernel(const double *cost, int B, int rows_per_group, int NV, int ND, int T, float finalweight,
+                                    const GroupWeights gw, const int *status, double *scores, double *scores_per_task) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const int b = gw.use ? gw.g0 * rows_per_group + i : i;
+    const int b_end = gw.use ? min(B, (gw.g0 + gw.n) * rows_per_group) : B;
+    if (b >= b_end) return;
+    const int ntask = NV * ND, gl = gw.use ? b / rows_per_group - gw.g0 : 0;
+    const bool poisoned = status && *status != 0;
+    double total = 0.0;
+    for (int col = 0; col < ntask; ++col) {
+        const double *cp = cost + ((long long)b * ntask + col) * T;
+        double acc = 0.0, wsum = 0.0;
+        for (int t = 0; t < T; ++t) {
+            const double w = (t == T - 1) ? (double)finalweight : 1.0;
+            acc += w * cp[t];
+            wsum += w;
+        }
+        const double sc = acc / wsum;
+        if (scores_per_task) scores_per_task[(long long)b * ntask + col] = poisoned ? __builtin_nan("") : sc;
+        total += gw.use ? (double)gw.w[gl][col] * sc : sc;
+    }
+    const double out = gw.use ? total : total / ntask;
+    scores[b] = poisoned ? __builtin_nan("") : out;
 }
 
 // ------------------------------------------------------------------------------------------

@@ -101,6 +101,20 @@ class CEMBaseController(Policy):
         plan = self._device_cem_plan()
         if plan is not None:
             return self._perform_device_CEM(state, plan)
+        steps = self._cem_iterations(state)
+        proposal = next(steps)
+        while proposal is not None:
+            scores = self.evaluate_rollouts(*proposal)
+            try:
+                proposal = steps.send(scores)
+            except StopIteration:       # behind the last iteration
+                proposal = None
+
+    def _cem_iterations(self, state):
+        """The host CEM loop as a generator: yields ``(candidates, itr)`` and is sent their ``scores [M]``; it selects the
+        elites, refits and proposes again, and ends behind the last iteration.  ``perform_CEM`` sends it
+        ``evaluate_rollouts``' scores; ``BatchedPixelCostPlanner`` steps the loops of several controllers side by side and
+        sends each the scores one batched rollout gave its candidates - the loop itself has this one source."""
         hp = self._hp
         self._logger.log('starting cem at t{}...'.format(self._t))
         n_elite = self._elite_count()
@@ -112,7 +126,7 @@ class CEMBaseController(Policy):
                 candidates = self._append_constant(candidates)
             self._logger.log('iteration: ', itr)
 
-            scores = self.evaluate_rollouts(candidates, itr)
+            scores = yield candidates, itr
             assert scores.shape == (candidates.shape[0],), "score shape should be (n_actions,)"
             self.plan_stat['scores_itr{}'.format(itr)] = scores
 
@@ -251,14 +265,18 @@ class CEMBaseController(Policy):
             action = np.concatenate((action, hp.append_action), axis=0)
         return action
 
-    def _action_from_plan(self, state):
-        """Replan when due, then read the next action off the best plan."""
+    def _replan_due(self):
         interval = self._hp.replan_interval
-        due = (not interval) or self._t_since_replan is None or self._t_since_replan + 1 >= interval
-        if due:
-            self.perform_CEM(state)
-        else:
-            self._t_since_replan += 1
+        return (not interval) or self._t_since_replan is None or self._t_since_replan + 1 >= interval
+
+    def _action_from_plan(self, state, planned=False):
+        """Replan when due, then read the next action off the best plan (``planned``: the caller has just run the due CEM
+        call itself - ``BatchedPixelCostPlanner``)."""
+        if not planned:
+            if self._replan_due():
+                self.perform_CEM(state)
+            else:
+                self._t_since_replan += 1
         return self._best_actions[0, self._t_since_replan]
 
     def act(self, t=None, i_tr=None, state=None):
@@ -268,6 +286,9 @@ class CEMBaseController(Policy):
             action = self._action_before_planning(t, state)
         else:
             action = self._action_from_plan(state)
+        return self._finish_act(t, action)
+
+    def _finish_act(self, t, action):
         assert action.shape == (self.agentparams['adim'],), "action shape does not match adim!"
         self._logger.log('time {}, action - {}'.format(t, action))
 

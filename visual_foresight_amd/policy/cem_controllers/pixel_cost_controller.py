@@ -177,13 +177,26 @@ class PixelCostController(CEMBaseController):
             self._chosen_distrib = None
 
     # ------------------------------------------------------------------ rollout scoring
-    def evaluate_rollouts(self, actions, cem_itr):
-        context = {
+    def _rollout_context(self, cem_itr):
+        """What the predictor is told of the present at CEM iteration ``cem_itr``."""
+        return {
             "context_frames": context_frames(self),
             "context_actions": self._sampler.chosen_actions,
             "context_pixel_distributions": self._make_input_distrib(cem_itr),
             "context_states": context_states(self),
         }
+
+    def _fused_scores_done(self, cem_itr, scores, scores_per_task, row_base=0):
+        """What follows the predictor's fused scores of iteration ``cem_itr``: the task log, and the distributions of the
+        best plan for ``predictor_propagation``.  ``row_base``: the predictor's index of this controller's first candidate
+        (``BatchedPixelCostPlanner``: the rows of several controllers lie in one rollout)."""
+        self._log_task_scores(scores, scores_per_task)
+        if self._hp.predictor_propagation and cem_itr == self._hp.iterations - 1:
+            bestind = scores.argsort()[0]
+            self._chosen_distrib = self.predictor.fetch_pixel_distributions(row_base + bestind)
+
+    def evaluate_rollouts(self, actions, cem_itr):
+        context = self._rollout_context(cem_itr)
         if hasattr(self.predictor, 'score'):
             weights = self._task_weights()
             on_device = weights is not None and getattr(self.predictor, 'supports_task_weights', False)
@@ -194,10 +207,7 @@ class PixelCostController(CEMBaseController):
                 only_take_first_view=self._hp.only_take_first_view, **kw)
             if weights is not None and not on_device:
                 scores = np.sum(scores_per_task * np.asarray(weights).reshape(1, -1), axis=1)
-            self._log_task_scores(scores, scores_per_task)
-            if self._hp.predictor_propagation and cem_itr == self._hp.iterations - 1:
-                bestind = scores.argsort()[0]
-                self._chosen_distrib = self.predictor.fetch_pixel_distributions(bestind)
+            self._fused_scores_done(cem_itr, scores, scores_per_task)
         else:
             prediction = self.predictor(context, {'actions': actions})
             gen_images = prediction['predicted_frames']
@@ -350,8 +360,12 @@ class PixelCostController(CEMBaseController):
         :param images: uint8 history ``[t+1, ncam, H, W, 3]``
         :param state: state history ``[t+1, sdim]``
         """
+        self._set_task(desig_pix, goal_pix, images, verbose_worker)
+        return super(PixelCostController, self).act(t, i_tr, state)
+
+    def _set_task(self, desig_pix, goal_pix, images, verbose_worker=None):
+        """The task part of an ``act`` call: where the designated pixels are and should go, and the image history."""
         self._desig_pix = np.array(desig_pix).reshape((self._n_cam, self._n_desig, 2))
         self._goal_pix = np.array(goal_pix).reshape((self._n_cam, self._n_desig, 2))
         self._images = images
         self._verbose_worker = verbose_worker
-        return super(PixelCostController, self).act(t, i_tr, state)

@@ -401,36 +401,8 @@ class HipVPredEvaluation(object):
         return ctypes.c_void_p(self._torch.cuda.current_stream(self.device).cuda_stream)
 
     def _set_context(self, context):
-        torch, nc, c = self._torch, self.n_context, self.cfg
-        ncam = self.n_cam
-        frames = np.ascontiguousarray(np.asarray(context['context_frames'])[-nc:, :ncam])
-        if self.camera_size is not None:
-            if frames.dtype != np.uint8 or frames.shape != (nc, ncam) + self.camera_size + (3,):
-                raise ValueError('context_frames must be uint8 [>=%d, %d, %d, %d, 3] at the camera size %d x %d (the model '
-                                 'size is %d x %d: they are shrunk on the device), got %s %s'
-                                 % ((nc, ncam) + self.camera_size + self.camera_size + (c.height, c.width, frames.dtype,
-                                                                                       frames.shape)))
-        elif frames.dtype != np.uint8 or frames.shape != (nc, ncam, c.height, c.width, 3):
-            raise ValueError('context_frames must be uint8 [>=%d, %d, %d, %d, 3], got %s %s'
-                             % (nc, ncam, c.height, c.width, frames.dtype, frames.shape))
-        if self.frames_only:
-            if context.get('context_pixel_distributions') is not None:
-                raise ValueError('this predictor is frames-only (designated_pixel_count 0 / no_pix_distrib): the context '
-                                 'must not carry context_pixel_distributions')
-            distrib = np.zeros((nc, ncam, c.height, c.width, 0), np.float32)
-        else:
-            distrib = np.ascontiguousarray(
-                np.asarray(context['context_pixel_distributions'], dtype=np.float32)[-nc:, :ncam])
-        states = np.ascontiguousarray(np.asarray(context['context_states'], dtype=np.float32)[-nc:])
-        if states.shape != (nc, c.sdim) or distrib.shape != (nc, ncam, c.height, c.width, c.ndesig):
-            raise ValueError('bad context shapes: states %s distrib %s' % (states.shape, distrib.shape))
-        if nc > 1:
-            acts = np.asarray(context['context_actions'], dtype=np.float32).reshape(-1, c.adim)[-(nc - 1):]
-            if acts.shape[0] != nc - 1:
-                raise ValueError('need at least %d executed actions as context' % (nc - 1))
-            acts = np.ascontiguousarray(acts)
-        else:
-            acts = np.zeros((1, c.adim), np.float32)
+        torch, c = self._torch, self.cfg
+        frames, states, acts, distrib = self._context_arrays(context)
         # the CEM iterations of one planning call pass the same context: upload it (and let the
         # engine recompute the context-only part of the network) only when it actually changed
         key = (frames, states, acts, distrib)
@@ -584,6 +556,134 @@ class HipVPredEvaluation(object):
 
         rows_np = score_rows(self, seqs, M, 1 + self.n_cam * self.cfg.ndesig, rows_of)
         return pixel_cost_columns(rows_np, only_take_first_view)
+
+    # ------------------------------------------------------------------ batched planning: G problems in one rollout
+    def _context_arrays(self, context):
+        """One context dictionary -> the arrays the engine is given: (frames, states, actions, distributions), the last
+        ``n_context`` steps, checked (frames at the model's or - ``camera_size`` - the camera's size).  The one source of
+        ``_set_context`` and ``_set_contexts``."""
+        nc, c = self.n_context, self.cfg
+        ncam = self.n_cam
+        frames = np.ascontiguousarray(np.asarray(context['context_frames'])[-nc:, :ncam])
+        if self.camera_size is not None:
+            if frames.dtype != np.uint8 or frames.shape != (nc, ncam) + self.camera_size + (3,):
+                raise ValueError('context_frames must be uint8 [>=%d, %d, %d, %d, 3] at the camera size %d x %d (the model '
+                                 'size is %d x %d: they are shrunk on the device), got %s %s'
+                                 % ((nc, ncam) + self.camera_size + self.camera_size + (c.height, c.width, frames.dtype,
+                                                                                       frames.shape)))
+        elif frames.dtype != np.uint8 or frames.shape != (nc, ncam, c.height, c.width, 3):
+            raise ValueError('context_frames must be uint8 [>=%d, %d, %d, %d, 3], got %s %s'
+                             % (nc, ncam, c.height, c.width, frames.dtype, frames.shape))
+        if self.frames_only:
+            if context.get('context_pixel_distributions') is not None:
+                raise ValueError('this predictor is frames-only (designated_pixel_count 0 / no_pix_distrib): the context '
+                                 'must not carry context_pixel_distributions')
+            distrib = np.zeros((nc, ncam, c.height, c.width, 0), np.float32)
+        else:
+            distrib = np.ascontiguousarray(
+                np.asarray(context['context_pixel_distributions'], dtype=np.float32)[-nc:, :ncam])
+        states = np.ascontiguousarray(np.asarray(context['context_states'], dtype=np.float32)[-nc:])
+        if states.shape != (nc, c.sdim) or distrib.shape != (nc, ncam, c.height, c.width, c.ndesig):
+            raise ValueError('bad context shapes: states %s distrib %s' % (states.shape, distrib.shape))
+        if nc > 1:
+            acts = np.asarray(context['context_actions'], dtype=np.float32).reshape(-1, c.adim)[-(nc - 1):]
+            if acts.shape[0] != nc - 1:
+                raise ValueError('need at least %d executed actions as context' % (nc - 1))
+            acts = np.ascontiguousarray(acts)
+        else:
+            acts = np.zeros((1, c.adim), np.float32)
+        return frames, states, acts, distrib
+
+    def grouped_refusal(self):
+        """Why this predictor cannot roll grouped contexts (``_set_contexts``), or None when it can."""
+        if self._lanes:
+            return 'grouped contexts drive one engine: this predictor has %d in-process lanes (n_gpus > 1)' % len(self._lanes)
+        if _dist_info()[1] > 1:
+            return 'grouped contexts drive one engine: torch.distributed has %d ranks' % _dist_info()[1]
+        if self.n_draws != 1:
+            return 'grouped contexts need n_draws = 1, this predictor has %d' % self.n_draws
+        if type(self)._prepare is not HipVPredEvaluation._prepare:
+            return 'grouped contexts roll the actions as they are given: %s overrides _prepare' % type(self).__name__
+        if self.arch != 'cdna':
+            return "grouped contexts need arch 'cdna', this predictor has %r" % (self.arch,)
+        return None
+
+    def score_batch_refusal(self):
+        """Why ``score_batch`` cannot serve this predictor, or None when it can: ``grouped_refusal``'s reasons, and a
+        frames-only engine (it may still roll grouped contexts; only the pixel cost is refused)."""
+        reason = self.grouped_refusal()
+        if reason is None and self.frames_only:
+            reason = ('score_batch needs pixel distributions; this predictor is frames-only (designated_pixel_count 0 / '
+                      'no_pix_distrib)')
+        return reason
+
+    def _set_contexts(self, contexts, rows_per_group):
+        """Upload ``contexts`` (a list of G context dictionaries) as the grouped contexts of the coming rollout of
+        ``G * rows_per_group`` rows: one ``vf_set_contexts``.  The single-context key is dropped - the next single-context call
+        uploads its context again."""
+        reason = self.grouped_refusal()
+        if reason:
+            raise ValueError(reason)
+        torch, c = self._torch, self.cfg
+        G = len(contexts)
+        if G < 1 or rows_per_group < 1 or G * rows_per_group > self.run_batch_size:
+            raise ValueError('grouped contexts: %d problems x %d rows do not fit run_batch_size = %d (all rows of a call '
+                             'stay resident in one chunk)' % (G, rows_per_group, self.run_batch_size))
+        parts = [self._context_arrays(ctx) for ctx in contexts]
+        frames, states, acts, distrib = (np.stack([p[i] for p in parts]) for i in range(4))
+        self._ctx_key = None
+        dev = self.device
+        with torch.cuda.device(dev):
+            f, s, a, d = self._ctx = [torch.from_numpy(x).to(dev) for x in (frames, states, acts, distrib)]
+            if self.camera_size is not None:    # [G, nc, ncam] images at the camera's size, shrunk where the engine reads them
+                f = self._ctx[0] = resample.area_resize_device(f, (c.height, c.width))
+            _lib.check(self._libh.vf_set_contexts(self._handle, G, int(rows_per_group), f.data_ptr(), s.data_ptr(),
+                                                  a.data_ptr(), None if self.frames_only else d.data_ptr(), self._stream()))
+
+    def score_batch(self, contexts, inputs, goal_pix, finalweight=10., only_take_first_view=False, task_weights=None):
+        """``score`` for G independent planning problems in ONE rollout launch.  ``contexts``: a list of G context
+        dictionaries, each what ``score`` takes; ``inputs['actions']`` ``[G, M, T, adim]``; ``goal_pix`` ``[G, ncam, ndesig,
+        2]``; ``task_weights`` ``[G, ncam, ndesig]`` or None -> float64 ``(scores [G, M], scores_per_task [G, M, tasks])``.
+        One ``vf_set_contexts``, one ``vf_rollout``, one ``vf_group_pixel_scores``; ``G * M <= run_batch_size``, so all rows
+        stay resident: ``fetch_pixel_distributions(g * M + i)`` returns row ``i`` of problem ``g``.  ValueError: see
+        ``score_batch_refusal``."""
+        reason = self.score_batch_refusal()
+        if reason:
+            raise ValueError(reason)
+        torch = self._torch
+        actions = np.asarray(inputs['actions'])
+        G = len(contexts)
+        T = self.sequence_length - self.n_context
+        if actions.ndim != 4 or actions.shape[0] != G or actions.shape[2:] != (T, self.cfg.adim) or actions.shape[1] < 1:
+            raise ValueError('actions must be [G=%d, M, %d, %d], got %s' % (G, T, self.cfg.adim, actions.shape))
+        M = actions.shape[1]
+        ntask = self.n_cam * self.cfg.ndesig
+        goal = np.ascontiguousarray(np.asarray(goal_pix).reshape(-1).astype(np.int32))
+        if goal.size != G * ntask * 2:
+            raise ValueError('goal_pix must hold [G=%d][ncam=%d][ndesig=%d][2] values, got %d'
+                             % (G, self.n_cam, self.cfg.ndesig, goal.size))
+        weights_c = None
+        if task_weights is not None:
+            w = np.asarray(task_weights, dtype=np.float64).reshape(-1)
+            if w.size != G * ntask:
+                raise ValueError('task_weights must hold G * ncam * ndesig = %d values' % (G * ntask))
+            weights_c = (ctypes.c_float * (G * ntask))(*[float(v) for v in w])
+        self._set_contexts(contexts, M)
+        with torch.cuda.device(self.device):
+            seqs = torch.from_numpy(np.ascontiguousarray(actions.reshape(G * M, T, -1), dtype=np.float32)).to(self.device)
+            goal_dev = torch.from_numpy(goal).to(self.device)
+            scores, per_task = (torch.empty(s, dtype=torch.float64, device=self.device) for s in ((G * M,), (G * M, ntask)))
+            # (vf_rollout's own scores - every row against problem 0's goal - are overwritten by the grouped cost)
+            self._rollout_chunk(seqs, goal[:2 * ntask], finalweight, scores, per_task)
+            _lib.check(self._libh.vf_group_pixel_scores(self._handle, goal_dev.data_ptr(), ctypes.c_float(finalweight),
+                                                        weights_c, scores.data_ptr(), per_task.data_ptr(), self._stream()))
+            rows_np = torch.cat([scores[:, None], per_task], dim=1).cpu().numpy()
+        # what is resident: rows [0, G * M) of this call; a fetch of anything else has nothing to re-roll from
+        self._last_lo, self._last_M = 0, G * M
+        self._last_prepared = None
+        self._check_scores(rows_np[:, 0])
+        scores_np, per_task_np = pixel_cost_columns(rows_np, only_take_first_view)
+        return scores_np.reshape(G, M), per_task_np.reshape(G, M, -1)
 
     def score_device_refusal(self):
         """Why ``score_device`` cannot serve this predictor, or None when it can (a planner asks before it commits a planning
