@@ -2,7 +2,12 @@
 // proposal (first part), for the time-correlated noise proposal (second part) and for the folding proposal (third part, which
 // shares the Gaussian workspace and refit and adds a sampling kernel); the fourth part draws a stochastic predictor's latents
 // and folds them into the candidates; the fifth is the autograsp proposal, the Gaussian one with a derived gripper column.
-// The later parts have header comments of their own.
+// The later parts' header comments say what differs from the first.  Every piece of arithmetic two kernels share is one
+// __device__ __forceinline__ function here (cem_select_elites, cem_fit_factor, cem_copy_elites, cem_normals, cem_gauss,
+// cem_chain, cem_store_held, cem_fill_tail, cem_draw, cem_emit, cem_store_moves), as the float64 twins share philox4x32_10,
+// standard_normals, fit_factor and draw: these lines are the numerical contract with them, each float64 operation the
+// explicit single-rounding intrinsic or fma, in one order (the build keeps -ffp-contract=off).  A function that shuffles or
+// votes is called by all 64 lanes of a wave.
 //
 // Specification: visual_foresight_amd/policy/cem_controllers/samplers/philox_gaussian_sampler.py (a float64 NumPy class that
 // is a sampler in its own right).  These kernels compute its numbers: elite indices, trial counts, mean and A bit for bit;
@@ -86,11 +91,33 @@ __device__ __forceinline__ void cem_select_elites(const double *scores, int M, i
     __syncthreads();
 }
 
+// The factor fit of dimension d (one thread): the elites' value of it lies at `at` of their plans of `plan` floats, `sum` is
+// their sum in rank order.  mean[d] = sum / K, A[k][d] = (e_k - mean) / sqrt(K - 1).
+__device__ __forceinline__ void cem_fit_factor(const float *actions, const int *s_elite, int K, int plan, long long at, double sum,
+                                               int D, int d, double *mean, double *A) {
+    const double m = __ddiv_rn(sum, (double)K);
+    const double scale = __dsqrt_rn((double)(K - 1));
+    mean[d] = m;
+    for (int k = 0; k < K; ++k) {
+        const double e = (double)actions[(long long)s_elite[k] * plan + at];
+        A[(long long)k * D + d] = __ddiv_rn(__dsub_rn(e, m), scale);
+    }
+}
+
+// elite_plans [K][plan]: the elites' plans in rank order (one workgroup, all of it)
+__device__ __forceinline__ void cem_copy_elites(const float *actions, const int *s_elite, int K, int plan, float *elite_plans) {
+    for (int e = threadIdx.x; e < K * plan; e += kCemThreads) {
+        const int k = e / plan;
+        elite_plans[e] = actions[(long long)s_elite[k] * plan + (e - k * plan)];
+    }
+}
+
 VF_GLOBAL VF_LAUNCH_BOUNDS(kCemThreads) void cem_refit_kernel(const CemParams p) {
     __shared__ double s_score[kCemMaxM];
     __shared__ int s_elite[kCemMaxK];
     const int tid = threadIdx.x;
     const int D = p.nactions * p.adim, T = p.nactions * p.repeat, W = p.adim + p.tail, K = p.K, M = p.M;
+    const int plan = T * W;
     cem_select_elites(p.scores, M, K, s_score, s_elite, p.elite_index, p.elite_score);
     char *ws = static_cast<char *>(p.workspace);
     double *mean = reinterpret_cast<double *>(ws + kCemHeaderBytes);
@@ -103,20 +130,10 @@ VF_GLOBAL VF_LAUNCH_BOUNDS(kCemThreads) void cem_refit_kernel(const CemParams p)
         const int a = tid / p.adim, c = tid % p.adim;
         const long long at = (long long)(a * p.repeat + p.repeat - 1) * W + c;      // the last step of the held action
         double sum = 0.0;
-        for (int k = 0; k < K; ++k) sum = __dadd_rn(sum, (double)p.actions_in[(long long)s_elite[k] * T * W + at]);
-        const double m = __ddiv_rn(sum, (double)K);
-        const double scale = __dsqrt_rn((double)(K - 1));
-        mean[tid] = m;
-        for (int k = 0; k < K; ++k) {
-            const double e = (double)p.actions_in[(long long)s_elite[k] * T * W + at];
-            A[(long long)k * D + tid] = __ddiv_rn(__dsub_rn(e, m), scale);
-        }
+        for (int k = 0; k < K; ++k) sum = __dadd_rn(sum, (double)p.actions_in[(long long)s_elite[k] * plan + at]);
+        cem_fit_factor(p.actions_in, s_elite, K, plan, at, sum, D, tid, mean, A);
     }
-    const int plan = T * W;
-    for (int e = tid; e < K * plan; e += kCemThreads) {
-        const int k = e / plan;
-        p.elite_plans[e] = p.actions_in[(long long)s_elite[k] * plan + (e - k * plan)];
-    }
+    cem_copy_elites(p.actions_in, s_elite, K, plan, p.elite_plans);
 }
 
 __device__ __forceinline__ void cem_philox(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1,
@@ -141,6 +158,63 @@ __device__ __forceinline__ void cem_pair(unsigned x, unsigned y, double &zc, dou
     zs = __dmul_rn(rho, sin(phi));
 }
 
+// Philox block `block` of (trial, sample, call) as four standard normals
+__device__ __forceinline__ void cem_normals(unsigned block, unsigned trial, unsigned sample, unsigned call, unsigned seed_lo,
+                                            unsigned seed_hi, double z[4]) {
+    unsigned w[4];
+    cem_philox(block, trial, sample, call, seed_lo, seed_hi, w);
+    cem_pair(w[0], w[1], z[0], z[1]);
+    cem_pair(w[2], w[3], z[2], z[3]);
+}
+
+// The Gaussian workspace as a sampling kernel reads it
+struct CemGauss {
+    int R, n_blocks;                    // columns of A in use; their Philox blocks (<= 64: one per lane)
+    const double *mean, *A;
+};
+__device__ __forceinline__ CemGauss cem_gauss(const void *workspace, int D, int K) {
+    const char *ws = static_cast<const char *>(workspace);
+    CemGauss g;
+    g.R = max(0, min(*reinterpret_cast<const int *>(ws), cem_rmax(D, K)));      // never past the workspace, whatever the header holds
+    g.n_blocks = (g.R + 3) >> 2;
+    g.mean = reinterpret_cast<const double *>(ws + kCemHeaderBytes);
+    g.A = g.mean + D;
+    return g;
+}
+
+// The factor-form chain of the lane's two dimensions, d = lane and lane + 64: x_d = fma(A[d, r], z_r, x_d) for r ascending
+// from the caller's x_d, z_r being z[r % 4] of lane r / 4 (every lane of the wave calls this: the shuffles are wave-wide).
+__device__ __forceinline__ void cem_chain(const CemGauss &g, int D, int lane, const double z[4], double &x0, double &x1) {
+    const int d0 = lane, d1 = lane + 64;
+    const bool live0 = d0 < D, live1 = d1 < D;
+    for (int j = 0; j < g.n_blocks; ++j) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int r = 4 * j + q;
+            const double zr = __shfl(z[q], j);
+            if (r < g.R) {
+                const double a0 = live0 ? g.A[(long long)r * D + d0] : 0.0;
+                const double a1 = live1 ? g.A[(long long)r * D + d1] : 0.0;
+                x0 = fma(a0, zr, x0);
+                x1 = fma(a1, zr, x1);
+            }
+        }
+    }
+}
+
+// column c of the `repeat` steps that hold action a of a sample's rows `out` of W floats
+__device__ __forceinline__ void cem_store_held(float *out, int a, int repeat, int W, int c, float f) {
+    for (int q = 0; q < repeat; ++q) out[(a * repeat + q) * W + c] = f;
+}
+
+// the appended constants: columns col .. col + count - 1 of all T rows of a sample take value[0 .. count - 1] (the wave's lanes)
+__device__ __forceinline__ void cem_fill_tail(float *out, int lane, int T, int W, int col, int count, const double *value) {
+    for (int e = lane; e < T * count; e += 64) {
+        const int t = e / count, k = e % count;
+        out[t * W + col + k] = (float)value[k];
+    }
+}
+
 __device__ __forceinline__ double cem_clip(double v, double lo, double hi) {     // NaN stays NaN
     return v < lo ? lo : (v > hi ? hi : v);
 }
@@ -157,44 +231,22 @@ struct CemLane {
 // The trials of sample i (every lane of its wave calls this: the shuffles and the vote are wave-wide).
 __device__ __forceinline__ CemLane cem_draw(const CemParams &p, int lane, int i) {
     const int D = p.nactions * p.adim;
-    const char *ws = static_cast<const char *>(p.workspace);
-    const double *mean = reinterpret_cast<const double *>(ws + kCemHeaderBytes);
-    const double *A = mean + D;
-    int R = *reinterpret_cast<const int *>(ws);
-    R = max(0, min(R, cem_rmax(D, p.K)));       // never past the workspace, whatever the header holds
-    const int n_blocks = (R + 3) >> 2;          // <= 64: one per lane
+    const CemGauss g = cem_gauss(p.workspace, D, p.K);
     CemLane s;
     s.d0 = lane; s.d1 = lane + 64;
     const int d0 = s.d0, d1 = s.d1;
     const bool live0 = d0 < D, live1 = d1 < D;
     s.c0 = live0 ? d0 % p.adim : 0; s.c1 = live1 ? d1 % p.adim : 0;
-    const double m0 = live0 ? mean[d0] : 0.0, m1 = live1 ? mean[d1] : 0.0;
+    const double m0 = live0 ? g.mean[d0] : 0.0, m1 = live1 ? g.mean[d1] : 0.0;
     const double lim0 = p.rej_lim[s.c0], lim1 = p.rej_lim[s.c1];
     double x0 = m0, x1 = m1;
     int n = 0;
     bool accepted = false;
     for (; n < p.max_trials; ++n) {
         double z[4] = {0.0, 0.0, 0.0, 0.0};
-        if (lane < n_blocks) {
-            unsigned w[4];
-            cem_philox((unsigned)lane, (unsigned)n, (unsigned)i, p.call, p.seed_lo, p.seed_hi, w);
-            cem_pair(w[0], w[1], z[0], z[1]);
-            cem_pair(w[2], w[3], z[2], z[3]);
-        }
+        if (lane < g.n_blocks) cem_normals((unsigned)lane, (unsigned)n, (unsigned)i, p.call, p.seed_lo, p.seed_hi, z);
         x0 = m0; x1 = m1;
-        for (int j = 0; j < n_blocks; ++j) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int r = 4 * j + q;
-                const double zr = __shfl(z[q], j);
-                if (r < R) {
-                    const double a0 = live0 ? A[(long long)r * D + d0] : 0.0;
-                    const double a1 = live1 ? A[(long long)r * D + d1] : 0.0;
-                    x0 = fma(a0, zr, x0);
-                    x1 = fma(a1, zr, x1);
-                }
-            }
-        }
+        cem_chain(g, D, lane, z, x0, x1);
         const bool ok = (!live0 || fabs(x0) <= lim0) && (!live1 || fabs(x1) <= lim1);
         if (!p.rejection || __all(ok)) { accepted = true; break; }
     }
@@ -216,29 +268,34 @@ __device__ __forceinline__ float cem_emit(const CemParams &p, const CemLane &s, 
     return (float)v;
 }
 
-VF_GLOBAL VF_LAUNCH_BOUNDS(kCemThreads) void cem_sample_kernel(const CemParams p) {
-    const int lane = threadIdx.x & 63;
-    const int i = blockIdx.x * kCemWaves + (threadIdx.x >> 6);
-    if (i >= p.M) return;               // whole waves leave: nothing below waits for another wave
-    const int D = p.nactions * p.adim, T = p.nactions * p.repeat, W = p.adim + p.tail;
-    const CemLane s = cem_draw(p, lane, i);
+// What cem_draw left goes out: trials / capped of sample i (lane 0) and the lane's two dimensions over their held steps of
+// the sample's rows `out`; f[half] is what the lane stored (0 where it owns no dimension).
+__device__ __forceinline__ void cem_store_moves(const CemParams &p, const CemLane &s, int lane, int i, float *out, float f[2]) {
+    const int D = p.nactions * p.adim, W = p.adim + p.tail;
     if (lane == 0) {
         p.trials[i] = s.accepted ? s.n + 1 : p.max_trials;
         p.capped[i] = s.accepted ? 0 : 1;
     }
-    float *out = p.actions_out + (long long)i * T * W;
+    f[0] = f[1] = 0.f;
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
         const int d = half ? s.d1 : s.d0, c = half ? s.c1 : s.c0;
         if (d >= D) continue;
-        const float f = cem_emit(p, s, half, i);
-        const int a = d / p.adim;
-        for (int q = 0; q < p.repeat; ++q) out[(a * p.repeat + q) * W + c] = f;
+        f[half] = cem_emit(p, s, half, i);
+        cem_store_held(out, d / p.adim, p.repeat, W, c, f[half]);
     }
-    for (int e = lane; e < T * p.tail; e += 64) {
-        const int t = e / p.tail, k = e % p.tail;
-        out[t * W + p.adim + k] = (float)p.tail_value[k];
-    }
+}
+
+VF_GLOBAL VF_LAUNCH_BOUNDS(kCemThreads) void cem_sample_kernel(const CemParams p) {
+    const int lane = threadIdx.x & 63;
+    const int i = blockIdx.x * kCemWaves + (threadIdx.x >> 6);
+    if (i >= p.M) return;               // whole waves leave: nothing below waits for another wave
+    const int T = p.nactions * p.repeat, W = p.adim + p.tail;
+    const CemLane s = cem_draw(p, lane, i);
+    float *out = p.actions_out + (long long)i * T * W;
+    float f[2];
+    cem_store_moves(p, s, lane, i, out, f);
+    cem_fill_tail(out, lane, T, W, p.adim, p.tail, p.tail_value);
 }
 
 // ------------------------------------------------------------------ the correlated-noise proposal
@@ -252,11 +309,10 @@ VF_GLOBAL VF_LAUNCH_BOUNDS(kCemThreads) void cem_sample_kernel(const CemParams p
 //   double soft[K]                     their weights
 //   double A[K][D]                     refit_cov only: A[d, k] at [k][d]
 //
-//   cem_soft_refit_kernel   ONE workgroup: cem_select_elites, soft_k staged in LDS, then one thread per d.
-//   cem_sample_corr_kernel  one wavefront per sample, four per workgroup.  Lane l makes Philox block l (D <= 128: 32 blocks)
-//                           and owns d = l and d = l + 64; the shaped values go to the wave's LDS strip, lanes c < adim run
-//                           the serial AR(1) chain of their column in it, every lane adds the centre.  No data-dependent
-//                           loop; the only barriers are the wave's own.
+//   cem_soft_refit_kernel   cem_refit_kernel with soft_k staged in LDS and the centre beside the fit (refit_cov only: the fit).
+//   cem_sample_corr_kernel  waves and lanes as cem_sample_kernel, one trial of D normals (<= 32 blocks).  The shaped values go
+//                           to the wave's LDS strip, lanes c < adim run the serial AR(1) chain of their column in it, every
+//                           lane adds the centre.  No data-dependent loop; the only barriers are the wave's own.
 struct CemCorrParams {
     int nactions, adim, tail, K, M;
     int refit_cov, has_first_prev;
@@ -310,20 +366,9 @@ VF_GLOBAL VF_LAUNCH_BOUNDS(kCemThreads) void cem_soft_refit_kernel(const CemCorr
             sum = __dadd_rn(sum, e);
         }
         centre[tid] = __ddiv_rn(num, __dadd_rn(den, 1e-4));
-        if (p.refit_cov) {
-            const double m = __ddiv_rn(sum, (double)K);
-            const double scale = __dsqrt_rn((double)(K - 1));
-            mean[tid] = m;
-            for (int k = 0; k < K; ++k) {
-                const double e = (double)p.actions_in[(long long)s_elite[k] * plan + at];
-                A[(long long)k * D + tid] = __ddiv_rn(__dsub_rn(e, m), scale);
-            }
-        }
+        if (p.refit_cov) cem_fit_factor(p.actions_in, s_elite, K, plan, at, sum, D, tid, mean, A);
     }
-    for (int e = tid; e < K * plan; e += kCemThreads) {
-        const int k = e / plan;
-        p.elite_plans[e] = p.actions_in[(long long)s_elite[k] * plan + (e - k * plan)];
-    }
+    cem_copy_elites(p.actions_in, s_elite, K, plan, p.elite_plans);
 }
 
 // what the other lanes of the wave wrote to LDS is visible behind this
@@ -350,12 +395,7 @@ VF_GLOBAL VF_LAUNCH_BOUNDS(kCemThreads) void cem_sample_corr_kernel(const CemCor
     const bool live0 = d0 < D, live1 = d1 < D;
     const int c0 = live0 ? d0 % p.adim : 0, c1 = live1 ? d1 % p.adim : 0;
     double z[4] = {0.0, 0.0, 0.0, 0.0};
-    if (lane < n_blocks) {
-        unsigned w[4];
-        cem_philox((unsigned)lane, 0u, (unsigned)i, p.call, p.seed_lo, p.seed_hi, w);
-        cem_pair(w[0], w[1], z[0], z[1]);
-        cem_pair(w[2], w[3], z[2], z[3]);
-    }
+    if (lane < n_blocks) cem_normals((unsigned)lane, 0u, (unsigned)i, p.call, p.seed_lo, p.seed_hi, z);
     double s0 = 0.0, s1 = 0.0;
     if (R == 0) {
         double w0 = 0.0, w1 = 0.0;      // w_d lies in lane d / 4 as z[d % 4]
@@ -416,20 +456,16 @@ VF_GLOBAL VF_LAUNCH_BOUNDS(kCemThreads) void cem_sample_corr_kernel(const CemCor
         if (centred) v = __dadd_rn(v, centre[d]);
         out[(d / p.adim) * W + c] = (float)v;
     }
-    for (int e = lane; e < p.nactions * p.tail; e += 64) {
-        const int t = e / p.tail, k = e % p.tail;
-        out[t * W + p.adim + k] = (float)p.tail_value[k];
-    }
+    cem_fill_tail(out, lane, p.nactions, W, p.adim, p.tail, p.tail_value);
 }
 
 // ------------------------------------------------------------------ the folding proposal
 // Specification: samplers/philox_folding_sampler.py.  The proposal, its workspace and its refit are the Gaussian one's
 // (cem_refit_kernel with adim = 4); only the sampling differs.  The actions up to the device's log / sin / cos.
 //
-//   cem_sample_fold_kernel  one wavefront per sample, four per workgroup, no LDS, no barrier, no data-dependent loop.
-//                           Sample i < n_scripted is TWO_PLACES, i < 2 n_scripted ONE_PLACE, the rest plain (a wave-uniform
-//                           branch).  Lane l makes Philox block l of a trial and owns d = l and d = l + 64, both of channel
-//                           c = l & 3.  Plain: trial 0, the chain of cem_sample_kernel.  Scripted: the places from trial 1,
+//   cem_sample_fold_kernel  waves and lanes as cem_sample_kernel (both dimensions of a lane are of channel c = l & 3), no
+//                           data-dependent loop.  Sample i < n_scripted is TWO_PLACES, i < 2 n_scripted ONE_PLACE, the rest
+//                           plain (a wave-uniform branch).  Plain: trial 0 through cem_chain.  Scripted: the places from trial 1,
 //                           block 0 (every lane makes it); then per scripted step s (trial 2 + s) the chain
 //                           y_c = sum_r A[c, r] z_r from 0.0 over row c of A, v_c = m_c + g_c y_c, and a lane keeps the value
 //                           of the step its action index maps to (ONE_PLACE holds its last step, TWO_PLACES leaves zero).
@@ -449,39 +485,16 @@ VF_GLOBAL VF_LAUNCH_BOUNDS(kCemThreads) void cem_sample_fold_kernel(const CemFol
     const int i = blockIdx.x * kCemWaves + (threadIdx.x >> 6);
     if (i >= p.M) return;               // whole waves leave: nothing below waits for another wave
     const int D = p.nactions * kCemFoldAdim, T = p.nactions * p.repeat, W = kCemFoldAdim + p.tail;
-    const char *ws = static_cast<const char *>(p.workspace);
-    const double *mean = reinterpret_cast<const double *>(ws + kCemHeaderBytes);
-    const double *A = mean + D;
-    int R = *reinterpret_cast<const int *>(ws);
-    R = max(0, min(R, cem_rmax(D, p.K)));       // never past the workspace, whatever the header holds
-    const int n_blocks = (R + 3) >> 2;          // <= 64: one per lane
+    const CemGauss g = cem_gauss(p.workspace, D, p.K);
     const int d0 = lane, d1 = lane + 64;
-    const bool live0 = d0 < D, live1 = d1 < D;
     const int c = lane & 3, a0 = lane >> 2, a1 = a0 + 16;
     double x0 = 0.0, x1 = 0.0;
     if (i >= 2 * p.n_scripted) {                // plain: the Gaussian sampler's unrejected draw
         double z[4] = {0.0, 0.0, 0.0, 0.0};
-        if (lane < n_blocks) {
-            unsigned w[4];
-            cem_philox((unsigned)lane, 0u, (unsigned)i, p.call, p.seed_lo, p.seed_hi, w);
-            cem_pair(w[0], w[1], z[0], z[1]);
-            cem_pair(w[2], w[3], z[2], z[3]);
-        }
-        x0 = live0 ? mean[d0] : 0.0;
-        x1 = live1 ? mean[d1] : 0.0;
-        for (int j = 0; j < n_blocks; ++j) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int r = 4 * j + q;
-                const double zr = __shfl(z[q], j);
-                if (r < R) {
-                    const double e0 = live0 ? A[(long long)r * D + d0] : 0.0;
-                    const double e1 = live1 ? A[(long long)r * D + d1] : 0.0;
-                    x0 = fma(e0, zr, x0);
-                    x1 = fma(e1, zr, x1);
-                }
-            }
-        }
+        if (lane < g.n_blocks) cem_normals((unsigned)lane, 0u, (unsigned)i, p.call, p.seed_lo, p.seed_hi, z);
+        x0 = d0 < D ? g.mean[d0] : 0.0;
+        x1 = d1 < D ? g.mean[d1] : 0.0;
+        cem_chain(g, D, lane, z, x0, x1);
     } else {
         const bool two = i < p.n_scripted;
         unsigned pw[4];
@@ -499,19 +512,15 @@ VF_GLOBAL VF_LAUNCH_BOUNDS(kCemThreads) void cem_sample_fold_kernel(const CemFol
         const int s1 = two ? -1 : n_steps - 1;  // (a1 >= 16 is past either script)
         for (int s = 0; s < n_steps; ++s) {
             double z[4] = {0.0, 0.0, 0.0, 0.0};
-            if (lane < n_blocks) {
-                unsigned w[4];
-                cem_philox((unsigned)lane, (unsigned)(2 + s), (unsigned)i, p.call, p.seed_lo, p.seed_hi, w);
-                cem_pair(w[0], w[1], z[0], z[1]);
-                cem_pair(w[2], w[3], z[2], z[3]);
-            }
+            if (lane < g.n_blocks) cem_normals((unsigned)lane, (unsigned)(2 + s), (unsigned)i, p.call, p.seed_lo, p.seed_hi, z);
+            // the one-row chain stays written out: through cem_chain it would carry a second, dead fma per step (d = c + 64)
             double y = 0.0;
-            for (int j = 0; j < n_blocks; ++j) {
+            for (int j = 0; j < g.n_blocks; ++j) {
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     const int r = 4 * j + q;
                     const double zr = __shfl(z[q], j);
-                    if (r < R) y = fma(A[(long long)r * D + c], zr, y);
+                    if (r < g.R) y = fma(g.A[(long long)r * D + c], zr, y);
                 }
             }
             const bool carry = two ? (s == 0 || s == 3) : s == 1;
@@ -531,23 +540,18 @@ VF_GLOBAL VF_LAUNCH_BOUNDS(kCemThreads) void cem_sample_fold_kernel(const CemFol
         if (d >= D) continue;
         double v = half ? x1 : x0;
         if (c < 3) v = cem_clip(v, -p.max_shift[c], p.max_shift[c]);
-        const float f = (float)v;
-        const int a = half ? a1 : a0;
-        for (int q = 0; q < p.repeat; ++q) out[(a * p.repeat + q) * W + c] = f;
+        cem_store_held(out, half ? a1 : a0, p.repeat, W, c, (float)v);
     }
-    for (int e = lane; e < T * p.tail; e += 64) {
-        const int t = e / p.tail, k = e % p.tail;
-        out[t * W + kCemFoldAdim + k] = (float)p.tail_value[k];
-    }
+    cem_fill_tail(out, lane, T, W, kCemFoldAdim, p.tail, p.tail_value);
 }
 
 // ------------------------------------------------------------------ latent draws of the stochastic predictor
 // Specification: video_prediction/stochastic_predictor.py, philox_latents / fold_latents.  The latents up to the device's
 // log / sin / cos; the fold is copying.
 //
-//   cem_latents_kernel       one wavefront per draw d, four per workgroup, no LDS, no barrier.  The N = T * zdim normals of
-//                            draw d are those of the counter {block, 0xFFFFFFFF, d, call}: a trial word no sampler uses, so
-//                            that equal seeds and call numbers share no counter with the candidates.  Lane l makes blocks
+//   cem_latents_kernel       one wavefront per draw d.  The N = T * zdim normals of draw d are those of the counter
+//                            {block, 0xFFFFFFFF, d, call}: a trial word no sampler uses, so that equal seeds and call
+//                            numbers share no counter with the candidates.  Lane l makes blocks
 //                            l, l + 64, ... < n_blocks (host-known: no data-dependent loop) and stores its four normals,
 //                            each float64 rounded once to float32.
 //   cem_fold_latents_kernel  row a * n_latent + d of the engine's sequences is [actions[a] | z[d]] per step: one output
@@ -569,11 +573,8 @@ VF_GLOBAL VF_LAUNCH_BOUNDS(kCemThreads) void cem_latents_kernel(const CemLatentP
     if (d >= p.n_latent) return;
     float *out = p.z + (long long)d * p.N;
     for (int b = lane; b < p.n_blocks; b += 64) {
-        unsigned w[4];
         double z[4];
-        cem_philox((unsigned)b, kCemLatentTrial, (unsigned)d, p.call, p.seed_lo, p.seed_hi, w);
-        cem_pair(w[0], w[1], z[0], z[1]);
-        cem_pair(w[2], w[3], z[2], z[3]);
+        cem_normals((unsigned)b, kCemLatentTrial, (unsigned)d, p.call, p.seed_lo, p.seed_hi, z);
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const long long e = 4LL * b + q;
@@ -618,9 +619,8 @@ VF_GLOBAL VF_LAUNCH_BOUNDS(kCemThreads) void cem_fold_latents_kernel(const CemFo
 //   cem_grip_share_kernel        ONE workgroup, share mode only: share[t] = float32(count_t) / float32(K), count_t the
 //                                elites whose gripper value at step t is the close command - one thread per step in a loop,
 //                                so that the sampling kernel reads T floats, not K * T elite values per sample.
-//   cem_sample_autograsp_kernel  one wavefront per sample, four per workgroup, no LDS, no barrier.  The moves as
-//                                cem_sample_kernel; the trial loop, bounded by max_trials, stays the only data-dependent
-//                                loop.  Steps go in rounds of 64, lane l owning step 64 * round + l.  Height mode: EVERY lane
+//   cem_sample_autograsp_kernel  the moves as cem_sample_kernel (its trial loop stays the only data-dependent loop).  Steps
+//                                go in rounds of 64, lane l owning step 64 * round + l.  Height mode: EVERY lane
 //                                runs the serial chain c_t = c_(t-1) + float64(z_t) * norm, h_t = c_t + state_z (z_t fetched
 //                                by __shfl from the lane that owns the lift of step t's action, every operation rounded
 //                                once, the latch carried along) and keeps the decision of its own step - a shuffle scan
@@ -651,23 +651,11 @@ VF_GLOBAL VF_LAUNCH_BOUNDS(kCemThreads) void cem_sample_autograsp_kernel(const C
     const int lane = threadIdx.x & 63;
     const int i = blockIdx.x * kCemWaves + (threadIdx.x >> 6);
     if (i >= p.M) return;               // whole waves leave: nothing below waits for another wave
-    const int D = p.nactions * p.adim, T = p.nactions * p.repeat, W = p.adim + p.tail;
+    const int T = p.nactions * p.repeat, W = p.adim + p.tail;
     const CemLane s = cem_draw(p, lane, i);
-    if (lane == 0) {
-        p.trials[i] = s.accepted ? s.n + 1 : p.max_trials;
-        p.capped[i] = s.accepted ? 0 : 1;
-    }
     float *out = p.actions_out + (long long)i * T * W;
-    float f0 = 0.f, f1 = 0.f;           // what this lane stores for d0 and d1
-#pragma unroll
-    for (int half = 0; half < 2; ++half) {
-        const int d = half ? s.d1 : s.d0, c = half ? s.c1 : s.c0;
-        if (d >= D) continue;
-        const float f = cem_emit(p, s, half, i);
-        if (half) f1 = f; else f0 = f;
-        const int a = d / p.adim;
-        for (int q = 0; q < p.repeat; ++q) out[(a * p.repeat + q) * W + c] = f;
-    }
+    float f[2];                         // what this lane stores for d0 and d1
+    cem_store_moves(p, s, lane, i, out, f);
     const bool by_height = g.mode == kCemGripHeight;
     const bool draws = !by_height || g.deviation_prob > 0.0;
     double c = 0.0;
@@ -678,7 +666,7 @@ VF_GLOBAL VF_LAUNCH_BOUNDS(kCemThreads) void cem_sample_autograsp_kernel(const C
             const int steps = min(64, T - base);
             for (int l = 0; l < steps; ++l) {
                 const int d = ((base + l) / p.repeat) * p.adim + kCemGripLift;      // < D: its lane stored a value
-                const float z0 = __shfl(f0, d & 63), z1 = __shfl(f1, d & 63);
+                const float z0 = __shfl(f[0], d & 63), z1 = __shfl(f[1], d & 63);
                 const double step = __dmul_rn((double)(d < 64 ? z0 : z1), g.norm);
                 c = base + l == 0 ? step : __dadd_rn(c, step);
                 bool below = __dadd_rn(c, g.state_z) < g.z_thresh;
@@ -703,11 +691,7 @@ VF_GLOBAL VF_LAUNCH_BOUNDS(kCemThreads) void cem_sample_autograsp_kernel(const C
             out[t * W + p.adim] = shut ? g.close_cmd : g.open_cmd;
         }
     }
-    const int consts = p.tail - 1;      // the appended constants follow the gripper column: tail_value[1 ..]
-    for (int e = lane; e < T * consts; e += 64) {
-        const int t = e / consts, k = e % consts;
-        out[t * W + p.adim + 1 + k] = (float)p.tail_value[1 + k];
-    }
+    cem_fill_tail(out, lane, T, W, p.adim + 1, p.tail - 1, p.tail_value + 1);    // (behind the gripper column: tail_value[1 ..])
 }
 
 }  // namespace vf

@@ -9,6 +9,13 @@ allocated once.  Every method only enqueues on the current stream of its device;
 synchronisation of a planning call.  PyTorch carries the buffers, the arithmetic is ``csrc/vf_cem.h``.  The controller
 drives either through ``begin`` / ``sample`` / ``refit`` / ``downloads`` / ``finish`` (a sampler names its driver:
 ``device_cem_driver``).
+
+Who owns what.  ``_Driver``: the device and library handles, ``_stream``, the buffers every driver has, the workspace-size
+query, the refit call under ``refit_cfg`` and, for the factor-form proposal ``(R, mean, A)`` of the Gaussian, folding and
+autograsp drivers, ``upload`` through the pinned stage and ``read_proposal``.  A driver adds ``configure`` (its configs),
+``begin`` / ``finish`` and ``sample``.  ``DeviceCEM`` also has ``trials`` / ``capped`` and downloads them;
+``DeviceAutograspCEM``, a ``DeviceCEM``, adds ``share``.  ``DeviceCorrelatedCEM`` keeps its own workspace layout, and with
+it ``upload`` (no stage), the size and refit entries it names, ``_steps`` and ``read_proposal``.
 """
 import ctypes
 
@@ -19,13 +26,21 @@ from visual_foresight_amd import _lib
 HEADER_BYTES = 16
 
 
+def _fill_tail(cfg, append_action):
+    """``tail`` / ``tail_value`` of a config: the constants appended to every action row."""
+    tail = [float(v) for v in (append_action or ())]
+    cfg.tail = len(tail)
+    for i in range(8):
+        cfg.tail_value[i] = tail[i] if i < len(tail) else 0.0
+
+
 def cem_config(sampler, n_elites, append_action=None):
     """The ``vf_cem_config`` of a ``PhiloxGaussianCEMSampler`` (its limits, key and post-processing switches)."""
     hp, adim = sampler._hp, sampler._adim
-    tail = [float(v) for v in (append_action or ())]
     rej, trunc, discrete = sampler.limits()
     cfg = _lib.VfCemConfig()
-    cfg.nactions, cfg.repeat, cfg.adim, cfg.tail = int(hp.nactions), int(hp.repeat), int(adim), len(tail)
+    cfg.nactions, cfg.repeat, cfg.adim = int(hp.nactions), int(hp.repeat), int(adim)
+    _fill_tail(cfg, append_action)
     cfg.n_elites = int(n_elites)
     cfg.max_trials = int(hp.max_trials) if hp.rejection_sampling else 1
     cfg.rejection = int(bool(hp.rejection_sampling))
@@ -35,7 +50,6 @@ def cem_config(sampler, n_elites, append_action=None):
     for i in range(8):
         cfg.rej_lim[i] = float(rej[i]) if i < adim else float('inf')
         cfg.trunc_lim[i] = float(trunc[i]) if i < adim else float('inf')
-        cfg.tail_value[i] = tail[i] if i < len(tail) else 0.0
     return cfg
 
 
@@ -58,48 +72,91 @@ def read_workspace(image, D):
     return R, body[0].copy(), body[1:1 + R].T.copy()
 
 
-class DeviceCEM(object):
-    config = staticmethod(cem_config)       # (sampler, n_elites, append_action) -> the vf_cem_config of workspace and refit
+class _Driver(object):
+    size_entry, refit_entry = 'vf_cem_workspace_bytes', 'vf_cem_refit'      # (the library's, under refit_cfg)
 
     def __init__(self, sampler, n_elites, n_iter, max_samples, device, append_action=None):
         import torch
         self._torch = torch
         self.device = torch.device(device)
         self._lib = _lib.load_library()
-        self.cfg = self.config(sampler, n_elites, append_action)
-        hp = sampler._hp
-        self.D, self.K = int(hp.nactions) * sampler._adim, int(n_elites)
-        self.T, self.W = int(hp.nactions) * int(hp.repeat), sampler._adim + self.cfg.tail
-        self.n_iter, self.max_samples = int(n_iter), int(max_samples)
-        nbytes = self._lib.vf_cem_workspace_bytes(ctypes.byref(self.cfg))
+        self.K, self.n_iter, self.max_samples = int(n_elites), int(n_iter), int(max_samples)
+        self.configure(sampler, self.max_samples, append_action)
+        rc = self.refit_cfg             # (the config of workspace and refit)
+        self.D, self.W = rc.nactions * rc.adim, rc.adim + rc.tail
+        self.T = self._steps(rc)
+        nbytes = getattr(self._lib, self.size_entry)(ctypes.byref(rc))
         if nbytes == 0:
             raise ValueError('device CEM: %s' % self._lib.vf_last_error().decode())
-        self.rmax = max(self.D, self.K)
-        dev = self.device
-        self.workspace = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
-        self.actions = torch.zeros((self.n_iter, self.max_samples, self.T, self.W), dtype=torch.float32, device=dev)
-        self.scores = torch.zeros((self.n_iter, self.max_samples), dtype=torch.float64, device=dev)
-        self.elite_index = torch.zeros((self.n_iter, self.K), dtype=torch.int32, device=dev)
-        self.elite_score = torch.zeros((self.n_iter, self.K), dtype=torch.float64, device=dev)
-        self.elite_plans = torch.zeros((self.K, self.T, self.W), dtype=torch.float32, device=dev)
-        self.trials = torch.zeros((self.n_iter, self.max_samples), dtype=torch.int32, device=dev)
-        self.capped = torch.zeros((self.n_iter, self.max_samples), dtype=torch.int32, device=dev)
-        self._staging = torch.zeros(nbytes, dtype=torch.uint8).pin_memory()
+        self.workspace = self._zeros(nbytes, torch.uint8)
+        self.actions = self._zeros((self.n_iter, self.max_samples, self.T, self.W), torch.float32)
+        self.scores = self._zeros((self.n_iter, self.max_samples), torch.float64)
+        self.elite_index = self._zeros((self.n_iter, self.K), torch.int32)
+        self.elite_score = self._zeros((self.n_iter, self.K), torch.float64)
+        self.elite_plans = self._zeros((self.K, self.T, self.W), torch.float32)
+        self._staging = self._stage(nbytes)
+
+    def _steps(self, cfg):
+        """Rows of a plan: every action held ``repeat`` steps."""
+        return cfg.nactions * cfg.repeat
+
+    def _stage(self, nbytes):
+        """The pinned host image ``upload`` copies the workspace from."""
+        return self._torch.zeros(nbytes, dtype=self._torch.uint8).pin_memory()
+
+    def _zeros(self, shape, dtype):
+        return self._torch.zeros(shape, dtype=dtype, device=self.device)
 
     def _stream(self):
         return ctypes.c_void_p(self._torch.cuda.current_stream(self.device).cuda_stream)
+
+    def downloads(self, M):
+        """What the call's one download carries besides scores, elite indices and the final elite plans."""
+        return []
+
+    def upload(self, mean, A):
+        """Make ``(mean, A [D, R])`` the proposal: one asynchronous copy of the workspace image."""
+        image = workspace_image(np.asarray(mean, np.float64), np.asarray(A, np.float64), max(self.D, self.K))
+        # (the pinned stage may still feed the previous call's copy: wait for that one, it is long done)
+        self._torch.cuda.current_stream(self.device).synchronize()
+        self._staging.numpy()[:] = image
+        self.workspace.copy_(self._staging, non_blocking=True)
+
+    def refit(self, itr, scores_dev, actions_dev):
+        """Elites of ``scores_dev [M]`` (float64) over ``actions_dev [M, T, W]``, and the refit into the workspace."""
+        entry = getattr(self._lib, self.refit_entry)
+        M = int(scores_dev.shape[0])
+        with self._torch.cuda.device(self.device):
+            _lib.check(entry(self.device.index, ctypes.byref(self.refit_cfg), scores_dev.data_ptr(), actions_dev.data_ptr(), M,
+                             self.elite_index[itr].data_ptr(), self.elite_score[itr].data_ptr(), self.elite_plans.data_ptr(),
+                             self.workspace.data_ptr(), self._stream()))
+
+    def read_proposal(self):
+        """(synchronises) -> ``(R, mean, A [D, R])`` of the workspace."""
+        return read_workspace(self.workspace.cpu().numpy(), self.D)
+
+
+class DeviceCEM(_Driver):
+    config = staticmethod(cem_config)       # (sampler, n_elites, append_action) -> the vf_cem_config of workspace and refit
+
+    def __init__(self, sampler, n_elites, n_iter, max_samples, device, append_action=None):
+        super(DeviceCEM, self).__init__(sampler, n_elites, n_iter, max_samples, device, append_action)
+        self.trials = self._zeros((self.n_iter, self.max_samples), self._torch.int32)
+        self.capped = self._zeros((self.n_iter, self.max_samples), self._torch.int32)
+
+    def configure(self, sampler, M, append_action):
+        self.cfg = self.refit_cfg = self.config(sampler, self.K, append_action)
 
     # ------------------------------------------------------------------ one planning call, as the controller drives it
     def begin(self, sampler, t, M, append_action=None, state=None):
         """Start a planning call at time ``t`` that draws ``M`` sequences per iteration: the sampler's first proposal.
         ``state``: the state row the call starts from (the folding driver reads it)."""
-        self.cfg = self.config(sampler, self.K, append_action)      # (reset() makes a new sampler: its key)
+        self.configure(sampler, M, append_action)           # (reset() makes a new sampler: its key)
         self._mean0, std = sampler.initial_proposal(t)
         assert sampler.draws_for(self.max_samples) == M
         self.upload(self._mean0, np.diag(std))
 
     def downloads(self, M):
-        """What the call's one download carries besides scores, elite indices and the final elite plans."""
         return [self.trials[:, :M], self.capped[:, :M]]
 
     def finish(self, sampler, extras):
@@ -109,14 +166,6 @@ class DeviceCEM(object):
         sampler.n_capped += int(capped.sum())
         sampler._mean, sampler._A = self._mean0, None       # (the fitted proposal stays on the device)
 
-    def upload(self, mean, A):
-        """Make ``(mean, A [D, R])`` the proposal: one asynchronous copy of the workspace image."""
-        image = workspace_image(np.asarray(mean, np.float64), np.asarray(A, np.float64), self.rmax)
-        # (the pinned stage may still feed the previous call's copy: wait for that one, it is long done)
-        self._torch.cuda.current_stream(self.device).synchronize()
-        self._staging.numpy()[:] = image
-        self.workspace.copy_(self._staging, non_blocking=True)
-
     def sample(self, itr, M, call):
         """Candidates of iteration ``itr`` -> the device tensor ``[M, T, adim + tail]`` the rollout reads."""
         out = self.actions[itr, :M]
@@ -125,19 +174,6 @@ class DeviceCEM(object):
                                                int(M), out.data_ptr(), self.trials[itr].data_ptr(),
                                                self.capped[itr].data_ptr(), self._stream()))
         return out
-
-    def refit(self, itr, scores_dev, actions_dev):
-        """Elites of ``scores_dev [M]`` (float64) over ``actions_dev [M, T, adim + tail]``, and the refit into the workspace."""
-        M = int(scores_dev.shape[0])
-        with self._torch.cuda.device(self.device):
-            _lib.check(self._lib.vf_cem_refit(self.device.index, ctypes.byref(self.cfg), scores_dev.data_ptr(),
-                                              actions_dev.data_ptr(), M, self.elite_index[itr].data_ptr(),
-                                              self.elite_score[itr].data_ptr(), self.elite_plans.data_ptr(),
-                                              self.workspace.data_ptr(), self._stream()))
-
-    def read_proposal(self):
-        """(synchronises) -> ``(R, mean, A [D, R])`` of the workspace."""
-        return read_workspace(self.workspace.cpu().numpy(), self.D)
 
 
 # ---------------------------------------------------------------------------------------------------- correlated noise
@@ -149,10 +185,10 @@ def corr_workspace_bytes(D, K, refit_cov):
 def corr_config(sampler, n_elites, append_action=None):
     """The ``vf_cem_corr_config`` of a ``PhiloxCorrelatedNoiseSampler`` (its scales, key and the filter's first step)."""
     hp, adim = sampler._hp, sampler._adim
-    tail = [float(v) for v in (append_action or ())]
     std, bias, first = sampler.std(), sampler.bias(), sampler.first_predecessor()
     cfg = _lib.VfCemCorrConfig()
-    cfg.nactions, cfg.adim, cfg.tail, cfg.n_elites = int(hp.nactions), int(adim), len(tail), int(n_elites)
+    cfg.nactions, cfg.adim, cfg.n_elites = int(hp.nactions), int(adim), int(n_elites)
+    _fill_tail(cfg, append_action)
     cfg.refit_cov, cfg.has_first_prev = int(bool(hp.refit_cov)), int(first is not None)
     cfg.seed_lo, cfg.seed_hi = sampler.key
     cfg.kappa, cfg.beta_0, cfg.beta_1 = float(hp.kappa), float(hp.beta_0), float(hp.beta_1)
@@ -160,7 +196,6 @@ def corr_config(sampler, n_elites, append_action=None):
         cfg.std[i] = float(std[i]) if i < adim else 0.0
         cfg.bias[i] = float(bias[i]) if i < adim else 0.0
         cfg.first_prev[i] = float(first[i]) if first is not None and i < adim else 0.0
-        cfg.tail_value[i] = tail[i] if i < len(tail) else 0.0
     return cfg
 
 
@@ -175,42 +210,29 @@ def read_corr_workspace(image, D, K, refit_cov):
                 A=A)
 
 
-class DeviceCorrelatedCEM(object):
-    def __init__(self, sampler, n_elites, n_iter, max_samples, device, append_action=None):
-        import torch
-        self._torch = torch
-        self.device = torch.device(device)
-        self._lib = _lib.load_library()
-        self.cfg = corr_config(sampler, n_elites, append_action)
-        hp = sampler._hp
-        self.D, self.K = int(hp.nactions) * sampler._adim, int(n_elites)
-        self.T, self.W = int(hp.nactions), sampler._adim + self.cfg.tail
-        self.refit_cov = bool(hp.refit_cov)
-        self.n_iter, self.max_samples = int(n_iter), int(max_samples)
-        nbytes = self._lib.vf_cem_corr_workspace_bytes(ctypes.byref(self.cfg))
-        if nbytes == 0:
-            raise ValueError('device CEM: %s' % self._lib.vf_last_error().decode())
-        assert nbytes == corr_workspace_bytes(self.D, self.K, self.refit_cov)
-        dev = self.device
-        self.workspace = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
-        self.actions = torch.zeros((self.n_iter, self.max_samples, self.T, self.W), dtype=torch.float32, device=dev)
-        self.scores = torch.zeros((self.n_iter, self.max_samples), dtype=torch.float64, device=dev)
-        self.elite_index = torch.zeros((self.n_iter, self.K), dtype=torch.int32, device=dev)
-        self.elite_score = torch.zeros((self.n_iter, self.K), dtype=torch.float64, device=dev)
-        self.elite_plans = torch.zeros((self.K, self.T, self.W), dtype=torch.float32, device=dev)
+class DeviceCorrelatedCEM(_Driver):
+    size_entry, refit_entry = 'vf_cem_corr_workspace_bytes', 'vf_cem_soft_refit'    # (header, centre, mean, soft, A)
 
-    def _stream(self):
-        return ctypes.c_void_p(self._torch.cuda.current_stream(self.device).cuda_stream)
+    def __init__(self, sampler, n_elites, n_iter, max_samples, device, append_action=None):
+        super(DeviceCorrelatedCEM, self).__init__(sampler, n_elites, n_iter, max_samples, device, append_action)
+        self.refit_cov = bool(sampler._hp.refit_cov)
+        assert self.workspace.numel() == corr_workspace_bytes(self.D, self.K, self.refit_cov)
+
+    def configure(self, sampler, M, append_action):
+        self.cfg = self.refit_cfg = corr_config(sampler, self.K, append_action)
+
+    def _steps(self, cfg):
+        return cfg.nactions         # (no action is held)
+
+    def _stage(self, nbytes):
+        return None                 # (upload only zeroes the header on the device)
 
     # ------------------------------------------------------------------ one planning call, as the controller drives it
     def begin(self, sampler, t, M, append_action=None, state=None):
         """Start a planning call: the first proposal has no centre, and the filter's first step is the sampler's."""
-        self.cfg = corr_config(sampler, self.K, append_action)      # (reset() makes a new sampler: its key)
+        self.configure(sampler, M, append_action)           # (reset() makes a new sampler: its key)
         sampler.start_planning_call()
         self.upload()
-
-    def downloads(self, M):
-        return []
 
     def finish(self, sampler, extras):
         sampler.start_planning_call()       # (the fit stays on the device)
@@ -227,15 +249,6 @@ class DeviceCorrelatedCEM(object):
                                                     int(call), int(M), out.data_ptr(), self._stream()))
         return out
 
-    def refit(self, itr, scores_dev, actions_dev):
-        """Elites of ``scores_dev [M]`` (float64) over ``actions_dev [M, nactions, adim + tail]``, and the soft refit."""
-        M = int(scores_dev.shape[0])
-        with self._torch.cuda.device(self.device):
-            _lib.check(self._lib.vf_cem_soft_refit(self.device.index, ctypes.byref(self.cfg), scores_dev.data_ptr(),
-                                                   actions_dev.data_ptr(), M, self.elite_index[itr].data_ptr(),
-                                                   self.elite_score[itr].data_ptr(), self.elite_plans.data_ptr(),
-                                                   self.workspace.data_ptr(), self._stream()))
-
     def read_proposal(self):
         """(synchronises) -> the workspace as ``read_corr_workspace`` gives it."""
         return read_corr_workspace(self.workspace.cpu().numpy(), self.D, self.K, self.refit_cov)
@@ -246,23 +259,22 @@ def fold_refit_config(sampler, n_elites, append_action=None):
     """The ``vf_cem_config`` under which ``vf_cem_workspace_bytes`` / ``vf_cem_refit`` serve a ``PhiloxFoldingCEMSampler``:
     the Gaussian proposal with ``adim = 4``, nothing rejected, nothing limited."""
     hp = sampler._hp
-    tail = [float(v) for v in (append_action or ())]
     cfg = _lib.VfCemConfig()
-    cfg.nactions, cfg.repeat, cfg.adim, cfg.tail = int(hp.nactions), int(hp.repeat), 4, len(tail)
+    cfg.nactions, cfg.repeat, cfg.adim = int(hp.nactions), int(hp.repeat), 4
+    _fill_tail(cfg, append_action)
     cfg.n_elites, cfg.max_trials = int(n_elites), 1
     cfg.seed_lo, cfg.seed_hi = sampler.key
     for i in range(8):
         cfg.rej_lim[i] = cfg.trunc_lim[i] = float('inf')
-        cfg.tail_value[i] = tail[i] if i < len(tail) else 0.0
     return cfg
 
 
 def fold_config(sampler, n_elites, M, append_action=None):
     """The ``vf_cem_fold_config`` of a ``PhiloxFoldingCEMSampler`` whose calls draw ``M`` sequences."""
     hp = sampler._hp
-    tail = [float(v) for v in (append_action or ())]
     cfg = _lib.VfCemFoldConfig()
-    cfg.nactions, cfg.repeat, cfg.tail, cfg.n_elites = int(hp.nactions), int(hp.repeat), len(tail), int(n_elites)
+    cfg.nactions, cfg.repeat, cfg.n_elites = int(hp.nactions), int(hp.repeat), int(n_elites)
+    _fill_tail(cfg, append_action)
     cfg.n_scripted = int(sampler.check_draws(M))
     cfg.seed_lo, cfg.seed_hi = sampler.key
     start = sampler.start_xy()
@@ -270,61 +282,24 @@ def fold_config(sampler, n_elites, M, append_action=None):
         cfg.start_xy[i] = float(start[i])
     for i in range(3):
         cfg.max_shift[i] = float(hp.max_shift[i])
-    for i in range(8):
-        cfg.tail_value[i] = tail[i] if i < len(tail) else 0.0
     return cfg
 
 
-class DeviceFoldingCEM(object):
-    def __init__(self, sampler, n_elites, n_iter, max_samples, device, append_action=None):
-        import torch
-        self._torch = torch
-        self.device = torch.device(device)
-        self._lib = _lib.load_library()
-        self.refit_cfg = fold_refit_config(sampler, n_elites, append_action)
-        self.cfg = fold_config(sampler, n_elites, max_samples, append_action)
-        hp = sampler._hp
-        self.D, self.K = int(hp.nactions) * 4, int(n_elites)
-        self.T, self.W = int(hp.nactions) * int(hp.repeat), 4 + self.cfg.tail
-        self.n_iter, self.max_samples = int(n_iter), int(max_samples)
-        nbytes = self._lib.vf_cem_workspace_bytes(ctypes.byref(self.refit_cfg))
-        if nbytes == 0:
-            raise ValueError('device CEM: %s' % self._lib.vf_last_error().decode())
-        self.rmax = max(self.D, self.K)
-        dev = self.device
-        self.workspace = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
-        self.actions = torch.zeros((self.n_iter, self.max_samples, self.T, self.W), dtype=torch.float32, device=dev)
-        self.scores = torch.zeros((self.n_iter, self.max_samples), dtype=torch.float64, device=dev)
-        self.elite_index = torch.zeros((self.n_iter, self.K), dtype=torch.int32, device=dev)
-        self.elite_score = torch.zeros((self.n_iter, self.K), dtype=torch.float64, device=dev)
-        self.elite_plans = torch.zeros((self.K, self.T, self.W), dtype=torch.float32, device=dev)
-        self._staging = torch.zeros(nbytes, dtype=torch.uint8).pin_memory()
-
-    def _stream(self):
-        return ctypes.c_void_p(self._torch.cuda.current_stream(self.device).cuda_stream)
+class DeviceFoldingCEM(_Driver):
+    def configure(self, sampler, M, append_action):
+        self.refit_cfg = fold_refit_config(sampler, self.K, append_action)
+        self.cfg = fold_config(sampler, self.K, M, append_action)
 
     # ------------------------------------------------------------------ one planning call, as the controller drives it
     def begin(self, sampler, t, M, append_action=None, state=None):
         """Start a planning call at time ``t`` from the state row ``state``: the gripper's xy goes into the config, the first
         proposal ``(0, diag(std))`` into the workspace."""
         mean, std = sampler.initial_proposal(t, state)
-        self.refit_cfg = fold_refit_config(sampler, self.K, append_action)      # (reset() makes a new sampler: its key)
-        self.cfg = fold_config(sampler, self.K, M, append_action)
+        self.configure(sampler, M, append_action)           # (reset() makes a new sampler: its key)
         self.upload(mean, np.diag(std))
-
-    def downloads(self, M):
-        return []
 
     def finish(self, sampler, extras):
         pass        # (the fitted proposal stays on the device; the next call starts from the first proposal)
-
-    def upload(self, mean, A):
-        """Make ``(mean, A [D, R])`` the proposal: one asynchronous copy of the workspace image."""
-        image = workspace_image(np.asarray(mean, np.float64), np.asarray(A, np.float64), self.rmax)
-        # (the pinned stage may still feed the previous call's copy: wait for that one, it is long done)
-        self._torch.cuda.current_stream(self.device).synchronize()
-        self._staging.numpy()[:] = image
-        self.workspace.copy_(self._staging, non_blocking=True)
 
     def sample(self, itr, M, call):
         """Candidates of iteration ``itr`` -> the device tensor ``[M, T, 4 + tail]`` the rollout reads."""
@@ -333,19 +308,6 @@ class DeviceFoldingCEM(object):
             _lib.check(self._lib.vf_cem_sample_fold(self.device.index, ctypes.byref(self.cfg), self.workspace.data_ptr(),
                                                     int(call), int(M), out.data_ptr(), self._stream()))
         return out
-
-    def refit(self, itr, scores_dev, actions_dev):
-        """Elites of ``scores_dev [M]`` (float64) over ``actions_dev [M, T, 4 + tail]``, and the refit into the workspace."""
-        M = int(scores_dev.shape[0])
-        with self._torch.cuda.device(self.device):
-            _lib.check(self._lib.vf_cem_refit(self.device.index, ctypes.byref(self.refit_cfg), scores_dev.data_ptr(),
-                                              actions_dev.data_ptr(), M, self.elite_index[itr].data_ptr(),
-                                              self.elite_score[itr].data_ptr(), self.elite_plans.data_ptr(),
-                                              self.workspace.data_ptr(), self._stream()))
-
-    def read_proposal(self):
-        """(synchronises) -> ``(R, mean, A [D, R])`` of the workspace."""
-        return read_workspace(self.workspace.cpu().numpy(), self.D)
 
 
 # ---------------------------------------------------------------------------------------------------- autograsp
@@ -372,7 +334,7 @@ class DeviceAutograspCEM(DeviceCEM):
 
     def __init__(self, sampler, n_elites, n_iter, max_samples, device, append_action=None):
         super(DeviceAutograspCEM, self).__init__(sampler, n_elites, n_iter, max_samples, device, append_action)
-        self.share = self._torch.zeros(self.T, dtype=self._torch.float32, device=self.device)
+        self.share = self._zeros(self.T, self._torch.float32)
         self._sampler = sampler
 
     def begin(self, sampler, t, M, append_action=None, state=None):
